@@ -66,7 +66,32 @@ def parse_args():
     ap.add_argument("--no-small", action="store_true",
                     help="skip the extra line for segments of 2^18 cycles (script/prove-block.sh's execution_po2)")
     ap.add_argument("--no-verify", action="store_true", help="leave rk_verify_segment out of the timed region")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step returned (the seal of the last segment, "
+                         "rank 0: of the gathered list) as DIR/seal.npy in float64; the inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.dump_outputs is not None:
+        if args.preset == "sp1-p3":
+            ap.error("--dump-outputs covers the segment-proof line, not --preset sp1-p3")
+        if args.steps < 1 and args.total_segments < 1:
+            ap.error("--dump-outputs needs at least one timed step")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (BabyBear words < 2^31 are exact in it)"""
+    import numpy as np
+    arrays = {name: np.asarray(a).astype(np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def device_segment(torch, seg_mod, po2, widths, seed, device, blowup_log2=2):
@@ -211,14 +236,17 @@ def main():
     barrier()
     t0 = time.perf_counter()
     seals = session(my_steps)
+    gathered = seals
     if world > 1:
         # rank r proved global segments r, r+world, ...: gather in that order (one collective)
-        gather_seals(seals, total_segments, device=coll_device)
+        gathered = gather_seals(seals, total_segments, device=coll_device)
     torch.cuda.synchronize()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     kstats = session_kernel_stats(gpu_index)
     session_set_kernel_timing(gpu_index, False)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"seal": gathered[-1]})
 
     # the same session from host-resident arrays: PCIe upload through the staging ring inside the region
     elapsed_h2d = None
