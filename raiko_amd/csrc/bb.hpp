@@ -125,6 +125,17 @@ RK_HD uint32_t uredc64(uint64_t t) {
     uint64_t w = t + (uint64_t)q * P;
     return (uint32_t)(w >> 32);
 }
+// t - 2p * hi32(t): the same residue, |result| <= (2^28 - 2) |hi32(t)| + 2^32 (2^32 - 2p = 2^28 - 2), so a signed
+// 64-bit sum below 2^63 comes back under 2^59.  Two v_mad_i64_i32 by -p (-2p does not fit 32 bits); for any |t| < 2^63.
+RK_HD int64_t fold64(int64_t t) {
+    const int32_t hi = (int32_t)(t >> 32);
+    int64_t u = t + (int64_t)hi * (int64_t)NEG_P;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // opaque in between: otherwise the two products merge into one by -2p, a 64 x 32-bit product of five instructions
+    asm("" : "+v"(u));
+#endif
+    return u + (int64_t)hi * (int64_t)NEG_P;
+}
 // acc + x as one 64-bit v_mad_u64_u32 (x * 1 + acc): hipcc otherwise zero-extends x with a
 // v_mov and adds with v_lshl_add_u64, two 4-cycle instructions per term
 RK_HD uint64_t acc_u32(uint64_t acc, uint32_t x) {

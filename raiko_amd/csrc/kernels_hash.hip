@@ -18,7 +18,7 @@ constexpr size_t CELLS_MAX_OUT = rk::HASH_FOLD_TOP_MAX;
 // pad_free: the last partial block leaves the remaining rate cells as they are (Plonky3
 // PaddingFreeSponge) instead of zero-padding them (risc0); an empty row then takes no permutation.
 template <class C>
-__global__ __launch_bounds__(HASH_BLOCK) void hash_rows_kernel(uint32_t* __restrict__ out,
+__global__ __launch_bounds__(HASH_BLOCK, 5) void hash_rows_kernel(uint32_t* __restrict__ out,
                                                                const uint32_t* __restrict__ matrix, size_t rows,
                                                                size_t cols, const typename C::Consts* __restrict__ kc,
                                                                int pad_free) {

@@ -39,7 +39,7 @@ struct ColRef {
 // nat_bits != 0: lane t is the NATURAL index of a layout-2 matrix (column-major, committed row r stored at index
 // bitrev(r)): its loads are then coalesced and the digest goes to row bitrev(t); otherwise lane t is the committed row
 template <class C>
-__global__ __launch_bounds__(HASH_BLOCK) void hash_rows_multi_kernel(uint32_t* __restrict__ out, uint64_t mats_addr, uint64_t cols_addr,
+__global__ __launch_bounds__(HASH_BLOCK, 5) void hash_rows_multi_kernel(uint32_t* __restrict__ out, uint64_t mats_addr, uint64_t cols_addr,
                                                                      uint32_t n_cols, size_t rows,
                                                                      const typename C::Consts* __restrict__ kc, int pad_free, unsigned nat_bits,
                                                                      unsigned bits) {

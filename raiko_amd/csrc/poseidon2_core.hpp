@@ -21,10 +21,16 @@
 //     partial rounds (one product for cell 0), the second block's by one product per OUTPUT cell
 //     after the last layer, so a caller that keeps only some cells (digest, sponge capacity)
 //     pays only for those;
-//   * internal layers: three instructions per cell per partial round, the addition of the cell sum
-//     riding inside the Montgomery reduction (see partial_rounds()).
+//   * internal layers: in blocks of PR_BLOCK rounds, the cells other than 0 are written once per block
+//     (PR_BLOCK products and one signed REDC per cell) while cell 0 runs every round (see partial_rounds()).
 #pragma once
 #include "bb.hpp"
+
+// Rounds per block of the partial rounds (2 or 3; 3 is the shipped choice).  RK_P2_DIRECT selects
+// the one-round-at-a-time form instead, for A/B in tools/ubench_p2.hip and tools/census_p2.py.
+#ifndef RK_P2_BLOCK
+#define RK_P2_BLOCK 3
+#endif
 
 namespace p2 {
 
@@ -36,6 +42,9 @@ constexpr int ROUNDS_HALF_FULL = 4;  // R_F = 8
 // s_nop 1 (its vcc write followed by an opaque SGPR read).
 RK_HD uint64_t mad_sc(uint64_t acc, uint32_t x, uint32_t c) { return acc + (uint64_t)x * (uint64_t)c; }
 RK_HD uint64_t mul_sc(uint32_t x, uint32_t c) { return (uint64_t)x * (uint64_t)c; }
+// signed forms (v_mad_i64_i32), same reason
+RK_HD int64_t smad_sc(int64_t acc, int32_t x, int32_t c) { return acc + (int64_t)x * (int64_t)c; }
+RK_HD int64_t smul_sc(int32_t x, int32_t c) { return (int64_t)x * (int64_t)c; }
 
 // acc + x * K with a literal multiplier: one v_mad_u64_u32
 template <int K>
@@ -91,8 +100,8 @@ struct KStream {
     // `acc` (the running sum the constant is about to be multiplied into) is threaded through the
     // wait so that the scheduler keeps it between the products of two chunks: without that it
     // bunches several wait + load pairs together and nothing overlaps the load latency
-    template <int POS>
-    __device__ __forceinline__ uint32_t get(uint64_t& acc) {
+    template <int POS, class A>
+    __device__ __forceinline__ uint32_t get(A& acc) {
         uint32_t c = cur[POS & 15];
         if constexpr ((POS & 15) == 15) {
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nxt), "+v"(acc));
@@ -108,8 +117,8 @@ struct KStream {
 struct KStream {
     const uint32_t* p;
     explicit KStream(const uint32_t* base) : p(base) {}
-    template <int POS>
-    uint32_t get(uint64_t&) { return p[POS]; }
+    template <int POS, class A>
+    uint32_t get(A&) { return p[POS]; }
     void drain() {}
 };
 #endif
@@ -119,6 +128,11 @@ template <int POS>
 RK_HD void pr_fma(KStream& ks, uint64_t& acc, uint32_t x) {
     uint32_t c = ks.template get<POS>(acc);
     acc = mad_sc(acc, x, c);
+}
+template <int POS>
+RK_HD void pr_sfma(KStream& ks, int64_t& acc, int32_t x) {
+    const int32_t c = (int32_t)ks.template get<POS>(acc);
+    acc = smad_sc(acc, x, c);
 }
 
 // One Poseidon2 instance family: width W (rate W - 8), RP partial rounds, 4x4 block M4K of the
@@ -131,12 +145,23 @@ static constexpr int RATE = W - 8;
 static constexpr int ROUNDS_PARTIAL = RP;
 static constexpr int M4_KIND = M4K;
 
-// per round r: 23 pairs d_i^r, r pairs c_(r-1-j), then d_0 + 1; at the end 23 x (d_i^21, d_i^(20-j))
-#if defined(RK_P2_CLOSED_FORM)
-static constexpr int PR_STREAM_USED = ROUNDS_PARTIAL * (2 * (CELLS - 1) + 1) + ROUNDS_PARTIAL * (ROUNDS_PARTIAL - 1) +
-                               (CELLS - 1) * 2 * (ROUNDS_PARTIAL + 1);
-#else
+#if defined(RK_P2_DIRECT)
 static constexpr int PR_STREAM_USED = ROUNDS_PARTIAL * CELLS;  // one multiplier per cell per round
+#else
+// blocks of PR_BLOCK rounds, the remainder (RP mod PR_BLOCK rounds) last: 21 = 7 x 3, 13 = 4 x 3 + 1
+static constexpr int PR_BLOCK = RK_P2_BLOCK;
+static_assert(PR_BLOCK >= 1 && PR_BLOCK <= 3, "the bounds of partial_rounds() are worked out for blocks of up to 3 rounds");
+static constexpr int PR_NB = (RP + PR_BLOCK - 1) / PR_BLOCK;
+static constexpr int blk_len(int b) { return b < RP / PR_BLOCK ? PR_BLOCK : RP % PR_BLOCK; }
+static constexpr int blk_next(int b) { return b + 1 < PR_NB ? blk_len(b + 1) : 1; }
+// stream: the entry cells' dot-product constants for block 0, then per block and per cell i >= 1 the
+// blk_len multipliers of the cell update and the blk_next - 1 dot-product constants of the next block
+static constexpr int blk_off(int b) {
+    int n = (CELLS - 1) * (blk_len(0) - 1);
+    for (int c = 0; c < b; c++) n += (CELLS - 1) * (blk_len(c) + blk_next(c) - 1);
+    return n;
+}
+static constexpr int PR_STREAM_USED = blk_off(PR_NB);
 #endif
 static constexpr int PR_STREAM_WORDS = (PR_STREAM_USED + 15) / 16 * 16 + 16;
 
@@ -153,10 +178,17 @@ struct Consts {
     uint32_t fix0_nq;                                  // fix[0] * (-p^-1) mod 2^32 (bb::umul_const companion)
     uint32_t fix1_q;                                   // fix[1] * p^-1 mod 2^32 (bb::smul_const companion)
     uint32_t sig0_c, sig0_nq;                          // fix[0] * 2^32 and its companion: entry sum -> Montgomery form
-    uint32_t r3_c, r3_nq;                              // 2^96 mod p and its companion: S -> S * 2^32 (see partial_rounds())
-    // partial rounds in closed form (see partial_rounds()): the constants in the order the
-    // code consumes them, each as a pair {c, c * 2^16 mod p} for the low / high 16-bit halves
-    // of the variable it multiplies (+ one chunk of padding for the read-ahead)
+    uint32_t r3_c, r3_nq;                              // 2^96 mod p and its companion: S -> S * 2^32 (direct form)
+    // blocked partial rounds (see partial_rounds()), centred representatives |c| <= (p - 1) / 2
+    int32_t pr_fix0;                                   // fix[0]: entry cell 0 and entry sum to Montgomery form
+    uint32_t pr_fix0_q;                                // its bb::smul_const companion
+    int32_t pr_d0;                                     // d_0 (Montgomery residue)
+    int32_t pr_r2;                                     // 2^64 mod p: S (plain) -> S * 2^32 inside a REDC
+    int32_t pr_r3;                                     // 2^96 mod p: S (plain) -> SM2 = S * 2^64 mod p
+    uint32_t pr_r3_q;                                  // its bb::smul_const companion
+    int32_t pr_csum[3];                                // c_n * 2^32 mod p, c_n = sum_{i >= 1} d_i^n (n < PR_BLOCK - 1)
+    // per-cell multipliers of the partial rounds in the order partial_rounds() consumes them (+ one
+    // chunk of padding for the read-ahead)
     uint32_t pr_stream[PR_STREAM_WORDS];
 };
 
@@ -178,7 +210,7 @@ static inline void derive(Consts& k) {
         // residue a * 2^(32 e) for the true state a, so the residue to add is rc * 2^(32 e):
         // bb::mul(v, f) = v * f / 2^32 with the residue f = 2^(32 e) = rpow(e - 1).
         uint32_t f = rpow((long)scale_exp(r) - 1);
-        const bool after_unsigned = r % ROUNDS_HALF_FULL == 0;  // input in [0, p + 2^22): offset rc - p
+        const bool after_unsigned = r % ROUNDS_HALF_FULL == 0;  // input in [0, p + 53): offset rc - p
         for (int i = 0; i < CELLS; i++) {
             uint32_t c = bb::mul(k.rc_ext[r * CELLS + i], f);
             // otherwise the input is a signed REDC output, |x| <= p/2 + 53: centred offset, |x + rc| < 2^31
@@ -198,38 +230,49 @@ static inline void derive(Consts& k) {
     k.sig0_nq = k.sig0_c * (0u - bb::MPRIME);
     k.r3_c = bb::encode(bb::encode(bb::ONE));
     k.r3_nq = k.r3_c * (0u - bb::MPRIME);
-#if defined(RK_P2_CLOSED_FORM)
-    // closed-form partial rounds: powers of the diagonal (Montgomery residues: they multiply a
-    // Montgomery-form variable and the sum goes through one REDC).  The constants that multiply
-    // the ENTRY cells also carry fix[0]: those cells arrive scaled by the first block.
-    const uint32_t two16 = bb::encode(65536u);
-    uint32_t pw[CELLS - 1][ROUNDS_PARTIAL + 1];
-    for (int i = 1; i < CELLS; i++) {
-        pw[i - 1][0] = bb::ONE;
-        for (int m = 1; m <= ROUNDS_PARTIAL; m++) pw[i - 1][m] = bb::mul(pw[i - 1][m - 1], k.diag[i]);
-    }
-    uint32_t csum[ROUNDS_PARTIAL];
-    for (int m = 0; m < ROUNDS_PARTIAL; m++) {
-        csum[m] = 0;
-        for (int i = 0; i < CELLS - 1; i++) csum[m] = bb::add(csum[m], pw[i][m]);
-    }
-    int n = 0;
-    auto put = [&](uint32_t c) { k.pr_stream[n++] = c; k.pr_stream[n++] = bb::mul(c, two16); };
-    for (int r = 0; r < ROUNDS_PARTIAL; r++) {
-        for (int i = 0; i < CELLS - 1; i++) put(bb::mul(pw[i][r], k.fix[0]));
-        for (int j = 0; j < r; j++) put(csum[r - 1 - j]);
-        k.pr_stream[n++] = bb::add(k.diag[0], bb::ONE);
-    }
-    for (int i = 0; i < CELLS - 1; i++) {
-        put(bb::mul(pw[i][ROUNDS_PARTIAL], k.fix[0]));
-        for (int j = 0; j < ROUNDS_PARTIAL; j++) put(pw[i][ROUNDS_PARTIAL - 1 - j]);
-    }
-#else
+#if defined(RK_P2_DIRECT)
     // direct partial rounds: round r, cell i multiplies by d_i (Montgomery residue); in round 0 the cells
     // other than 0 still carry the first block's scale, so their multiplier is d_i * fix[0] / 2^32
     int n = 0;
     for (int r = 0; r < ROUNDS_PARTIAL; r++)
         for (int i = 0; i < CELLS; i++) k.pr_stream[n++] = (r == 0 && i > 0) ? bb::mul(k.diag[i], k.fix[0]) : k.diag[i];
+#else
+    // blocked partial rounds.  Plain field arithmetic here: a value v "carries" 2^32 when v = x 2^32 mod p for
+    // the element x (Montgomery form), and a REDC takes one 2^32 away.  The entry cells carry 2^32 / G with
+    // G = fix[0] / 2^32 (the first block of full rounds), so whatever multiplies them in block 0 also carries G.
+    auto mulp = [](uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % bb::P); };
+    auto cen = [](uint32_t c) { return c > bb::P / 2 ? (int32_t)(c - bb::P) : (int32_t)c; };
+    const uint32_t R1 = bb::ONE, R2 = mulp(R1, R1), R3 = mulp(R2, R1), G = bb::decode(k.fix[0]);
+    uint32_t pw[CELLS][PR_BLOCK + 1];  // d_i^n, plain
+    for (int i = 0; i < CELLS; i++) {
+        pw[i][0] = 1;
+        for (int m = 1; m <= PR_BLOCK; m++) pw[i][m] = mulp(pw[i][m - 1], bb::decode(k.diag[i]));
+    }
+    for (int m = 0; m < 3; m++) {
+        uint32_t c = 0;
+        for (int i = 1; i < CELLS && m < PR_BLOCK; i++) c = (c + pw[i][m]) % bb::P;
+        k.pr_csum[m] = cen(mulp(c, R1));
+    }
+    k.pr_fix0 = cen(k.fix[0]);
+    k.pr_fix0_q = (uint32_t)k.pr_fix0 * bb::MPRIME;
+    k.pr_d0 = cen(k.diag[0]);
+    k.pr_r2 = cen(R2);
+    k.pr_r3 = cen(R3);
+    k.pr_r3_q = (uint32_t)k.pr_r3 * bb::MPRIME;
+    int n = 0;
+    auto put = [&](uint32_t c) { k.pr_stream[n++] = (uint32_t)cen(c); };
+    // D_j = sum_i d_i^j x_i over the entry cells: the dot products feed a sum that carries 2^32
+    for (int i = 1; i < CELLS; i++)
+        for (int j = 1; j < blk_len(0); j++) put(mulp(pw[i][j], G));
+    for (int b = 0; b < PR_NB; b++) {
+        const int K = blk_len(b);
+        const uint32_t g = b == 0 ? G : 1;
+        for (int i = 1; i < CELLS; i++) {
+            put(mulp(mulp(pw[i][K], R1), g));                                // d_i^K x_i: REDC of it carries 2^32
+            for (int m = 0; m + 1 < K; m++) put(mulp(pw[i][K - 1 - m], R2));  // d_i^(K-1-m) S_m, S_m plain
+            for (int j = 1; j < blk_next(b); j++) put(pw[i][j]);              // the next block's D_j
+        }
+    }
 #endif
     while (n < PR_STREAM_WORDS) k.pr_stream[n++] = 0;
 }
@@ -328,81 +371,11 @@ static RK_HD void full_round(uint32_t* s, const Consts& k, int r) {
     for (int i = 0; i < CELLS; i++) s[i] = (uint32_t)o[i];
 }
 
-// All 21 partial rounds in closed form.  Entry: any 32-bit representatives of the cells, scaled by
-// the first block of full rounds (see permute()); exit: Montgomery form, cells in [0, p + 2^22).
-// With v = cells 1..23 at entry, y_k the S-box output of
-// round k and S_k = y_k + sum(cells 1..23 before round k):
-//     cells_i before round k   = d_i^k v_i + sum_{j<k} d_i^(k-1-j) S_j
-//     sum of them              = sum_i d_i^k v_i + sum_{j<k} c_(k-1-j) S_j,     c_m = sum_i d_i^m
-//     cell 0 after round k     = (d_0 + 1) y_k + that sum
-//     cells_i after round 20   = d_i^21 v_i + sum_j d_i^(20-j) S_j
-// so no cell is touched between entry and exit: each round is one dot product with constant
-// vectors, and every product is accumulated exactly in 64 bits -- variables are split into
-// 16-bit halves, constants come as {c, c 2^16}, so a term is < 2^47 and one v_mad_u64_u32 --
-// with one REDC per sum.  ~3.0 k instructions instead of ~4.1 k for 21 rounds of
-// multiply / reduce / add on every cell.
 // Reader of Consts::pr_stream.  On the device the constants live in scalar registers: chunks of
 // 16 are fetched with s_load_dwordx16 one chunk ahead of their use (the compiler's own scheduling
 // of ~2400 scalar loads spills SGPRs), and the wait is attached to the chunk's registers so that
 // no use can move above it.  Positions are consumed strictly in order.
-#if defined(RK_P2_CLOSED_FORM)
-static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
-    constexpr int NV = CELLS - 1;
-    uint32_t vlo[NV], vhi[NV], slo[ROUNDS_PARTIAL], shi[ROUNDS_PARTIAL];
-#pragma unroll
-    for (int i = 0; i < NV; i++) {
-        vlo[i] = s[i + 1] & 0xffffu;
-        vhi[i] = s[i + 1] >> 16;
-    }
-    KStream ks(k.pr_stream);
-    // cell 0 feeds an S-box, so it needs its true (Montgomery) value: one product by fix[0]; the other
-    // cells only enter linear forms, whose constants carry fix[0] (derive())
-    uint32_t x0 = bb::ucanon(bb::umul_const(s[0], k.fix[0], k.fix0_nq));
-    static_for<0, ROUNDS_PARTIAL>([&](auto rc) __attribute__((always_inline)) {
-        constexpr int R = decltype(rc)::value;
-        constexpr int BASE = (2 * NV + 1) * R + R * (R - 1);
-        uint32_t y = bb::canon(sbox7_lazy(x0, k.rc_int_mp[R]));
-        uint64_t acc = 0;
-        pr_fma<BASE>(ks, acc, vlo[0]);
-        pr_fma<BASE + 1>(ks, acc, vhi[0]);
-        static_for<1, NV>([&](auto ic) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value;
-            pr_fma<BASE + 2 * I>(ks, acc, vlo[I]);
-            pr_fma<BASE + 2 * I + 1>(ks, acc, vhi[I]);
-        });
-        static_for<0, R>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int J = decltype(jc)::value;
-            pr_fma<BASE + 2 * NV + 2 * J>(ks, acc, slo[J]);
-            pr_fma<BASE + 2 * NV + 2 * J + 1>(ks, acc, shi[J]);
-        });
-        // acc < 88 * 2^47: sigma < p + 2^22, S = y + sigma < 2p + 2^22 < 2^32 (any representative
-        // serves: only its halves are used)
-        uint32_t S = y + bb::uredc64(acc);
-        slo[R] = S & 0xffffu;
-        shi[R] = S >> 16;
-        // acc + (d_0 + 1) y < 2^54 + 2^62: REDC < 2p
-        pr_fma<BASE + 2 * NV + 2 * R>(ks, acc, y);
-        x0 = bb::ucanon(bb::uredc64(acc));
-    });
-    s[0] = x0;
-    constexpr int FIN = (2 * NV + 1) * ROUNDS_PARTIAL + ROUNDS_PARTIAL * (ROUNDS_PARTIAL - 1);
-    static_for<0, NV>([&](auto ic) __attribute__((always_inline)) {
-        constexpr int I = decltype(ic)::value;
-        constexpr int BASE = FIN + I * 2 * (ROUNDS_PARTIAL + 1);
-        uint64_t acc = 0;
-        pr_fma<BASE>(ks, acc, vlo[I]);
-        pr_fma<BASE + 1>(ks, acc, vhi[I]);
-        static_for<0, ROUNDS_PARTIAL>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int J = decltype(jc)::value;
-            pr_fma<BASE + 2 + 2 * J>(ks, acc, slo[J]);
-            pr_fma<BASE + 2 + 2 * J + 1>(ks, acc, shi[J]);
-        });
-        s[I + 1] = bb::uredc64(acc);  // < p + 2^22
-    });
-    ks.drain();
-}
-
-#else
+#if defined(RK_P2_DIRECT)
 // The partial rounds, one at a time, at three instructions per cell per round.  With S the sum of
 // the cells (after the S-box on cell 0) the layer is y_i = d_i x_i + S.  In Montgomery form
 // (everything times 2^32) and with SM2 = S * 2^32 (mod p) as a plain 32-bit addend,
@@ -412,11 +385,13 @@ static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
 // the product tolerates any 32-bit x (d_i * x + SM2 + q p < 2^64 for x, SM2 < 2^32 - p).  Per round:
 // 17 for the S-box chain of cell 0, 6 to turn the 64-bit sum into SM2 (REDC, then a product by
 // 2^96), 3 x CELLS for the cells and CELLS - 1 to accumulate the next sum: 118 at width 24 against
-// ~144 for the closed form this replaces (all rounds as dot products with constant vectors:
-// ~3.0 k instructions for 21 rounds, kept behind RK_P2_CLOSED_FORM).
-// Entry: any 32-bit representatives scaled by the first block (see permute()); exit: Montgomery
+// ~144 for the closed form of round 1 (every round a dot product with constant vectors).
+// Entry: signed cells |x| <= p/2 + 53 scaled by the first block (see permute()); exit: Montgomery
 // form, canonical.
 static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
+    // + p gives non-negative representatives, which is all the unsigned products below need
+#pragma unroll
+    for (int i = 0; i < CELLS; i++) s[i] += bb::P;
     KStream ks(k.pr_stream);
     // cell 0 feeds an S-box: its true (Montgomery) value, one product by fix[0]
     uint32_t x0 = bb::ucanon(bb::umul_const(s[0], k.fix[0], k.fix0_nq));
@@ -450,17 +425,116 @@ static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
     for (int i = 1; i < CELLS; i++) s[i] = bb::ucanon(s[i]);
     ks.drain();
 }
+#else
+// The partial rounds in blocks of K = PR_BLOCK rounds.  Round r of the layer, with the internal
+// diagonal d:  y = (x_0 + c_r)^7,  S_r = y + sigma_r  (sigma_r = sum_{i >= 1} x_i),  x_0 <- d_0 y + S_r,
+// x_i <- d_i x_i + S_r.  Over a block starting at round a, the cells i >= 1 are a fixed linear map of
+// their values x_i at the start of the block and of the block's sums:
+//     x_i(a + K)   = d_i^K x_i + sum_{m < K} d_i^(K-1-m) S_(a+m)
+//     sigma_(a+j)  = D_j + sum_{m < j} c_(j-1-m) S_(a+m),   D_j = sum_{i >= 1} d_i^j x_i,  c_n = sum_{i >= 1} d_i^n
+// Cell 0 runs explicitly every round (it feeds the S-box); its sums need D_1 .. D_(K-1), dot products
+// over the block's entry values that are accumulated while the previous block writes the cells.  The
+// other cells are written once per block: K products by wave-uniform constants and one signed REDC, the
+// block's last sum riding inside that REDC as the addend SM2 = S * 2^64 mod p.  At width 24, K = 3:
+// 8 instructions per cell per block (3 products, 2 REDC, 1 into the next sum, 2 into the next D)
+// against 12 for three direct rounds.
+//
+// Everything is signed and every constant centred, |c| <= h = (p - 1) / 2; bb::redc64 returns
+// |r| <= |t| / 2^32 + p / 2.  Worst-case bounds for K = 3 (W = 24; W = 16 is below them):
+//   entry cells |x| <= p/2 + 53 (m_ext_redc_s);  block cells |X| <= 0.979 p < 2^31
+//   y = S-box output of x_0 in [0, p) with the offset rc - p: |y| <= 0.934 p
+//   D accumulators: terms |c X| <= 2^60.9, bb::fold64 after every 4th, so |D| < 2^62.9 before a fold,
+//     < 2^58.5 after the last one
+//   sums T_j (64-bit, carry 2^32): |T| < 2^60.5; S_j = REDC(T_j) (plain): |S| <= 1.37 h; |SM2| <= 1.27 h
+//   cell 0 before the canonicalisation: |x_0| <= 0.88 p < p (bb::canon needs (-p, p))
+//   cell update t = c_K X + sum c S + SM2: |t| < 2^61.9
+// (the closed recurrence for |X|: |X'| <= h (|X| + |S_0| + |S_1|) / 2^32 + |SM2| / 2^32 + p/2).
+// Exit: Montgomery form, canonical.
+static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
+    constexpr int NV = CELLS - 1;
+    KStream ks(k.pr_stream);
+    // cell 0 feeds an S-box: its true (Montgomery) value, one product by fix[0] (|.| <= 1.24 h)
+    uint32_t x0 = bb::canon(bb::smul_const((int32_t)s[0], k.pr_fix0, k.pr_fix0_q));
+    // the entry sum: REDC of the raw sum (|.| < 24 p) and one product by fix[0] carry it like y
+    int64_t sig = 0;
+#pragma unroll
+    for (int i = 1; i < CELLS; i++) sig = smadk<1>((int32_t)s[i], sig);
+    sig = smul_sc(bb::redc64(sig), k.pr_fix0);
+    // D_1 .. D_(K-1) of the first block, over the entry cells
+    int64_t D[PR_BLOCK];
+    static_for<1, PR_BLOCK>([&](auto jc) __attribute__((always_inline)) { D[decltype(jc)::value] = 0; });
+    static_for<1, CELLS>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int I = decltype(ic)::value;
+        static_for<1, blk_len(0)>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value;
+            pr_sfma<(I - 1) * (blk_len(0) - 1) + J - 1>(ks, D[J], (int32_t)s[I]);
+            if constexpr (I % 4 == 0 && I < NV) D[J] = bb::fold64(D[J]);
+        });
+    });
+    static_for<0, PR_NB>([&](auto bc) __attribute__((always_inline)) {
+        constexpr int B = decltype(bc)::value;
+        constexpr int K = blk_len(B), KN = blk_next(B), R0 = B * PR_BLOCK;
+        int32_t sp[PR_BLOCK];
+        int64_t sm2 = 0;
+        static_for<0, K>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value;
+            const int32_t y = sbox7_lazy(x0, k.rc_int_mp[R0 + J]);
+            // T = (y + sigma) 2^32 mod p, 64-bit
+            int64_t T;
+            if constexpr (J == 0) {
+                T = smadk<1>(y, sig);
+            } else {
+                T = smadk<1>(y, bb::fold64(D[J]));
+                static_for<0, J>([&](auto mc) __attribute__((always_inline)) {
+                    constexpr int M = decltype(mc)::value;
+                    T = smad_sc(T, sp[M], k.pr_csum[J - 1 - M]);
+                });
+            }
+            sp[J] = bb::redc64(T);  // S, plain
+            if constexpr (J + 1 < K) {
+                x0 = bb::canon(bb::redc64(smad_sc(smul_sc(y, k.pr_d0), sp[J], k.pr_r2)));
+            } else {
+                sm2 = bb::smul_const(sp[J], k.pr_r3, k.pr_r3_q);
+                x0 = bb::canon(bb::redc64(smad_sc(sm2, y, k.pr_d0)));
+            }
+        });
+        // the other cells, the next block's entry sum and its D_j
+        int64_t nsig = 0, nD[PR_BLOCK];
+        static_for<1, KN>([&](auto jc) __attribute__((always_inline)) { nD[decltype(jc)::value] = 0; });
+        static_for<1, CELLS>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int I = decltype(ic)::value;
+            constexpr int POS = blk_off(B) + (I - 1) * (K + KN - 1);
+            int64_t t = sm2;
+            pr_sfma<POS>(ks, t, (int32_t)s[I]);
+            static_for<0, K - 1>([&](auto mc) __attribute__((always_inline)) {
+                constexpr int M = decltype(mc)::value;
+                pr_sfma<POS + 1 + M>(ks, t, sp[M]);
+            });
+            const int32_t v = bb::redc64(t);
+            s[I] = (uint32_t)v;
+            nsig = smadk<1>(v, nsig);
+            static_for<1, KN>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int J = decltype(jc)::value;
+                pr_sfma<POS + K + J - 1>(ks, nD[J], v);
+                if constexpr (I % 4 == 0 && I < NV) nD[J] = bb::fold64(nD[J]);
+            });
+        });
+        sig = nsig;
+        static_for<1, KN>([&](auto jc) __attribute__((always_inline)) { D[decltype(jc)::value] = nD[decltype(jc)::value]; });
+    });
+    s[0] = x0;
+#pragma unroll
+    for (int i = 1; i < CELLS; i++) s[i] = bb::canon((int32_t)s[i]);
+    ks.drain();
+}
 #endif
 
 static RK_HD void permute(uint32_t* s, const Consts& k) {
     m_ext_redc(s);  // canonical Montgomery input -> plain residues (scale 2^0), cells in [0, p + 53)
 #pragma unroll 1
     for (int r = 0; r < ROUNDS_HALF_FULL; r++) full_round(s, k, r);
-    // signed cells (|x| <= p/2 + 53) scaled by 2^(32 * -2800): + p gives non-negative representatives,
-    // which is all partial_rounds() needs (it splits them into halves and owns the scale)
-#pragma unroll
-    for (int i = 0; i < CELLS; i++) s[i] += bb::P;
-    partial_rounds(s, k);  // Montgomery form again, cells in [0, p + 2^22)
+    // signed cells (|x| <= p/2 + 53) scaled by 2^(32 * -2800): partial_rounds() owns the scale
+    partial_rounds(s, k);  // Montgomery form again, canonical
 #pragma unroll 1
     for (int r = ROUNDS_HALF_FULL; r < 2 * ROUNDS_HALF_FULL; r++) full_round(s, k, r);
     // per-cell rescale to Montgomery form + canonical range: cells the caller never reads cost nothing

@@ -6,8 +6,12 @@ the kernel at its two rolled loops (four full rounds each, `#pragma unroll 1` in
 poseidon2_core.hpp) and weights their bodies by the trip count.  The result is the constant
 raiko_amd/segment.py:P2_VALU_PER_PERMUTATION used by bench.py's `roofline.alu`.
 
-  python tools/census_p2.py          (needs hipcc; no GPU)
+  python tools/census_p2.py                       (needs hipcc; no GPU)
+  python tools/census_p2.py -D RK_P2_DIRECT       (the one-round-at-a-time partial rounds)
+  python tools/census_p2.py -D RK_P2_BLOCK=2      (blocks of two partial rounds)
+  python tools/census_p2.py --width 16            (SP1's instance, p2::Core<16, 13, 1>)
 """
+import argparse
 import os
 import re
 import subprocess
@@ -18,10 +22,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-D", dest="defines", action="append", default=[], help="preprocessor definition for the build")
+    ap.add_argument("--width", type=int, choices=(24, 16), default=24)
+    args = ap.parse_args()
+    defs = ["-D" + d for d in args.defines] + (["-DP2_UBENCH_W16"] if args.width == 16 else [])
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, "p2.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "raiko_amd", "csrc"),
-                               os.path.join(ROOT, "tools", "ubench_p2.hip"), "-S", "--cuda-device-only", "-o", asm],
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "raiko_amd", "csrc")] + defs +
+                              [os.path.join(ROOT, "tools", "ubench_p2.hip"), "-S", "--cuda-device-only", "-o", asm],
                               stderr=subprocess.DEVNULL)
         text = open(asm).read()
     start = text.index("_Z6k_perm")
@@ -32,7 +41,7 @@ def main():
     labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
     loops = []
     for i, l in enumerate(lines):
-        m = re.search(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", l)
+        m = re.search(r"s_(?:cbranch_\w+|branch)\s+(\.LBB\d+_\d+)", l)
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             loops.append((labels[m.group(1)], i))
     loops.sort()

@@ -1,7 +1,9 @@
 // Poseidon2 permutation throughput harness: runs p2::permute (the product's shared header) at a
 // chosen residency and prints cycles per wave-permutation per SIMD, so code variants of
 // poseidon2_core.hpp / bb.hpp can be A/B-ed in one gpurun call.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I raiko_amd/csrc [-DP2_...] tools/ubench_p2.hip -o tools/_build/ubench_p2
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I raiko_amd/csrc [-DRK_P2_DIRECT | -DRK_P2_BLOCK=2] [-DP2_UBENCH_W16] \
+//         tools/ubench_p2.hip -o tools/_build/ubench_p2
+// P2_UBENCH_W16 runs SP1's instance p2::Core<16, 13, 1> instead of risc0's width-24 one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,18 +16,25 @@
 #include "poseidon2_consts.inc"
 
 constexpr int P2_ITERS = 32;
+#if defined(P2_UBENCH_W16)
+using Inst = p2::Core<16, 13, 1>;
+#define P2_TAB(name) P2W16_##name
+#else
+using Inst = p2::C24;
+#define P2_TAB(name) P2_##name
+#endif
 
-__global__ __launch_bounds__(256) void k_perm(uint32_t* out, const p2::Consts* __restrict__ kc,
+__global__ __launch_bounds__(256) void k_perm(uint32_t* out, const Inst::Consts* __restrict__ kc,
                                               unsigned long long* stamps) {
-    uint32_t s[p2::CELLS];
+    uint32_t s[Inst::CELLS];
 #pragma unroll
-    for (int i = 0; i < p2::CELLS; i++) s[i] = (threadIdx.x * 977u + i * 131u + blockIdx.x) % bb::P;
+    for (int i = 0; i < Inst::CELLS; i++) s[i] = (threadIdx.x * 977u + i * 131u + blockIdx.x) % bb::P;
     unsigned long long c0 = clock64();
-    for (int it = 0; it < P2_ITERS; it++) p2::permute(s, *kc);
+    for (int it = 0; it < P2_ITERS; it++) Inst::permute(s, *kc);
     unsigned long long c1 = clock64();
     uint32_t acc = 0;
 #pragma unroll
-    for (int i = 0; i < p2::CELLS; i++) acc ^= s[i];
+    for (int i = 0; i < Inst::CELLS; i++) acc ^= s[i];
     out[blockIdx.x * blockDim.x + threadIdx.x] = acc;
     if (threadIdx.x == 0) stamps[blockIdx.x] = c1 - c0;
 }
@@ -39,12 +48,12 @@ int main() {
     hipFuncAttributes fa;
     CK(hipFuncGetAttributes(&fa, (const void*)k_perm));
     printf("k_perm: %d VGPRs, %zu B scratch\n", fa.numRegs, (size_t)fa.localSizeBytes);
-    p2::Consts h;
-    p2::Consts* d;
-    memcpy(h.rc_ext, P2_RC_EXT_MONT, sizeof h.rc_ext);
-    memcpy(h.rc_int, P2_RC_INT_MONT, sizeof h.rc_int);
-    memcpy(h.diag, P2_INT_DIAG_MONT, sizeof h.diag);
-    p2::derive(h);
+    Inst::Consts h;
+    Inst::Consts* d;
+    memcpy(h.rc_ext, P2_TAB(RC_EXT_MONT), sizeof h.rc_ext);
+    memcpy(h.rc_int, P2_TAB(RC_INT_MONT), sizeof h.rc_int);
+    memcpy(h.diag, P2_TAB(INT_DIAG_MONT), sizeof h.diag);
+    Inst::derive(h);
     CK(hipMalloc(&d, sizeof h));
     CK(hipMemcpy(d, &h, sizeof h, hipMemcpyHostToDevice));
     for (int per_cu : {1, 2, 4, 8}) {
