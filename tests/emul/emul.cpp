@@ -223,6 +223,44 @@ void emul_poseidon2_permute_cfg(uint32_t* cells, int width, int m4, const uint32
     k.set(width, m4, false, rc_ext, rc_int, diag);
     k.permute(cells);
 }
+// the raw 32-bit cells partial_rounds() receives for the input `cells`: the first external layer and the four full
+// rounds of the first half, nothing after (signed representatives scaled by the first block, see Core::permute)
+void emul_p2_entry_cells(int width, int m4, const uint32_t* rc_ext, const uint32_t* rc_int, const uint32_t* diag,
+                         uint32_t* cells) {
+    static p2::Any k;
+    k.set(width, m4, false, rc_ext, rc_int, diag);
+    auto run = [&](auto core, const auto& kc) {
+        using C = decltype(core);
+        C::m_ext_redc(cells);
+        for (int r = 0; r < p2::ROUNDS_HALF_FULL; r++) C::full_round(cells, kc, r);
+    };
+    switch (k.kind) {
+        case 0: run(p2::K0{}, k.k0); break;
+        case 1: run(p2::K1{}, k.k1); break;
+        case 2: run(p2::K2{}, k.k2); break;
+        default: run(p2::K3{}, k.k3); break;
+    }
+}
+// the words derive() builds for the partial rounds: pr_stream[0 .. PR_STREAM_USED), then pr_fix0, pr_d0, pr_r2, pr_r3,
+// pr_csum[0..2] (as int32 patterns).  Returns PR_STREAM_USED.
+int emul_p2_derived(int width, int m4, const uint32_t* rc_ext, const uint32_t* rc_int, const uint32_t* diag, uint32_t* out) {
+    static p2::Any k;
+    k.set(width, m4, false, rc_ext, rc_int, diag);
+    auto put = [&](auto core, const auto& kc) {
+        using C = decltype(core);
+        int n = 0;
+        for (; n < C::PR_STREAM_USED; n++) out[n] = kc.pr_stream[n];
+        for (int32_t v : {kc.pr_fix0, kc.pr_d0, kc.pr_r2, kc.pr_r3, kc.pr_csum[0], kc.pr_csum[1], kc.pr_csum[2]})
+            out[n++] = (uint32_t)v;
+        return C::PR_STREAM_USED;
+    };
+    switch (k.kind) {
+        case 0: return put(p2::K0{}, k.k0);
+        case 1: return put(p2::K1{}, k.k1);
+        case 2: return put(p2::K2{}, k.k2);
+        default: return put(p2::K3{}, k.k3);
+    }
+}
 // the extension product / inverse for a caller-chosen W (Montgomery form)
 void emul_ext_mul_w(const uint32_t* a, const uint32_t* b, uint32_t wm, uint32_t* out) {
     bb::Ext x, y;

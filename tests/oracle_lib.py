@@ -25,6 +25,12 @@ def build_oracle(force=False):
     return ORACLE_SO
 
 
+def emul_build_cmd(out, flags=()):
+    """the g++ line of the emulator library; `flags` (-D..., -fsanitize=...) give the variants the tests build elsewhere"""
+    csrc = os.path.join(ROOT, "raiko_amd", "csrc")
+    return ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", *flags, "-I", csrc, "-o", out, os.path.join(EMUL_DIR, "emul.cpp")]
+
+
 def build_emul(force=False):
     csrc = os.path.join(ROOT, "raiko_amd", "csrc")
     srcs = [os.path.join(EMUL_DIR, "emul.cpp")] + [os.path.join(csrc, f) for f in
@@ -33,8 +39,7 @@ def build_emul(force=False):
     if not force and os.path.exists(EMUL_SO) and all(os.path.getmtime(EMUL_SO) >= os.path.getmtime(s) for s in srcs):
         return EMUL_SO
     os.makedirs(os.path.dirname(EMUL_SO), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", csrc, "-o", EMUL_SO, srcs[0]],
-                   check=True, capture_output=True)
+    subprocess.run(emul_build_cmd(EMUL_SO), check=True, capture_output=True)
     return EMUL_SO
 
 
@@ -175,38 +180,47 @@ def oracle():
 def emul():
     global _emul
     if _emul is None:
-        lib = C.CDLL(build_emul())
-        sz, u32, vp = C.c_size_t, C.c_uint32, C.c_void_p
-        lib.emul_ntt_reverse.restype = C.c_int
-        lib.emul_ntt_reverse.argtypes = [vp, sz, sz, C.c_int, C.c_uint, C.c_uint]
-        lib.emul_ntt_forward.restype = C.c_int
-        lib.emul_ntt_forward.argtypes = [vp, vp, sz, sz, C.c_uint, C.c_uint, C.c_uint]
-        lib.emul_poseidon2_permute.restype = None
-        lib.emul_poseidon2_permute.argtypes = [vp]
-        lib.emul_poseidon2_permute_with.restype = None
-        lib.emul_poseidon2_permute_with.argtypes = [vp, vp, vp, vp]
-        lib.emul_poseidon2_permute_cfg.restype = None
-        lib.emul_poseidon2_permute_cfg.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-        lib.emul_ext_mul_w.restype = None
-        lib.emul_ext_mul_w.argtypes = [vp, vp, u32, vp]
-        lib.emul_ext_inv_w.restype = None
-        lib.emul_ext_inv_w.argtypes = [vp, u32, vp]
-        for n in ("emul_mul", "emul_add", "emul_sub"):
-            getattr(lib, n).restype = u32
-            getattr(lib, n).argtypes = [u32, u32]
-        for n in ("emul_inv", "emul_encode", "emul_decode", "emul_pow3"):
-            getattr(lib, n).restype = u32
-            getattr(lib, n).argtypes = [u32]
-        lib.emul_ext_mul.restype = None
-        lib.emul_ext_mul.argtypes = [vp, vp, vp]
-        lib.emul_ext_inv.restype = None
-        lib.emul_ext_inv.argtypes = [vp, vp]
-        lib.emul_perm_entries.restype = None
-        lib.emul_perm_entries.argtypes = [vp, vp, vp, sz, sz, u32, u32, u32, u32, u32]
-        lib.emul_p2_chip_rows.restype = C.c_int
-        lib.emul_p2_chip_rows.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int]
-        _emul = lib
+        _emul = bind_emul(build_emul())
     return _emul
+
+
+def bind_emul(path):
+    """ctypes binding of an emulator library (the default build, or a variant built with emul_build_cmd)"""
+    lib = C.CDLL(path)
+    sz, u32, vp = C.c_size_t, C.c_uint32, C.c_void_p
+    lib.emul_ntt_reverse.restype = C.c_int
+    lib.emul_ntt_reverse.argtypes = [vp, sz, sz, C.c_int, C.c_uint, C.c_uint]
+    lib.emul_ntt_forward.restype = C.c_int
+    lib.emul_ntt_forward.argtypes = [vp, vp, sz, sz, C.c_uint, C.c_uint, C.c_uint]
+    lib.emul_poseidon2_permute.restype = None
+    lib.emul_poseidon2_permute.argtypes = [vp]
+    lib.emul_poseidon2_permute_with.restype = None
+    lib.emul_poseidon2_permute_with.argtypes = [vp, vp, vp, vp]
+    lib.emul_poseidon2_permute_cfg.restype = None
+    lib.emul_poseidon2_permute_cfg.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.emul_ext_mul_w.restype = None
+    lib.emul_ext_mul_w.argtypes = [vp, vp, u32, vp]
+    lib.emul_ext_inv_w.restype = None
+    lib.emul_ext_inv_w.argtypes = [vp, u32, vp]
+    for n in ("emul_mul", "emul_add", "emul_sub"):
+        getattr(lib, n).restype = u32
+        getattr(lib, n).argtypes = [u32, u32]
+    for n in ("emul_inv", "emul_encode", "emul_decode", "emul_pow3"):
+        getattr(lib, n).restype = u32
+        getattr(lib, n).argtypes = [u32]
+    lib.emul_ext_mul.restype = None
+    lib.emul_ext_mul.argtypes = [vp, vp, vp]
+    lib.emul_ext_inv.restype = None
+    lib.emul_ext_inv.argtypes = [vp, vp]
+    lib.emul_perm_entries.restype = None
+    lib.emul_perm_entries.argtypes = [vp, vp, vp, sz, sz, u32, u32, u32, u32, u32]
+    lib.emul_p2_chip_rows.restype = C.c_int
+    lib.emul_p2_chip_rows.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int]
+    lib.emul_p2_entry_cells.restype = None
+    lib.emul_p2_entry_cells.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.emul_p2_derived.restype = C.c_int
+    lib.emul_p2_derived.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
+    return lib
 
 
 # ---- numpy helpers (exact integer arithmetic, independent of both C implementations) ----
