@@ -97,6 +97,10 @@ int rk_set_params(rk_ctx* ctx, const rk_params* params);
 int rk_get_params(rk_ctx* ctx, rk_params* out);    /* pointers in *out refer to the context's own copies */
 
 /* ---- Hal trait operators (risc0-zkp 1.0.1 hal/mod.rs `trait Hal`) ---- */
+/* Alignment: the five entry points below (interpolate, evaluate, zk_shift, expand-into-evaluate, bit reverse) accept
+ * device pointers that are only word (4-byte) aligned, e.g. a slice t[1:] of a tensor: the NTTs then take the
+ * general passes instead of the 2^18 .. 2^22 fused kernels, with the same result.  Entry points that take
+ * extension-element buffers (`_ext` arguments) read them with 16-byte loads and need 16-byte aligned pointers. */
 /* Hal::batch_interpolate_ntt: `count` columns of `size` natural-order evaluations ->
  * bit-reversed coefficients, in place. */
 int rk_batch_interpolate_ntt(rk_ctx* ctx, uint32_t* d_io, size_t size, size_t count);
