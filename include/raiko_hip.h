@@ -567,6 +567,43 @@ int rk_exec_witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint3
 /* the 16 data columns as ONE row-major matrix (2^po2 rows x RK_TRACE_DATA_COLS words) in device memory: the form an
  * on_device rk_p3_table takes (the execution proven as uni-stark shards: raiko_amd/executor.py p3_trace_air) */
 int rk_exec_witness_device_rows(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_rows);
+/* The machine's registers x0..x31 at the start and at the end of executed segment `index` (32 words each). */
+int rk_exec_registers(const rk_exec* ex, uint32_t index, uint32_t* start, uint32_t* end);
+/* The ecall rows of segment `index` (needs record_trace): *n pairs (cycle within the segment, a0 after the call) in
+ * cycle order.  An ecall READ writes a0 outside the trace row (whose rd written flag stays 0); the rv32i chip set treats
+ * every ecall row as a write of x10 with this value.  The executor traps every other word of the SYSTEM opcode (ebreak,
+ * rd != 0, ...), so the rows of word 0x00000073 are all the SYSTEM rows a trace holds.  RK_ERR_CAPACITY with *n set when
+ * more than `capacity` pairs. */
+int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n);
+/* THE RV32I CHIP SET: segment `index` as the five tables of a uni-stark shard whose AIRs constrain the register file
+ * and the integer ALU (raiko_amd/rv32.py builds the same tables in numpy, names every column and writes the AIRs):
+ *   cpu       2^po2 x RK_RV32_CPU_COLS: the 16 data columns above at the same places, the decoded fields, three register
+ *             accesses per row at timestamps 3 row + 1 / 2 / 3 (read rs1, read rs2, write the destination) with their
+ *             previous timestamps, operand / carry / borrow / sign / byte columns of the ALU
+ *   program   program_rows x RK_RV32_PROGRAM_COLS: one row per word of the executed pc range, the fields decoded from
+ *             its 32 bits (which the program AIR proves from those bits) and how often the shard ran it
+ *   register  RK_RV32_REGISTER_ROWS x RK_RV32_REGISTER_COLS: every register's initial value at timestamp 0 and final
+ *             (value, timestamp), bound to the shard's public values by shift registers
+ *   byte      2^RK_RV32_BYTE_LOG_ROWS x RK_RV32_BYTE_COLS: (op, x, y, x op y) for AND / OR / XOR of bytes, with counts
+ *   range     65536 x 2: (v, count) over the 16-bit limbs the cpu rows send
+ * Row-major Montgomery words in device memory, ready to be on_device rk_p3_tables.  Registers follow an offline memory
+ * argument on a REGISTER bus.  CONSTRAINED: the value written by ADD, SUB, ADDI, AND, OR, XOR, ANDI, ORI, XORI, SLT,
+ * SLTU, SLTI, SLTIU, LUI, AUIPC and the link value of JAL / JALR.  FREE: results of shifts, of the M extension and of
+ * loads; branch and jump decisions and targets; memory (a store is two register reads); the a0 an ecall leaves.
+ * Written on the GPU from the executed cycles (28 bytes each) and the ecall side list; the host does no per-cycle work.
+ * Needs record_trace.  rk_exec_rv32_sizes: the program table's rows (a power of two >= 2).  rk_exec_rv32_shard_device
+ * runs on the ctx stream and returns when the tables are complete; RK_ERR_CAPACITY when program_rows is not the size
+ * rk_exec_rv32_sizes gives or the executed pc range is wider than 2^22 words, RK_ERR_INVALID when one pc ran two
+ * different instruction words in the segment. */
+#define RK_RV32_CPU_COLS 68
+#define RK_RV32_PROGRAM_COLS 77
+#define RK_RV32_REGISTER_COLS 131
+#define RK_RV32_REGISTER_ROWS 32
+#define RK_RV32_BYTE_COLS 24
+#define RK_RV32_BYTE_LOG_ROWS 18
+int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows);
+int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                              size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 

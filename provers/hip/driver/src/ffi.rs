@@ -71,6 +71,12 @@ pub const RK_MAX_QUERIES: u32 = 256;
 pub const RK_COMM_ID_BYTES: u32 = 128;
 pub const RK_TRACE_CODE_COLS: u32 = 2;
 pub const RK_TRACE_DATA_COLS: u32 = 16;
+pub const RK_RV32_CPU_COLS: u32 = 68;
+pub const RK_RV32_PROGRAM_COLS: u32 = 77;
+pub const RK_RV32_REGISTER_COLS: u32 = 131;
+pub const RK_RV32_REGISTER_ROWS: u32 = 32;
+pub const RK_RV32_BYTE_COLS: u32 = 24;
+pub const RK_RV32_BYTE_LOG_ROWS: u32 = 18;
 
 #[repr(C)]
 pub struct rk_air {
@@ -443,6 +449,10 @@ extern "C" {
     pub fn rk_exec_lookup_tables(ex: *const rk_exec, index: u32, range_table: *mut u32, program_table: *mut u32, program_rows: *mut usize) -> c_int;
     pub fn rk_exec_witness_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_code: *mut u32, d_data: *mut u32) -> c_int;
     pub fn rk_exec_witness_device_rows(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_rows: *mut u32) -> c_int;
+    pub fn rk_exec_registers(ex: *const rk_exec, index: u32, start: *mut u32, end: *mut u32) -> c_int;
+    pub fn rk_exec_ecalls(ex: *const rk_exec, index: u32, out: *mut u32, capacity: usize, n: *mut usize) -> c_int;
+    pub fn rk_exec_rv32_sizes(ex: *const rk_exec, index: u32, program_rows: *mut usize) -> c_int;
+    pub fn rk_exec_rv32_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;

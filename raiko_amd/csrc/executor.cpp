@@ -12,6 +12,7 @@
 // the journal) and the state digest.  The witness layout of the rv32im circuit is not available
 // either, so a segment here carries its bounds and state digests, not trace columns.
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <map>
 #include <thread>
@@ -108,6 +109,11 @@ struct TraceRow {
 struct rk_exec {
     std::vector<rk_exec_segment> segments;
     std::vector<std::vector<TraceRow>> traces;   // per segment, when rk_exec_opts.record_trace is set
+    std::vector<std::array<uint32_t, 64>> regs;  // per segment: x0..x31 at its start, then at its end
+    // per segment, with record_trace: (cycle, a0 after the call) of every ecall row -- an ecall READ writes a0 outside
+    // TraceRow -- and the lowest / highest pc executed (the rv32i chip set's program table, rk_exec_rv32_*)
+    std::vector<std::vector<std::array<uint32_t, 2>>> ecalls;
+    std::vector<std::array<uint32_t, 2>> pc_range;
     // the machine between segments (rk_exec_open / rk_exec_next_segment run it one segment at a time)
     Machine m;
     std::unique_ptr<p2::Any> k;                  // the default Poseidon2 instance: state digests at the boundaries
@@ -363,6 +369,10 @@ int exec_next(rk_exec* ex, int* more) {
     state_digest(*ex->k, m, seg.pre_state);
     uint64_t cycles = 0;
     std::vector<TraceRow> trace;
+    std::array<uint32_t, 64> regs{};
+    std::copy(m.x, m.x + 32, regs.begin());
+    std::vector<std::array<uint32_t, 2>> ecalls;
+    uint32_t pc_lo = 0xffffffffu, pc_hi = 0;
     if (o.record_trace) trace.reserve((size_t)std::min<uint64_t>(limit, (uint64_t)1 << 22));  // 28 bytes per cycle, no regrowth copies
     while (cycles < limit) {
         if (o.session_limit && ex->total >= o.session_limit) {
@@ -374,7 +384,12 @@ int exec_next(rk_exec* ex, int* more) {
         if (o.profile) ex->pc_cycles[m.pc]++;
         int r = step(m, *ex, o, ex->in_pos, ex->error, o.record_trace ? &row : nullptr);
         if (r < 0) { ex->st = r; break; }
-        if (o.record_trace) trace.push_back(row);
+        if (o.record_trace) {
+            trace.push_back(row);
+            if (row.ins == 0x00000073u) ecalls.push_back({(uint32_t)cycles, m.x[10]});
+            pc_lo = std::min(pc_lo, row.pc);
+            pc_hi = std::max(pc_hi, row.pc);
+        }
         cycles++;
         ex->total++;
         if (r == 1) { ex->halted = true; break; }
@@ -388,7 +403,13 @@ int exec_next(rk_exec* ex, int* more) {
         seg.exit = ex->halted ? RK_EXIT_HALTED : RK_EXIT_SYSTEM_SPLIT;
         state_digest(*ex->k, m, seg.post_state);
         ex->segments.push_back(seg);
-        if (o.record_trace) ex->traces.push_back(std::move(trace));
+        std::copy(m.x, m.x + 32, regs.begin() + 32);
+        ex->regs.push_back(regs);
+        if (o.record_trace) {
+            ex->traces.push_back(std::move(trace));
+            ex->ecalls.push_back(std::move(ecalls));
+            ex->pc_range.push_back({pc_lo, pc_hi});
+        }
         if (ex->segments.size() > (1u << 20)) { ex->error = "more than 2^20 segments"; ex->st = RK_ERR_CAPACITY; }
     }
     refresh_summary(ex);
@@ -653,6 +674,538 @@ const char* rk_exec_error(const rk_exec* ex) { return ex ? ex->error.c_str() : "
 int rk_exec_free(rk_exec* ex) {
     delete ex;
     return RK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The rv32i chip set (include/raiko_hip.h rk_exec_rv32_shard_device; raiko_amd/rv32.py is the same in numpy and names
+// every column).  Per segment on the GPU: prep (decode, recompute the written value, pack the three accesses, count
+// program hits) -> block_last (last access per register per 128 rows) -> scan (exclusive max-scan of those 32-vectors)
+// -> rows (in-block resolve of each access's predecessor, the cpu row staged through LDS, RANGE16 / BYTE counts) ->
+// the program, register, byte and range tables.
+namespace rv32 {
+
+constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS)
+constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_W = RK_RV32_REGISTER_COLS,
+                   BYTE_W = RK_RV32_BYTE_COLS;
+enum : unsigned {
+    PC_LO, PC_HI, NX_LO, NX_HI, INS_LO, INS_HI, SEQ, CARRY, A_LO, A_HI, B_LO, B_HI, RES_LO, RES_HI, WR, ACTIVE,
+    RS1, RS2, WREG, IMM_LO, IMM_HI, IS_ADD, IS_SUB, IS_SLT, IS_SLTU, IS_BIT, BOP, IS_IMM, IS_LUI, IS_AUIPC, IS_LINK,
+    TSA, TSB, TSW, PA_TS, PB_TS, PW_TS, PW_LO, PW_HI, DA_LO, DA_HI, DB_LO, DB_HI, DW_LO, DW_HI,
+    OB_LO, OB_HI, C0, C1, D_LO, D_HI, SA, SB, SNE, SA_CHK, SB_CHK, BA, BB = BA + 4, BR = BB + 4
+};
+constexpr uint32_t OPCODES[11] = {0x37, 0x17, 0x6f, 0x67, 0x63, 0x03, 0x23, 0x13, 0x33, 0x0f, 0x73};
+enum { O_LUI, O_AUIPC, O_JAL, O_JALR, O_BRANCH, O_LOAD, O_STORE, O_OPIMM, O_OP, O_FENCE, O_SYSTEM };
+
+struct Dec {
+    int opc;   // index into OPCODES, -1 for none
+    uint32_t f3, rd, rs1, rs2, wreg, imm, opr, is_add, is_sub, is_slt, is_sltu, is_bit, bop, is_imm, is_lui, is_auipc,
+        is_link, wr;
+};
+
+__host__ __device__ inline Dec decode(uint32_t ins) {
+    Dec d{};
+    d.opc = -1;
+    for (int k = 0; k < 11; k++)
+        if ((ins & 0x7fu) == OPCODES[k]) d.opc = k;
+    d.f3 = (ins >> 12) & 7;
+    d.rd = (ins >> 7) & 31;
+    d.rs1 = (ins >> 15) & 31;
+    d.rs2 = (ins >> 20) & 31;
+    const uint32_t b25 = (ins >> 25) & 1, b30 = (ins >> 30) & 1;
+    d.opr = d.opc == O_OP && !b25;
+    const uint32_t opimm = d.opc == O_OPIMM, alu = d.opr | opimm;
+    d.is_add = (d.f3 == 0) && ((d.opr && !b30) || opimm);
+    d.is_sub = d.opr && d.f3 == 0 && b30;
+    d.is_slt = alu && d.f3 == 2;
+    d.is_sltu = alu && d.f3 == 3;
+    d.is_bit = alu && (d.f3 == 4 || d.f3 == 6 || d.f3 == 7);
+    d.bop = !alu ? 0 : d.f3 == 4 ? 3 : d.f3 == 6 ? 2 : d.f3 == 7 ? 1 : 0;
+    d.is_imm = opimm;
+    d.is_lui = d.opc == O_LUI;
+    d.is_auipc = d.opc == O_AUIPC;
+    d.is_link = d.opc == O_JAL || d.opc == O_JALR;
+    if (opimm || d.opc == O_LOAD || d.opc == O_JALR) d.imm = (uint32_t)((int32_t)ins >> 20);
+    else if (d.is_lui || d.is_auipc) d.imm = ins & 0xfffff000u;
+    const bool writes = d.is_lui || d.is_auipc || d.is_link || d.opc == O_LOAD || opimm || d.opc == O_OP;
+    d.wr = (writes && d.rd != 0) || d.opc == O_SYSTEM;
+    d.wreg = d.rd + (d.opc == O_SYSTEM ? 10u : 0u);
+    return d;
+}
+
+// the value a row writes: recomputed for the constrained ops, the side list's for an ecall, TraceRow.res otherwise
+__device__ inline uint32_t written(const Dec& d, const TraceRow& r, uint32_t ecall_a0) {
+    const uint32_t a = r.a, ob = d.is_imm ? d.imm : r.b;
+    if (d.is_add) return a + ob;
+    if (d.is_sub) return a - ob;
+    if (d.is_sltu) return a < ob;
+    if (d.is_slt) return (int32_t)a < (int32_t)ob;
+    if (d.is_bit) return d.f3 == 4 ? a ^ ob : d.f3 == 6 ? a | ob : a & ob;
+    if (d.is_lui) return d.imm;
+    if (d.is_auipc) return r.pc + d.imm;
+    if (d.is_link) return r.pc + 4;
+    if (d.opc == O_SYSTEM) return ecall_a0;
+    return r.res;
+}
+
+__device__ inline uint32_t enc(uint32_t canon) { return bb::mul(canon, bb::R2); }
+
+// a histogram bin += 1 for every lane with `on`; the lanes of a wave that agree with its first active lane add once
+__device__ inline void hist_add(uint32_t* h, uint32_t v, bool on) {
+    const uint64_t act = __ballot(on);
+    if (!act) return;
+    const int first = __ffsll((unsigned long long)act) - 1;
+    const uint32_t lv = __shfl(v, first);
+    const uint64_t same = __ballot(on && v == lv);
+    if ((int)(threadIdx.x & 63) == first) atomicAdd(&h[lv], (uint32_t)__popcll(same));
+    else if (on && v != lv) atomicAdd(&h[v], 1u);
+}
+
+// the row a cpu lane writes row-major: staged in LDS (odd stride: no bank conflicts), then whole lines to HBM
+template <unsigned W>
+__device__ inline void flush_rows(uint32_t* out, const uint32_t* s, size_t r0, size_t n_rows) {
+    constexpr unsigned SW = W | 1;
+    const size_t rows = n_rows - r0 < blockDim.x ? n_rows - r0 : blockDim.x;
+    for (size_t k = threadIdx.x; k < rows * W; k += blockDim.x) out[r0 * W + k] = s[(k / W) * SW + k % W];
+}
+
+__global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
+                            uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
+                            uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
+                            uint32_t* __restrict__ err) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i >= cycles) {
+        wval[i] = 0;
+        acc[i] = 0;
+        return;
+    }
+    const TraceRow r = tr[i];
+    const Dec d = decode(r.ins);
+    uint32_t a0 = 0;
+    if (d.opc == O_SYSTEM) {   // the side list is in cycle order: binary search
+        uint32_t lo = 0, hi = n_ecalls;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (ecalls[2 * mid] < i) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < n_ecalls && ecalls[2 * lo] == i) a0 = ecalls[2 * lo + 1];
+        else atomicOr(err, 2u);
+    }
+    wval[i] = written(d, r, a0);
+    acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16;
+    const uint32_t slot = (r.pc - pc_base) >> 2;
+    if (slot >= n_slots) {
+        atomicOr(err, 4u);
+        return;
+    }
+    atomicAdd(&prog_mult[slot], 1u);
+    const uint32_t old = atomicCAS(&prog_ins[slot], 0u, r.ins);
+    if (old != 0 && old != r.ins) atomicOr(err, 1u);    // one pc, two instruction words in one shard
+}
+
+__device__ inline void unpack(uint32_t v, uint32_t& rs1, uint32_t& rs2, uint32_t& wreg, bool& wr, bool& active) {
+    rs1 = v & 31;
+    rs2 = (v >> 5) & 31;
+    wreg = (v >> 10) & 31;
+    wr = (v >> 15) & 1;
+    active = (v >> 16) & 1;
+}
+
+__global__ void block_last_kernel(const uint32_t* __restrict__ acc, uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s[32];
+    if (threadIdx.x < 32) s[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    uint32_t rs1, rs2, wreg;
+    bool wr, active;
+    unpack(acc[i], rs1, rs2, wreg, wr, active);
+    if (active) {
+        const uint32_t tsa = (uint32_t)(3 * i + 1);
+        atomicMax(&s[rs1], tsa);
+        atomicMax(&s[rs2], tsa + 1);
+        if (wr) atomicMax(&s[wreg], tsa + 2);
+    }
+    __syncthreads();
+    if (threadIdx.x < 32) blk[(size_t)blockIdx.x * 32 + threadIdx.x] = s[threadIdx.x];
+}
+
+// one workgroup of 1024: lane = register (t & 31) x chunk of blocks (t >> 5); blk becomes its exclusive prefix max
+__global__ void scan_kernel(uint32_t* __restrict__ blk, size_t nb, uint32_t* __restrict__ final_ts) {
+    __shared__ uint32_t cm[32][32];
+    const unsigned r = threadIdx.x & 31, c = threadIdx.x >> 5;
+    const size_t j0 = nb * c / 32, j1 = nb * (c + 1) / 32;
+    uint32_t m = 0;
+    for (size_t j = j0; j < j1; j++) m = max(m, blk[j * 32 + r]);
+    cm[c][r] = m;
+    __syncthreads();
+    uint32_t run = 0;
+    for (unsigned k = 0; k < c; k++) run = max(run, cm[k][r]);
+    for (size_t j = j0; j < j1; j++) {
+        const uint32_t v = blk[j * 32 + r];
+        blk[j * 32 + r] = run;
+        run = max(run, v);
+    }
+    if (c == 31) final_ts[r] = run;
+}
+
+__device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* tr, const uint32_t* wval, const uint32_t* init) {
+    if (ts == 0) return init[reg];
+    const uint32_t j = (ts - 1) / 3, k = (ts - 1) % 3;
+    return k == 0 ? tr[j].a : k == 1 ? tr[j].b : wval[j];
+}
+
+__global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ tr, size_t cycles, uint32_t end_pc,
+                                                   const uint32_t* __restrict__ acc, const uint32_t* __restrict__ wval,
+                                                   const uint32_t* __restrict__ pre, const uint32_t* __restrict__ init,
+                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ hist,
+                                                   uint32_t* __restrict__ byte_mult, size_t n) {
+    extern __shared__ uint32_t s_rows[];            // TB x (CPU_W | 1)
+    __shared__ uint32_t s_wave[32][TB / 64];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t rs1, rs2, wreg;
+    bool wr, active;
+    unpack(acc[i], rs1, rs2, wreg, wr, active);
+    const uint32_t tsa = (uint32_t)(3 * i + 1);
+    // per register: the latest access among this wave's rows up to this one (inclusive max-scan over the lanes)
+    uint32_t incl[32];
+#pragma unroll
+    for (unsigned r = 0; r < 32; r++) {
+        uint32_t v = 0;
+        if (active) {
+            if (rs1 == r) v = tsa;
+            if (rs2 == r) v = tsa + 1;
+            if (wr && wreg == r) v = tsa + 2;
+        }
+#pragma unroll
+        for (unsigned off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(v, off);
+            if (lane >= off) v = max(v, t);
+        }
+        incl[r] = v;
+        if (lane == 63) s_wave[r][wave] = v;
+    }
+    __syncthreads();
+    uint32_t e1 = 0, e2 = 0, e3 = 0;
+#pragma unroll
+    for (unsigned r = 0; r < 32; r++) {
+        uint32_t ex = __shfl_up(incl[r], 1);
+        if (lane == 0) ex = 0;
+        for (unsigned w = 0; w < wave; w++) ex = max(ex, s_wave[r][w]);
+        ex = max(ex, pre[(size_t)blockIdx.x * 32 + r]);
+        if (rs1 == r) e1 = ex;
+        if (rs2 == r) e2 = ex;
+        if (wreg == r) e3 = ex;
+    }
+    uint32_t* row = s_rows + threadIdx.x * (CPU_W | 1);
+    for (unsigned c = 0; c < CPU_W; c++) row[c] = 0;
+    uint32_t res = 0, bop = 0, ba = 0, bb_ = 0, pa = 0, pb = 0, pw = 0, sa = 0, sb = 0, is_slt = 0, d_lo = 0, d_hi = 0;
+    if (active) {
+        const TraceRow r = tr[i];
+        const Dec d = decode(r.ins);
+        res = wval[i];
+        pa = e1;
+        pb = rs2 == rs1 ? tsa : e2;
+        pw = wr ? (wreg == rs2 ? tsa + 1 : wreg == rs1 ? tsa : e3) : 0;
+        const uint32_t pwv = wr ? value_at(pw, wreg, tr, wval, init) : 0;
+        const uint32_t ob = d.is_imm ? d.imm : r.b;
+        const uint32_t seq = (r.next == r.pc + 4 && r.pc <= 0xfffffffbu) ? 1u : 0u;
+        const uint32_t carry = ((r.pc & 0xffffu) + 4 > 0xffffu) ? 1u : 0u;
+        const bool sublt = d.is_sub || d.is_slt || d.is_sltu;
+        const uint32_t dd = sublt ? r.a - ob : 0;
+        uint32_t x = 0, y = 0;
+        if (d.is_add) x = r.a, y = ob;
+        else if (d.is_auipc) x = r.pc, y = d.imm;
+        else if (d.is_link) x = r.pc, y = 4;
+        else if (sublt) x = dd, y = ob;
+        const uint32_t c0 = ((x & 0xffffu) + (y & 0xffffu)) >> 16, c1 = ((x >> 16) + (y >> 16) + c0) >> 16;
+        sa = r.a >> 31;
+        sb = ob >> 31;
+        is_slt = d.is_slt;
+        d_lo = dd & 0xffffu;
+        d_hi = dd >> 16;
+        const uint32_t da = tsa - pa - 1, db = tsa + 1 - pb - 1, dw = wr ? tsa + 2 - pw - 1 : 0;
+        const uint32_t vals[][2] = {
+            {PC_LO, r.pc & 0xffffu}, {PC_HI, r.pc >> 16}, {NX_LO, r.next & 0xffffu}, {NX_HI, r.next >> 16},
+            {INS_LO, r.ins & 0xffffu}, {INS_HI, r.ins >> 16}, {SEQ, seq}, {CARRY, seq & carry},
+            {A_LO, r.a & 0xffffu}, {A_HI, r.a >> 16}, {B_LO, r.b & 0xffffu}, {B_HI, r.b >> 16},
+            {RES_LO, res & 0xffffu}, {RES_HI, res >> 16}, {WR, d.wr}, {ACTIVE, 1},
+            {RS1, d.rs1}, {RS2, d.rs2}, {WREG, d.wreg}, {IMM_LO, d.imm & 0xffffu}, {IMM_HI, d.imm >> 16},
+            {IS_ADD, d.is_add}, {IS_SUB, d.is_sub}, {IS_SLT, d.is_slt}, {IS_SLTU, d.is_sltu}, {IS_BIT, d.is_bit},
+            {BOP, d.bop}, {IS_IMM, d.is_imm}, {IS_LUI, d.is_lui}, {IS_AUIPC, d.is_auipc}, {IS_LINK, d.is_link},
+            {PA_TS, pa}, {PB_TS, pb}, {PW_TS, pw}, {PW_LO, pwv & 0xffffu}, {PW_HI, pwv >> 16},
+            {DA_LO, da & 0x3fffu}, {DA_HI, da >> 14}, {DB_LO, db & 0x3fffu}, {DB_HI, db >> 14},
+            {DW_LO, dw & 0x3fffu}, {DW_HI, dw >> 14}, {OB_LO, ob & 0xffffu}, {OB_HI, ob >> 16}, {C0, c0}, {C1, c1},
+            {D_LO, d_lo}, {D_HI, d_hi}, {SA, sa}, {SB, sb}, {SNE, sa ^ sb},
+            {SA_CHK, 2 * (r.a >> 16) - 65536 * sa}, {SB_CHK, 2 * (ob >> 16) - 65536 * sb}};
+        for (const auto& kv : vals) row[kv[0]] = kv[1];
+        if (d.is_bit) {
+            bop = d.bop;
+            ba = r.a;
+            bb_ = ob;
+            for (unsigned k = 0; k < 4; k++) {
+                row[BA + k] = (r.a >> (8 * k)) & 255;
+                row[BB + k] = (ob >> (8 * k)) & 255;
+                row[BR + k] = (res >> (8 * k)) & 255;
+            }
+        }
+    } else {
+        row[PC_LO] = row[NX_LO] = end_pc & 0xffffu;
+        row[PC_HI] = row[NX_HI] = end_pc >> 16;
+    }
+    row[TSA] = tsa;
+    row[TSB] = tsa + 1;
+    row[TSW] = tsa + 2;
+    // RANGE16: the limbs the row sends (rv32.py RANGE_SENDS), BYTE: four triples of a bitwise row
+    const unsigned rc[] = {PC_LO, PC_HI, NX_LO, NX_HI, RES_LO, RES_HI, D_LO, D_HI, DA_LO, DA_HI, DB_LO, DB_HI};
+    for (unsigned c : rc) hist_add(hist, row[c], active);
+    hist_add(hist, row[DW_LO], wr);
+    hist_add(hist, row[DW_HI], wr);
+    hist_add(hist, row[SA_CHK], is_slt);
+    hist_add(hist, row[SB_CHK], is_slt);
+    if (bop)
+        for (unsigned k = 0; k < 4; k++)
+            atomicAdd(&byte_mult[(bop - 1) << 16 | ((ba >> (8 * k)) & 255) << 8 | ((bb_ >> (8 * k)) & 255)], 1u);
+    for (unsigned c = 0; c < CPU_W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    flush_rows<CPU_W>(out, s_rows, (size_t)blockIdx.x * TB, n);
+}
+
+__global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint32_t* __restrict__ prog_mult,
+                               uint32_t n_slots, uint32_t pc_base, size_t n_rows, uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t* row = s_rows + threadIdx.x * (PROG_W | 1);
+    for (unsigned c = 0; c < PROG_W; c++) row[c] = 0;
+    if (s < n_rows) {   // past the executed range: the row of word 0 at pc 0, multiplicity 0
+        const bool in = s < n_slots;
+        const uint32_t pc = in ? pc_base + 4 * (uint32_t)s : 0u, ins = in ? prog_ins[s] : 0u;
+        const Dec d = decode(ins);
+        const uint32_t v[20] = {pc & 0xffffu, pc >> 16, ins & 0xffffu, ins >> 16, d.rs1, d.rs2, d.wreg, d.imm & 0xffffu,
+                                d.imm >> 16, d.is_add, d.is_sub, d.is_slt, d.is_sltu, d.is_bit, d.bop, d.is_imm,
+                                d.is_lui, d.is_auipc, d.is_link, d.wr};
+        for (unsigned c = 0; c < 20; c++) row[c] = v[c];
+        row[20] = in ? prog_mult[s] : 0u;
+        for (unsigned k = 0; k < 32; k++) row[21 + k] = (ins >> k) & 1;
+        if (d.opc >= 0) {
+            row[53 + d.opc] = 1;
+            row[64 + d.f3] = 1;
+        }
+        const uint32_t b = ins >> 7;
+        const uint32_t z1 = (~b & 1) & (~b >> 1 & 1), z2 = z1 & (~b >> 2 & 1), rdz = z2 & (~b >> 3 & 1) & (~b >> 4 & 1);
+        row[72] = d.opr;
+        row[73] = z1;
+        row[74] = z2;
+        row[75] = rdz;
+        row[76] = d.rd;
+    }
+    for (unsigned c = 0; c < PROG_W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    flush_rows<PROG_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, n_rows);
+}
+
+__global__ void byte_kernel(const uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t* row = s_rows + threadIdx.x * (BYTE_W | 1);
+    for (unsigned c = 0; c < BYTE_W; c++) row[c] = 0;
+    if (r < (3u << 16)) {
+        const uint32_t op = (uint32_t)(r >> 16) + 1, x = (r >> 8) & 255, y = r & 255;
+        row[0] = op;
+        row[1] = x;
+        row[2] = y;
+        row[3] = op == 1 ? (x & y) : op == 2 ? (x | y) : (x ^ y);
+        for (unsigned k = 0; k < 8; k++) {
+            row[4 + k] = (x >> k) & 1;
+            row[12 + k] = (y >> k) & 1;
+        }
+        row[19 + op] = 1;
+        row[23] = byte_mult[r];
+    }
+    for (unsigned c = 0; c < BYTE_W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    flush_rows<BYTE_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32_BYTE_LOG_ROWS);
+}
+
+__global__ void range_kernel(const uint32_t* __restrict__ hist, uint32_t* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= (1u << 16)) return;
+    out[2 * v] = enc(v);
+    out[2 * v + 1] = enc(hist[v]);
+}
+
+// 32 lanes: the register table (rv32.py register_rows); fin gets the final values
+__global__ void register_kernel(const uint32_t* __restrict__ final_ts, const uint32_t* __restrict__ init,
+                                const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval,
+                                uint32_t* __restrict__ fin, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_fin[32];
+    extern __shared__ uint32_t s_rows[];
+    const unsigned r = threadIdx.x;
+    s_fin[r] = value_at(final_ts[r], r, tr, wval, init);
+    fin[r] = s_fin[r];
+    __syncthreads();
+    uint32_t* row = s_rows + r * (REG_W | 1);
+    row[0] = r;
+    row[1] = 0;
+    row[2] = final_ts[r];
+    for (unsigned j = 0; j < 32; j++) {
+        const bool in = r + j < 32;
+        row[3 + j] = in ? init[r + j] & 0xffffu : 0;
+        row[35 + j] = in ? init[r + j] >> 16 : 0;
+        row[67 + j] = in ? s_fin[r + j] & 0xffffu : 0;
+        row[99 + j] = in ? s_fin[r + j] >> 16 : 0;
+    }
+    for (unsigned c = 0; c < REG_W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    flush_rows<REG_W>(out, s_rows, 0, 32);
+}
+
+}  // namespace rv32
+
+static size_t rv32_program_rows(const rk_exec* ex, uint32_t index, uint32_t* n_slots) {
+    const auto& pr = ex->pc_range[index];
+    const uint32_t slots = ex->traces[index].empty() ? 0 : (pr[1] - pr[0]) / 4 + 1;
+    size_t rows = 2;
+    while (rows < slots) rows <<= 1;
+    if (n_slots) *n_slots = slots;
+    return rows;
+}
+
+static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                             size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range) {
+    using namespace rv32;
+    if (!ctx || !ex || !d_cpu || !d_program || !d_register || !d_byte || !d_range || index >= ex->segments.size() ||
+        index >= ex->traces.size())
+        return RK_ERR_INVALID;
+    const rk_exec_segment& seg = ex->segments[index];
+    const std::vector<TraceRow>& tr = ex->traces[index];
+    const auto& ec = ex->ecalls[index];
+    const size_t n = (size_t)1 << seg.po2, nb = n / TB;
+    if (tr.size() != seg.cycles || tr.size() > n || n % TB) return RK_ERR_INTERNAL;
+    uint32_t n_slots = 0;
+    if (rv32_program_rows(ex, index, &n_slots) != program_rows) return RK_ERR_CAPACITY;
+    if (n_slots > (1u << 22)) {
+        ctx->last_error = "rk_exec_rv32_shard_device: executed pc range wider than 2^22 words";
+        return RK_ERR_CAPACITY;
+    }
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // scratch, in one allocation: trace | ecalls | wval | acc | blk | final_ts | fin | init | err | hist | byte | prog mult / ins
+    const size_t w_tr = (std::max<size_t>(tr.size(), 1) * sizeof(TraceRow) + 3) / 4, w_ec = 2 * std::max<size_t>(ec.size(), 1);
+    size_t off[13], at = 0;
+    const size_t words[13] = {w_tr, w_ec, n, n, nb * 32, 32, 32, 32, 1, (size_t)1 << 16, (size_t)3 << 16,
+                              std::max<uint32_t>(n_slots, 1), std::max<uint32_t>(n_slots, 1)};
+    for (int k = 0; k < 13; k++) off[k] = at, at += (words[k] + 63) & ~(size_t)63;
+    void* base = nullptr;
+    RK_TRY(rk::dev_alloc(ctx, at * 4, &base));
+    uint32_t* w = (uint32_t*)base;
+    const TraceRow* d_tr = (const TraceRow*)(w + off[0]);
+    uint32_t *d_ec = w + off[1], *wval = w + off[2], *acc = w + off[3], *blk = w + off[4], *final_ts = w + off[5],
+             *fin = w + off[6], *init = w + off[7], *err = w + off[8], *hist = w + off[9], *bmult = w + off[10],
+             *pmult = w + off[11], *pins = w + off[12];
+    std::vector<uint32_t> ec_flat(2 * ec.size());
+    for (size_t k = 0; k < ec.size(); k++) ec_flat[2 * k] = ec[k][0], ec_flat[2 * k + 1] = ec[k][1];
+    uint32_t host_fin[33] = {0};
+    int st = RK_OK;
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && st == RK_OK) {
+            ctx->last_error = std::string("rk_exec_rv32_shard_device ") + what + ": " + hipGetErrorString(e);
+            st = RK_ERR_HIP;
+        }
+    };
+    auto launched = [&](const char* what) {
+        if (st == RK_OK) st = rk::post_launch(ctx, what);
+    };
+    if (!tr.empty()) hip(hipMemcpyAsync((void*)d_tr, tr.data(), tr.size() * sizeof(TraceRow), hipMemcpyHostToDevice, ctx->stream), "h2d");
+    if (!ec.empty()) hip(hipMemcpyAsync(d_ec, ec_flat.data(), ec_flat.size() * 4, hipMemcpyHostToDevice, ctx->stream), "h2d");
+    hip(hipMemcpyAsync(init, ex->regs[index].data(), 32 * 4, hipMemcpyHostToDevice, ctx->stream), "h2d");
+    hip(hipMemsetAsync(err, 0, (off[12] + words[12] - off[8]) * 4, ctx->stream), "memset");   // err .. prog ins
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, d_ec,
+                           (uint32_t)ec.size(), ex->pc_range[index][0], n_slots, wval, acc, pmult, pins, err);
+        launched("rv32 prep_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(block_last_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, acc, blk);
+        launched("rv32 block_last_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, final_ts);
+        launched("rv32 scan_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(rows_kernel, dim3((unsigned)nb), dim3(TB), TB * (CPU_W | 1) * 4, ctx->stream, d_tr, tr.size(),
+                           seg.end_pc, acc, wval, blk, init, d_cpu, hist, bmult, n);
+        launched("rv32 rows_kernel");
+    }
+    if (st == RK_OK) {
+        const unsigned b = (unsigned)std::min<size_t>(program_rows, TB);
+        hipLaunchKernelGGL(program_kernel, dim3((unsigned)((program_rows + b - 1) / b)), dim3(b), b * (PROG_W | 1) * 4,
+                           ctx->stream, pins, pmult, n_slots, ex->pc_range[index][0], program_rows, d_program);
+        launched("rv32 program_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(byte_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4,
+                           ctx->stream, bmult, d_byte);
+        launched("rv32 byte_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(range_kernel, dim3((1u << 16) / TB), dim3(TB), 0, ctx->stream, hist, d_range);
+        launched("rv32 range_kernel");
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(register_kernel, dim3(1), dim3(32), 32 * (REG_W | 1) * 4, ctx->stream, final_ts, init, d_tr,
+                           wval, fin, d_register);
+        launched("rv32 register_kernel");
+    }
+    // the tables are complete and the scratch can go: read back the final registers and the error flags
+    hip(hipMemcpyAsync(host_fin, fin, 32 * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    hip(hipMemcpyAsync(host_fin + 32, err, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    hip(hipStreamSynchronize(ctx->stream), "sync");
+    rk::dev_free(ctx, base);
+    if (st != RK_OK) return st;
+    if (host_fin[32]) {
+        ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
+                                           : "rk_exec_rv32_shard_device: trace and side list disagree";
+        return RK_ERR_INVALID;
+    }
+    if (!std::equal(host_fin, host_fin + 32, ex->regs[index].begin() + 32)) {
+        ctx->last_error = "rk_exec_rv32_shard_device: the register accesses do not end in the executor's registers";
+        return RK_ERR_INTERNAL;
+    }
+    return RK_OK;
+}
+
+extern "C" {
+
+int rk_exec_registers(const rk_exec* ex, uint32_t index, uint32_t* start, uint32_t* end) {
+    if (!ex || !start || !end || index >= ex->regs.size()) return RK_ERR_INVALID;
+    std::copy(ex->regs[index].begin(), ex->regs[index].begin() + 32, start);
+    std::copy(ex->regs[index].begin() + 32, ex->regs[index].end(), end);
+    return RK_OK;
+}
+int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n) {
+    if (!ex || !n || index >= ex->ecalls.size()) return RK_ERR_INVALID;
+    const auto& ec = ex->ecalls[index];
+    *n = ec.size();
+    if (ec.size() > capacity || (!out && !ec.empty())) return RK_ERR_CAPACITY;
+    for (size_t k = 0; k < ec.size(); k++) out[2 * k] = ec[k][0], out[2 * k + 1] = ec[k][1];
+    return RK_OK;
+}
+int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows) {
+    RK_GUARD_BEGIN
+    if (!ex || !program_rows || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
+    *program_rows = rv32_program_rows(ex, index, nullptr);
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                              size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range) {
+    RK_GUARD_BEGIN
+    return rv32_shard_device(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range);
+    RK_GUARD_END
 }
 
 }  // extern "C"

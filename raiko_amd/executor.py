@@ -48,6 +48,9 @@ class Execution:
     # with record_trace: per segment (program table (rows, 5), range table (65536, 2)), row-major Montgomery words
     # (rk_exec_lookup_tables): what p3_shards(lookups=True) puts beside the cpu table
     lookup_tables: Optional[list] = None
+    # with record_trace: per segment (registers at its start (32,), at its end (32,), ecall rows (k, 2): cycle, a0 after)
+    # (rk_exec_registers / rk_exec_ecalls): the side data of the rv32i chip set (p3_rv32_shards)
+    rv32: Optional[list] = None
 
 
 class ExecutorError(RuntimeError):
@@ -106,6 +109,7 @@ def execute(elf: bytes, input_words: Sequence[int] = (), segment_limit_po2: int 
                 prog = np.zeros((rows.value, 5), dtype=np.uint32)
                 _lib.check(None, lib.rk_exec_lookup_tables(handle, sg.index, rng.ctypes.data_as(_lib.u32p), prog.ctypes.data_as(_lib.u32p), C.byref(rows)))
                 ex.lookup_tables.append((prog, rng))
+            ex.rv32 = [_rv32_side(lib, handle, sg.index) for sg in segs]
         if profile:
             cnt = C.c_size_t(0)
             lib.rk_exec_profile(handle, None, None, 0, C.byref(cnt))
@@ -205,6 +209,24 @@ class Stepper:
         hal.sync()       # the rows are complete before another context's stream reads them
         self.n += 1
         return seg, rows, prog, rng
+
+    def next_rv32_shard(self, hal, airs):
+        """the next executed segment as the five tables of an rv32i shard written on hal's GPU (rv32_shard_device) ->
+        (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words), or None after
+        the last"""
+        if not self.more:
+            return None
+        more = C.c_int(0)
+        st = self._lib.rk_exec_next_segment(self._h, C.byref(more))
+        if st != 0:
+            raise ExecutorError("%s: %s" % (self._lib.rk_strerror(st).decode(), self._lib.rk_exec_error(self._h).decode()))
+        self.more = bool(more.value)
+        s = RkExecSegment()
+        self._lib.rk_exec_segment_get(self._h, self.n, C.byref(s))
+        seg = ExecSegment(s.index, s.po2, int(s.cycles), s.start_pc, s.end_pc, s.exit, tuple(s.pre_state), tuple(s.post_state))
+        tables, bufs, init = rv32_shard_device(hal, self._h, self.n, seg, airs)
+        self.n += 1
+        return seg, tables, bufs, init
 
     def finish(self) -> Execution:
         summ = RkExecSummary()
@@ -417,20 +439,25 @@ class P3Pipeline:
     (rk_exec_witness_device_rows: the trace never exists on the host) and builds its lookup tables; a second thread proves
     the shards as they arrive (rk_p3_prove on its own context, the cpu table an on_device input); a small pool verifies
     the proofs (rk_p3_verify is host code).  The contexts and the (compiled) AIRs live as long as the object: run() any
-    number of programs, then close()."""
+    number of programs, then close().  chips="rv32i": every shard's five tables of the rv32i chip set are written on the
+    GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run by
+    check_rv32_chain."""
 
-    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True):
+    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace"):
         from . import p3
         from .hal import HipHal, make_params
+        if chips not in CHIPS:
+            raise ValueError("chips must be one of %s" % (CHIPS,))
         self.params = params if params is not None else make_params(1)
-        self.lookups = lookups
+        self.lookups, self.chips = lookups, chips
         ext_w = int(self.params.ext_w)
+        self.rv32_airs = p3_rv32_airs(ext_w) if chips == "rv32i" else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
         _lib.check(self.prove_hal._ctx, self.prove_hal._lib.rk_set_params(self.prove_hal._ctx, C.byref(self.params)))
         if compile_airs:
-            for a in (self.cpu_air, self.prog_air, self.range_air):
+            for a in self.rv32_airs or (self.cpu_air, self.prog_air, self.range_air):
                 if a is not None:
                     a.compile(self.prove_hal)
 
@@ -450,9 +477,9 @@ class P3Pipeline:
         mont = lambda v: (int(v) << 32) % P
         todo = queue.Queue(maxsize=3)           # back-pressure: at most three shards' tables wait for the prover
         done = queue.Queue()                    # cpu tables the prover is through with: freed by the thread that owns their context
-        proofs, checks, kept, errors = [], [], [], []
+        proofs, checks, kept, errors, stmts = [], [], [], [], []
         pool = ThreadPoolExecutor(max_workers=4)
-        lookups, params = self.lookups, self.params
+        lookups, params, rv32i = self.lookups, self.params, self.chips == "rv32i"
 
         def prover():
             try:
@@ -460,6 +487,18 @@ class P3Pipeline:
                     item = todo.get()
                     if item is None:
                         return
+                    if rv32i:
+                        seg, tables, bufs, init = item
+                        pf = p3.prove(self.prove_hal, tables, init, device_traces=[(_ptr(b), lg) for b, lg in bufs])
+                        proofs.append(pf)
+                        stmts.append((tables, init))
+                        if verify:
+                            checks.append(pool.submit(verify_rv32_shard, tables, pf, init, params))
+                        if keep_tables:
+                            kept.append(([p3.Table(t.air, b.to_host().reshape(1 << lg, t.air.width), t.public_values)
+                                          for t, (b, lg) in zip(tables, bufs)], init))
+                        done.put(bufs)
+                        continue
                     seg, rows, prog, rng = item
                     pub = np.array([mont(v) for v in (seg.start_pc & 0xFFFF, seg.start_pc >> 16, seg.end_pc & 0xFFFF, seg.end_pc >> 16)], dtype=np.uint32)
                     cpu = p3.Table(self.cpu_air, None, pub)
@@ -486,8 +525,8 @@ class P3Pipeline:
         try:
             while True:
                 while not done.empty():
-                    done.get().free()
-                item = stepper.next_shard(self.wit_hal, lookups)
+                    _free(done.get())
+                item = stepper.next_rv32_shard(self.wit_hal, self.rv32_airs) if rv32i else stepper.next_shard(self.wit_hal, lookups)
                 if item is None or errors:
                     break
                 metas.append(item[0])
@@ -498,7 +537,7 @@ class P3Pipeline:
             todo.put(None)
             th.join()
             while not done.empty():
-                done.get().free()
+                _free(done.get())
             stepper.close()
             bad = [i for i, c in enumerate(checks) if c.result() != 0]
             pool.shutdown()
@@ -506,13 +545,21 @@ class P3Pipeline:
             raise errors[0]
         if bad:
             raise _lib.RkError(_lib.RK_ERR_VERIFY, "shard %d does not verify" % bad[0])
+        if rv32i and verify:
+            check_rv32_chain(rv32_publics(stmts), entry_pc=metas[0].start_pc if metas else None)
         return ex, proofs, kept
 
 
+def _free(bufs):
+    """a device buffer, or the [(device buffer, log_height)] of an rv32i shard"""
+    for b in bufs if isinstance(bufs, list) else [bufs]:
+        (b[0] if isinstance(b, tuple) else b).free()
+
+
 def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 20, params=None, device: int = 0,
-                                   lookups=True, compile_airs=True, verify=True, keep_tables=False):
+                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace"):
     """one program through a P3Pipeline of its own"""
-    pipe = P3Pipeline(params, device, lookups, compile_airs)
+    pipe = P3Pipeline(params, device, lookups, compile_airs, chips)
     try:
         return pipe.run(elf, input_words, shard_po2, verify, keep_tables)
     finally:
@@ -520,14 +567,182 @@ def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), 
 
 
 def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, params=None, device: int = 0, batch: int = 3,
-                         lookups=False):
+                         lookups=False, chips="trace"):
     """ELF -> executed shards -> one uni-stark proof per shard through rk_p3_prove_shards (every proof verified inside):
     the shape of `client.prove(&pk, stdin)` on the SP1 side (provers/sp1/driver/src/lib.rs:44-57; SHARD_SIZE / SHARD_BATCH_SIZE,
-    docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)"""
+    docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)
+    chips="rv32i": the rv32i chip set instead (raiko_amd/rv32.py; `lookups` does not apply): every shard's five tables
+    written on the GPU (rk_exec_rv32_shard_device), every proof verified inside and the run checked by
+    verify_rv32_execution."""
     from . import p3
     from .hal import make_params
     params = params if params is not None else make_params(1)
+    if chips not in CHIPS:
+        raise ValueError("chips must be one of %s" % (CHIPS,))
+    if chips == "rv32i":
+        from .hal import HipHal
+        hal = HipHal(device)
+        try:
+            ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w))
+            hal.sync()
+            try:
+                proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces)
+            finally:
+                for d in bufs:
+                    for b, _lg in d:
+                        b.free()
+        finally:
+            hal.close()
+        verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None)
+        return ex, shards, proofs
     ex = execute(elf, input_words, segment_limit_po2=shard_po2, record_trace=True)
     shards = p3_shards(ex, lookups=lookups, ext_w=int(params.ext_w))
     proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True)
     return ex, shards, proofs
+
+
+# ---- the rv32i chip set (raiko_amd/rv32.py): the register file and the integer ALU constrained ------------------------
+CHIPS = ("trace", "rv32i")
+
+
+def _rv32_side(lib, handle, index):
+    start, end = np.zeros(32, dtype=np.uint32), np.zeros(32, dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_registers(handle, index, start.ctypes.data_as(_lib.u32p), end.ctypes.data_as(_lib.u32p)))
+    n = C.c_size_t(0)
+    st = lib.rk_exec_ecalls(handle, index, None, 0, C.byref(n))
+    if st != _lib.RK_ERR_CAPACITY:
+        _lib.check(None, st)
+    ec = np.zeros((max(n.value, 1), 2), dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_ecalls(handle, index, ec.ctypes.data_as(_lib.u32p), ec.shape[0], C.byref(n)))
+    return start, end, ec[: n.value]
+
+
+def p3_rv32_airs(ext_w=None):
+    """(cpu, program, register, byte, range): the AIRs of one rv32i shard, in table order (raiko_amd/rv32.py)"""
+    from . import rv32
+    return rv32.airs(ext_w)
+
+
+def _rv32_publics(seg, start, end):
+    from . import rv32
+    from .p3 import to_mont
+    pub_cpu = to_mont(np.array([seg.start_pc & 0xFFFF, seg.start_pc >> 16, seg.end_pc & 0xFFFF, seg.end_pc >> 16], dtype=np.uint64))
+    return pub_cpu, to_mont(rv32.register_publics(start, end))
+
+
+def p3_rv32_shards(ex: Execution, ext_w=None, airs=None):
+    """one rv32i shard per executed segment, every table built in numpy from ex.witness and ex.rv32 -> [(tables, init
+    words)]: tables = cpu, program, register, byte, range (p3_rv32_airs), init = the state digests as in p3_shards.
+    The yardstick for the tables rk_exec_rv32_shard_device writes on the GPU."""
+    from . import p3, rv32
+    if ex.witness is None or ex.rv32 is None:
+        raise ValueError("execute(..., record_trace=True) first")
+    airs = airs or p3_rv32_airs(ext_w)
+    out = []
+    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
+        canon, _pc, _regs = rv32.shard_tables(s, data, start, end, ecalls)
+        pub_cpu, pub_reg = _rv32_publics(s, start, end)
+        pubs = [pub_cpu, (), pub_reg, (), ()]
+        tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
+        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
+    return out
+
+
+def rv32_shard_device(hal, handle, index, seg, airs):
+    """rk_exec_rv32_shard_device: segment `index` of an open executor as the five tables of an rv32i shard, written on
+    hal's GPU -> (tables without host traces, [(device buffer, log_height)] per table, init words)"""
+    from . import p3, rv32
+    lib = _lib.load()
+    start, end, _ec = _rv32_side(lib, handle, index)
+    rows = C.c_size_t(0)
+    _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
+    logs = [seg.po2, rows.value.bit_length() - 1, 5, rv32.BYTE_LOG_ROWS, 16]
+    bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
+    _lib.check(hal._ctx, lib.rk_exec_rv32_shard_device(hal._ctx, handle, index, *[C.c_void_p(b.ptr) for b in bufs[:2]], rows.value,
+                                                       *[C.c_void_p(b.ptr) for b in bufs[2:]]))
+    pub_cpu, pub_reg = _rv32_publics(seg, start, end)
+    tables = []
+    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), ()]):
+        t = p3.Table(a, None, pv)
+        t.log_height = lg
+        tables.append(t)
+    init = np.array(list(seg.pre_state) + list(seg.post_state), dtype=np.uint32)
+    return tables, list(zip(bufs, logs)), init
+
+
+def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None):
+    """ELF -> rv32i shards whose tables are written on hal's GPU, one segment at a time (the executor's trace of a
+    segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device traces],
+    [[(device buffer, log_height)]] to free)"""
+    from .hal import _ptr
+    airs = airs or p3_rv32_airs(ext_w)
+    st = Stepper(elf, input_words, shard_po2)
+    shards, dev, metas = [], [], []
+    try:
+        while True:
+            item = st.next_rv32_shard(hal, airs)
+            if item is None:
+                break
+            seg, tables, bufs, init = item
+            shards.append((tables, init))
+            dev.append(bufs)
+            metas.append(seg)
+        ex = st.finish()
+        ex.segments = metas
+    finally:
+        st.close()
+    return ex, shards, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev
+
+
+def check_rv32_chain(publics, entry_pc=None):
+    """the chaining of an rv32i run over its shards' public values: publics = [(cpu public values, register public
+    values)] canonical per shard.  Every value a 16-bit limb, the first shard starting from all-zero registers (at
+    entry_pc when given), shard k ending in the pc and registers shard k + 1 starts from.  Raises ValueError naming the
+    shard."""
+    prev_end = None
+    for k, (pc, regs) in enumerate(publics):
+        pc, regs = np.asarray(pc, dtype=np.int64), np.asarray(regs, dtype=np.int64)
+        if pc.shape != (4,) or regs.shape != (128,) or (pc >= 1 << 16).any() or (regs >= 1 << 16).any():
+            raise ValueError("shard %d: the public values are not 4 + 128 16-bit limbs" % k)
+        start_pc, end_pc = int(pc[0] | pc[1] << 16), int(pc[2] | pc[3] << 16)
+        if k == 0:
+            if regs[:64].any():
+                raise ValueError("shard 0: the registers do not start at zero")
+            if entry_pc is not None and start_pc != entry_pc:
+                raise ValueError("shard 0: does not start at the entry point")
+        elif (start_pc, tuple(regs[:64])) != prev_end:
+            raise ValueError("shard %d: does not start where shard %d ended" % (k, k - 1))
+        prev_end = (end_pc, tuple(regs[64:]))
+    return True
+
+
+def rv32_publics(shards):
+    """[(cpu public values, register public values)] canonical, per shard of [(tables, init)]"""
+    from . import p3
+    return [(p3.from_mont(t[0].public_values), p3.from_mont(t[2].public_values)) for t, _init in shards]
+
+
+def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
+    """Checks a run proven with the rv32i chip set: every shard's proof (rk_p3_verify; the register / byte / range tables
+    pinned to 32 / 2^18 / 2^16 rows, the cpu table to the shard's height), then check_rv32_chain over the public
+    values.  shards: [(tables, init)] as p3_rv32_shards / execute_rv32_device give them.  Raises ValueError naming the
+    shard; returns True."""
+    if len(proofs) != len(shards):
+        raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
+    for k, ((tables, init), pf) in enumerate(zip(shards, proofs)):
+        rc = verify_rv32_shard(tables, pf, init, params)
+        if rc != 0:
+            raise ValueError("shard %d: the proof does not verify (reason %d)" % (k, rc))
+    return check_rv32_chain(rv32_publics(shards), entry_pc)
+
+
+def verify_rv32_shard(tables, proof, init, params=None) -> int:
+    """rk_p3_verify of one rv32i shard with the register / byte / range tables pinned to 32 / 2^18 / 2^16 rows and the
+    cpu table to the height the statement gives -> 0 or the verifier's reason"""
+    from . import p3, rv32
+    vt = []
+    for i, t in enumerate(tables):
+        v = p3.Table(t.air, None, t.public_values)
+        v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16)[i]
+        vt.append(v)
+    return p3.verify(vt, proof, init, params)
