@@ -604,6 +604,27 @@ int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capa
 int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows);
 int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                               size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range);
+/* THE RV32I-CF CHIP SET: rv32i's five tables with the control flow and the shifts constrained as well, plus a sixth
+ * (raiko_amd/rv32cf.py builds the same tables in numpy, names every column and writes the AIRs):
+ *   cpu       2^po2 x RK_RV32CF_CPU_COLS: columns 0..67 the rv32i row above, word for word; then the decoded branch /
+ *             jump / shift selectors and the branch or jump offset, the branch decision's difference, borrow and
+ *             equality columns, the next pc's carries and dropped bit, the shift amount's decomposition, the shifted
+ *             operand's bytes with their shift-table parts and the assembled result
+ *   program   program_rows x RK_RV32CF_PROGRAM_COLS: columns 0..76 the rv32i row, then the twelve fields above
+ *   register, byte, range   as for rv32i
+ *   shift     2^RK_RV32CF_SHIFT_LOG_ROWS x RK_RV32CF_SHIFT_COLS: (k, x, lo, hi) with x 2^k = lo + 256 hi for k in 0..8
+ *             and x in 0..255 (2304 rows, the rest the tuple (0, 0, 0, 0)), with counts and bit decompositions
+ * CONSTRAINED: everything rv32i constrains; the next pc of every row (pc + imm_B on a taken branch, pc + imm_J on JAL,
+ * (rs1 + imm_I) & ~1 on JALR, pc + 4 otherwise); the decision of BEQ, BNE, BLT, BGE, BLTU, BGEU; the value written by
+ * SLL, SRL, SRA, SLLI, SRLI, SRAI.  FREE: results of the M extension and of loads; memory (LB, LH, LW, LBU, LHU, SB, SH,
+ * SW); the a0 an ecall leaves.  Sizes, errors and stream behaviour as for rk_exec_rv32_shard_device. */
+#define RK_RV32CF_CPU_COLS 121
+#define RK_RV32CF_PROGRAM_COLS 89
+#define RK_RV32CF_SHIFT_COLS 38
+#define RK_RV32CF_SHIFT_LOG_ROWS 12
+int rk_exec_rv32cf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
+                                uint32_t* d_shift);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 

@@ -77,6 +77,10 @@ pub const RK_RV32_REGISTER_COLS: u32 = 131;
 pub const RK_RV32_REGISTER_ROWS: u32 = 32;
 pub const RK_RV32_BYTE_COLS: u32 = 24;
 pub const RK_RV32_BYTE_LOG_ROWS: u32 = 18;
+pub const RK_RV32CF_CPU_COLS: u32 = 121;
+pub const RK_RV32CF_PROGRAM_COLS: u32 = 89;
+pub const RK_RV32CF_SHIFT_COLS: u32 = 38;
+pub const RK_RV32CF_SHIFT_LOG_ROWS: u32 = 12;
 
 #[repr(C)]
 pub struct rk_air {
@@ -453,6 +457,7 @@ extern "C" {
     pub fn rk_exec_ecalls(ex: *const rk_exec, index: u32, out: *mut u32, capacity: usize, n: *mut usize) -> c_int;
     pub fn rk_exec_rv32_sizes(ex: *const rk_exec, index: u32, program_rows: *mut usize) -> c_int;
     pub fn rk_exec_rv32_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32) -> c_int;
+    pub fn rk_exec_rv32cf_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;

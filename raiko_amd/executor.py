@@ -210,10 +210,10 @@ class Stepper:
         self.n += 1
         return seg, rows, prog, rng
 
-    def next_rv32_shard(self, hal, airs):
-        """the next executed segment as the five tables of an rv32i shard written on hal's GPU (rv32_shard_device) ->
-        (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words), or None after
-        the last"""
+    def next_rv32_shard(self, hal, airs, chips="rv32i"):
+        """the next executed segment as the tables of an rv32i (five) or rv32i-cf (six) shard written on hal's GPU
+        (rv32_shard_device) -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init
+        words), or None after the last"""
         if not self.more:
             return None
         more = C.c_int(0)
@@ -224,7 +224,7 @@ class Stepper:
         s = RkExecSegment()
         self._lib.rk_exec_segment_get(self._h, self.n, C.byref(s))
         seg = ExecSegment(s.index, s.po2, int(s.cycles), s.start_pc, s.end_pc, s.exit, tuple(s.pre_state), tuple(s.post_state))
-        tables, bufs, init = rv32_shard_device(hal, self._h, self.n, seg, airs)
+        tables, bufs, init = rv32_shard_device(hal, self._h, self.n, seg, airs, chips)
         self.n += 1
         return seg, tables, bufs, init
 
@@ -439,9 +439,9 @@ class P3Pipeline:
     (rk_exec_witness_device_rows: the trace never exists on the host) and builds its lookup tables; a second thread proves
     the shards as they arrive (rk_p3_prove on its own context, the cpu table an on_device input); a small pool verifies
     the proofs (rk_p3_verify is host code).  The contexts and the (compiled) AIRs live as long as the object: run() any
-    number of programs, then close().  chips="rv32i": every shard's five tables of the rv32i chip set are written on the
-    GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run by
-    check_rv32_chain."""
+    number of programs, then close().  chips="rv32i" / "rv32i-cf": every shard's tables of that chip set are written on
+    the GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run
+    by check_rv32_chain."""
 
     def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace"):
         from . import p3
@@ -451,7 +451,7 @@ class P3Pipeline:
         self.params = params if params is not None else make_params(1)
         self.lookups, self.chips = lookups, chips
         ext_w = int(self.params.ext_w)
-        self.rv32_airs = p3_rv32_airs(ext_w) if chips == "rv32i" else None
+        self.rv32_airs = p3_rv32_airs(ext_w) if chips == "rv32i" else p3_rv32cf_airs(ext_w) if chips == "rv32i-cf" else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
@@ -479,7 +479,7 @@ class P3Pipeline:
         done = queue.Queue()                    # cpu tables the prover is through with: freed by the thread that owns their context
         proofs, checks, kept, errors, stmts = [], [], [], [], []
         pool = ThreadPoolExecutor(max_workers=4)
-        lookups, params, rv32i = self.lookups, self.params, self.chips == "rv32i"
+        lookups, params, rv32i = self.lookups, self.params, self.chips in RV32_CHIPS
 
         def prover():
             try:
@@ -526,7 +526,8 @@ class P3Pipeline:
             while True:
                 while not done.empty():
                     _free(done.get())
-                item = stepper.next_rv32_shard(self.wit_hal, self.rv32_airs) if rv32i else stepper.next_shard(self.wit_hal, lookups)
+                item = (stepper.next_rv32_shard(self.wit_hal, self.rv32_airs, self.chips) if rv32i
+                        else stepper.next_shard(self.wit_hal, lookups))
                 if item is None or errors:
                     break
                 metas.append(item[0])
@@ -573,17 +574,19 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)
     chips="rv32i": the rv32i chip set instead (raiko_amd/rv32.py; `lookups` does not apply): every shard's five tables
     written on the GPU (rk_exec_rv32_shard_device), every proof verified inside and the run checked by
-    verify_rv32_execution."""
+    verify_rv32_execution.  chips="rv32i-cf": the same with the rv32i-cf chip set's six tables (raiko_amd/rv32cf.py,
+    rk_exec_rv32cf_shard_device)."""
     from . import p3
     from .hal import make_params
     params = params if params is not None else make_params(1)
     if chips not in CHIPS:
         raise ValueError("chips must be one of %s" % (CHIPS,))
-    if chips == "rv32i":
+    if chips in RV32_CHIPS:
         from .hal import HipHal
         hal = HipHal(device)
         try:
-            ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w))
+            ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
+                                                               chips=chips)
             hal.sync()
             try:
                 proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces)
@@ -602,7 +605,8 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
 
 
 # ---- the rv32i chip set (raiko_amd/rv32.py): the register file and the integer ALU constrained ------------------------
-CHIPS = ("trace", "rv32i")
+CHIPS = ("trace", "rv32i", "rv32i-cf")
+RV32_CHIPS = ("rv32i", "rv32i-cf")
 
 
 def _rv32_side(lib, handle, index):
@@ -621,6 +625,13 @@ def p3_rv32_airs(ext_w=None):
     """(cpu, program, register, byte, range): the AIRs of one rv32i shard, in table order (raiko_amd/rv32.py)"""
     from . import rv32
     return rv32.airs(ext_w)
+
+
+def p3_rv32cf_airs(ext_w=None):
+    """(cpu, program, register, byte, range, shift): the AIRs of one rv32i-cf shard, in table order
+    (raiko_amd/rv32cf.py)"""
+    from . import rv32cf
+    return rv32cf.airs(ext_w)
 
 
 def _rv32_publics(seg, start, end):
@@ -648,21 +659,47 @@ def p3_rv32_shards(ex: Execution, ext_w=None, airs=None):
     return out
 
 
-def rv32_shard_device(hal, handle, index, seg, airs):
-    """rk_exec_rv32_shard_device: segment `index` of an open executor as the five tables of an rv32i shard, written on
-    hal's GPU -> (tables without host traces, [(device buffer, log_height)] per table, init words)"""
-    from . import p3, rv32
+def p3_rv32cf_shards(ex: Execution, ext_w=None, airs=None):
+    """one rv32i-cf shard per executed segment, every table built in numpy (rv32cf.shard_tables) -> [(tables, init
+    words)]: tables = cpu, program, register, byte, range, shift (p3_rv32cf_airs).  The yardstick for the tables
+    rk_exec_rv32cf_shard_device writes on the GPU."""
+    from . import p3, rv32cf
+    if ex.witness is None or ex.rv32 is None:
+        raise ValueError("execute(..., record_trace=True) first")
+    airs = airs or p3_rv32cf_airs(ext_w)
+    out = []
+    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
+        canon, _pc, _regs = rv32cf.shard_tables(s, data, start, end, ecalls)
+        pub_cpu, pub_reg = _rv32_publics(s, start, end)
+        pubs = [pub_cpu, (), pub_reg, (), (), ()]
+        tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
+        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
+    return out
+
+
+def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
+    """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf"): segment `index` of an open
+    executor as the tables of a shard of that chip set, written on hal's GPU -> (tables without host traces, [(device
+    buffer, log_height)] per table, init words)"""
+    from . import p3, rv32, rv32cf
+    if chips not in RV32_CHIPS:
+        raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
     _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
     logs = [seg.po2, rows.value.bit_length() - 1, 5, rv32.BYTE_LOG_ROWS, 16]
+    if chips == "rv32i-cf":
+        logs.append(rv32cf.SHIFT_LOG_ROWS)
+    if len(airs) != len(logs):
+        raise ValueError("%d AIRs for the %d tables of %s" % (len(airs), len(logs), chips))
     bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
-    _lib.check(hal._ctx, lib.rk_exec_rv32_shard_device(hal._ctx, handle, index, *[C.c_void_p(b.ptr) for b in bufs[:2]], rows.value,
-                                                       *[C.c_void_p(b.ptr) for b in bufs[2:]]))
+    entry = lib.rk_exec_rv32_shard_device if chips == "rv32i" else lib.rk_exec_rv32cf_shard_device
+    _lib.check(hal._ctx, entry(hal._ctx, handle, index, *[C.c_void_p(b.ptr) for b in bufs[:2]], rows.value,
+                               *[C.c_void_p(b.ptr) for b in bufs[2:]]))
     pub_cpu, pub_reg = _rv32_publics(seg, start, end)
     tables = []
-    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), ()]):
+    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), (), ()]):
         t = p3.Table(a, None, pv)
         t.log_height = lg
         tables.append(t)
@@ -670,17 +707,20 @@ def rv32_shard_device(hal, handle, index, seg, airs):
     return tables, list(zip(bufs, logs)), init
 
 
-def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None):
-    """ELF -> rv32i shards whose tables are written on hal's GPU, one segment at a time (the executor's trace of a
-    segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device traces],
-    [[(device buffer, log_height)]] to free)"""
+def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
+                        chips="rv32i"):
+    """ELF -> rv32i (or rv32i-cf) shards whose tables are written on hal's GPU, one segment at a time (the executor's
+    trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device
+    traces], [[(device buffer, log_height)]] to free)"""
     from .hal import _ptr
-    airs = airs or p3_rv32_airs(ext_w)
+    if chips not in RV32_CHIPS:
+        raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
+    airs = airs or (p3_rv32_airs(ext_w) if chips == "rv32i" else p3_rv32cf_airs(ext_w))
     st = Stepper(elf, input_words, shard_po2)
     shards, dev, metas = [], [], []
     try:
         while True:
-            item = st.next_rv32_shard(hal, airs)
+            item = st.next_rv32_shard(hal, airs, chips)
             if item is None:
                 break
             seg, tables, bufs, init = item
@@ -723,10 +763,10 @@ def rv32_publics(shards):
 
 
 def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
-    """Checks a run proven with the rv32i chip set: every shard's proof (rk_p3_verify; the register / byte / range tables
-    pinned to 32 / 2^18 / 2^16 rows, the cpu table to the shard's height), then check_rv32_chain over the public
-    values.  shards: [(tables, init)] as p3_rv32_shards / execute_rv32_device give them.  Raises ValueError naming the
-    shard; returns True."""
+    """Checks a run proven with the rv32i or the rv32i-cf chip set: every shard's proof (rk_p3_verify; the register /
+    byte / range / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows, the cpu table to the shard's height), then
+    check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards / p3_rv32cf_shards /
+    execute_rv32_device give them.  Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
     for k, ((tables, init), pf) in enumerate(zip(shards, proofs)):
@@ -737,12 +777,13 @@ def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
 
 
 def verify_rv32_shard(tables, proof, init, params=None) -> int:
-    """rk_p3_verify of one rv32i shard with the register / byte / range tables pinned to 32 / 2^18 / 2^16 rows and the
-    cpu table to the height the statement gives -> 0 or the verifier's reason"""
-    from . import p3, rv32
+    """rk_p3_verify of one rv32i (five tables) or rv32i-cf (six) shard with the register / byte / range / shift tables
+    pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives -> 0 or the verifier's
+    reason"""
+    from . import p3, rv32, rv32cf
     vt = []
     for i, t in enumerate(tables):
         v = p3.Table(t.air, None, t.public_values)
-        v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16)[i]
+        v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16, rv32cf.SHIFT_LOG_ROWS)[i]
         vt.append(v)
     return p3.verify(vt, proof, init, params)

@@ -19,6 +19,8 @@ Constrained: the value written to rd by ADD, SUB, ADDI, AND, OR, XOR, ANDI, ORI,
 AUIPC and the link value pc + 4 of JAL / JALR.  Free (witness cells the AIR does not tie to anything): results of
 shifts, the M extension and loads; branch / jump decisions and targets (a `seq` row keeps the pc + 4 constraint);
 memory (a store is two register reads); the a0 an ecall leaves (every ecall row writes x10 with a free value).
+rv32cf.py builds the rv32i-cf chip set on this one (the same cpu / program bodies and columns, more appended): there
+branches, jumps, the next pc of every row and the shifts are constrained too.
 The witness recomputes the ALU result of constrained ops (TraceRow.res is 0 when rd is x0), so the ALU constraints
 hold on every active row, written or not.
 
@@ -64,8 +66,15 @@ RANGE_SENDS = [(c, ACTIVE) for c in (PC_LO, PC_HI, NX_LO, NX_HI, RES_LO, RES_HI,
 def cpu_air(ext_w=None):
     from . import p3
     b = p3.AirBuilder(CPU_COLS, N_PUBLIC_CPU, p3.EXT_W if ext_w is None else ext_w)
+    cpu_constraints(b, PROGRAM_TUPLE)
+    return b.build()
+
+
+def cpu_constraints(b, program_tuple):
+    """the rv32i cpu AIR's interactions and constraints into builder b (whose width may be wider: the rv32i-cf cpu
+    table appends its columns, rv32cf.py); program_tuple: the cpu columns looked up in the program table"""
     L = b.local
-    b.send(BUS_PROGRAM, PROGRAM_TUPLE, mult=ACTIVE, mult_is_const=False)
+    b.send(BUS_PROGRAM, program_tuple, mult=ACTIVE, mult_is_const=False)
     b.receive(BUS_REGISTER, [RS1, A_LO, A_HI, PA_TS], mult=ACTIVE, mult_is_const=False)
     b.send(BUS_REGISTER, [RS1, A_LO, A_HI, TSA], mult=ACTIVE, mult_is_const=False)
     b.receive(BUS_REGISTER, [RS2, B_LO, B_HI, PB_TS], mult=ACTIVE, mult_is_const=False)
@@ -141,25 +150,32 @@ def cpu_air(ext_w=None):
     for base, lo, hi in ((BA, a_lo, a_hi), (BB, ob_lo, ob_hi), (BR, r_lo, r_hi)):
         b.assert_zero(bit * (lo - L(base) - L(base + 1) * 256))
         b.assert_zero(bit * (hi - L(base + 2) - L(base + 3) * 256))
-    return b.build()
 
 
 def program_air(ext_w=None):
     from . import p3
     b = p3.AirBuilder(PROGRAM_COLS, 0, p3.EXT_W if ext_w is None else ext_w)
+    program_constraints(b, list(range(20)))
+    return b.build()
+
+
+def lin(terms):
+    """sum of expression * constant over (expression, constant) pairs"""
+    acc = None
+    for e, c in terms:
+        x = e * c if c != 1 else e
+        acc = x if acc is None else acc + x
+    return acc
+
+
+def program_constraints(b, tuple_cols):
+    """the rv32i program AIR's interaction and constraints into builder b (the rv32i-cf program table appends its
+    columns, rv32cf.py); tuple_cols: the program columns the PROGRAM bus receives"""
     L = b.local
-    b.receive(BUS_PROGRAM, list(range(20)), mult=P_MULT, mult_is_const=False)
+    b.receive(BUS_PROGRAM, tuple_cols, mult=P_MULT, mult_is_const=False)
     bit = [L(P_BITS + i) for i in range(32)]
     opc = [L(P_OPC + k) for k in range(11)]
     f3 = [L(P_F3 + j) for j in range(8)]
-
-    def lin(terms):
-        acc = None
-        for e, c in terms:
-            x = e * c if c != 1 else e
-            acc = x if acc is None else acc + x
-        return acc
-
     for v in bit + opc + f3:
         b.assert_zero(v * (v - 1))
     b.assert_eq(L(2), lin([(bit[i], 1 << i) for i in range(16)]))
@@ -198,7 +214,6 @@ def program_air(ext_w=None):
     u_lo = lin([(bit[i], 1 << i) for i in range(12, 16)])
     b.assert_eq(L(7), sel_i * i_lo + sel_u * u_lo)
     b.assert_eq(L(8), sel_i * (bit[31] * 65535) + sel_u * L(3))
-    return b.build()
 
 
 def register_air(ext_w=None):
