@@ -36,6 +36,29 @@ P3_CASES = {
     # compression up in the Poseidon2 chip (rk_p2_chip_air: one permutation per row, 314 columns); beside a plain table
     "sp1_merkle_paths_poseidon2_chip": (1, dict(queries=4, pow_bits=2), [("merkle", 6, 9), ("fib", 5, None)], [2]),
     "sp1_wide_tuples_k9": (1, dict(queries=3, pow_bits=1), [("widetuple", 9, 130)], []),
+    # quotients in 4, 8 and 16 chunks: "power" is power_air(D) below (one constraint of degree exactly D, lqd =
+    # log2ceil(D - 1)); the quotient domain sits at stride blowup_log2 - lqd in the LDE.  risc0's preset (blow-up 4):
+    # D = 5 fills the top chunk, D = 4 leaves it partly empty
+    "risc0_deg5_k5": (0, dict(queries=4, pow_bits=2), [("power", 5, 5)], [3]),
+    "risc0_deg4_k6": (0, dict(queries=4, pow_bits=2), [("power", 6, 4)], []),
+    # blow-up 8: lqd 3, 2, 0 (strides 0, 1, 3); blow-up 16: lqd 4, 3, 0 (strides 0, 1, 4)
+    "risc0_blow3_deg9_deg5_fib": (0, dict(queries=4, pow_bits=2, blowup_log2=3), [("power", 4, 9), ("power", 6, 5), ("fib", 7, None)], [1]),
+    "risc0_blow4_deg17_deg9_fib": (0, dict(queries=3, pow_bits=2, blowup_log2=4), [("power", 3, 17), ("power", 5, 9), ("fib", 6, None)], [2, 7]),
+    # SP1's preset (W = +11, the width-16 Poseidon2) with its blow-up raised
+    "sp1_blow2_deg5_k6": (1, dict(queries=4, pow_bits=2, blowup_log2=2), [("power", 6, 5)], [4]),
+    "sp1_blow3_deg9_deg5_cubic": (1, dict(queries=4, pow_bits=2, blowup_log2=3), [("power", 5, 9), ("cubic", 4, 5), ("power", 3, 5)], []),
+    "sp1_blow4_deg17_deg5": (1, dict(queries=3, pow_bits=2, blowup_log2=4), [("power", 4, 17), ("power", 3, 5)], [6]),
+    # two rows at qd = 16: a quotient domain of 32 points, less than one workgroup; 2^12 rows at qd = 16: 2^16 points
+    "sp1_blow4_deg17_k1": (1, dict(queries=3, pow_bits=1, blowup_log2=4), [("power", 1, 17)], [8]),
+    "sp1_blow4_deg17_k12": (1, dict(queries=2, pow_bits=1, blowup_log2=4), [("power", 12, 17)], []),
+    # lqd 0 .. 4 in one proof, the tallest table with the fewest chunks: chunk heights do not follow trace heights
+    "sp1_blow4_lqd0_to_4": (1, dict(queries=3, pow_bits=2, blowup_log2=4),
+                            [("fib", 8, None), ("cubic", 6, 5), ("power", 5, 5), ("power", 3, 9), ("power", 2, 17)], [9]),
+    # lookups at high lqd: the demo tables beside a degree-9 table; a table whose interactions sit beside a constraint of
+    # degree 5 / 9 (the permutation trace's taps at stride 1 with 4 / 8 chunks)
+    "sp1_blow4_lookup_beside_deg9": (1, dict(queries=3, pow_bits=2, blowup_log2=4), [("lookup", 5, 3), ("power", 4, 9)], [1]),
+    "risc0_blow3_powerperm_deg5": (0, dict(queries=3, pow_bits=2, blowup_log2=3), [("powerperm", 5, 5)], [2]),
+    "sp1_blow4_powerperm_deg9": (1, dict(queries=3, pow_bits=2, blowup_log2=4), [("powerperm", 4, 9), ("fib", 5, None)], []),
 }
 
 EXT_W = {0: p3.P - 11, 1: 11}     # the W of the presets' extension x^4 - W (risc0: x^4 + 11)
@@ -66,6 +89,52 @@ def widetuple_air(width, ext_w):
     return b.build()
 
 
+def power_air(D, ext_w=None):
+    """columns (x, y, acc), public values (x0, c, total); the maximum constraint degree is exactly D >= 2:
+      first row: x = x0, acc = 0;   every row: y = 5 - x^2;   transition: next.x = x^D + c + 3 (degree D),
+      next.acc = acc + y;   last row: acc + y = total.
+    ext_w: the same constraints with four interactions that cancel within the table (two batches of two: tuples
+    (x, y) with multiplicity 1, (y) with multiplicity acc), whose constraints the front end writes for x^4 - ext_w."""
+    b = p3.AirBuilder(3, 3, ext_w or p3.EXT_W)
+    x, y, acc, nx, nacc = b.local(0), b.local(1), b.local(2), b.next(0), b.next(2)
+    f = b.when_first_row()
+    f.assert_eq(x, b.public(0))
+    f.assert_zero(acc)
+    b.assert_eq(y, -(x * x) + 5)
+    xd = x
+    for _ in range(D - 1):
+        xd = xd * x
+    t = b.when_transition()
+    t.assert_eq(nx, xd + b.public(1) + 3)
+    t.assert_eq(nacc, acc + y)
+    b.when_last_row().assert_eq(acc + y, b.public(2))
+    if ext_w is not None:
+        b.send(20, [0, 1])
+        b.receive(20, [0, 1])
+        b.send(21, [1], mult=2, mult_is_const=False)
+        b.receive(21, [1], mult=2, mult_is_const=False)
+    return b.build()
+
+
+def power_trace(log_n, D, seed=1, kick_row=None):
+    """a valid trace of power_air(D): canonical (2^log_n, 3), public values.  kick_row = r > 0: x of row r is moved by
+    one and the rows after it follow from there, so that only the degree-D transition into row r is broken"""
+    n = 1 << log_n
+    rng = np.random.default_rng(seed)
+    P = p3.P
+    x0, c = int(rng.integers(0, P)), int(rng.integers(0, P))
+    t = np.zeros((n, 3), dtype=np.uint64)
+    x, acc = x0, 0
+    for i in range(n):
+        if i == kick_row:
+            x = (x + 1) % P
+        y = (5 - x * x) % P
+        t[i] = (x, y, acc)
+        acc = (acc + y) % P
+        x = (pow(x, D, P) + c + 3) % P
+    return t, [x0, c, acc]
+
+
 def merkle_tables(depth, n_paths, preset, seed):
     """[path table, Poseidon2 chip table] for n_paths random leaves of a random tree of 2^depth leaves (numpy restatement
     of the chip rows: tests/p2_chip_ref.py; the oracle must be on the case's parameter set)"""
@@ -93,7 +162,7 @@ def merkle_tables(depth, n_paths, preset, seed):
 
 
 def air_of(name, arg, preset=1):
-    key = (name, arg, preset if name in ("lookup", "selfperm", "widetuple", "p2chip", "merklepath") else None)
+    key = (name, arg, preset if name in ("lookup", "selfperm", "widetuple", "p2chip", "merklepath", "powerperm") else None)
     if key not in _AIRS:
         if name == "empty":      # `width` columns, nothing asserted: a valid AIR whose quotient is zero
             b = p3.AirBuilder(arg)
@@ -110,6 +179,10 @@ def air_of(name, arg, preset=1):
             _AIRS[key] = p3.poseidon2_chip_air(hal.make_params(preset))
         elif name == "merklepath":
             _AIRS[key] = p3.merkle_path_air(EXT_W[preset])
+        elif name == "power":
+            _AIRS[key] = power_air(arg)
+        elif name == "powerperm":
+            _AIRS[key] = power_air(arg, EXT_W[preset])
         else:
             _AIRS[key] = p3.fibonacci_air() if name == "fib" else p3.cubic_air(arg) if name == "cubic" else p3.wide_air(arg)
     return _AIRS[key]
@@ -130,12 +203,32 @@ def tables_of(case):
             tr, pv = p3.fibonacci_trace(k, 1 + i, 2)
         elif name == "cubic":
             tr, pv = p3.cubic_trace(k, arg, seed=10 + i)
+        elif name in ("power", "powerperm"):
+            tr, pv = power_trace(k, arg, seed=60 + i)
         elif name in ("empty", "selfperm", "widetuple"):
             tr, pv = np.random.default_rng(30 + i).integers(0, p3.P, size=(1 << k, arg)), []
         else:
             tr, pv = p3.wide_trace(air, k, seed=20 + i)
         out.append(p3.Table.from_canonical(air, tr, pv))
     return out
+
+
+def shapes(case):
+    """[(log_height, lqd, has interactions)] of a case's tables, from its AIRs alone (no trace is built)"""
+    preset, _, specs, _ = P3_CASES[case]
+    out = []
+    for name, k, arg in specs:
+        if name == "merkle":            # a path table of depth x paths rows beside the Poseidon2 chip, both with lookups
+            out += [(max(1, (k * arg - 1).bit_length()), a.log_quotient_degree(), True) for a in (air_of("merklepath", None, preset), air_of("p2chip", None, preset))]
+            continue
+        air = air_of(name, arg, preset)
+        for a in air if isinstance(air, tuple) else [air]:
+            out.append((max(k, arg) if name == "lookup" else k, a.log_quotient_degree(), bool(a.perm_width)))
+    return out
+
+
+# every case whose quotient domains hold at most 2^12 points (the exact reference's matrices stay small)
+REF_CASES = [c for c in sorted(P3_CASES) if all(k + lqd <= 12 for k, lqd, _ in shapes(c))]
 
 
 def init_of(case):

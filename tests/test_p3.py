@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as o
-from p3_cases import P3_CASES, init_of, sha, tables_of
+from p3_cases import P3_CASES, REF_CASES, init_of, sha, shapes, tables_of
 from raiko_amd import _lib, hal, p3
 
 P = o.P
@@ -338,3 +338,98 @@ def test_full_parameter_set_verifier_threads_agree_with_the_oracle(params):
         seen.add(got)
     assert len(seen) >= 2
     assert p3.verify(tables, pf[:-3], init, params=blob) == 1 == o.oracle_p3_verify(tables, pf[:-3], init)
+
+
+# ---------------------------------------------------------------- quotients in 4, 8 and 16 chunks
+def _blowup(preset, over):
+    return over.get("blowup_log2", hal.make_params(preset).blowup_log2)
+
+
+def test_high_degree_cases_cover_every_stride_and_both_presets():
+    """the seeded cases prove quotients of 4, 8 and 16 chunks under blow-ups 4, 8 and 16 in both parameter sets, at
+    quotient-domain strides blowup_log2 - lqd of 0, 1, 3 and 4, lookups beside and inside a table of lqd >= 2; the
+    exact reference runs on all of them but the 2^12-row table at qd = 16"""
+    seen, strides, lookups = set(), set(), set()
+    for case, (preset, over, _, _) in P3_CASES.items():
+        blow = _blowup(preset, over)
+        for k, lqd, perm in shapes(case):
+            seen.add((preset, blow, lqd))
+            strides.add(blow - lqd)
+            if lqd >= 2 and perm:
+                lookups.add((preset, blow - lqd))
+    for preset in (0, 1):
+        assert {(preset, 2, 2), (preset, 3, 2), (preset, 3, 3), (preset, 4, 3), (preset, 4, 4)} <= seen
+    assert {0, 1, 3, 4} <= strides
+    assert (0, 1) in lookups and (1, 1) in lookups
+    assert shapes("sp1_blow4_deg17_k1") == [(1, 4, False)] and shapes("sp1_blow4_deg17_k12") == [(12, 4, False)]
+    assert set(P3_CASES) - set(REF_CASES) == {"sp1_blow4_deg17_k12"}
+
+
+@pytest.mark.parametrize("D,lqd", [(2, 0), (3, 1), (4, 2), (5, 2), (6, 3), (9, 3), (10, 4), (17, 4)])
+def test_power_air_degree(D, lqd):
+    from p3_cases import power_air, power_trace
+    air = power_air(D)
+    steps = np.ascontiguousarray(air.steps, dtype=np.uint32)
+    assert air.log_quotient_degree() == lqd == air.info()["log_quotient_degree"]
+    assert o.oracle().or_air_log_quotient_degree(o.OrAir(steps=steps.ctypes.data, n_steps=steps.shape[0])) == lqd
+    tr, pv = power_trace(4, D, seed=D)
+    assert air.check_trace(tr, pv) == []
+    bad, pv2 = power_trace(4, D, seed=D, kick_row=6)
+    assert not np.array_equal(bad, tr)
+    assert air.check_trace(bad, pv2) == [(5, 3)]          # the degree-D transition into row 6, nothing else
+
+
+@pytest.mark.parametrize("case", REF_CASES)
+def test_exact_reference_matches_the_oracle_proof(params, case):
+    """transcript, trace openings, quotient chunks and the zps recombination of tests/p3_ref.py against the oracle's
+    proof words (lookup tables: the trace openings)"""
+    import p3_ref as R
+    preset, over, _, _ = P3_CASES[case]
+    R.p2_tables(preset)                    # read the preset's constants before the parameter set changes
+    params(preset, **over)
+    tables, init = tables_of(case), init_of(case)
+    pf = o.oracle_p3_prove(tables, init)
+    R.check_proof(preset, _blowup(preset, over), tables, init, pf)
+
+
+@pytest.mark.parametrize("preset", [0, 1])
+@pytest.mark.parametrize("D", [5, 9, 17])
+def test_broken_high_degree_trace_is_refused(params, preset, D):
+    """lqd 2, 3, 4 at blow-up 16: a trace whose degree-D transition fails once is proven, and both verifiers refuse the
+    proof with reason 3; the exact reference still reproduces the opened chunks, but their recombination is no longer
+    fold(zeta) / Z_H(zeta)"""
+    import p3_ref as R
+    from p3_cases import air_of, power_trace
+    R.p2_tables(preset)
+    over = dict(queries=3, pow_bits=2, blowup_log2=4)
+    params(preset, **over)
+    blob = hal.make_params(preset, **over)
+    air = air_of("power", D)
+    good = [p3.Table.from_canonical(air, *power_trace(5, D, seed=70 + D))]
+    bad = [p3.Table.from_canonical(air, *power_trace(5, D, seed=70 + D, kick_row=9))]
+    init = p3.to_mont([D])
+    pf = o.oracle_p3_prove(good, init)
+    assert o.oracle_p3_verify(good, pf, init) == 0 == p3.verify(good, pf, init, params=blob)
+    pfb = o.oracle_p3_prove(bad, init)
+    assert o.oracle_p3_verify(bad, pfb, init) == 3 == p3.verify(bad, pfb, init, params=blob)
+    with pytest.raises(AssertionError, match="zps recombination"):
+        R.check_proof(preset, 4, bad, init, pfb)
+
+
+def test_exact_reference_notices_a_changed_opening(params):
+    """the reference is not vacuous: a chunk word or a trace word moved by one, or a root, is reported"""
+    import p3_ref as R
+    case = "sp1_blow4_lqd0_to_4"
+    preset, over, _, _ = P3_CASES[case]
+    R.p2_tables(preset)
+    params(preset, **over)
+    tables, init = tables_of(case), init_of(case)
+    pf = o.oracle_p3_prove(tables, init)
+    head = 1 + len(tables) + 16
+    at_chunks = head + sum(8 * t.air.width + (16 << t.air.log_quotient_degree()) for t in tables[:4]) + 8 * tables[4].air.width
+    for at, what in ((head + 1, "table 0: trace_local"), (at_chunks + 16 * 11 + 5, "table 4: quotient chunk 11 of 16"),
+                     (1 + len(tables) + 3, "trace_local")):
+        s = pf.copy()
+        s[at] = (int(s[at]) + 1) % P
+        with pytest.raises(AssertionError, match=what):
+            R.check_proof(preset, 4, tables, init, s)
