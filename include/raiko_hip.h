@@ -625,6 +625,31 @@ int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, ui
 int rk_exec_rv32cf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                                 size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
                                 uint32_t* d_shift);
+/* THE RV32IM CHIP SET: rv32i-cf's six tables with the M extension constrained as well, plus a seventh
+ * (raiko_amd/rv32im.py builds the same tables in numpy, names every column and writes the AIRs):
+ *   cpu       2^po2 x RK_RV32IM_CPU_COLS: columns 0..120 the rv32i-cf row above, word for word; then IS_MUL .. IS_REMU and
+ *             their sum IS_M (looked up in the program table), the op (funct3) and M_W = IS_M * WR, the multiplicity of
+ *             the row's (op, rs1 value, rs2 value, result) send to the muldiv table
+ *   program   program_rows x RK_RV32IM_PROGRAM_COLS: columns 0..88 the rv32i-cf row, then the nine fields above and the
+ *             three partial products of the funct7 = 0000001 test
+ *   register, byte, range, shift   as for rv32i-cf (the counts include the muldiv table's lookups)
+ *   muldiv    muldiv_rows x RK_RV32IM_MULDIV_COLS: one row per cpu row with M_W = 1, in execution order, then padding
+ *             rows of multiplicity 0: the op, operands and result, their byte limbs, the 64-bit product (or q b + r) with
+ *             its carries, sign bits, the b = 0 and overflow flags and the remainder bound's magnitudes
+ * CONSTRAINED: everything rv32i-cf constrains; the result of MUL / MULH / MULHSU / MULHU / DIV / DIVU / REM / REMU with
+ * the RISC-V conventions for b = 0 and -2^31 / -1.  FREE: loads, stores and memory; the a0 an ecall leaves.
+ * rk_exec_rv32im_sizes: the muldiv table's rows for segment `index` (2^max(RK_RV32IM_MULDIV_MIN_LOG_ROWS, ceil(log2
+ * count))).  rk_exec_rv32im_shard_device takes any power of two from that up to 2^po2 as muldiv_rows: RK_ERR_CAPACITY
+ * (nothing written, nothing launched) when it is smaller, RK_ERR_INVALID when it is not a power of two or taller;
+ * otherwise sizes, errors and stream behaviour as for rk_exec_rv32_shard_device. */
+#define RK_RV32IM_CPU_COLS 132
+#define RK_RV32IM_PROGRAM_COLS 101
+#define RK_RV32IM_MULDIV_COLS 78
+#define RK_RV32IM_MULDIV_MIN_LOG_ROWS 1
+int rk_exec_rv32im_sizes(const rk_exec* ex, uint32_t index, size_t* muldiv_rows);
+int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
+                                uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 

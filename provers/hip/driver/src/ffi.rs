@@ -81,6 +81,10 @@ pub const RK_RV32CF_CPU_COLS: u32 = 121;
 pub const RK_RV32CF_PROGRAM_COLS: u32 = 89;
 pub const RK_RV32CF_SHIFT_COLS: u32 = 38;
 pub const RK_RV32CF_SHIFT_LOG_ROWS: u32 = 12;
+pub const RK_RV32IM_CPU_COLS: u32 = 132;
+pub const RK_RV32IM_PROGRAM_COLS: u32 = 101;
+pub const RK_RV32IM_MULDIV_COLS: u32 = 78;
+pub const RK_RV32IM_MULDIV_MIN_LOG_ROWS: u32 = 1;
 
 #[repr(C)]
 pub struct rk_air {
@@ -458,6 +462,8 @@ extern "C" {
     pub fn rk_exec_rv32_sizes(ex: *const rk_exec, index: u32, program_rows: *mut usize) -> c_int;
     pub fn rk_exec_rv32_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32) -> c_int;
     pub fn rk_exec_rv32cf_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
+    pub fn rk_exec_rv32im_sizes(ex: *const rk_exec, index: u32, muldiv_rows: *mut usize) -> c_int;
+    pub fn rk_exec_rv32im_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;

@@ -686,10 +686,13 @@ int rk_exec_free(rk_exec* ex) {
 // the program, register, byte and range tables.
 namespace rv32 {
 
-constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 for rv32i-cf)
+constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 for rv32i-cf / rv32im)
 constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_W = RK_RV32_REGISTER_COLS,
                    BYTE_W = RK_RV32_BYTE_COLS, CF_CPU_W = RK_RV32CF_CPU_COLS, CF_PROG_W = RK_RV32CF_PROGRAM_COLS,
-                   SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256;
+                   SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256, IM_CPU_W = RK_RV32IM_CPU_COLS,
+                   IM_PROG_W = RK_RV32IM_PROGRAM_COLS, MD_W = RK_RV32IM_MULDIV_COLS;
+// the chip set a kernel writes: each one's tables are the previous one's with columns (and tables) appended
+enum ChipSet : int { CS_I, CS_CF, CS_IM };
 enum : unsigned {
     PC_LO, PC_HI, NX_LO, NX_HI, INS_LO, INS_HI, SEQ, CARRY, A_LO, A_HI, B_LO, B_HI, RES_LO, RES_HI, WR, ACTIVE,
     RS1, RS2, WREG, IMM_LO, IMM_HI, IS_ADD, IS_SUB, IS_SLT, IS_SLTU, IS_BIT, BOP, IS_IMM, IS_LUI, IS_AUIPC, IS_LINK,
@@ -698,9 +701,12 @@ enum : unsigned {
     // rv32i-cf (raiko_amd/rv32cf.py): the twelve looked-up fields, then the branch, next-pc and shift columns
     IS_JAL = BR + 4, IS_BEQ, IS_BNE, IS_BLT, IS_BGE, IS_BLTU, IS_BGEU, JIMM_LO, JIMM_HI, IS_SLL, IS_SRL, IS_SRA,
     IS_BR, TAKEN, BD_LO, BD_HI, BC0, BC1, EQ, INV, M_SA, M_SB, NC0, NC1, DROP, NXH,
-    IS_SHIFT, KB, Q = KB + 3, SK = Q + 4, T, FILL, U_LO, U_HI, V_LO, V_HI, SX, SLO = SX + 4, SHI = SLO + 4
+    IS_SHIFT, KB, Q = KB + 3, SK = Q + 4, T, FILL, U_LO, U_HI, V_LO, V_HI, SX, SLO = SX + 4, SHI = SLO + 4,
+    // rv32im (raiko_amd/rv32im.py): the eight M selectors and their sum (looked up), the op, the multiplicity
+    IS_MUL = SHI + 4, IS_M = IS_MUL + 8, MOP, M_W
 };
 static_assert(SHI + 4 == CF_CPU_W, "rv32i-cf cpu columns");
+static_assert(M_W + 1 == IM_CPU_W, "rv32im cpu columns");
 constexpr uint32_t OPCODES[11] = {0x37, 0x17, 0x6f, 0x67, 0x63, 0x03, 0x23, 0x13, 0x33, 0x0f, 0x73};
 enum { O_LUI, O_AUIPC, O_JAL, O_JALR, O_BRANCH, O_LOAD, O_STORE, O_OPIMM, O_OP, O_FENCE, O_SYSTEM };
 
@@ -711,6 +717,7 @@ struct Dec {
     // rv32i-cf: bsel = the branch (0..5: BEQ BNE BLT BGE BLTU BGEU) or -1; jimm = imm_B of a branch, imm_J of JAL
     int bsel;
     uint32_t is_jal, jimm, is_sll, is_srl, is_sra;
+    uint32_t is_m;   // rv32im: an M word (OP, funct7 = 1); its op is f3
 };
 
 __host__ __device__ inline Dec decode(uint32_t ins) {
@@ -753,6 +760,7 @@ __host__ __device__ inline Dec decode(uint32_t ins) {
     d.is_sll = alu && d.f3 == 1;
     d.is_srl = alu && d.f3 == 5 && !b30;
     d.is_sra = alu && d.f3 == 5 && b30;
+    d.is_m = d.opc == O_OP && (ins >> 25) == 1;
     return d;
 }
 
@@ -795,16 +803,18 @@ __device__ inline void flush_rows(uint32_t* out, const uint32_t* s, size_t r0, s
 __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
                             uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
                             uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
-                            uint32_t* __restrict__ err) {
+                            uint32_t* __restrict__ err, uint32_t* __restrict__ mflag) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i >= cycles) {
         wval[i] = 0;
         acc[i] = 0;
+        if (mflag) mflag[i] = 0;
         return;
     }
     const TraceRow r = tr[i];
     const Dec d = decode(r.ins);
+    if (mflag) mflag[i] = d.is_m && d.wr;   // rv32im: the rows with M_W = 1, one muldiv row each
     uint32_t a0 = 0;
     if (d.opc == O_SYSTEM) {   // the side list is in cycle order: binary search
         uint32_t lo = 0, hi = n_ecalls;
@@ -879,15 +889,17 @@ __device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* t
     return k == 0 ? tr[j].a : k == 1 ? tr[j].b : wval[j];
 }
 
-// CF: the rv32i-cf row (columns 0..67 are the rv32i row, the rest rv32cf.py's) and its SHIFT counts
-template <bool CF>
+// CS_CF: the rv32i-cf row (columns 0..67 are the rv32i row, the rest rv32cf.py's) and its SHIFT counts; CS_IM: the
+// rv32i-cf row with rv32im.py's M columns appended
+template <int CS>
 __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ tr, size_t cycles, uint32_t end_pc,
                                                    const uint32_t* __restrict__ acc, const uint32_t* __restrict__ wval,
                                                    const uint32_t* __restrict__ pre, const uint32_t* __restrict__ init,
                                                    uint32_t* __restrict__ out, uint32_t* __restrict__ hist,
                                                    uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
                                                    size_t n) {
-    constexpr unsigned W = CF ? CF_CPU_W : CPU_W;
+    constexpr bool CF = CS != CS_I;
+    constexpr unsigned W = CS == CS_IM ? IM_CPU_W : CF ? CF_CPU_W : CPU_W;
     extern __shared__ uint32_t s_rows[];            // TB x (W | 1)
     __shared__ uint32_t s_wave[32][TB / 64];
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
@@ -1042,6 +1054,14 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
                 }
             }
         }
+        if constexpr (CS == CS_IM) {
+            if (d.is_m) {
+                row[IS_MUL + d.f3] = 1;
+                row[IS_M] = 1;
+                row[MOP] = d.f3;
+                row[M_W] = d.wr;
+            }
+        }
     } else {
         row[PC_LO] = row[NX_LO] = end_pc & 0xffffu;
         row[PC_HI] = row[NX_HI] = end_pc >> 16;
@@ -1073,11 +1093,13 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
     flush_rows<W>(out, s_rows, (size_t)blockIdx.x * TB, n);
 }
 
-// CF: the rv32i-cf program row, rv32i's 77 columns and the twelve fields the cf cpu row looks up
-template <bool CF>
+// CS_CF: the rv32i-cf program row, rv32i's 77 columns and the twelve fields the cf cpu row looks up; CS_IM: then the
+// nine M fields and the funct7 test's three partial products
+template <int CS>
 __global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint32_t* __restrict__ prog_mult,
                                uint32_t n_slots, uint32_t pc_base, size_t n_rows, uint32_t* __restrict__ out) {
-    constexpr unsigned W = CF ? CF_PROG_W : PROG_W;
+    constexpr bool CF = CS != CS_I;
+    constexpr unsigned W = CS == CS_IM ? IM_PROG_W : CF ? CF_PROG_W : PROG_W;
     extern __shared__ uint32_t s_rows[];
     const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t* row = s_rows + threadIdx.x * (W | 1);
@@ -1112,6 +1134,16 @@ __global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint
             e[IS_SLL] = d.is_sll;
             e[IS_SRL] = d.is_srl;
             e[IS_SRA] = d.is_sra;
+        }
+        if constexpr (CS == CS_IM) {
+            uint32_t* m = row + CF_PROG_W;          // IS_MUL .. IS_REMU, IS_M, then op b25 !b26, !b27 !b28, !b29 !b30
+            const auto nb = [&](unsigned k) { return ((ins >> k) & 1u) ^ 1u; };
+            const uint32_t f7a = (d.opc == O_OP) & (ins >> 25) & 1u & nb(26), f7b = f7a & nb(27) & nb(28), f7c = f7b & nb(29) & nb(30);
+            if (d.is_m) m[d.f3] = 1;
+            m[8] = d.is_m;
+            m[9] = f7a;
+            m[10] = f7b;
+            m[11] = f7c;
         }
     }
     for (unsigned c = 0; c < W; c++) row[c] = enc(row[c]);
@@ -1196,6 +1228,167 @@ __global__ void register_kernel(const uint32_t* __restrict__ final_ts, const uin
     flush_rows<REG_W>(out, s_rows, 0, 32);
 }
 
+// ---- rv32im: the muldiv table (raiko_amd/rv32im.py muldiv_witness names every column)
+enum : unsigned {
+    D_SEL, D_MULT = 8, D_OP, D_A_LO, D_A_HI, D_B_LO, D_B_HI, D_R_LO, D_R_HI, D_ONE, D_X, D_Y = D_X + 4, D_Z = D_Y + 4,
+    D_C = D_Z + 4, D_CY = D_C + 8, D_S = D_CY + 8, D_L = D_S + 4, D_E = D_L + 4, D_AND = D_E + 4, D_BZ = D_AND + 8, D_BINV,
+    D_OVF, D_OINV, D_BM_LO, D_BM_HI, D_KB, D_RM_LO, D_RM_HI, D_KR, D_DL_LO, D_DL_HI, D_K0
+};
+static_assert(D_K0 + 1 == MD_W, "rv32im muldiv columns");
+// the byte pairs looked up as ANDs (rv32im.py BYTE_PAIRS), the top bytes looked up in the shift table (SIGN_BYTES)
+constexpr unsigned MD_PAIRS[8][2] = {{D_X, D_X + 1}, {D_X + 2, D_Y}, {D_Y + 1, D_Y + 2}, {D_Z, D_Z + 1}, {D_Z + 2, D_C},
+                                     {D_C + 1, D_C + 2}, {D_C + 4, D_C + 5}, {D_C + 6, D_C + 7}};
+constexpr unsigned MD_RANGE[14] = {D_CY, D_CY + 1, D_CY + 2, D_CY + 3, D_CY + 4, D_CY + 5, D_CY + 6, D_CY + 7,
+                                   D_BM_LO, D_BM_HI, D_RM_LO, D_RM_HI, D_DL_LO, D_DL_HI};
+
+// per block of TB cpu rows: how many have M_W = 1
+__global__ void mcount_kernel(const uint32_t* __restrict__ mflag, uint32_t* __restrict__ mblk) {
+    const int c = __syncthreads_count(mflag[(size_t)blockIdx.x * TB + threadIdx.x] != 0);
+    if (threadIdx.x == 0) mblk[blockIdx.x] = (uint32_t)c;
+}
+
+// one workgroup of 1024: mblk becomes its exclusive prefix sum, total the sum
+__global__ void mscan_kernel(uint32_t* __restrict__ mblk, size_t nb, uint32_t* __restrict__ total) {
+    __shared__ uint32_t part[1024];
+    const unsigned t = threadIdx.x;
+    const size_t j0 = nb * t / 1024, j1 = nb * (t + 1) / 1024;
+    uint32_t sum = 0;
+    for (size_t j = j0; j < j1; j++) sum += mblk[j];
+    part[t] = sum;
+    __syncthreads();
+    for (unsigned off = 1; off < 1024; off <<= 1) {   // inclusive Hillis-Steele scan of the chunk sums
+        const uint32_t v = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    for (size_t j = j0; j < j1; j++) {
+        const uint32_t v = mblk[j];
+        mblk[j] = run;
+        run += v;
+    }
+    if (t == 1023) *total = run;
+}
+
+// the muldiv index of every row with M_W = 1: its block's offset + the flagged rows before it in the block; idx[k] = the
+// cpu row of muldiv row k (k < count)
+__global__ void mcompact_kernel(const uint32_t* __restrict__ mflag, const uint32_t* __restrict__ mblk, size_t count,
+                                uint32_t* __restrict__ idx) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool on = mflag[i] != 0;
+    const uint64_t bal = __ballot(on);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t k = mblk[blockIdx.x] + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+    for (unsigned w = 0; w < wave; w++) k += s_wave[w];
+    if (on && k < count) idx[k] = (uint32_t)i;
+}
+
+// one lane per muldiv row: row k < count is the witness of cpu row idx[k]'s op on its 32-bit operands (64-bit products
+// and the division's quotient / remainder, the executor's conventions), rows past count padding (ONE = 1, the rest 0);
+// the RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms
+__global__ void muldiv_kernel(const TraceRow* __restrict__ tr, size_t cycles, const uint32_t* __restrict__ wval,
+                              const uint32_t* __restrict__ idx, size_t count, size_t n_rows, uint32_t* __restrict__ out,
+                              uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
+                              uint32_t* __restrict__ err) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t* row = s_rows + threadIdx.x * (MD_W | 1);
+    for (unsigned c = 0; c < MD_W; c++) row[c] = 0;
+    row[D_ONE] = 1;
+    bool on = k < count;
+    const uint32_t i = on ? idx[k] : 0u;
+    if (on && i >= cycles) {   // the device's count is not the host's (reported after the run)
+        atomicOr(err, 16u);
+        on = false;
+    }
+    if (on) {
+        const TraceRow r = tr[i];
+        const uint32_t op = (r.ins >> 12) & 7, a = r.a, b = r.b, res = wval[i];
+        const bool is_mul = op < 4, divs = op == 4 || op == 6, bz = b == 0, ovf = divs && a == 0x80000000u && b == 0xffffffffu;
+        const bool sgn_x = op == 1 || op == 2 || divs, sgn_y = op == 1 || divs;
+        uint32_t q, rm;
+        if (bz) q = 0xffffffffu, rm = a;
+        else if (ovf) q = 0x80000000u, rm = 0;
+        else if (divs) q = (uint32_t)((int32_t)a / (int32_t)b), rm = (uint32_t)((int32_t)a % (int32_t)b);
+        else q = a / b, rm = a % b;
+        const uint32_t x = is_mul ? a : q, z = is_mul ? 0u : rm;
+        uint32_t xe[8], ye[8], ze[8], cb[8];
+        const uint32_t ex = sgn_x && (x >> 31), ey = sgn_y && (b >> 31), ez = divs && (z >> 31);
+        for (unsigned j = 0; j < 4; j++) {
+            xe[j] = (x >> (8 * j)) & 255u, ye[j] = (b >> (8 * j)) & 255u, ze[j] = (z >> (8 * j)) & 255u;
+            xe[j + 4] = 255u * ex, ye[j + 4] = 255u * ey, ze[j + 4] = 255u * ez;
+            row[D_X + j] = xe[j];
+            row[D_Y + j] = ye[j];
+            row[D_Z + j] = ze[j];
+        }
+        uint32_t carry = 0;   // < 8 * 255^2 + 255 + carry < 2^20: no overflow
+        for (unsigned c = 0; c < 8; c++) {
+            uint32_t acc = ze[c] + carry;
+            for (unsigned j = 0; j <= c; j++) acc += xe[j] * ye[c - j];
+            cb[c] = acc & 255u;
+            carry = acc >> 8;
+            row[D_C + c] = cb[c];
+            row[D_CY + c] = carry;
+        }
+        const uint32_t sc = cb[3] >> 7, ec = divs && sc;
+        const uint32_t lo_w = cb[0] | cb[1] << 8 | cb[2] << 16 | cb[3] << 24, hi_w = cb[4] | cb[5] << 8 | cb[6] << 16 | cb[7] << 24;
+        const uint32_t want = op == 0 ? lo_w : is_mul ? hi_w : (op == 4 || op == 5) ? q : rm;
+        if (want != res) atomicOr(err, 8u);   // the executor's result is not the op's
+        row[D_SEL + op] = 1;
+        row[D_MULT] = 1;
+        row[D_OP] = op;
+        row[D_A_LO] = a & 0xffffu;
+        row[D_A_HI] = a >> 16;
+        row[D_B_LO] = b & 0xffffu;
+        row[D_B_HI] = b >> 16;
+        row[D_R_LO] = res & 0xffffu;
+        row[D_R_HI] = res >> 16;
+        const uint32_t sgn[4] = {x >> 31, b >> 31, z >> 31, sc}, ext[4] = {ex, ey, ez, ec},
+                       top[4] = {xe[3], ye[3], ze[3], cb[3]};
+        for (unsigned j = 0; j < 4; j++) {
+            row[D_S + j] = sgn[j];
+            row[D_L + j] = (2 * top[j]) & 255u;
+            row[D_E + j] = ext[j];
+        }
+        for (unsigned j = 0; j < 8; j++) row[D_AND + j] = row[MD_PAIRS[j][0]] & row[MD_PAIRS[j][1]];
+        if (!is_mul) {
+            const uint32_t bsum = (b & 0xffffu) + (b >> 16);
+            row[D_BZ] = bz;
+            row[D_BINV] = bsum ? bb::decode(bb::inv(enc(bsum))) : 0u;
+        }
+        if (divs) {
+            uint32_t dev = 2 * (cb[0] + cb[1] + cb[2]) + 2 * (1 - sc) + row[D_L + 3];
+            for (unsigned j = 0; j < 4; j++) dev += 2 * (255u - ye[j]);
+            row[D_OVF] = ovf;
+            row[D_OINV] = dev ? bb::decode(bb::inv(enc(dev))) : 0u;
+        }
+        const uint32_t bm = ey ? 0u - b : b, zm = ez ? 0u - z : z;   // |b|, |r| (two's complement; |-2^31| = 2^31)
+        row[D_BM_LO] = bm & 0xffffu;
+        row[D_BM_HI] = bm >> 16;
+        row[D_KB] = ey && (b & 0xffffu);
+        row[D_RM_LO] = zm & 0xffffu;
+        row[D_RM_HI] = zm >> 16;
+        row[D_KR] = ez && (z & 0xffffu);
+        if (!is_mul && !bz) {   // |r| + 1 + DL = |b|
+            const uint32_t dl = bm - zm - 1;
+            row[D_DL_LO] = dl & 0xffffu;
+            row[D_DL_HI] = dl >> 16;
+            row[D_K0] = ((zm & 0xffffu) + 1 + (dl & 0xffffu)) >> 16;
+        }
+    }
+    for (unsigned c : MD_RANGE) hist_add(hist, row[c], on);
+    for (unsigned j = 0; j < 4; j++) hist_add(shift_mult, 256u + row[D_X + 3 + 4 * j], on);   // (1, top byte) -> row 256 + x
+    // AND (op 1) of each byte pair; the wave-aggregated add, as M loops repeat their operands
+    for (unsigned j = 0; j < 8; j++) hist_add(byte_mult, row[MD_PAIRS[j][0]] << 8 | row[MD_PAIRS[j][1]], on);
+    for (unsigned c = 0; c < MD_W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    flush_rows<MD_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, n_rows);
+}
+
 }  // namespace rv32
 
 static size_t rv32_program_rows(const rk_exec* ex, uint32_t index, uint32_t* n_slots) {
@@ -1207,13 +1400,28 @@ static size_t rv32_program_rows(const rk_exec* ex, uint32_t index, uint32_t* n_s
     return rows;
 }
 
-// CF: the rv32i-cf tables (d_shift the sixth); otherwise rv32i's five
-template <bool CF>
+// the rows of a segment's trace with M_W = 1 (an M word writing a register other than x0): its muldiv rows
+static size_t rv32im_count(const rk_exec* ex, uint32_t index) {
+    size_t c = 0;   // decode(ins).is_m && decode(ins).wr: opcode OP, funct7 = 1, rd != 0
+    for (const TraceRow& r : ex->traces[index]) c += (r.ins & 0xfe00007fu) == 0x02000033u && (r.ins & 0xf80u);
+    return c;
+}
+
+static size_t rv32im_muldiv_rows(size_t count) {
+    size_t rows = (size_t)1 << RK_RV32IM_MULDIV_MIN_LOG_ROWS;
+    while (rows < count) rows <<= 1;
+    return rows;
+}
+
+// CS_CF: the rv32i-cf tables (d_shift the sixth); CS_IM: the rv32im tables (d_muldiv the seventh, muldiv_rows rows);
+// CS_I: rv32i's five
+template <int CS>
 static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                              size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
-                             uint32_t* d_shift) {
+                             uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows) {
     using namespace rv32;
-    if (!ctx || !ex || !d_cpu || !d_program || !d_register || !d_byte || !d_range || (CF && !d_shift) ||
+    constexpr bool CF = CS != CS_I, IM = CS == CS_IM;
+    if (!ctx || !ex || !d_cpu || !d_program || !d_register || !d_byte || !d_range || (CF && !d_shift) || (IM && !d_muldiv) ||
         index >= ex->segments.size() || index >= ex->traces.size())
         return RK_ERR_INVALID;
     const rk_exec_segment& seg = ex->segments[index];
@@ -1227,24 +1435,34 @@ static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uin
         ctx->last_error = "rk_exec_rv32_shard_device: executed pc range wider than 2^22 words";
         return RK_ERR_CAPACITY;
     }
+    const size_t m_count = IM ? rv32im_count(ex, index) : 0;
+    if (IM) {   // a power of two that holds every muldiv row, no taller than the cpu table; nothing is written otherwise
+        if (muldiv_rows < rv32im_muldiv_rows(m_count)) {
+            ctx->last_error = "rk_exec_rv32im_shard_device: the muldiv table has fewer rows than the segment needs";
+            return RK_ERR_CAPACITY;
+        }
+        if (muldiv_rows & (muldiv_rows - 1) || muldiv_rows > std::max<size_t>(n, rv32im_muldiv_rows(0))) return RK_ERR_INVALID;
+    }
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // scratch, in one allocation: trace | ecalls | wval | acc | blk | final_ts | fin | init | err | hist | byte | prog mult / ins
-    // | shift counts
+    // | shift counts | rv32im: M flags | block counts | total | muldiv row -> cpu row
     const size_t w_tr = (std::max<size_t>(tr.size(), 1) * sizeof(TraceRow) + 3) / 4, w_ec = 2 * std::max<size_t>(ec.size(), 1);
-    size_t off[14], at = 0;
-    const size_t words[14] = {w_tr, w_ec, n, n, nb * 32, 32, 32, 32, 1, (size_t)1 << 16, (size_t)3 << 16,
-                              std::max<uint32_t>(n_slots, 1), std::max<uint32_t>(n_slots, 1), CF ? SHIFT_USED : 1u};
-    for (int k = 0; k < 14; k++) off[k] = at, at += (words[k] + 63) & ~(size_t)63;
+    size_t off[18], at = 0;
+    const size_t words[18] = {w_tr, w_ec, n, n, nb * 32, 32, 32, 32, 1, (size_t)1 << 16, (size_t)3 << 16,
+                              std::max<uint32_t>(n_slots, 1), std::max<uint32_t>(n_slots, 1), CF ? SHIFT_USED : 1u,
+                              IM ? n : 1, IM ? nb : 1, 1, std::max<size_t>(m_count, 1)};
+    for (int k = 0; k < 18; k++) off[k] = at, at += (words[k] + 63) & ~(size_t)63;
     void* base = nullptr;
     RK_TRY(rk::dev_alloc(ctx, at * 4, &base));
     uint32_t* w = (uint32_t*)base;
     const TraceRow* d_tr = (const TraceRow*)(w + off[0]);
     uint32_t *d_ec = w + off[1], *wval = w + off[2], *acc = w + off[3], *blk = w + off[4], *final_ts = w + off[5],
              *fin = w + off[6], *init = w + off[7], *err = w + off[8], *hist = w + off[9], *bmult = w + off[10],
-             *pmult = w + off[11], *pins = w + off[12], *smult = w + off[13];
+             *pmult = w + off[11], *pins = w + off[12], *smult = w + off[13], *mflag = w + off[14], *mblk = w + off[15],
+             *mtotal = w + off[16], *midx = w + off[17];
     std::vector<uint32_t> ec_flat(2 * ec.size());
     for (size_t k = 0; k < ec.size(); k++) ec_flat[2 * k] = ec[k][0], ec_flat[2 * k + 1] = ec[k][1];
-    uint32_t host_fin[33] = {0};
+    uint32_t host_fin[34] = {0};
     int st = RK_OK;
     auto hip = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && st == RK_OK) {
@@ -1261,7 +1479,8 @@ static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uin
     hip(hipMemsetAsync(err, 0, (off[13] + words[13] - off[8]) * 4, ctx->stream), "memset");   // err .. shift counts
     if (st == RK_OK) {
         hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, d_ec,
-                           (uint32_t)ec.size(), ex->pc_range[index][0], n_slots, wval, acc, pmult, pins, err);
+                           (uint32_t)ec.size(), ex->pc_range[index][0], n_slots, wval, acc, pmult, pins, err,
+                           IM ? mflag : nullptr);
         launched("rv32 prep_kernel");
     }
     if (st == RK_OK) {
@@ -1273,14 +1492,37 @@ static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uin
         launched("rv32 scan_kernel");
     }
     if (st == RK_OK) {
-        hipLaunchKernelGGL(rows_kernel<CF>, dim3((unsigned)nb), dim3(TB), TB * ((CF ? CF_CPU_W : CPU_W) | 1) * 4, ctx->stream,
-                           d_tr, tr.size(), seg.end_pc, acc, wval, blk, init, d_cpu, hist, bmult, smult, n);
+        const size_t lds = TB * ((IM ? IM_CPU_W : CF ? CF_CPU_W : CPU_W) | 1) * 4;
+        if (lds > 64 * 1024)   // rv32im's 133-word rows: past the default dynamic LDS limit (160 KiB per CU)
+            hip(hipFuncSetAttribute((const void*)rows_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "lds");
+        if (st == RK_OK)
+            hipLaunchKernelGGL(rows_kernel<CS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), seg.end_pc, acc,
+                               wval, blk, init, d_cpu, hist, bmult, smult, n);
         launched("rv32 rows_kernel");
+    }
+    if (IM && st == RK_OK) {   // the muldiv rows: count per block, scan, compact, then one lane per row (before the
+                               // byte / range / shift tables: its counts go into theirs)
+        hipLaunchKernelGGL(mcount_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk);
+        launched("rv32 mcount_kernel");
+        if (st == RK_OK) {
+            hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, mblk, nb, mtotal);
+            launched("rv32 mscan_kernel");
+        }
+        if (st == RK_OK) {
+            hipLaunchKernelGGL(mcompact_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk, m_count, midx);
+            launched("rv32 mcompact_kernel");
+        }
+        if (st == RK_OK) {
+            const unsigned b = (unsigned)std::min<size_t>(muldiv_rows, TB);
+            hipLaunchKernelGGL(muldiv_kernel, dim3((unsigned)(muldiv_rows / b)), dim3(b), b * (MD_W | 1) * 4, ctx->stream, d_tr,
+                               tr.size(), wval, midx, m_count, muldiv_rows, d_muldiv, hist, bmult, smult, err);
+            launched("rv32 muldiv_kernel");
+        }
     }
     if (st == RK_OK) {
         const unsigned b = (unsigned)std::min<size_t>(program_rows, TB);
-        hipLaunchKernelGGL(program_kernel<CF>, dim3((unsigned)((program_rows + b - 1) / b)), dim3(b),
-                           b * ((CF ? CF_PROG_W : PROG_W) | 1) * 4, ctx->stream, pins, pmult, n_slots, ex->pc_range[index][0],
+        hipLaunchKernelGGL(program_kernel<CS>, dim3((unsigned)((program_rows + b - 1) / b)), dim3(b),
+                           b * ((IM ? IM_PROG_W : CF ? CF_PROG_W : PROG_W) | 1) * 4, ctx->stream, pins, pmult, n_slots, ex->pc_range[index][0],
                            program_rows, d_program);
         launched("rv32 program_kernel");
     }
@@ -1298,7 +1540,7 @@ static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uin
                            wval, fin, d_register);
         launched("rv32 register_kernel");
     }
-    if (CF && st == RK_OK) {   // after rows_kernel on the stream: the counts are complete
+    if (CF && st == RK_OK) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
         hipLaunchKernelGGL(shift_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4,
                            ctx->stream, smult, d_shift);
         launched("rv32 shift_kernel");
@@ -1306,13 +1548,18 @@ static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uin
     // the tables are complete and the scratch can go: read back the final registers and the error flags
     hip(hipMemcpyAsync(host_fin, fin, 32 * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     hip(hipMemcpyAsync(host_fin + 32, err, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    if (IM) hip(hipMemcpyAsync(host_fin + 33, mtotal, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     hip(hipStreamSynchronize(ctx->stream), "sync");
     rk::dev_free(ctx, base);
     if (st != RK_OK) return st;
-    if (host_fin[32]) {
+    if (host_fin[32] & 7) {
         ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
                                            : "rk_exec_rv32_shard_device: trace and side list disagree";
         return RK_ERR_INVALID;
+    }
+    if (IM && (host_fin[32] || host_fin[33] != m_count)) {
+        ctx->last_error = "rk_exec_rv32im_shard_device: an M result or the muldiv row count is not the executor's";
+        return RK_ERR_INTERNAL;
     }
     if (!std::equal(host_fin, host_fin + 32, ex->regs[index].begin() + 32)) {
         ctx->last_error = "rk_exec_rv32_shard_device: the register accesses do not end in the executor's registers";
@@ -1347,14 +1594,31 @@ int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows) 
 int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                               size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range) {
     RK_GUARD_BEGIN
-    return rv32_shard_device<false>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, nullptr);
+    return rv32_shard_device<rv32::CS_I>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, nullptr,
+                                         nullptr, 0);
     RK_GUARD_END
 }
 int rk_exec_rv32cf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                                 size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
                                 uint32_t* d_shift) {
     RK_GUARD_BEGIN
-    return rv32_shard_device<true>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift);
+    return rv32_shard_device<rv32::CS_CF>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
+                                          nullptr, 0);
+    RK_GUARD_END
+}
+int rk_exec_rv32im_sizes(const rk_exec* ex, uint32_t index, size_t* muldiv_rows) {
+    RK_GUARD_BEGIN
+    if (!ex || !muldiv_rows || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
+    *muldiv_rows = rv32im_muldiv_rows(rv32im_count(ex, index));
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
+                                uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows) {
+    RK_GUARD_BEGIN
+    return rv32_shard_device<rv32::CS_IM>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
+                                          d_muldiv, muldiv_rows);
     RK_GUARD_END
 }
 

@@ -211,7 +211,7 @@ class Stepper:
         return seg, rows, prog, rng
 
     def next_rv32_shard(self, hal, airs, chips="rv32i"):
-        """the next executed segment as the tables of an rv32i (five) or rv32i-cf (six) shard written on hal's GPU
+        """the next executed segment as the tables of an rv32i (five), rv32i-cf (six) or rv32im (seven) shard written on hal's GPU
         (rv32_shard_device) -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init
         words), or None after the last"""
         if not self.more:
@@ -439,7 +439,7 @@ class P3Pipeline:
     (rk_exec_witness_device_rows: the trace never exists on the host) and builds its lookup tables; a second thread proves
     the shards as they arrive (rk_p3_prove on its own context, the cpu table an on_device input); a small pool verifies
     the proofs (rk_p3_verify is host code).  The contexts and the (compiled) AIRs live as long as the object: run() any
-    number of programs, then close().  chips="rv32i" / "rv32i-cf": every shard's tables of that chip set are written on
+    number of programs, then close().  chips="rv32i" / "rv32i-cf" / "rv32im": every shard's tables of that chip set are written on
     the GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run
     by check_rv32_chain."""
 
@@ -451,7 +451,7 @@ class P3Pipeline:
         self.params = params if params is not None else make_params(1)
         self.lookups, self.chips = lookups, chips
         ext_w = int(self.params.ext_w)
-        self.rv32_airs = p3_rv32_airs(ext_w) if chips == "rv32i" else p3_rv32cf_airs(ext_w) if chips == "rv32i-cf" else None
+        self.rv32_airs = _rv32_airs_of(chips, ext_w) if chips in RV32_CHIPS else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
@@ -575,7 +575,8 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     chips="rv32i": the rv32i chip set instead (raiko_amd/rv32.py; `lookups` does not apply): every shard's five tables
     written on the GPU (rk_exec_rv32_shard_device), every proof verified inside and the run checked by
     verify_rv32_execution.  chips="rv32i-cf": the same with the rv32i-cf chip set's six tables (raiko_amd/rv32cf.py,
-    rk_exec_rv32cf_shard_device)."""
+    rk_exec_rv32cf_shard_device); chips="rv32im" with the rv32im chip set's seven (raiko_amd/rv32im.py,
+    rk_exec_rv32im_shard_device)."""
     from . import p3
     from .hal import make_params
     params = params if params is not None else make_params(1)
@@ -605,8 +606,13 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
 
 
 # ---- the rv32i chip set (raiko_amd/rv32.py): the register file and the integer ALU constrained ------------------------
-CHIPS = ("trace", "rv32i", "rv32i-cf")
-RV32_CHIPS = ("rv32i", "rv32i-cf")
+CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im")
+RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im")
+
+
+def _rv32_airs_of(chips, ext_w=None):
+    """the AIRs of one shard of chip set `chips`, in table order"""
+    return {"rv32i": p3_rv32_airs, "rv32i-cf": p3_rv32cf_airs, "rv32im": p3_rv32im_airs}[chips](ext_w)
 
 
 def _rv32_side(lib, handle, index):
@@ -632,6 +638,13 @@ def p3_rv32cf_airs(ext_w=None):
     (raiko_amd/rv32cf.py)"""
     from . import rv32cf
     return rv32cf.airs(ext_w)
+
+
+def p3_rv32im_airs(ext_w=None):
+    """(cpu, program, register, byte, range, shift, muldiv): the AIRs of one rv32im shard, in table order
+    (raiko_amd/rv32im.py)"""
+    from . import rv32im
+    return rv32im.airs(ext_w)
 
 
 def _rv32_publics(seg, start, end):
@@ -677,10 +690,33 @@ def p3_rv32cf_shards(ex: Execution, ext_w=None, airs=None):
     return out
 
 
+def p3_rv32im_shards(ex: Execution, ext_w=None, airs=None):
+    """one rv32im shard per executed segment, every table built in numpy (rv32im.shard_tables) -> [(tables, init
+    words)]: tables = cpu, program, register, byte, range, shift, muldiv (p3_rv32im_airs).  The yardstick for the tables
+    rk_exec_rv32im_shard_device writes on the GPU."""
+    from . import p3, rv32im
+    if ex.witness is None or ex.rv32 is None:
+        raise ValueError("execute(..., record_trace=True) first")
+    airs = airs or p3_rv32im_airs(ext_w)
+    out = []
+    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
+        canon, _pc, _regs = rv32im.shard_tables(s, data, start, end, ecalls)
+        pub_cpu, pub_reg = _rv32_publics(s, start, end)
+        pubs = [pub_cpu, (), pub_reg, (), (), (), ()]
+        tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
+        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
+    return out
+
+
+# per chip set: the entry point that writes a shard's tables on the GPU and the fixed tables' log heights past rv32i's
+_RV32_DEVICE = {"rv32i": ("rk_exec_rv32_shard_device", ()), "rv32i-cf": ("rk_exec_rv32cf_shard_device", ("shift",)),
+                "rv32im": ("rk_exec_rv32im_shard_device", ("shift", "muldiv"))}
+
+
 def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
-    """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf"): segment `index` of an open
-    executor as the tables of a shard of that chip set, written on hal's GPU -> (tables without host traces, [(device
-    buffer, log_height)] per table, init words)"""
+    """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
+    rk_exec_rv32im_shard_device ("rv32im"): segment `index` of an open executor as the tables of a shard of that chip
+    set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per table, init words)"""
     from . import p3, rv32, rv32cf
     if chips not in RV32_CHIPS:
         raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
@@ -689,17 +725,22 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
     rows = C.c_size_t(0)
     _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
     logs = [seg.po2, rows.value.bit_length() - 1, 5, rv32.BYTE_LOG_ROWS, 16]
-    if chips == "rv32i-cf":
+    entry, extra = _RV32_DEVICE[chips]
+    md_rows = C.c_size_t(0)
+    if "shift" in extra:
         logs.append(rv32cf.SHIFT_LOG_ROWS)
+    if "muldiv" in extra:
+        _lib.check(None, lib.rk_exec_rv32im_sizes(handle, index, C.byref(md_rows)))
+        logs.append(md_rows.value.bit_length() - 1)
     if len(airs) != len(logs):
         raise ValueError("%d AIRs for the %d tables of %s" % (len(airs), len(logs), chips))
     bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
-    entry = lib.rk_exec_rv32_shard_device if chips == "rv32i" else lib.rk_exec_rv32cf_shard_device
-    _lib.check(hal._ctx, entry(hal._ctx, handle, index, *[C.c_void_p(b.ptr) for b in bufs[:2]], rows.value,
-                               *[C.c_void_p(b.ptr) for b in bufs[2:]]))
+    ptrs = [C.c_void_p(b.ptr) for b in bufs]
+    args = ptrs[:2] + [rows.value] + ptrs[2:] + ([md_rows.value] if "muldiv" in extra else [])
+    _lib.check(hal._ctx, getattr(lib, entry)(hal._ctx, handle, index, *args))
     pub_cpu, pub_reg = _rv32_publics(seg, start, end)
     tables = []
-    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), (), ()]):
+    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), (), (), ()]):
         t = p3.Table(a, None, pv)
         t.log_height = lg
         tables.append(t)
@@ -709,13 +750,13 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
 
 def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
                         chips="rv32i"):
-    """ELF -> rv32i (or rv32i-cf) shards whose tables are written on hal's GPU, one segment at a time (the executor's
+    """ELF -> rv32i (rv32i-cf, rv32im) shards whose tables are written on hal's GPU, one segment at a time (the executor's
     trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device
     traces], [[(device buffer, log_height)]] to free)"""
     from .hal import _ptr
     if chips not in RV32_CHIPS:
         raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
-    airs = airs or (p3_rv32_airs(ext_w) if chips == "rv32i" else p3_rv32cf_airs(ext_w))
+    airs = airs or _rv32_airs_of(chips, ext_w)
     st = Stepper(elf, input_words, shard_po2)
     shards, dev, metas = [], [], []
     try:
@@ -763,10 +804,9 @@ def rv32_publics(shards):
 
 
 def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
-    """Checks a run proven with the rv32i or the rv32i-cf chip set: every shard's proof (rk_p3_verify; the register /
-    byte / range / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows, the cpu table to the shard's height), then
+    """Checks a run proven with the rv32i, rv32i-cf or rv32im chip set: every shard's proof (verify_rv32_shard), then
     check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards / p3_rv32cf_shards /
-    execute_rv32_device give them.  Raises ValueError naming the shard; returns True."""
+    p3_rv32im_shards / execute_rv32_device give them.  Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
     for k, ((tables, init), pf) in enumerate(zip(shards, proofs)):
@@ -777,13 +817,20 @@ def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
 
 
 def verify_rv32_shard(tables, proof, init, params=None) -> int:
-    """rk_p3_verify of one rv32i (five tables) or rv32i-cf (six) shard with the register / byte / range / shift tables
-    pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives -> 0 or the verifier's
-    reason"""
+    """rk_p3_verify of one rv32i (five tables), rv32i-cf (six) or rv32im (seven) shard with the register / byte / range
+    / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
+    muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
+    verifier's reason"""
     from . import p3, rv32, rv32cf
     vt = []
     for i, t in enumerate(tables):
         v = p3.Table(t.air, None, t.public_values)
-        v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16, rv32cf.SHIFT_LOG_ROWS)[i]
+        if i == 6:
+            lg = int(proof[1 + i]) if len(proof) > 1 + i else 0
+            if not 0 < lg <= tables[0].log_height:
+                return 2
+            v.log_height = lg
+        else:
+            v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16, rv32cf.SHIFT_LOG_ROWS)[i]
         vt.append(v)
     return p3.verify(vt, proof, init, params)

@@ -82,7 +82,17 @@ def cpu_air(ext_w=None):
     Air.check_trace's (row, k))"""
     from . import p3
     b = p3.AirBuilder(CPU_COLS, rv32.N_PUBLIC_CPU, p3.EXT_W if ext_w is None else ext_w)
-    rv32.cpu_constraints(b, PROGRAM_TUPLE)
+    names = cpu_constraints(b, PROGRAM_TUPLE)
+    air = b.build()
+    air.constraint_names = names
+    return air
+
+
+def cpu_constraints(b, program_tuple):
+    """the rv32i-cf cpu AIR's interactions and constraints into builder b (the rv32im cpu table appends its columns,
+    rv32im.py); program_tuple: the cpu columns looked up in the program table -> {name: constraint index}"""
+    from . import p3
+    rv32.cpu_constraints(b, program_tuple)
     L = b.local
     names = {}
 
@@ -158,15 +168,20 @@ def cpu_air(ext_w=None):
         b.assert_eq(L(u_col), terms)
         b.assert_eq(L(v_col), L(u_col) + fill * (65535 - L(u_col) * 2))
         named("result %d" % half, shift * L(WR) * (L(res_col) - L(v_col)))
-    air = b.build()
-    air.constraint_names = names
-    return air
+    return names
 
 
 def program_air(ext_w=None):
     from . import p3
     b = p3.AirBuilder(PROGRAM_COLS, 0, p3.EXT_W if ext_w is None else ext_w)
-    rv32.program_constraints(b, list(range(20)) + list(range(P_EXT, PROGRAM_COLS)))
+    program_constraints(b, list(range(20)) + list(range(P_EXT, PROGRAM_COLS)))
+    return b.build()
+
+
+def program_constraints(b, tuple_cols):
+    """the rv32i-cf program AIR's interaction and constraints into builder b (the rv32im program table appends its
+    columns, rv32im.py); tuple_cols: the program columns the PROGRAM bus receives"""
+    rv32.program_constraints(b, tuple_cols)
     L = b.local
     bit = [L(rv32.P_BITS + i) for i in range(32)]
     opc = [L(rv32.P_OPC + k) for k in range(11)]
@@ -191,7 +206,6 @@ def program_air(ext_w=None):
     high = lin([(bit[i], 1) for i in (25, 26, 27, 28, 29, 31)])
     b.assert_zero(mult * (c(IS_SLL) + c(IS_SRL) + c(IS_SRA)) * high)
     b.assert_zero(mult * c(IS_SLL) * bit[30])
-    return b.build()
 
 
 def shift_air(ext_w=None):
