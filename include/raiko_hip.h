@@ -775,6 +775,41 @@ int rk_p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_
  * *n_permutations set when `states` holds fewer than that many: call again. */
 int rk_p3_verify_hashes(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
                         const uint32_t* proof, size_t proof_words, uint32_t* states, size_t capacity_permutations, size_t* n_permutations);
+/* The commit phase of the FRI query check as lookup tables (one more piece of a recursion / compress layer; AIRs and host
+ * witness: raiko_amd/fri_chip.py).  Parameter sets with the width-16 Poseidon2 and fri_fold_log2 = 1 (SP1's preset and
+ * its blowup_log2 variants); any other is RK_ERR_INVALID.  L = log_max (tallest LDE), R = L - blowup_log2 rounds,
+ * lfh(rd) = L - 1 - rd the height of round rd's commit-phase tree.
+ * rk_p3_fri_openings: rk_p3_verify (same arguments, same verdict) that on verdict 0 also hands back, as Montgomery words,
+ *   shape:   L, R, blowup_log2, queries
+ *   publics: beta of every round (4 R) | commit-phase roots (8 R) | final polynomial (4)
+ *   records: per query: the index | per round: the reduced opening that joins before it (rop[lfh + 1] when a table of
+ *            that height exists, else zero) 4, the sibling value 4, its Merkle path 8 lfh
+ * RK_ERR_CAPACITY with *publics_words / *records_words set when a buffer is too small: call again.  On any other verdict
+ * nothing is written and both sizes are 0. */
+int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                       const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* publics, size_t publics_capacity,
+                       uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words);
+/* The four tables of that statement for a shape: fold (one row per query and round), path (one row per Merkle step),
+ * claims (query, round, index, reduced opening: the seam to tables not written yet) and the Poseidon2 chip (one row per
+ * leaf sponge and compression).  *_rows = rows in use, *_log_height = the power of two they are padded to (>= 1). */
+typedef struct {
+    uint32_t n_rounds;
+    uint32_t fold_width, path_width, claims_width, chip_width;
+    uint32_t fold_log_height, path_log_height, claims_log_height, chip_log_height;
+    uint32_t reserved;
+    uint64_t fold_rows, path_rows, chip_rows;
+    uint64_t publics_words, records_words;
+} rk_fri_chip_size_info;
+int rk_fri_chip_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, rk_fri_chip_size_info* out);
+/* The rows of all four tables on the GPU from the uploaded publics and records (d_*, as rk_p3_fri_openings wrote them),
+ * under the context's parameter set: a fold kernel (one lane per query walks its rounds: fold and claim rows), a path
+ * kernel (one lane per query and round, round-major so that a wave's lanes share the path length: leaf sponge, lfh
+ * compressions, path rows, the chip's inputs), then rk_p2_chip_trace over those inputs (padding inputs: multiplicity 0).
+ * Each d_* table is 2^log_height x width Montgomery words row-major (rk_fri_chip_sizes), ready as an on_device
+ * rk_p3_table; *_capacity in words.  A buffer smaller than its table: RK_ERR_CAPACITY before anything is launched. */
+int rk_fri_chip_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* d_publics,
+                            const uint32_t* d_records, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
+                            uint32_t* d_claims, size_t claims_capacity, uint32_t* d_chip, size_t chip_capacity);
 /* exact proof size for the tables' shapes (log_height, width, air); 0 for shapes rk_p3_prove rejects */
 size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables);
 /* Many independent proofs -- the shards of one SP1 execution -- with `batch` of them in flight per GPU: what SP1's

@@ -133,6 +133,12 @@ class RkP3Table(C.Structure):
                 ("public_values", u32p), ("n_public", C.c_uint32), ("on_device", C.c_uint32)]
 
 
+class RkFriChipSizeInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "fold_width", "path_width", "claims_width", "chip_width", "fold_log_height",
+                                          "path_log_height", "claims_log_height", "chip_log_height", "reserved")] + \
+               [(n, C.c_uint64) for n in ("fold_rows", "path_rows", "chip_rows", "publics_words", "records_words")]
+
+
 class RkP3Shard(C.Structure):
     _fields_ = [("tables", C.POINTER(RkP3Table)), ("n_tables", C.c_uint32), ("init_words", u32p), ("n_init", C.c_size_t),
                 ("h_proof", u32p), ("capacity_words", C.c_size_t), ("proof_words", C.c_size_t)]
@@ -274,6 +280,10 @@ SYMBOLS = {
     "rk_p3_verify": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz]),
     "rk_p3_proof_bound_words": (_sz, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32]),
     "rk_p3_verify_hashes": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, _sz, C.POINTER(_sz)]),
+    "rk_p3_fri_openings": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
+                                     C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_fri_chip_sizes": (C.c_int, [_u32, _u32, _u32, C.POINTER(RkFriChipSizeInfo)]),
+    "rk_fri_chip_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "rk_p3_last_timing": (C.c_int, [_vp, C.POINTER(RkP3Timing)]),
     "rk_p3_prove_shards": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
     "rk_comm_unique_id": (C.c_int, [C.c_char_p]),

@@ -746,8 +746,15 @@ Ext load_ext(const uint32_t* p) { return Ext{{p[0], p[1], p[2], p[3]}}; }
 // 0 accept; 1 malformed / short / trailing / non-canonical word, 2 shape mismatch, 3 constraint identity
 // (OodEvaluationMismatch), 4 proof of work, 5 input opening, 6 commit-phase opening, 7 final polynomial, 8 the
 // lookups' cumulative sums do not cancel
+// rk_p3_fri_openings: what the commit-phase check of every query read, kept while p3_verify runs
+struct FriCapture {
+    uint32_t log_max = 0, n_rounds = 0, blowup_log2 = 0, queries = 0;
+    std::vector<uint32_t> publics;   // beta 4 R | commit-phase roots 8 R | final polynomial 4
+    std::vector<uint32_t> records;   // per query: index | per round: joining reduced opening 4, sibling 4, path 8 lfh
+    size_t per_record = 0;
+};
 int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init,
-              const uint32_t* proof, size_t words, bool one_thread = false) {
+              const uint32_t* proof, size_t words, bool one_thread = false, FriCapture* cap = nullptr) {
     rk_params def;
     rk::params_preset(&def, RK_PRESET_SP1);
     const rk_params& par = params ? *params : def;
@@ -894,7 +901,7 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         }
     }
     const size_t qrow = 4 * qh.size();
-    auto check_query = [&](uint32_t index, Reader r) -> int {
+    auto check_query = [&](uint32_t index, Reader r, uint32_t* rec) -> int {
         // every table is in the trace and the quotient batch: both trees have the global maximum height; the permutation
         // batch only holds the tables with lookups
         const uint32_t* trows = r.take(trow);
@@ -945,12 +952,19 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         }
         Ext folded = bb::ext_zero();
         uint32_t idx = index;
+        if (rec) *rec++ = bb::encode(index);
         for (uint32_t rd = 0; rd < n_rounds; rd++) {
             const unsigned lfh = log_max - 1 - rd;
             if (used[lfh + 1]) folded = bb::add(folded, rop[lfh + 1]);
             const uint32_t* sib = r.take(4);
             const uint32_t* path = r.take(8 * (size_t)lfh);
             if (r.bad) return 1;
+            if (rec) {
+                std::memcpy(rec, used[lfh + 1] ? rop[lfh + 1].c : bb::ext_zero().c, 16);
+                std::memcpy(rec + 4, sib, 16);
+                std::memcpy(rec + 8, path, 32 * (size_t)lfh);
+                rec += 8 + 8 * (size_t)lfh;
+            }
             uint32_t pair[8];
             std::memcpy(pair + 4 * (idx & 1), folded.c, 16);
             std::memcpy(pair + 4 * ((idx ^ 1) & 1), sib, 16);
@@ -975,6 +989,15 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
     if (q0 + per_query * sys.queries != words) return 1;   // short or trailing words
     std::vector<uint32_t> indices(sys.queries);
     for (uint32_t qi = 0; qi < sys.queries; qi++) indices[qi] = ch.sample_bits(log_max);
+    if (cap) {
+        cap->log_max = log_max, cap->n_rounds = n_rounds, cap->blowup_log2 = blow, cap->queries = sys.queries;
+        for (uint32_t rd = 0; rd < n_rounds; rd++) cap->publics.insert(cap->publics.end(), betas[rd].c, betas[rd].c + 4);
+        cap->publics.insert(cap->publics.end(), commits, commits + 8 * (size_t)n_rounds);
+        cap->publics.insert(cap->publics.end(), fp, fp + 4);
+        cap->per_record = 1;
+        for (uint32_t rd = 0; rd < n_rounds; rd++) cap->per_record += 8 + 8 * (size_t)(log_max - 1 - rd);
+        cap->records.assign(cap->per_record * sys.queries, 0);
+    }
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_thr = sys.queries >= 16 && !one_thread ? std::max(1u, std::min(4u, hw / 2)) : 1u;
     std::vector<int> first_bad(n_thr, 0);
@@ -983,7 +1006,7 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         for (uint32_t qi = t; qi < sys.queries; qi += n_thr) {
             Reader rq{proof, words};
             rq.pos = q0 + per_query * qi;
-            const int rc = check_query(indices[qi], rq);
+            const int rc = check_query(indices[qi], rq, cap ? cap->records.data() + cap->per_record * qi : nullptr);
             if (rc != 0) {
                 first_bad[t] = rc;
                 first_at[t] = qi;
@@ -1322,6 +1345,29 @@ int rk_p3_verify_hashes(const rk_params* params, const rk_p3_table* tables, uint
     if (*n_permutations > capacity) return RK_ERR_CAPACITY;
     std::memcpy(states, log.data(), log.size() * 4);
     return verdict;
+    RK_GUARD_END
+}
+
+int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                       const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* publics, size_t publics_capacity,
+                       uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words) {
+    RK_GUARD_BEGIN
+    if (!shape || !publics_words || !records_words || (publics_capacity && !publics) || (records_capacity && !records)) return RK_ERR_INVALID;
+    *publics_words = *records_words = 0;
+    rk_params def;
+    rk::params_preset(&def, RK_PRESET_SP1);
+    const rk_params& par = params ? *params : def;
+    if (par.p2_width != 16 || par.fri_fold_log2 != 1) return RK_ERR_INVALID;   // the tables are written for the width-16 instance and a fold by two
+    FriCapture cap;
+    const int verdict = p3_verify(&par, tables, n_tables, init_words, n_init, proof, proof_words, false, &cap);
+    if (verdict != 0) return verdict;
+    *publics_words = cap.publics.size();
+    *records_words = cap.records.size();
+    if (cap.publics.size() > publics_capacity || cap.records.size() > records_capacity) return RK_ERR_CAPACITY;
+    shape[0] = bb::encode(cap.log_max), shape[1] = bb::encode(cap.n_rounds), shape[2] = bb::encode(cap.blowup_log2), shape[3] = bb::encode(cap.queries);
+    std::memcpy(publics, cap.publics.data(), cap.publics.size() * 4);
+    std::memcpy(records, cap.records.data(), cap.records.size() * 4);
+    return 0;
     RK_GUARD_END
 }
 

@@ -1,7 +1,8 @@
 // The AIR front end of rk_p3_* (include/raiko_hip.h): rk_air_create / rk_air_create_lookup -- validation, symbolic degree,
 // translation of the step list into an rk_program for the GPU evaluator, sp1-core's eval_permutation_constraints written
 // as steps (PermStepGen) -- and the Poseidon2 chip: its AIR written from the configured instance's constants and its rows
-// written on the GPU (rk_p2_chip_*).  Prover and verifier are in p3.hip.  Reference call site of the path:
+// written on the GPU (rk_p2_chip_*), and the rows of the FRI commit-phase tables (rk_fri_chip_*; AIRs: raiko_amd/fri_chip.py).
+// Prover and verifier are in p3.hip.  Reference call site of the path:
 // provers/sp1/driver/src/lib.rs:44-57; p3-uni-stark symbolic_builder.rs / symbolic_expression.rs, sp1-core
 // stark/permutation.rs, sp1-recursion-core's Poseidon2 wide chip: outside the reference tree, RECALLED.
 #include "p3_air.hpp"
@@ -235,9 +236,95 @@ __global__ void __launch_bounds__(128) p2_chip_trace_kernel(uint32_t* __restrict
     p3k::chip_row<W, RP, M4>(out + r * L.width, in + r * W, mult ? mult[r] : bb::ONE, tab, L);
 }
 
+std::vector<uint32_t> p2_chip_tab(const p2::Any& k) {   // rc_ext | rc_int | diag: what p3k::chip_permute reads
+    const P2ChipLayout L = p2_chip_layout(k);
+    std::vector<uint32_t> tab(k.rc_ext(), k.rc_ext() + 8 * L.W);
+    tab.insert(tab.end(), k.rc_int(), k.rc_int() + L.RP);
+    tab.insert(tab.end(), k.diag(), k.diag() + L.W);
+    return tab;
+}
+
+// the FRI commit-phase tables (rk_fri_chip_rows_device): lane bodies in p3_kernels.hpp.  Every lane stores its own rows
+// cell by cell; staging a step's 64 rows in LDS and storing them in whole lines was measured and dropped (path kernel,
+// 2 000 lanes / 21 000 rows: 0.59 ms against 0.40 -- the lane is bound by its chain of permutations, and the staged
+// form adds two barriers and a 64-row copy loop per step)
+__global__ void __launch_bounds__(64) fri_fold_kernel(p3k::FriArgs a) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < a.Q) p3k::fri_fold_lane(a, q);
+}
+template <int M4>
+__global__ void __launch_bounds__(64) fri_path_kernel(p3k::FriArgs a, const uint32_t* __restrict__ tab, P2ChipLayout L) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.Q * a.R) p3k::fri_path_lane<M4>(a, t, tab, L);
+}
+int fri_sizes(uint32_t log_max, uint32_t blow, uint32_t queries, rk_fri_chip_size_info* o) {
+    if (!o || blow < 1 || blow > 4 || log_max <= blow || log_max > ntt::LAMBDA || queries == 0 || queries > RK_MAX_QUERIES) return RK_ERR_INVALID;
+    p3k::FriArgs a{};
+    a.L = log_max, a.R = log_max - blow, a.Q = queries;
+    auto lh = [](uint64_t rows) { return std::max(1u, log2u((size_t)rows)); };
+    *o = rk_fri_chip_size_info{};
+    o->n_rounds = a.R;
+    o->fold_width = a.fold_width(), o->path_width = a.path_width(), o->claims_width = p3k::FRI_CLAIMS_WIDTH, o->chip_width = 314;
+    o->fold_rows = (uint64_t)a.Q * a.R;
+    o->path_rows = (uint64_t)a.Q * a.steps_before(a.R);
+    o->chip_rows = o->fold_rows + o->path_rows;
+    o->fold_log_height = o->claims_log_height = lh(o->fold_rows);
+    o->path_log_height = lh(o->path_rows);
+    o->chip_log_height = lh(o->chip_rows);
+    o->publics_words = 12 * (uint64_t)a.R + 4;
+    o->records_words = (uint64_t)a.Q * a.per_record();
+    return RK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rk_fri_chip_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, rk_fri_chip_size_info* out) {
+    return fri_sizes(log_max, blowup_log2, queries, out);
+}
+int rk_fri_chip_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* d_publics,
+                            const uint32_t* d_records, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
+                            uint32_t* d_claims, size_t claims_capacity, uint32_t* d_chip, size_t chip_capacity) {
+    RK_GUARD_BEGIN
+    if (!ctx || !d_publics || !d_records || !d_fold || !d_path || !d_claims || !d_chip) return RK_ERR_INVALID;
+    rk_fri_chip_size_info sz;
+    RK_TRY(fri_sizes(log_max, blowup_log2, queries, &sz));
+    const p2::Any& k = ctx->h_p2;
+    if (k.cells() != 16 || ctx->sys.blowup_log2 != blowup_log2 || ctx->sys.fri_fold_log2 != 1) return RK_ERR_INVALID;
+    const size_t fold_words = ((size_t)sz.fold_width) << sz.fold_log_height, path_words = ((size_t)sz.path_width) << sz.path_log_height;
+    const size_t claims_words = ((size_t)sz.claims_width) << sz.claims_log_height, chip_words = ((size_t)sz.chip_width) << sz.chip_log_height;
+    if (fold_capacity < fold_words || path_capacity < path_words || claims_capacity < claims_words || chip_capacity < chip_words) return RK_ERR_CAPACITY;
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const P2ChipLayout L = p2_chip_layout(k);
+    const std::vector<uint32_t> tab = p2_chip_tab(k);
+    const size_t chip_n = (size_t)1 << sz.chip_log_height;
+    DevBuf d_tab, d_in, d_mult;
+    RK_TRY(d_tab.alloc(ctx, tab.size() * 4));
+    RK_TRY(d_in.alloc(ctx, chip_n * 16 * 4));
+    RK_TRY(d_mult.alloc(ctx, chip_n * 4));
+    RK_TRY(rk::upload(ctx, d_tab.p, tab.data(), tab.size() * 4));
+    // rows and inputs the lanes do not write are padding: all zero (multiplicity 0, no selector set)
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_fold, 0, fold_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_path, 0, path_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_claims, 0, claims_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_in.p, 0, chip_n * 16 * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_mult.p, 0, chip_n * 4, ctx->stream));
+    p3k::FriArgs a{};
+    a.L = log_max, a.R = sz.n_rounds, a.Q = queries;
+    a.gen_l = bb::pow(ctx->sys.root27m, (uint64_t)1 << (27 - log_max));
+    a.wm = ctx->sys.wm;
+    a.pub = d_publics, a.rec = d_records;
+    a.fold = d_fold, a.path = d_path, a.claims = d_claims, a.chip_in = d_in.u32(), a.chip_mult = d_mult.u32();
+    hipLaunchKernelGGL(fri_fold_kernel, dim3((queries + 63) / 64), dim3(64), 0, ctx->stream, a);
+    RK_TRY(rk::post_launch(ctx, "fri_fold_kernel"));
+    const dim3 grid((unsigned)((sz.fold_rows + 63) / 64)), block(64);
+    if (k.m4()) hipLaunchKernelGGL((fri_path_kernel<1>), grid, block, 0, ctx->stream, a, (const uint32_t*)d_tab.u32(), L);
+    else hipLaunchKernelGGL((fri_path_kernel<0>), grid, block, 0, ctx->stream, a, (const uint32_t*)d_tab.u32(), L);
+    RK_TRY(rk::post_launch(ctx, "fri_path_kernel"));
+    return rk_p2_chip_trace(ctx, d_in.u32(), d_mult.u32(), chip_n, d_chip);
+    RK_GUARD_END
+}
 
 int rk_air_create(const rk_air_step* steps, size_t n_steps, uint32_t width, uint32_t n_public, rk_air** out) {
     return rk_air_create_lookup(steps, n_steps, width, n_public, nullptr, 0, 0, 0, out);
@@ -395,9 +482,7 @@ int rk_p2_chip_trace(rk_ctx* ctx, const uint32_t* d_inputs, const uint32_t* d_mu
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const p2::Any& k = ctx->h_p2;
     const P2ChipLayout L = p2_chip_layout(k);
-    std::vector<uint32_t> tab(k.rc_ext(), k.rc_ext() + 8 * L.W);
-    tab.insert(tab.end(), k.rc_int(), k.rc_int() + L.RP);
-    tab.insert(tab.end(), k.diag(), k.diag() + L.W);
+    const std::vector<uint32_t> tab = p2_chip_tab(k);
     DevBuf d_tab;
     RK_TRY(d_tab.alloc(ctx, tab.size() * 4));
     RK_TRY(rk::upload(ctx, d_tab.p, tab.data(), tab.size() * 4));

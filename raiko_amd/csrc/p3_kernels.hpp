@@ -118,19 +118,17 @@ RK_HD void chip_m_ext(uint32_t (&c)[W]) {
 #pragma unroll
     for (int i = 0; i < W; i++) c[i] = bb::add(c[i], sums[i & 3]);
 }
-template <int W, int RP, int M4>
-RK_HD void chip_row(uint32_t* row, const uint32_t* in, uint32_t mult, const uint32_t* tab, const P2ChipLayout& L) {
+// the permutation: c = the input state on entry, the output on return; ROWS: the intermediate values go to their columns
+template <int W, int RP, int M4, bool ROWS>
+RK_HD void chip_permute(uint32_t (&c)[W], uint32_t* row, const uint32_t* tab, const P2ChipLayout& L) {
     const uint32_t *rc_ext = tab, *rc_int = tab + 8 * W, *diag = rc_int + RP;
-    uint32_t c[W];
-#pragma unroll
-    for (int i = 0; i < W; i++) row[i] = c[i] = in[i];
     chip_m_ext<W, M4>(c);
     for (int rd = 0; rd < 8; rd++) {
         if (rd == 4) {
             for (int k = 0; k < RP; k++) {
-                if (k > 0) row[L.s0(k)] = c[0];
+                if (ROWS && k > 0) row[L.s0(k)] = c[0];
                 const uint32_t t = bb::add(c[0], rc_int[k]), x3 = bb::mul(bb::sqr(t), t);
-                row[L.x3i(k)] = x3;
+                if (ROWS) row[L.x3i(k)] = x3;
                 c[0] = bb::mul(bb::sqr(x3), t);
                 uint32_t sum = 0;
 #pragma unroll
@@ -138,20 +136,150 @@ RK_HD void chip_row(uint32_t* row, const uint32_t* in, uint32_t mult, const uint
 #pragma unroll
                 for (int i = 0; i < W; i++) c[i] = bb::add(sum, bb::mul(c[i], diag[i]));
             }
+            if (ROWS) {
 #pragma unroll
-            for (int i = 0; i < W; i++) row[L.int_out() + i] = c[i];
+                for (int i = 0; i < W; i++) row[L.int_out() + i] = c[i];
+            }
         }
 #pragma unroll
         for (int i = 0; i < W; i++) {
             const uint32_t s = bb::add(c[i], rc_ext[rd * W + i]), x3 = bb::mul(bb::sqr(s), s);
-            row[L.x3(rd) + i] = x3;
+            if (ROWS) row[L.x3(rd) + i] = x3;
             c[i] = bb::mul(bb::sqr(x3), s);
         }
         chip_m_ext<W, M4>(c);
+        if (ROWS) {
 #pragma unroll
-        for (int i = 0; i < W; i++) row[L.post(rd) + i] = c[i];
+            for (int i = 0; i < W; i++) row[L.post(rd) + i] = c[i];
+        }
     }
+}
+template <int W, int RP, int M4>
+RK_HD void chip_row(uint32_t* row, const uint32_t* in, uint32_t mult, const uint32_t* tab, const P2ChipLayout& L) {
+    uint32_t c[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) row[i] = c[i] = in[i];
+    chip_permute<W, RP, M4, true>(c, row, tab, L);
     row[L.mult()] = mult;
+}
+
+// ---- the FRI commit-phase tables (rk_fri_chip_rows_device; column plans: raiko_amd/fri_chip.py).  pub = beta 4 R | roots
+// 8 R | final 4; rec = per query: index | per round: joining reduced opening 4, sibling 4, path 8 lfh (rk_p3_fri_openings).
+// Every cell is a Montgomery word; rows the lanes do not write stay zero (the caller clears the buffers).
+struct FriArgs {
+    uint32_t L, R, Q;           // log_max, rounds, queries
+    uint32_t gen_l, wm;         // the generator of the 2^L subgroup, the extension's W
+    const uint32_t *pub, *rec;
+    uint32_t *fold, *path, *claims, *chip_in, *chip_mult;
+    RK_HD uint32_t lfh(uint32_t rd) const { return L - 1 - rd; }
+    RK_HD size_t per_record() const { return 1 + 8 * (size_t)R + 8 * steps_before(R); }
+    RK_HD size_t steps_before(uint32_t rd) const { return (size_t)rd * (L - 1) - (size_t)rd * (rd - 1) / 2; }   // sum of lfh(r), r < rd
+    RK_HD size_t rec_round(uint32_t rd) const { return 1 + 8 * (size_t)rd + 8 * steps_before(rd); }
+    RK_HD uint32_t fold_width() const { return 41 + R + 2 * (L - 1); }
+    RK_HD uint32_t path_width() const { return 48 + R; }
+};
+constexpr uint32_t FRI_CLAIMS_WIDTH = 8;
+// fold columns: query | round | real | idx | bit | pidx | ro 4 | sib 4 | cur 4 | e0 4 | e1 4 | folded 4 | x0 | x0^2 |
+// leaf digest 8 | zero | round one-hot R | bits of pidx L-1 | partial products of x0 L-1 (round 0 only)
+// One lane per query walks its rounds (the chain is sequential): fold rows q R + rd (all but the digest) and claim rows.
+RK_HD void fri_fold_lane(const FriArgs& a, uint32_t q) {
+    const uint32_t* rec = a.rec + a.per_record() * q;
+    uint32_t idx = bb::decode(rec[0]);
+    const uint32_t fw = a.fold_width();
+    bb::Ext folded = bb::ext_zero();
+    uint32_t x0 = 0;
+    for (uint32_t rd = 0; rd < a.R; rd++) {
+        const uint32_t lfh = a.lfh(rd), bit = idx & 1u, pidx = idx >> 1;
+        const uint32_t* rr = rec + a.rec_round(rd);
+        uint32_t* row = a.fold + ((size_t)q * a.R + rd) * fw;
+        const bb::Ext ro{{rr[0], rr[1], rr[2], rr[3]}}, sib{{rr[4], rr[5], rr[6], rr[7]}};
+        const bb::Ext cur = rd ? bb::add(folded, ro) : ro;
+        const bb::Ext e0 = bit ? sib : cur, e1 = bit ? cur : sib;
+        uint32_t* pp = row + 41 + a.R + (a.L - 1);
+        if (rd == 0) {   // x0 = gen(L)^bitrev(pidx, L-1) as the product over the bits, c_j = gen(L)^(2^(L-2-j))
+            uint32_t c[32];
+            c[a.L - 2] = a.gen_l;
+            for (uint32_t j = a.L - 2; j > 0; j--) c[j - 1] = bb::sqr(c[j]);
+            x0 = bb::ONE;
+            for (uint32_t j = 0; j + 1 < a.L; j++) {
+                if ((pidx >> j) & 1u) x0 = bb::mul(x0, c[j]);
+                pp[j] = x0;
+            }
+        } else {
+            x0 = bit ? bb::neg(bb::sqr(x0)) : bb::sqr(x0);
+        }
+        const bb::Ext beta{{a.pub[4 * rd], a.pub[4 * rd + 1], a.pub[4 * rd + 2], a.pub[4 * rd + 3]}};
+        const bb::Ext slope = bb::scale(bb::sub(e1, e0), bb::inv(bb::sub(bb::neg(x0), x0)));
+        folded = bb::add(e0, bb::mul(bb::sub(beta, bb::ext_from(x0)), slope, a.wm));
+        const uint32_t qm = bb::encode(q), rdm = bb::encode(rd), idxm = bb::encode(idx);
+        row[0] = qm, row[1] = rdm, row[2] = bb::ONE, row[3] = idxm, row[4] = bit ? bb::ONE : 0u, row[5] = bb::encode(pidx);
+        for (int k = 0; k < 4; k++) {
+            row[6 + k] = ro.c[k], row[10 + k] = sib.c[k], row[14 + k] = cur.c[k];
+            row[18 + k] = e0.c[k], row[22 + k] = e1.c[k], row[26 + k] = folded.c[k];
+        }
+        row[30] = x0, row[31] = bb::sqr(x0);
+        row[41 + rd] = bb::ONE;
+        for (uint32_t j = 0; j < lfh; j++) row[41 + a.R + j] = (pidx >> j) & 1u ? bb::ONE : 0u;
+        uint32_t* cl = a.claims + ((size_t)q * a.R + rd) * FRI_CLAIMS_WIDTH;
+        cl[0] = qm, cl[1] = rdm, cl[2] = idxm, cl[7] = bb::ONE;
+        for (int k = 0; k < 4; k++) cl[3 + k] = ro.c[k];
+        idx = pidx;
+    }
+}
+// path columns: merkle_path_air's 43 (cur 8 | sib 8 | bit | left 8 | right 8 | parent 8 | real | last) | first | pos |
+// steps left | query | round | round one-hot R.  Lane t = rd Q + q (round-major: the lanes of a wave share the path
+// length) hashes the leaf (e0 | e1 of its fold row, whose digest cells it fills), walks the lfh compressions and writes
+// the path rows steps_before(rd) Q + q lfh + s and the chip's inputs (row offset + t: the leaf state, then left | right of every step).
+struct FriPathState {
+    uint32_t cur[8];
+    uint32_t pos, rd, q, lfh, t;
+    size_t off;   // first path row; off + t = first chip input
+};
+template <int M4>
+RK_HD void fri_path_begin(const FriArgs& a, uint32_t t, const uint32_t* tab, const P2ChipLayout& L, FriPathState& st) {
+    st.t = t, st.rd = t / a.Q, st.q = t % a.Q, st.lfh = a.lfh(st.rd);
+    st.off = a.steps_before(st.rd) * a.Q + (size_t)st.q * st.lfh;
+    uint32_t* frow = a.fold + ((size_t)st.q * a.R + st.rd) * a.fold_width();
+    uint32_t* cin = a.chip_in + (st.off + t) * 16;
+    uint32_t c[16];
+    for (int i = 0; i < 8; i++) cin[i] = c[i] = frow[18 + i];
+    for (int i = 8; i < 16; i++) cin[i] = c[i] = 0;
+    a.chip_mult[st.off + t] = bb::ONE;
+    chip_permute<16, 13, M4, false>(c, nullptr, tab, L);
+    for (int i = 0; i < 8; i++) frow[32 + i] = st.cur[i] = c[i];
+    st.pos = (bb::decode(a.rec[a.per_record() * st.q]) >> st.rd) >> 1;
+}
+// step s of the lane's path: every cell of the row (path_width words at `row`), the chip input of the compression
+template <int M4>
+RK_HD void fri_path_step(const FriArgs& a, FriPathState& st, uint32_t s, const uint32_t* tab, const P2ChipLayout& L, uint32_t* row) {
+    const uint32_t* sib = a.rec + a.per_record() * st.q + a.rec_round(st.rd) + 8 + 8 * s;
+    uint32_t* cin = a.chip_in + (st.off + st.t + 1 + s) * 16;
+    const uint32_t bit = st.pos & 1u;
+    uint32_t c[16];
+    for (int i = 0; i < 8; i++) {
+        c[i] = bit ? sib[i] : st.cur[i];
+        c[8 + i] = bit ? st.cur[i] : sib[i];
+        row[i] = st.cur[i], row[8 + i] = sib[i], row[17 + i] = c[i], row[25 + i] = c[8 + i];
+    }
+    for (int i = 0; i < 16; i++) cin[i] = c[i];
+    a.chip_mult[st.off + st.t + 1 + s] = bb::ONE;
+    chip_permute<16, 13, M4, false>(c, nullptr, tab, L);
+    for (int i = 0; i < 8; i++) row[33 + i] = st.cur[i] = c[i];
+    row[16] = bit ? bb::ONE : 0u;
+    row[41] = bb::ONE;
+    row[42] = s + 1 == st.lfh ? bb::ONE : 0u;
+    row[43] = s == 0 ? bb::ONE : 0u;
+    row[44] = bb::encode(st.pos);
+    row[45] = bb::encode(st.lfh - s);
+    row[46] = bb::encode(st.q), row[47] = bb::encode(st.rd);
+    for (uint32_t r = 0; r < a.R; r++) row[48 + r] = r == st.rd ? bb::ONE : 0u;
+    st.pos >>= 1;
+}
+template <int M4>
+RK_HD void fri_path_lane(const FriArgs& a, uint32_t t, const uint32_t* tab, const P2ChipLayout& L) {
+    FriPathState st;
+    fri_path_begin<M4>(a, t, tab, L, st);
+    for (uint32_t s = 0; s < st.lfh; s++) fri_path_step<M4>(a, st, s, tab, L, a.path + (st.off + s) * a.path_width());
 }
 
 }  // namespace p3k
