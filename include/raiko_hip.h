@@ -790,7 +790,7 @@ int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint3
                        const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* publics, size_t publics_capacity,
                        uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words);
 /* The four tables of that statement for a shape: fold (one row per query and round), path (one row per Merkle step),
- * claims (query, round, index, reduced opening: the seam to tables not written yet) and the Poseidon2 chip (one row per
+ * claims (query, round, index, reduced opening: free cells here; rk_fri_reduce_* below replaces them) and the Poseidon2 chip (one row per
  * leaf sponge and compression).  *_rows = rows in use, *_log_height = the power of two they are padded to (>= 1). */
 typedef struct {
     uint32_t n_rounds;
@@ -810,6 +810,52 @@ int rk_fri_chip_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, 
 int rk_fri_chip_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* d_publics,
                             const uint32_t* d_records, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
                             uint32_t* d_claims, size_t claims_capacity, uint32_t* d_chip, size_t chip_capacity);
+/* The reduced openings of the FRI query check as a lookup table: a second, larger statement beside the one above (AIRs
+ * and host witness: raiko_amd/fri_reduce.py; same scope).  Its four tables are fold' (the fold table with one more
+ * column, the domain point X of the query in that round, which joins the claim it sends), path, reduce and the chip: the
+ * claims table is gone, the reduced opening that joins the fold chain in a round is now the one the reduce table computes
+ * from the rows the shard proof opened.  For one query and one LDE height the verifier's sum over every opened column,
+ * sum_k alpha^k (p_k(x) - y_k) / (x - z_k), is grouped by (matrix, point) into (sum_k alpha^k p_k(x) - S) / (x - z) with
+ * S = sum_k alpha^k y_k over the same absolute powers; S, the group's first power A and z do not depend on the query.
+ * Still free in that statement: the query indices, the opened values themselves (one cell P per query and column: their
+ * Merkle openings are not proven) and the transcript-derived public values, which the host binds to the shard proof.
+ * rk_p3_fri_inputs: rk_p3_verify (same arguments, same verdict) that on verdict 0 also hands back, as Montgomery words,
+ *   shape:   L, R, blowup_log2, queries
+ *   layout:  per opened matrix, in the verifier's order (trace batch per table, then the permutation batch, then every
+ *            quotient chunk): batch (0 trace, 1 permutation, 2 quotient), round L - lh, width, points (2: zeta and
+ *            zeta gen(log_n); quotient chunks 1: zeta), log_n
+ *   publics: alpha 4 | zeta 4 | per matrix, per point: A 4, S 4
+ *   records: per query: the index | trace rows | permutation rows | quotient rows (no Merkle paths)
+ * RK_ERR_CAPACITY with the three *_words set when a buffer is too small: call again.  On any other verdict nothing is
+ * written and the sizes are 0. */
+int rk_p3_fri_inputs(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                     const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* layout, size_t layout_capacity, uint32_t* publics,
+                     size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* layout_words, size_t* publics_words,
+                     size_t* records_words);
+/* The four tables of that statement for a shape and a layout (n_matrices entries of 5 words, as rk_p3_fri_inputs wrote
+ * them).  The reduce table has one row per (query, slot, column): the slots are the matrices ordered by round (the
+ * layout's order within a round) and one single-row slot for every round without a matrix; rows_per_query = the sum of
+ * their widths.  reduce_publics_words = 8 + 16 n_slots: alpha | zeta | per slot A, S of the first point, A, S of the
+ * second (zero where the slot has no such point). */
+typedef struct {
+    uint32_t n_rounds, n_slots;
+    uint32_t fold_width, path_width, reduce_width, chip_width;
+    uint32_t fold_log_height, path_log_height, reduce_log_height, chip_log_height;
+    uint64_t fold_rows, path_rows, reduce_rows, chip_rows, rows_per_query;
+    uint64_t fold_publics_words, fold_records_words, reduce_publics_words, inputs_words;
+} rk_fri_reduce_size_info;
+int rk_fri_reduce_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                        rk_fri_reduce_size_info* out);
+/* The rows of all four tables on the GPU: the fold and path kernels of rk_fri_chip_rows_device (the fold rows with the
+ * extra column, no claim rows) over d_fold_publics / d_fold_records (as rk_p3_fri_openings wrote them), a reduce kernel
+ * over d_reduce_publics (slot order, rk_fri_reduce_sizes) and d_inputs (the records of rk_p3_fri_inputs) -- a workgroup
+ * per (query, round), its lanes along the columns of a matrix, running sums by wave scans --, then rk_p2_chip_trace.
+ * `layout` is host memory.  A buffer smaller than its table (RK_ERR_CAPACITY), a layout that does not fit the shape or a
+ * blow-up that is not the context's (RK_ERR_INVALID) is refused before anything is launched. */
+int rk_fri_reduce_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                              const uint32_t* d_fold_publics, const uint32_t* d_fold_records, const uint32_t* d_reduce_publics,
+                              const uint32_t* d_inputs, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
+                              uint32_t* d_reduce, size_t reduce_capacity, uint32_t* d_chip, size_t chip_capacity);
 /* exact proof size for the tables' shapes (log_height, width, air); 0 for shapes rk_p3_prove rejects */
 size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables);
 /* Many independent proofs -- the shards of one SP1 execution -- with `batch` of them in flight per GPU: what SP1's

@@ -336,6 +336,30 @@ pub struct rk_fri_chip_size_info {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct rk_fri_reduce_size_info {
+    pub n_rounds: u32,
+    pub n_slots: u32,
+    pub fold_width: u32,
+    pub path_width: u32,
+    pub reduce_width: u32,
+    pub chip_width: u32,
+    pub fold_log_height: u32,
+    pub path_log_height: u32,
+    pub reduce_log_height: u32,
+    pub chip_log_height: u32,
+    pub fold_rows: u64,
+    pub path_rows: u64,
+    pub reduce_rows: u64,
+    pub chip_rows: u64,
+    pub rows_per_query: u64,
+    pub fold_publics_words: u64,
+    pub fold_records_words: u64,
+    pub reduce_publics_words: u64,
+    pub inputs_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct rk_p3_shard {
     pub tables: *const rk_p3_table,
     pub n_tables: u32,
@@ -501,6 +525,9 @@ extern "C" {
     pub fn rk_p3_fri_openings(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
     pub fn rk_fri_chip_sizes(log_max: u32, blowup_log2: u32, queries: u32, out: *mut rk_fri_chip_size_info) -> c_int;
     pub fn rk_fri_chip_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, d_publics: *const u32, d_records: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_claims: *mut u32, claims_capacity: usize, d_chip: *mut u32, chip_capacity: usize) -> c_int;
+    pub fn rk_p3_fri_inputs(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, layout: *mut u32, layout_capacity: usize, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, layout_words: *mut usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
+    pub fn rk_fri_reduce_sizes(log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, out: *mut rk_fri_reduce_size_info) -> c_int;
+    pub fn rk_fri_reduce_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, d_fold_publics: *const u32, d_fold_records: *const u32, d_reduce_publics: *const u32, d_inputs: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_reduce: *mut u32, reduce_capacity: usize, d_chip: *mut u32, chip_capacity: usize) -> c_int;
     pub fn rk_p3_proof_bound_words(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
     pub fn rk_p3_prove_shards(opts: *const rk_p3_session_opts, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
     pub fn rk_p3_last_timing(ctx: *mut rk_ctx, out: *mut rk_p3_timing) -> c_int;

@@ -753,8 +753,18 @@ struct FriCapture {
     std::vector<uint32_t> records;   // per query: index | per round: joining reduced opening 4, sibling 4, path 8 lfh
     size_t per_record = 0;
 };
+// rk_p3_fri_inputs: what the reduced openings of every query are computed from (the loop over `reduce` below, grouped by
+// matrix and point: every group is (sum_k alpha^k p_k(x) - S) / (x - z) with S = sum_k alpha^k y_k over the same powers)
+struct FriInputs {
+    uint32_t log_max = 0, n_rounds = 0, blowup_log2 = 0, queries = 0;
+    std::vector<uint32_t> layout;    // per opened matrix, the verifier's order: batch, round L - lh, width, points, log_n
+    std::vector<uint32_t> publics;   // alpha 4 | zeta 4 | per matrix and point: first power A 4, S 4
+    std::vector<uint32_t> records;   // per query: index | trace rows | permutation rows | quotient rows
+    size_t per_record = 0;
+};
 int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init,
-              const uint32_t* proof, size_t words, bool one_thread = false, FriCapture* cap = nullptr) {
+              const uint32_t* proof, size_t words, bool one_thread = false, FriCapture* cap = nullptr,
+              FriInputs* inp = nullptr) {
     rk_params def;
     rk::params_preset(&def, RK_PRESET_SP1);
     const rk_params& par = params ? *params : def;
@@ -901,7 +911,42 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         }
     }
     const size_t qrow = 4 * qh.size();
-    auto check_query = [&](uint32_t index, Reader r, uint32_t* rec) -> int {
+    if (inp) {   // the query-independent side of every group, with the powers the loop in check_query gives its terms
+        Ext ap[ntt::LAMBDA + 1];
+        for (unsigned i = 0; i <= ntt::LAMBDA; i++) ap[i] = bb::ext_one();
+        auto matrix = [&](uint32_t batch, unsigned lh, uint32_t width, uint32_t points, unsigned ln) {
+            const uint32_t e[5] = {batch, log_max - lh, width, points, ln};
+            for (uint32_t v : e) inp->layout.push_back(bb::encode(v));
+        };
+        auto group = [&](unsigned lh, const uint32_t* y, uint32_t width) {
+            Ext s = bb::ext_zero();
+            inp->publics.insert(inp->publics.end(), ap[lh].c, ap[lh].c + 4);
+            for (uint32_t c = 0; c < width; c++) {
+                s = bb::add(s, bb::mul(ap[lh], load_ext(y + 4 * c), wm));
+                ap[lh] = bb::mul(ap[lh], alpha2, wm);
+            }
+            inp->publics.insert(inp->publics.end(), s.c, s.c + 4);
+        };
+        inp->publics.insert(inp->publics.end(), alpha2.c, alpha2.c + 4);
+        inp->publics.insert(inp->publics.end(), zeta.c, zeta.c + 4);
+        for (uint32_t t = 0; t < n_tables; t++) {
+            matrix(0, log_n[t] + blow, tables[t].width, 2, log_n[t]);
+            group(log_n[t] + blow, y_local[t], tables[t].width);
+            group(log_n[t] + blow, y_next[t], tables[t].width);
+        }
+        for (uint32_t t = 0; t < n_tables; t++) {
+            if (!pwid[t]) continue;
+            matrix(1, log_n[t] + blow, pwid[t], 2, log_n[t]);
+            group(log_n[t] + blow, yp_local[t], pwid[t]);
+            group(log_n[t] + blow, yp_next[t], pwid[t]);
+        }
+        for (uint32_t t = 0; t < n_tables; t++)
+            for (uint32_t j = 0; j < (1u << lqd[t]); j++) {
+                matrix(2, log_n[t] + blow, 4, 1, log_n[t]);
+                group(log_n[t] + blow, y_chunk[t] + 16 * (size_t)j, 4);
+            }
+    }
+    auto check_query = [&](uint32_t index, Reader r, uint32_t* rec, uint32_t* inrec) -> int {
         // every table is in the trace and the quotient batch: both trees have the global maximum height; the permutation
         // batch only holds the tables with lookups
         const uint32_t* trows = r.take(trow);
@@ -911,6 +956,12 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         const uint32_t* qrows = r.take(qrow);
         const uint32_t* qpath = r.take(8 * (size_t)log_max);
         if (r.bad) return 1;
+        if (inrec) {
+            *inrec++ = bb::encode(index);
+            std::memcpy(inrec, trows, 4 * trow);
+            if (n_perm) std::memcpy(inrec + trow, prows, 4 * prow);
+            std::memcpy(inrec + trow + prow, qrows, 4 * qrow);
+        }
         if (rk_mmcs_verify(&par, th.data(), tw.data(), n_tables, index, trows, tpath, troot) != 0) return 5;
         if (n_perm && rk_mmcs_verify(&par, ph.data(), pwd.data(), n_perm, index >> (log_max - log_pmax), prows, ppath, proot) != 0) return 5;
         if (rk_mmcs_verify(&par, qh.data(), qw.data(), (uint32_t)qh.size(), index, qrows, qpath, qroot) != 0) return 5;
@@ -998,6 +1049,11 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         for (uint32_t rd = 0; rd < n_rounds; rd++) cap->per_record += 8 + 8 * (size_t)(log_max - 1 - rd);
         cap->records.assign(cap->per_record * sys.queries, 0);
     }
+    if (inp) {
+        inp->log_max = log_max, inp->n_rounds = n_rounds, inp->blowup_log2 = blow, inp->queries = sys.queries;
+        inp->per_record = 1 + trow + prow + qrow;
+        inp->records.assign(inp->per_record * sys.queries, 0);
+    }
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_thr = sys.queries >= 16 && !one_thread ? std::max(1u, std::min(4u, hw / 2)) : 1u;
     std::vector<int> first_bad(n_thr, 0);
@@ -1006,7 +1062,8 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         for (uint32_t qi = t; qi < sys.queries; qi += n_thr) {
             Reader rq{proof, words};
             rq.pos = q0 + per_query * qi;
-            const int rc = check_query(indices[qi], rq, cap ? cap->records.data() + cap->per_record * qi : nullptr);
+            const int rc = check_query(indices[qi], rq, cap ? cap->records.data() + cap->per_record * qi : nullptr,
+                                       inp ? inp->records.data() + inp->per_record * qi : nullptr);
             if (rc != 0) {
                 first_bad[t] = rc;
                 first_at[t] = qi;
@@ -1367,6 +1424,32 @@ int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint3
     shape[0] = bb::encode(cap.log_max), shape[1] = bb::encode(cap.n_rounds), shape[2] = bb::encode(cap.blowup_log2), shape[3] = bb::encode(cap.queries);
     std::memcpy(publics, cap.publics.data(), cap.publics.size() * 4);
     std::memcpy(records, cap.records.data(), cap.records.size() * 4);
+    return 0;
+    RK_GUARD_END
+}
+
+int rk_p3_fri_inputs(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                     const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* layout, size_t layout_capacity, uint32_t* publics,
+                     size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* layout_words, size_t* publics_words,
+                     size_t* records_words) {
+    RK_GUARD_BEGIN
+    if (!shape || !layout_words || !publics_words || !records_words || (layout_capacity && !layout) || (publics_capacity && !publics) ||
+        (records_capacity && !records))
+        return RK_ERR_INVALID;
+    *layout_words = *publics_words = *records_words = 0;
+    rk_params def;
+    rk::params_preset(&def, RK_PRESET_SP1);
+    const rk_params& par = params ? *params : def;
+    if (par.p2_width != 16 || par.fri_fold_log2 != 1) return RK_ERR_INVALID;
+    FriInputs in;
+    const int verdict = p3_verify(&par, tables, n_tables, init_words, n_init, proof, proof_words, false, nullptr, &in);
+    if (verdict != 0) return verdict;
+    *layout_words = in.layout.size(), *publics_words = in.publics.size(), *records_words = in.records.size();
+    if (in.layout.size() > layout_capacity || in.publics.size() > publics_capacity || in.records.size() > records_capacity) return RK_ERR_CAPACITY;
+    shape[0] = bb::encode(in.log_max), shape[1] = bb::encode(in.n_rounds), shape[2] = bb::encode(in.blowup_log2), shape[3] = bb::encode(in.queries);
+    std::memcpy(layout, in.layout.data(), in.layout.size() * 4);
+    std::memcpy(publics, in.publics.data(), in.publics.size() * 4);
+    std::memcpy(records, in.records.data(), in.records.size() * 4);
     return 0;
     RK_GUARD_END
 }

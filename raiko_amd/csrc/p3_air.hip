@@ -276,9 +276,195 @@ int fri_sizes(uint32_t log_max, uint32_t blow, uint32_t queries, rk_fri_chip_siz
     return RK_OK;
 }
 
+
+// the reduced-openings table (rk_fri_reduce_rows_device): lane bodies in p3_kernels.hpp.  A workgroup takes one (query,
+// round) and walks the round's matrices; within a matrix its 256 lanes take 256 consecutive columns at a time.  A lane's
+// power A alpha^col comes from the alpha^(2^i) of fri_reduce_pows_kernel, its running sum from a shuffle scan across the
+// wave, the carry across waves and across 256-column pieces through LDS.  Every lane stores its own row cell by cell, as
+// the other two kernels.
+__global__ void fri_reduce_pows_kernel(uint32_t* __restrict__ apow, const uint32_t* __restrict__ pub, uint32_t wm) {
+    if (blockIdx.x || threadIdx.x) return;
+    bb::Ext p = p3k::fri_load_ext(pub);
+    for (int i = 0; i < 32; i++) {
+        for (int k = 0; k < 4; k++) apow[4 * i + k] = p.c[k];
+        p = bb::mul(p, p, wm);
+    }
+}
+__global__ void __launch_bounds__(p3k::FRI_REDUCE_TPB) fri_reduce_kernel(p3k::FriReduceArgs a) {
+    constexpr uint32_t WAVES = p3k::FRI_REDUCE_TPB / 64;
+    __shared__ bb::Ext wtot[2][WAVES];
+    __shared__ bb::Ext s_rop;
+    const uint32_t q = blockIdx.x / a.R, rd = blockIdx.x % a.R, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const p3k::FriReduceCtx cx = p3k::fri_reduce_begin(a, q, rd);
+    bb::Ext rop = bb::ext_zero();
+    for (uint32_t m = 0; m < a.M; m++) {
+        const uint32_t* slot = a.slots + p3k::FRI_REDUCE_SLOT_WORDS * m;
+        if (slot[0] != rd) continue;                      // the same for every lane of the workgroup
+        const uint32_t width = slot[1];
+        bb::Ext carry[2] = {bb::ext_zero(), bb::ext_zero()};
+        for (uint32_t base = 0; base < width; base += p3k::FRI_REDUCE_TPB) {
+            const uint32_t col = base + tid;
+            p3k::FriReduceLane ln;
+            if (col < width) {
+                p3k::fri_reduce_term(a, q, m, col, ln);
+            } else {
+                ln.p = 0;
+                ln.pw[0] = ln.pw[1] = ln.sum[0] = ln.sum[1] = bb::ext_zero();
+            }
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                bb::Ext s0, s1;
+                for (int k = 0; k < 4; k++) s0.c[k] = __shfl_up(ln.sum[0].c[k], d), s1.c[k] = __shfl_up(ln.sum[1].c[k], d);
+                if (lane >= d) p3k::fri_reduce_join(ln, s0, s1);
+            }
+            if (lane == 63) wtot[0][wave] = ln.sum[0], wtot[1][wave] = ln.sum[1];
+            __syncthreads();
+            bb::Ext before[2] = {carry[0], carry[1]};
+            for (uint32_t w = 0; w < WAVES; w++)
+                for (int j = 0; j < 2; j++) {
+                    if (w < wave) before[j] = bb::add(before[j], wtot[j][w]);
+                    carry[j] = bb::add(carry[j], wtot[j][w]);
+                }
+            p3k::fri_reduce_join(ln, before[0], before[1]);
+            if (col < width) {
+                const bb::Ext after = p3k::fri_reduce_row(a, q, m, col, cx, ln, rop);
+                if (col + 1 == width) s_rop = after;
+            }
+            __syncthreads();
+        }
+        rop = s_rop;
+    }
+}
+
+struct FriReducePlan {
+    rk_fri_reduce_size_info sz;
+    std::vector<uint32_t> slots;      // FRI_REDUCE_SLOT_WORDS per slot, gen(log_n) left 0 (the context's root fills it)
+    std::vector<uint32_t> log_n;
+};
+// the schedule of the reduce table from the layout of rk_p3_fri_inputs (Montgomery words; 5 per matrix): the matrices by
+// round, in the layout's order within a round, and one single-row slot for every round without a matrix
+int fri_reduce_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint32_t* layout, uint32_t n_matrices, FriReducePlan* plan) {
+    rk_fri_chip_size_info chip;
+    RK_TRY(fri_sizes(log_max, blow, queries, &chip));
+    if (!layout || n_matrices == 0 || n_matrices > 4096) return RK_ERR_INVALID;
+    const uint32_t R = chip.n_rounds;
+    struct M { uint32_t batch, rd, width, points, log_n, off; };
+    std::vector<M> ms(n_matrices);
+    uint64_t off = 0;
+    for (uint32_t i = 0; i < n_matrices; i++) {
+        for (int k = 0; k < 5; k++)
+            if (layout[5 * i + k] >= bb::P) return RK_ERR_INVALID;
+        M& m = ms[i];
+        m.batch = bb::decode(layout[5 * i]), m.rd = bb::decode(layout[5 * i + 1]), m.width = bb::decode(layout[5 * i + 2]);
+        m.points = bb::decode(layout[5 * i + 3]), m.log_n = bb::decode(layout[5 * i + 4]);
+        if (m.batch > 2 || (i && m.batch < ms[i - 1].batch) || m.rd >= R || m.width == 0 || m.width > (1u << 16)) return RK_ERR_INVALID;
+        if (m.points != (m.batch == 2 ? 1u : 2u) || m.log_n + blow + m.rd != log_max) return RK_ERR_INVALID;
+        m.off = (uint32_t)off;
+        off += m.width;
+    }
+    plan->slots.clear(), plan->log_n.clear();
+    uint64_t rows = 0;
+    for (uint32_t rd = 0; rd < R; rd++) {
+        const size_t first = plan->slots.size();
+        for (const M& m : ms)
+            if (m.rd == rd) {
+                plan->slots.insert(plan->slots.end(), {rd, m.width, m.points, m.off, 0u, 0u, (uint32_t)rows, 0u});
+                plan->log_n.push_back(m.log_n);
+                rows += m.width;
+            }
+        if (plan->slots.size() == first) {
+            plan->slots.insert(plan->slots.end(), {rd, 1u, 0u, 0u, 0u, 0u, (uint32_t)rows, 0u});
+            plan->log_n.push_back(0);
+            rows += 1;
+        }
+        plan->slots[plan->slots.size() - p3k::FRI_REDUCE_SLOT_WORDS + 5] = 1;
+    }
+    auto lh = [](uint64_t r) { return std::max(1u, log2u((size_t)r)); };
+    rk_fri_reduce_size_info& o = plan->sz;
+    o = rk_fri_reduce_size_info{};
+    o.n_rounds = R, o.n_slots = (uint32_t)(plan->slots.size() / p3k::FRI_REDUCE_SLOT_WORDS);
+    o.fold_width = chip.fold_width + 1, o.path_width = chip.path_width, o.reduce_width = p3k::FRI_REDUCE_FIXED + o.n_slots, o.chip_width = chip.chip_width;
+    o.fold_rows = chip.fold_rows, o.path_rows = chip.path_rows, o.chip_rows = chip.chip_rows, o.reduce_rows = rows * queries;
+    if (o.reduce_rows > ((uint64_t)1 << 26)) return RK_ERR_INVALID;
+    o.fold_log_height = chip.fold_log_height, o.path_log_height = chip.path_log_height, o.chip_log_height = chip.chip_log_height;
+    o.reduce_log_height = lh(o.reduce_rows);
+    o.fold_publics_words = chip.publics_words, o.fold_records_words = chip.records_words;
+    o.reduce_publics_words = 8 + 16 * (uint64_t)o.n_slots, o.inputs_words = (uint64_t)queries * (1 + off);
+    o.rows_per_query = rows;
+    return RK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rk_fri_reduce_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                        rk_fri_reduce_size_info* out) {
+    RK_GUARD_BEGIN
+    if (!out) return RK_ERR_INVALID;
+    FriReducePlan plan;
+    RK_TRY(fri_reduce_plan(log_max, blowup_log2, queries, layout, n_matrices, &plan));
+    *out = plan.sz;
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_fri_reduce_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                              const uint32_t* d_fold_publics, const uint32_t* d_fold_records, const uint32_t* d_reduce_publics,
+                              const uint32_t* d_inputs, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
+                              uint32_t* d_reduce, size_t reduce_capacity, uint32_t* d_chip, size_t chip_capacity) {
+    RK_GUARD_BEGIN
+    if (!ctx || !d_fold_publics || !d_fold_records || !d_reduce_publics || !d_inputs || !d_fold || !d_path || !d_reduce || !d_chip) return RK_ERR_INVALID;
+    FriReducePlan plan;
+    RK_TRY(fri_reduce_plan(log_max, blowup_log2, queries, layout, n_matrices, &plan));
+    const rk_fri_reduce_size_info& sz = plan.sz;
+    const p2::Any& k = ctx->h_p2;
+    if (k.cells() != 16 || ctx->sys.blowup_log2 != blowup_log2 || ctx->sys.fri_fold_log2 != 1) return RK_ERR_INVALID;
+    const size_t fold_words = ((size_t)sz.fold_width) << sz.fold_log_height, path_words = ((size_t)sz.path_width) << sz.path_log_height;
+    const size_t reduce_words = ((size_t)sz.reduce_width) << sz.reduce_log_height, chip_words = ((size_t)sz.chip_width) << sz.chip_log_height;
+    if (fold_capacity < fold_words || path_capacity < path_words || reduce_capacity < reduce_words || chip_capacity < chip_words) return RK_ERR_CAPACITY;
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (uint32_t m = 0; m < sz.n_slots; m++)
+        plan.slots[p3k::FRI_REDUCE_SLOT_WORDS * m + 4] = bb::pow(ctx->sys.root27m, (uint64_t)1 << (27 - plan.log_n[m]));
+    const P2ChipLayout L = p2_chip_layout(k);
+    const std::vector<uint32_t> tab = p2_chip_tab(k);
+    const size_t chip_n = (size_t)1 << sz.chip_log_height;
+    DevBuf d_tab, d_in, d_mult, d_slots, d_apow;
+    RK_TRY(d_tab.alloc(ctx, tab.size() * 4));
+    RK_TRY(d_in.alloc(ctx, chip_n * 16 * 4));
+    RK_TRY(d_mult.alloc(ctx, chip_n * 4));
+    RK_TRY(d_slots.alloc(ctx, plan.slots.size() * 4));
+    RK_TRY(d_apow.alloc(ctx, 32 * 4 * 4));
+    RK_TRY(rk::upload(ctx, d_tab.p, tab.data(), tab.size() * 4));
+    RK_TRY(rk::upload(ctx, d_slots.p, plan.slots.data(), plan.slots.size() * 4));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_fold, 0, fold_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_path, 0, path_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_reduce, 0, reduce_words * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_in.p, 0, chip_n * 16 * 4, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(d_mult.p, 0, chip_n * 4, ctx->stream));
+    p3k::FriArgs a{};
+    a.L = log_max, a.R = sz.n_rounds, a.Q = queries;
+    a.gen_l = bb::pow(ctx->sys.root27m, (uint64_t)1 << (27 - log_max));
+    a.wm = ctx->sys.wm;
+    a.pub = d_fold_publics, a.rec = d_fold_records;
+    a.fold = d_fold, a.path = d_path, a.claims = nullptr, a.chip_in = d_in.u32(), a.chip_mult = d_mult.u32();
+    a.xcol = 1, a.shiftm = ctx->sys.shiftm;
+    hipLaunchKernelGGL(fri_fold_kernel, dim3((queries + 63) / 64), dim3(64), 0, ctx->stream, a);
+    RK_TRY(rk::post_launch(ctx, "fri_fold_kernel"));
+    const dim3 grid((unsigned)((sz.fold_rows + 63) / 64)), block(64);
+    if (k.m4()) hipLaunchKernelGGL((fri_path_kernel<1>), grid, block, 0, ctx->stream, a, (const uint32_t*)d_tab.u32(), L);
+    else hipLaunchKernelGGL((fri_path_kernel<0>), grid, block, 0, ctx->stream, a, (const uint32_t*)d_tab.u32(), L);
+    RK_TRY(rk::post_launch(ctx, "fri_path_kernel"));
+    p3k::FriReduceArgs r{};
+    r.L = log_max, r.R = sz.n_rounds, r.Q = queries, r.M = sz.n_slots;
+    r.rows_per_query = (uint32_t)sz.rows_per_query, r.wm = ctx->sys.wm, r.shiftm = ctx->sys.shiftm, r.gen_l = a.gen_l;
+    r.per_record = (size_t)(sz.inputs_words / queries);
+    r.slots = d_slots.u32(), r.pub = d_reduce_publics, r.rec = d_inputs, r.apow = d_apow.u32(), r.out = d_reduce;
+    hipLaunchKernelGGL(fri_reduce_pows_kernel, dim3(1), dim3(64), 0, ctx->stream, d_apow.u32(), d_reduce_publics, r.wm);
+    RK_TRY(rk::post_launch(ctx, "fri_reduce_pows_kernel"));
+    hipLaunchKernelGGL(fri_reduce_kernel, dim3(queries * sz.n_rounds), dim3(p3k::FRI_REDUCE_TPB), 0, ctx->stream, r);
+    RK_TRY(rk::post_launch(ctx, "fri_reduce_kernel"));
+    return rk_p2_chip_trace(ctx, d_in.u32(), d_mult.u32(), chip_n, d_chip);
+    RK_GUARD_END
+}
 
 int rk_fri_chip_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, rk_fri_chip_size_info* out) {
     return fri_sizes(log_max, blowup_log2, queries, out);

@@ -171,11 +171,12 @@ struct FriArgs {
     uint32_t gen_l, wm;         // the generator of the 2^L subgroup, the extension's W
     const uint32_t *pub, *rec;
     uint32_t *fold, *path, *claims, *chip_in, *chip_mult;
+    uint32_t xcol, shiftm;      // xcol = 1: the fold rows end in X = shift (1 - 2 bit) x0 (rk_fri_reduce_rows_device); claims may then be null
     RK_HD uint32_t lfh(uint32_t rd) const { return L - 1 - rd; }
     RK_HD size_t per_record() const { return 1 + 8 * (size_t)R + 8 * steps_before(R); }
     RK_HD size_t steps_before(uint32_t rd) const { return (size_t)rd * (L - 1) - (size_t)rd * (rd - 1) / 2; }   // sum of lfh(r), r < rd
     RK_HD size_t rec_round(uint32_t rd) const { return 1 + 8 * (size_t)rd + 8 * steps_before(rd); }
-    RK_HD uint32_t fold_width() const { return 41 + R + 2 * (L - 1); }
+    RK_HD uint32_t fold_width() const { return 41 + R + 2 * (L - 1) + xcol; }
     RK_HD uint32_t path_width() const { return 48 + R; }
 };
 constexpr uint32_t FRI_CLAIMS_WIDTH = 8;
@@ -220,9 +221,12 @@ RK_HD void fri_fold_lane(const FriArgs& a, uint32_t q) {
         row[30] = x0, row[31] = bb::sqr(x0);
         row[41 + rd] = bb::ONE;
         for (uint32_t j = 0; j < lfh; j++) row[41 + a.R + j] = (pidx >> j) & 1u ? bb::ONE : 0u;
-        uint32_t* cl = a.claims + ((size_t)q * a.R + rd) * FRI_CLAIMS_WIDTH;
-        cl[0] = qm, cl[1] = rdm, cl[2] = idxm, cl[7] = bb::ONE;
-        for (int k = 0; k < 4; k++) cl[3 + k] = ro.c[k];
+        if (a.xcol) row[fw - 1] = bb::mul(a.shiftm, bit ? bb::neg(x0) : x0);   // the point of the height-(L - rd) coset at idx
+        if (a.claims) {
+            uint32_t* cl = a.claims + ((size_t)q * a.R + rd) * FRI_CLAIMS_WIDTH;
+            cl[0] = qm, cl[1] = rdm, cl[2] = idxm, cl[7] = bb::ONE;
+            for (int k = 0; k < 4; k++) cl[3 + k] = ro.c[k];
+        }
         idx = pidx;
     }
 }
@@ -280,6 +284,84 @@ RK_HD void fri_path_lane(const FriArgs& a, uint32_t t, const uint32_t* tab, cons
     FriPathState st;
     fri_path_begin<M4>(a, t, tab, L, st);
     for (uint32_t s = 0; s < st.lfh; s++) fri_path_step<M4>(a, st, s, tab, L, a.path + (st.off + s) * a.path_width());
+}
+
+// ---- the reduced-openings table (rk_fri_reduce_rows_device; column plan and schedule: raiko_amd/fri_reduce.py).  One row
+// per (query, slot, column); a slot is an opened matrix or the single row of a round without one.  slots = 8 plain words
+// each: round | width | points | offset of the matrix's row in a record | gen(log_n) (Montgomery) | last slot of its round |
+// first row within a query | 0.  pub = alpha 4 | zeta 4 | per slot and point: first power A 4, S 4 (zero where the slot has
+// no such point); rec = per query: index | the opened rows (rk_p3_fri_inputs); apow = alpha^(2^i), i < 32.
+// columns: query | round | idx | X | real | last column | receives | ends the query | column | P | per point: power 4,
+// running sum 4, quotient 4 | the round's running reduced opening 4 | slot one-hot M
+constexpr uint32_t FRI_REDUCE_FIXED = 38, FRI_REDUCE_TPB = 256, FRI_REDUCE_SLOT_WORDS = 8;
+struct FriReduceArgs {
+    uint32_t L, R, Q, M;        // log_max, rounds, queries, slots
+    uint32_t rows_per_query, wm, shiftm, gen_l;
+    size_t per_record;
+    const uint32_t *slots, *pub, *rec, *apow;
+    uint32_t* out;
+    RK_HD uint32_t width() const { return FRI_REDUCE_FIXED + M; }
+};
+RK_HD bb::Ext fri_load_ext(const uint32_t* p) { return bb::Ext{{p[0], p[1], p[2], p[3]}}; }
+struct FriReduceCtx {
+    uint32_t idx, x;            // the query's index entering the round, the point of the round's coset there
+};
+RK_HD FriReduceCtx fri_reduce_begin(const FriReduceArgs& a, uint32_t q, uint32_t rd) {
+    const uint32_t idx = bb::decode(a.rec[a.per_record * q]) >> rd;
+    uint32_t g = a.gen_l;
+    for (uint32_t i = 0; i < rd; i++) g = bb::sqr(g);
+    return FriReduceCtx{idx, bb::mul(a.shiftm, bb::pow(g, bb::bitrev(idx, a.L - rd)))};
+}
+// what a lane carries for its column: the opened value, per point the power A alpha^col and -- `sum` -- first its own
+// term power * P, after the scan the running sum up to and including its column
+struct FriReduceLane {
+    uint32_t p;
+    bb::Ext pw[2], sum[2];
+};
+RK_HD void fri_reduce_term(const FriReduceArgs& a, uint32_t q, uint32_t m, uint32_t col, FriReduceLane& ln) {
+    const uint32_t* slot = a.slots + FRI_REDUCE_SLOT_WORDS * m;
+    ln.p = slot[2] ? a.rec[a.per_record * q + 1 + slot[3] + col] : 0u;
+    bb::Ext ac = bb::ext_one();
+    for (uint32_t i = 0; col >> i; i++)
+        if ((col >> i) & 1u) ac = bb::mul(ac, fri_load_ext(a.apow + 4 * i), a.wm);
+#pragma unroll
+    for (uint32_t j = 0; j < 2; j++) {
+        ln.pw[j] = j < slot[2] ? bb::mul(fri_load_ext(a.pub + 8 + 16 * m + 8 * j), ac, a.wm) : bb::ext_zero();
+        ln.sum[j] = bb::scale(ln.pw[j], ln.p);
+    }
+}
+// one step of a scan: the running sums of a lane further down join this lane's
+RK_HD void fri_reduce_join(FriReduceLane& ln, const bb::Ext& s0, const bb::Ext& s1) {
+    ln.sum[0] = bb::add(ln.sum[0], s0), ln.sum[1] = bb::add(ln.sum[1], s1);
+}
+// the row of (query, slot m, column) once the lane's sums are final; rop = the round's reduced opening before this
+// matrix.  Returns it after this row: on a matrix's last column the quotients (sum - S) / (X - z) join.
+RK_HD bb::Ext fri_reduce_row(const FriReduceArgs& a, uint32_t q, uint32_t m, uint32_t col, const FriReduceCtx& cx, const FriReduceLane& ln,
+                             bb::Ext rop) {
+    const uint32_t* slot = a.slots + FRI_REDUCE_SLOT_WORDS * m;
+    uint32_t* row = a.out + ((size_t)q * a.rows_per_query + slot[6] + col) * a.width();
+    const bool last = col + 1 == slot[1];
+    bb::Ext quot[2] = {bb::ext_zero(), bb::ext_zero()};
+    if (last) {
+        const bb::Ext zeta = fri_load_ext(a.pub + 4);
+#pragma unroll
+        for (uint32_t j = 0; j < 2; j++) {   // fixed trip count: quot and the lane's sums stay in registers
+            if (j >= slot[2]) break;
+            const bb::Ext z = j ? bb::scale(zeta, slot[4]) : zeta;
+            const bb::Ext num = bb::sub(ln.sum[j], fri_load_ext(a.pub + 8 + 16 * m + 8 * j + 4));
+            quot[j] = bb::mul(num, bb::inv(bb::sub(bb::ext_from(cx.x), z), a.wm), a.wm);
+            rop = bb::add(rop, quot[j]);
+        }
+    }
+    row[0] = bb::encode(q), row[1] = bb::encode(slot[0]), row[2] = bb::encode(cx.idx), row[3] = cx.x, row[4] = bb::ONE;
+    row[5] = last ? bb::ONE : 0u, row[6] = last && slot[5] ? bb::ONE : 0u, row[7] = last && m + 1 == a.M ? bb::ONE : 0u;
+    row[8] = bb::encode(col), row[9] = ln.p;
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+        for (int k = 0; k < 4; k++) row[10 + 12 * j + k] = ln.pw[j].c[k], row[14 + 12 * j + k] = ln.sum[j].c[k], row[18 + 12 * j + k] = quot[j].c[k];
+    for (int k = 0; k < 4; k++) row[34 + k] = rop.c[k];
+    for (uint32_t s = 0; s < a.M; s++) row[FRI_REDUCE_FIXED + s] = s == m ? bb::ONE : 0u;
+    return rop;
 }
 
 }  // namespace p3k

@@ -101,7 +101,7 @@ def _gen(shape, bits):
     return pow(shape.root_2_27, 1 << (27 - bits), P)
 
 
-def fri_fold_air(shape, ext_w=p3.EXT_W):
+def fri_fold_air(shape, ext_w=p3.EXT_W, coset_shift=None):
     """One row per (query, round), the rounds of a query on consecutive rows.  Enforced per row (degree <= 3):
       pair order      (e0, e1) = (cur, sib) ordered by bit; cur = the joining reduced opening in round 0, afterwards the
                       previous row's folded + this row's joining reduced opening
@@ -111,11 +111,15 @@ def fri_fold_air(shape, ext_w=p3.EXT_W):
       domain point    round 0: x0 = prod_j (1 + b_j (c_j - 1)), c_j = gen(L)^(2^(L-2-j)), through partial-product columns;
                       afterwards x0' = (1 - 2 bit') x0^2   [bitrev(2 p' + b, n) = b 2^(n-1) + bitrev(p', n-1), gen(n+1)^2 = gen(n)]
       final           in the last round folded = the public final polynomial
-    and three sends with multiplicity `real` (0 on padding rows)."""
+    and three sends with multiplicity `real` (0 on padding rows).
+    coset_shift = s (raiko_amd.fri_reduce): one more column X = s (1 - 2 bit) x0 behind the others, the point of the
+    height-(L - rd) coset at idx [bitrev(2 p + b, n) = b 2^(n-1) + bitrev(p, n-1), gen(n)^(2^(n-1)) = -1]; the claim sent
+    becomes (query, round, idx, X, reduced opening).  None: the AIR without it."""
     L, R = shape.log_max, shape.n_rounds
     nb = L - 1
     c = FoldCols(shape)
-    b = AirBuilder(c.width, 12 * R + 4, ext_w)
+    with_x = coset_shift is not None
+    b = AirBuilder(c.width + (1 if with_x else 0), 12 * R + 4, ext_w)
     loc, nxt = b.local, b.next
     ext = lambda at, f=loc: ExtExpr([f(at + k) for k in range(4)], ext_w % P)
     real, bit = loc(c.REAL), loc(c.BIT)
@@ -167,10 +171,12 @@ def fri_fold_air(shape, ext_w=p3.EXT_W):
         for k in range(4):
             tr.assert_zero(cont * (ncur.c[k] - folded.c[k] - nro.c[k]))
         tr.assert_zero(cont * (nxt(c.X0) - (nxt(c.BIT) * (P - 2) + 1) * x0sq))
+    if with_x:
+        b.assert_eq(loc(c.width), x0 * (coset_shift % P) * (1 - bit * 2))
     pair = list(range(c.E0, c.E0 + 8))
     b.send(p3.BUS_POSEIDON2, pair + [c.ZERO] * 8 + list(range(c.DIG, c.DIG + 8)), mult=c.REAL, mult_is_const=False)
     b.send(BUS_FRI_OPEN, [c.Q, c.RD] + list(range(c.DIG, c.DIG + 8)) + [c.PIDX], mult=c.REAL, mult_is_const=False)
-    b.send(BUS_FRI_CLAIM, [c.Q, c.RD, c.IDX] + list(range(c.RO, c.RO + 4)), mult=c.REAL, mult_is_const=False)
+    b.send(BUS_FRI_CLAIM, [c.Q, c.RD, c.IDX] + ([c.width] if with_x else []) + list(range(c.RO, c.RO + 4)), mult=c.REAL, mult_is_const=False)
     return b.build()
 
 
