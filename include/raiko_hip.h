@@ -730,6 +730,10 @@ int rk_air_compile(rk_air* air, rk_ctx* ctx);
  * ready to be an on_device rk_p3_table.  params NULL = the SP1 preset. */
 uint32_t rk_p2_chip_width(const rk_params* params);
 int rk_p2_chip_air(const rk_params* params, uint32_t bus, rk_air** out);
+/* rk_p2_chip_air_ex: the same step list and width with the receive (in[0..W), out[0..n_out)), n_out 8 or 16: with 16 the
+ * chip hands out the whole state after the permutation, what a sponge over more than one block carries from one
+ * permutation to the next.  rk_p2_chip_air is n_out = 8; rk_p2_chip_trace writes the rows of either. */
+int rk_p2_chip_air_ex(const rk_params* params, uint32_t bus, uint32_t n_out, rk_air** out);
 int rk_p2_chip_trace(rk_ctx* ctx, const uint32_t* d_inputs, const uint32_t* d_mult, size_t n, uint32_t* d_trace);
 /* One table of a proof.  trace: row-major 2^log_height x width Montgomery words (Plonky3's RowMajorMatrix), in host
  * memory or -- on_device = 1 -- in the memory of the context's GPU (left untouched). */
@@ -818,7 +822,8 @@ int rk_fri_chip_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2,
  * sum_k alpha^k (p_k(x) - y_k) / (x - z_k), is grouped by (matrix, point) into (sum_k alpha^k p_k(x) - S) / (x - z) with
  * S = sum_k alpha^k y_k over the same absolute powers; S, the group's first power A and z do not depend on the query.
  * Still free in that statement: the query indices, the opened values themselves (one cell P per query and column: their
- * Merkle openings are not proven) and the transcript-derived public values, which the host binds to the shard proof.
+ * Merkle openings are not proven here; rk_fri_open_* below does) and the transcript-derived public values, which the host
+ * binds to the shard proof.
  * rk_p3_fri_inputs: rk_p3_verify (same arguments, same verdict) that on verdict 0 also hands back, as Montgomery words,
  *   shape:   L, R, blowup_log2, queries
  *   layout:  per opened matrix, in the verifier's order (trace batch per table, then the permutation batch, then every
@@ -856,6 +861,43 @@ int rk_fri_reduce_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log
                               const uint32_t* d_fold_publics, const uint32_t* d_fold_records, const uint32_t* d_reduce_publics,
                               const uint32_t* d_inputs, uint32_t* d_fold, size_t fold_capacity, uint32_t* d_path, size_t path_capacity,
                               uint32_t* d_reduce, size_t reduce_capacity, uint32_t* d_chip, size_t chip_capacity);
+/* The input-batch Merkle openings of the FRI query check as lookup tables: a third statement beside the two above (AIRs
+ * and host witness: raiko_amd/fri_open.py; the scope of the other two and p2_pad_free = 1).  Six tables: fold', path,
+ * reduce'' (the reduce table with sponge columns: the opened cells P of the matrices of one (round, batch) are absorbed
+ * in place, the group's digest is sent to ipath), ipath (one row per query, batch and Merkle level of the three input
+ * trees: compress with the proof's sibling, and where shorter matrices join compress(node, their digest), up to the
+ * batch's root, a public value), the chip, and a state chip (the same permutation AIR with all 16 output cells in its
+ * receive, rk_p2_chip_air_ex) that the sponge's permutations are looked up in.
+ * rk_p3_fri_input_paths: rk_p3_verify (same arguments, same verdict) that on verdict 0 also hands back, as Montgomery words,
+ *   publics: trace root 8 | permutation root 8 (zeros when no table has lookups) | quotient root 8 | log_pmax (the log
+ *            LDE height of the permutation batch's tallest matrix, 0 without one)
+ *   records: per query: trace path 8 L | permutation path 8 log_pmax | quotient path 8 L
+ * with the capacity protocol of rk_p3_fri_inputs. */
+int rk_p3_fri_input_paths(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                          const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* publics, size_t publics_capacity,
+                          uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words);
+/* The six tables for a shape and a layout.  n_groups = the (round, batch) groups of a query, n_batches = the input trees
+ * (2 or 3); state_rows = queries x the sponge permutations of a query, chip_rows = those of the reduce statement plus one
+ * per ipath row and injection.  roots_words / paths_words: what rk_p3_fri_input_paths hands back. */
+typedef struct {
+    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, reserved;
+    uint32_t fold_width, path_width, reduce_width, ipath_width, chip_width, state_width;
+    uint32_t fold_log_height, path_log_height, reduce_log_height, ipath_log_height, chip_log_height, state_log_height;
+    uint64_t fold_rows, path_rows, reduce_rows, ipath_rows, chip_rows, state_rows, rows_per_query;
+    uint64_t fold_publics_words, fold_records_words, reduce_publics_words, inputs_words, roots_words, paths_words;
+} rk_fri_open_size_info;
+int rk_fri_open_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                      rk_fri_open_size_info* out);
+/* The rows of all six tables on the GPU: the kernels of rk_fri_reduce_rows_device (the reduce rows at the wider stride),
+ * then a sponge kernel (one lane per query and group: the chain of permutations over the group's cells), a fill kernel
+ * (one lane per reduce row: the sponge columns), an ipath kernel (one lane per query and batch over d_paths, the records
+ * of rk_p3_fri_input_paths; d_roots = its publics) and rk_p2_chip_trace twice.  Refusals as rk_fri_reduce_rows_device,
+ * and a context whose sponge pads (p2_pad_free = 0) is RK_ERR_INVALID; all before anything is launched. */
+int rk_fri_open_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                            const uint32_t* d_fold_publics, const uint32_t* d_fold_records, const uint32_t* d_reduce_publics,
+                            const uint32_t* d_inputs, const uint32_t* d_roots, const uint32_t* d_paths, uint32_t* d_fold, size_t fold_capacity,
+                            uint32_t* d_path, size_t path_capacity, uint32_t* d_reduce, size_t reduce_capacity, uint32_t* d_ipath,
+                            size_t ipath_capacity, uint32_t* d_chip, size_t chip_capacity, uint32_t* d_state, size_t state_capacity);
 /* exact proof size for the tables' shapes (log_height, width, air); 0 for shapes rk_p3_prove rejects */
 size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables);
 /* Many independent proofs -- the shards of one SP1 execution -- with `batch` of them in flight per GPU: what SP1's

@@ -130,6 +130,15 @@ class RkFriReduceSizeInfo(C.Structure):
                                           "fold_records_words", "reduce_publics_words", "inputs_words")]
 
 
+class RkFriOpenSizeInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "reserved", "fold_width", "path_width",
+                                          "reduce_width", "ipath_width", "chip_width", "state_width", "fold_log_height", "path_log_height",
+                                          "reduce_log_height", "ipath_log_height", "chip_log_height", "state_log_height")] + \
+               [(n, C.c_uint64) for n in ("fold_rows", "path_rows", "reduce_rows", "ipath_rows", "chip_rows", "state_rows", "rows_per_query",
+                                          "fold_publics_words", "fold_records_words", "reduce_publics_words", "inputs_words", "roots_words",
+                                          "paths_words")]
+
+
 class RkAirInfo(C.Structure):
     _fields_ = [("n_steps", C.c_uint64), ("n_ops", C.c_uint64), ("n_constraints", C.c_uint32), ("max_degree", C.c_uint32),
                 ("log_quotient_degree", C.c_uint32), ("n_fp_slots", C.c_uint32)]
@@ -278,6 +287,7 @@ SYMBOLS = {
     "rk_air_create_lookup": (C.c_int, [_vp, _sz, _u32, _u32, u32p, _u32, _sz, _u32, C.POINTER(_vp)]),
     "rk_p2_chip_width": (_u32, [C.POINTER(RkParams)]),
     "rk_p2_chip_air": (C.c_int, [C.POINTER(RkParams), _u32, C.POINTER(_vp)]),
+    "rk_p2_chip_air_ex": (C.c_int, [C.POINTER(RkParams), _u32, _u32, C.POINTER(_vp)]),
     "rk_p2_chip_trace": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "rk_air_get_steps": (C.c_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "rk_air_destroy": (C.c_int, [_vp]),
@@ -295,6 +305,11 @@ SYMBOLS = {
                                    C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "rk_fri_reduce_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, C.POINTER(RkFriReduceSizeInfo)]),
     "rk_fri_reduce_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
+    "rk_p3_fri_input_paths": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
+                                        C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_fri_open_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, C.POINTER(RkFriOpenSizeInfo)]),
+    "rk_fri_open_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
+                                          _vp, _sz, _vp, _sz]),
     "rk_p3_last_timing": (C.c_int, [_vp, C.POINTER(RkP3Timing)]),
     "rk_p3_prove_shards": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
     "rk_comm_unique_id": (C.c_int, [C.c_char_p]),

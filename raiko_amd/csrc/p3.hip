@@ -762,9 +762,16 @@ struct FriInputs {
     std::vector<uint32_t> records;   // per query: index | trace rows | permutation rows | quotient rows
     size_t per_record = 0;
 };
+// rk_p3_fri_input_paths: the commitments of the three input batches and, per query, the Merkle paths of their openings
+struct FriPaths {
+    uint32_t log_max = 0, n_rounds = 0, blowup_log2 = 0, queries = 0;
+    std::vector<uint32_t> publics;   // trace root 8 | permutation root 8 (zeros without one) | quotient root 8 | log_pmax
+    std::vector<uint32_t> records;   // per query: trace path 8 L | permutation path 8 log_pmax | quotient path 8 L
+    size_t per_record = 0;
+};
 int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init,
               const uint32_t* proof, size_t words, bool one_thread = false, FriCapture* cap = nullptr,
-              FriInputs* inp = nullptr) {
+              FriInputs* inp = nullptr, FriPaths* pth = nullptr) {
     rk_params def;
     rk::params_preset(&def, RK_PRESET_SP1);
     const rk_params& par = params ? *params : def;
@@ -946,7 +953,7 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
                 group(log_n[t] + blow, y_chunk[t] + 16 * (size_t)j, 4);
             }
     }
-    auto check_query = [&](uint32_t index, Reader r, uint32_t* rec, uint32_t* inrec) -> int {
+    auto check_query = [&](uint32_t index, Reader r, uint32_t* rec, uint32_t* inrec, uint32_t* prec) -> int {
         // every table is in the trace and the quotient batch: both trees have the global maximum height; the permutation
         // batch only holds the tables with lookups
         const uint32_t* trows = r.take(trow);
@@ -961,6 +968,11 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
             std::memcpy(inrec, trows, 4 * trow);
             if (n_perm) std::memcpy(inrec + trow, prows, 4 * prow);
             std::memcpy(inrec + trow + prow, qrows, 4 * qrow);
+        }
+        if (prec) {
+            std::memcpy(prec, tpath, 32 * (size_t)log_max);
+            if (n_perm) std::memcpy(prec + 8 * (size_t)log_max, ppath, 32 * (size_t)log_pmax);
+            std::memcpy(prec + 8 * (size_t)(log_max + log_pmax), qpath, 32 * (size_t)log_max);
         }
         if (rk_mmcs_verify(&par, th.data(), tw.data(), n_tables, index, trows, tpath, troot) != 0) return 5;
         if (n_perm && rk_mmcs_verify(&par, ph.data(), pwd.data(), n_perm, index >> (log_max - log_pmax), prows, ppath, proot) != 0) return 5;
@@ -1054,6 +1066,16 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         inp->per_record = 1 + trow + prow + qrow;
         inp->records.assign(inp->per_record * sys.queries, 0);
     }
+    if (pth) {
+        pth->log_max = log_max, pth->n_rounds = n_rounds, pth->blowup_log2 = blow, pth->queries = sys.queries;
+        pth->publics.assign(25, 0);
+        std::memcpy(pth->publics.data(), troot, 32);
+        if (n_perm) std::memcpy(pth->publics.data() + 8, proot, 32);
+        std::memcpy(pth->publics.data() + 16, qroot, 32);
+        pth->publics[24] = bb::encode(log_pmax);
+        pth->per_record = 8 * (size_t)(2 * log_max + log_pmax);
+        pth->records.assign(pth->per_record * sys.queries, 0);
+    }
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_thr = sys.queries >= 16 && !one_thread ? std::max(1u, std::min(4u, hw / 2)) : 1u;
     std::vector<int> first_bad(n_thr, 0);
@@ -1063,7 +1085,8 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
             Reader rq{proof, words};
             rq.pos = q0 + per_query * qi;
             const int rc = check_query(indices[qi], rq, cap ? cap->records.data() + cap->per_record * qi : nullptr,
-                                       inp ? inp->records.data() + inp->per_record * qi : nullptr);
+                                       inp ? inp->records.data() + inp->per_record * qi : nullptr,
+                                       pth ? pth->records.data() + pth->per_record * qi : nullptr);
             if (rc != 0) {
                 first_bad[t] = rc;
                 first_at[t] = qi;
@@ -1450,6 +1473,29 @@ int rk_p3_fri_inputs(const rk_params* params, const rk_p3_table* tables, uint32_
     std::memcpy(layout, in.layout.data(), in.layout.size() * 4);
     std::memcpy(publics, in.publics.data(), in.publics.size() * 4);
     std::memcpy(records, in.records.data(), in.records.size() * 4);
+    return 0;
+    RK_GUARD_END
+}
+
+int rk_p3_fri_input_paths(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                          const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* publics, size_t publics_capacity,
+                          uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words) {
+    RK_GUARD_BEGIN
+    if (!shape || !publics_words || !records_words || (publics_capacity && !publics) || (records_capacity && !records)) return RK_ERR_INVALID;
+    *publics_words = *records_words = 0;
+    rk_params def;
+    rk::params_preset(&def, RK_PRESET_SP1);
+    const rk_params& par = params ? *params : def;
+    if (par.p2_width != 16 || par.fri_fold_log2 != 1 || par.p2_pad_free != 1) return RK_ERR_INVALID;   // the sponge columns follow the padding-free sponge
+    FriPaths pth;
+    const int verdict = p3_verify(&par, tables, n_tables, init_words, n_init, proof, proof_words, false, nullptr, nullptr, &pth);
+    if (verdict != 0) return verdict;
+    *publics_words = pth.publics.size();
+    *records_words = pth.records.size();
+    if (pth.publics.size() > publics_capacity || pth.records.size() > records_capacity) return RK_ERR_CAPACITY;
+    shape[0] = bb::encode(pth.log_max), shape[1] = bb::encode(pth.n_rounds), shape[2] = bb::encode(pth.blowup_log2), shape[3] = bb::encode(pth.queries);
+    std::memcpy(publics, pth.publics.data(), pth.publics.size() * 4);
+    std::memcpy(records, pth.records.data(), pth.records.size() * 4);
     return 0;
     RK_GUARD_END
 }

@@ -300,7 +300,9 @@ struct FriReduceArgs {
     size_t per_record;
     const uint32_t *slots, *pub, *rec, *apow;
     uint32_t* out;
+    uint32_t stride;            // words from one row to the next; 0 = the table's own width (rk_fri_open_rows_device: the wider row of reduce'')
     RK_HD uint32_t width() const { return FRI_REDUCE_FIXED + M; }
+    RK_HD uint32_t row_words() const { return stride ? stride : width(); }
 };
 RK_HD bb::Ext fri_load_ext(const uint32_t* p) { return bb::Ext{{p[0], p[1], p[2], p[3]}}; }
 struct FriReduceCtx {
@@ -339,7 +341,7 @@ RK_HD void fri_reduce_join(FriReduceLane& ln, const bb::Ext& s0, const bb::Ext& 
 RK_HD bb::Ext fri_reduce_row(const FriReduceArgs& a, uint32_t q, uint32_t m, uint32_t col, const FriReduceCtx& cx, const FriReduceLane& ln,
                              bb::Ext rop) {
     const uint32_t* slot = a.slots + FRI_REDUCE_SLOT_WORDS * m;
-    uint32_t* row = a.out + ((size_t)q * a.rows_per_query + slot[6] + col) * a.width();
+    uint32_t* row = a.out + ((size_t)q * a.rows_per_query + slot[6] + col) * a.row_words();
     const bool last = col + 1 == slot[1];
     bb::Ext quot[2] = {bb::ext_zero(), bb::ext_zero()};
     if (last) {
@@ -362,6 +364,133 @@ RK_HD bb::Ext fri_reduce_row(const FriReduceArgs& a, uint32_t q, uint32_t m, uin
     for (int k = 0; k < 4; k++) row[34 + k] = rop.c[k];
     for (uint32_t s = 0; s < a.M; s++) row[FRI_REDUCE_FIXED + s] = s == m ? bb::ONE : 0u;
     return rop;
+}
+
+// ---- the input-batch openings (rk_fri_open_rows_device; column plans: raiko_amd/fri_open.py).  reduce'' = the reduce row
+// with the sponge columns behind the slot one-hot: PTR 8 | BUF 8 | CAP 8 | OUT 16 | FLUSH | GEND | BATCH.  A group = the
+// matrices of one (round, batch): consecutive slots, hence consecutive reduce rows, one absorbed cell per row.
+// groups = 8 plain words each: first slot | slots | cells | first row within a query | permutations of the groups before
+// it (per query) | batch | round | 0.  rowinfo = 2 words per row of a query: the cell's number within its group | flags
+// (1 absorbs, 2 ends its group, batch << 2).  levels = 40 words per batch present: batch | B (tree height) | rows of the
+// batches before it | chip inputs of the batches before it | injections | offset of the batch's path in a path record |
+// the group its leaf is | L - B | then per step the group injected there (FRI_OPEN_NONE: none).
+// digests = 8 words per (query, group), written by the sponge lanes and read by the ipath lanes.
+constexpr uint32_t FRI_OPEN_SPONGE_COLS = 43, FRI_OPEN_GROUP_WORDS = 8, FRI_OPEN_LEVEL_WORDS = 40, FRI_OPEN_NONE = 0xffffffffu;
+constexpr uint32_t FRI_OPEN_IPATH_FIXED = 68;
+struct FriOpenArgs {
+    uint32_t L, Q, M, G, NB;    // log_max, queries, slots, groups, batches present
+    uint32_t rows_per_query, stride, sponge_at;   // reduce'': words per row, the first sponge column
+    size_t per_record, per_path, chip_base;       // chip_base: the chip's first input row behind the commit-phase paths
+    const uint32_t *slots, *groups, *rowinfo, *levels, *rec, *paths;
+    uint32_t *reduce, *ipath, *state_in, *state_mult, *chip_in, *chip_mult, *digests;
+    RK_HD uint32_t ipath_width() const { return FRI_OPEN_IPATH_FIXED + NB; }
+};
+// One lane per (query, group), t = g Q + q (group-major: the lanes of a wave share the chain's length): the sponge of
+// hash_elems with pad_free over the group's cells.  OUT goes into the flush rows, the 16 cells entering every permutation
+// into the state chip's inputs, the digest into `digests`.
+template <int M4>
+RK_HD void fri_open_sponge_lane(const FriOpenArgs& a, uint32_t t, const uint32_t* tab, const P2ChipLayout& L) {
+    const uint32_t g = t / a.Q, q = t % a.Q;
+    const uint32_t* gr = a.groups + FRI_OPEN_GROUP_WORDS * g;
+    const uint32_t n_perm = (gr[2] + 7) / 8;
+    const size_t srow0 = (size_t)gr[4] * a.Q + (size_t)q * n_perm;
+    uint32_t* row = a.reduce + ((size_t)q * a.rows_per_query + gr[3]) * a.stride + a.sponge_at + 24;
+    const uint32_t* rec = a.rec + a.per_record * q + 1;
+    uint32_t s[16];
+    for (int i = 0; i < 16; i++) s[i] = 0;
+    uint32_t pos = 0, blk = 0, cell = 0;
+    for (uint32_t m = gr[0]; m < gr[0] + gr[1]; m++) {
+        const uint32_t* slot = a.slots + FRI_REDUCE_SLOT_WORDS * m;
+        for (uint32_t col = 0; col < slot[1]; col++, cell++, row += a.stride) {
+            s[pos++] = rec[slot[3] + col];
+            if (pos == 8 || cell + 1 == gr[2]) {
+                uint32_t* sin = a.state_in + (srow0 + blk) * 16;
+                for (int i = 0; i < 16; i++) sin[i] = s[i];
+                a.state_mult[srow0 + blk] = bb::ONE;
+                chip_permute<16, 13, M4, false>(s, nullptr, tab, L);
+                for (int i = 0; i < 16; i++) row[i] = s[i];
+                pos = 0, blk++;
+            }
+        }
+    }
+    uint32_t* dig = a.digests + ((size_t)q * a.G + g) * 8;
+    for (int i = 0; i < 8; i++) dig[i] = s[i];
+}
+// One lane per reduce row: PTR, BUF, CAP, FLUSH, GEND and BATCH from the P cells of the row's block (the reduce kernel wrote
+// them) and the OUT of the flush row before the block (the sponge lanes wrote it).  No row reads what another lane writes here.
+RK_HD void fri_open_fill_lane(const FriOpenArgs& a, size_t r) {
+    const uint32_t i = (uint32_t)(r % a.rows_per_query);
+    const uint32_t cell = a.rowinfo[2 * i], flags = a.rowinfo[2 * i + 1];
+    if (!(flags & 1u)) return;
+    uint32_t* row = a.reduce + r * a.stride;
+    uint32_t* sp = row + a.sponge_at;
+    const uint32_t pos = cell & 7u;
+    const bool gend = (flags & 2u) != 0;
+    for (uint32_t j = 0; j < 8; j++) sp[j] = j == pos ? bb::ONE : 0u;
+    for (uint32_t j = 0; j <= pos; j++) sp[8 + j] = (row - (size_t)(pos - j) * a.stride)[9];
+    if (cell >= 8) {
+        const uint32_t* prev = row - (size_t)(pos + 1) * a.stride + a.sponge_at + 24;
+        for (uint32_t j = pos + 1; j < 8; j++) sp[8 + j] = prev[j];
+        for (uint32_t j = 0; j < 8; j++) sp[16 + j] = prev[8 + j];
+    }
+    sp[40] = pos == 7 || gend ? bb::ONE : 0u;
+    sp[41] = gend ? bb::ONE : 0u;
+    sp[42] = bb::encode(flags >> 2);
+}
+// ipath columns: cur 8 | sib 8 | bit | left 8 | right 8 | parent 8 | real | last | first | pos | steps left | query | batch |
+// pos >> 1 | injects | ex 8 | node 8 | round of the leaf (first row) | round of the injection | batch one-hot NB.
+// One lane per (query, batch), t = k Q + q (batch-major: the lanes of a wave share the tree's height), walks the levels of
+// rk_mmcs_verify: parent = compress(left, right), and where a group of shorter matrices joins node = compress(parent, ex);
+// rows (rows before + q B + s), and the chip inputs of its compressions in the order it performs them.
+template <int M4>
+RK_HD void fri_open_ipath_lane(const FriOpenArgs& a, uint32_t t, const uint32_t* tab, const P2ChipLayout& L) {
+    const uint32_t k = t / a.Q, q = t % a.Q;
+    const uint32_t* lv = a.levels + FRI_OPEN_LEVEL_WORDS * k;
+    const uint32_t B = lv[1], w = a.ipath_width();
+    uint32_t pos = bb::decode(a.rec[a.per_record * q]) >> lv[7];
+    uint32_t cur[8];
+    const uint32_t* leaf = a.digests + ((size_t)q * a.G + lv[6]) * 8;
+    for (int i = 0; i < 8; i++) cur[i] = leaf[i];
+    uint32_t* row = a.ipath + ((size_t)lv[2] + (size_t)q * B) * w;
+    size_t chip = a.chip_base + lv[3] + (size_t)q * (B + lv[4]);
+    const uint32_t* sib = a.paths + a.per_path * q + lv[5];
+    for (uint32_t s = 0; s < B; s++, row += w, sib += 8) {
+        const uint32_t bit = pos & 1u, cnt = B - s;
+        uint32_t c[16];
+        for (int i = 0; i < 8; i++) {
+            c[i] = bit ? sib[i] : cur[i];
+            c[8 + i] = bit ? cur[i] : sib[i];
+            row[i] = cur[i], row[8 + i] = sib[i], row[17 + i] = c[i], row[25 + i] = c[8 + i];
+        }
+        uint32_t* cin = a.chip_in + chip * 16;
+        for (int i = 0; i < 16; i++) cin[i] = c[i];
+        a.chip_mult[chip++] = bb::ONE;
+        chip_permute<16, 13, M4, false>(c, nullptr, tab, L);
+        for (int i = 0; i < 8; i++) row[33 + i] = cur[i] = c[i];
+        row[16] = bit ? bb::ONE : 0u;
+        row[41] = bb::ONE;
+        row[42] = s + 1 == B ? bb::ONE : 0u;
+        row[43] = s == 0 ? bb::ONE : 0u;
+        row[44] = bb::encode(pos);
+        row[45] = bb::encode(cnt);
+        row[46] = bb::encode(q), row[47] = bb::encode(lv[0]), row[48] = bb::encode(pos >> 1);
+        const uint32_t gi = lv[8 + s];
+        if (gi != FRI_OPEN_NONE) {
+            const uint32_t* ex = a.digests + ((size_t)q * a.G + gi) * 8;
+            for (int i = 0; i < 8; i++) c[i] = cur[i], c[8 + i] = row[50 + i] = ex[i];
+            cin = a.chip_in + chip * 16;
+            for (int i = 0; i < 16; i++) cin[i] = c[i];
+            a.chip_mult[chip++] = bb::ONE;
+            chip_permute<16, 13, M4, false>(c, nullptr, tab, L);
+            for (int i = 0; i < 8; i++) cur[i] = c[i];
+            row[49] = bb::ONE;
+            row[67] = bb::encode(a.L + 1 - cnt);
+        }
+        for (int i = 0; i < 8; i++) row[58 + i] = cur[i];
+        if (s == 0) row[66] = bb::encode(a.L - cnt);
+        for (uint32_t j = 0; j < a.NB; j++) row[FRI_OPEN_IPATH_FIXED + j] = j == k ? bb::ONE : 0u;
+        pos >>= 1;
+    }
 }
 
 }  // namespace p3k

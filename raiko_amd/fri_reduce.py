@@ -22,8 +22,8 @@ group's first power A do not depend on the query: they are public values, recomp
           dropped, repeated or reordered.
   chip    p3.poseidon2_chip_air.
 
-Still free: the query indices, the opened values P (THE SEAM: an input-openings table will have to receive them from the
-Merkle openings of the three input batches) and the transcript-derived public values (alpha, zeta, A, S, beta, roots,
+Still free: the query indices, the opened values P (THE SEAM of this statement: raiko_amd.fri_open closes it with a sponge
+over the P cells and the Merkle paths of the three input batches) and the transcript-derived public values (alpha, zeta, A, S, beta, roots,
 final polynomial), which verify_reduce_statement recomputes from the shard proof and verifies the proof against.
 
 statement / airs / witness / host_tables / device_tables / prove / verify_reduce_statement are the calls, as in fri_chip."""
@@ -89,11 +89,59 @@ def reduce_public_at(m, j):
     return 8 + 16 * m + 8 * j, 8 + 16 * m + 8 * j + 4
 
 
-def fri_reduce_air(shape, slots, ext_w=p3.EXT_W):
-    """the reduce table (module docstring).  Every constraint has degree <= 3."""
+SPONGE_COLS = 43        # PTR 8 | BUF 8 | CAP 8 | OUT 16 | FLUSH | GEND | BATCH, behind the slot one-hot (raiko_amd.fri_open)
+BUS_POSEIDON2_STATE, BUS_IN_LEAF = 9, 10
+
+
+def _sponge_constraints(b, c, slots, batches, pick, nsel):
+    """reduce'' of raiko_amd.fri_open: the padding-free sponge of every (round, batch) group over the P cells of its rows,
+    one cell per row.  batches: per slot its batch, None for the single row of a round without a matrix."""
+    M = len(slots)
+    loc, nxt = b.local, b.next
+    PTR, BUF, CAP, OUT, FLUSH, GEND, BATCH = (c.width + k for k in (0, 8, 16, 24, 40, 41, 42))
+    first, tr = b.when_first_row(), b.when_transition()
+    real, lastc, pv, flush, gend = loc(c.REAL), loc(c.LASTC), loc(c.PV), loc(FLUSH), loc(GEND)
+    ptr, nptr = [loc(PTR + j) for j in range(8)], [nxt(PTR + j) for j in range(8)]
+    absorbs = pick([0 if bt is None else 1 for bt in batches])
+    nabsorbs = F._sum([nsel[m] for m in range(M) if batches[m] is not None])
+    ends = [int(batches[m] is not None and (m + 1 == M or batches[m + 1] != batches[m] or slots[m + 1].rd != slots[m].rd)) for m in range(M)]
+    for v in ptr:
+        b.assert_zero(v * (v - 1))
+    b.assert_eq(F._sum(ptr), absorbs)                              # one position on an absorbing row, none elsewhere
+    for j in range(8):
+        b.assert_zero(ptr[j] * (loc(BUF + j) - pv))
+    b.assert_eq(gend, lastc * pick(ends))
+    b.assert_eq(loc(BATCH), pick([bt or 0 for bt in batches]))
+    b.assert_eq(flush, ptr[7] + gend - ptr[7] * gend)
+    # a group starts from the zero state at position 0: on the first row, behind a group end and behind the single row of
+    # a round without a matrix
+    start = gend + real - absorbs
+    first.assert_eq(ptr[0], absorbs)
+    tr.assert_zero(start * (nptr[0] - nabsorbs))
+    for j in range(16):
+        if j:
+            first.assert_zero(loc(BUF + j))
+            tr.assert_zero(start * nxt(BUF + j))                   # BUF 1..7 and CAP 0..7 (CAP follows BUF)
+    cont = absorbs - flush                                         # the next row goes on in this block
+    tr.assert_zero(cont * nptr[0])
+    for j in range(7):
+        tr.assert_zero(cont * (nptr[j + 1] - ptr[j]))
+    for j in range(8):
+        tr.assert_zero(cont * (1 - nptr[j]) * (nxt(BUF + j) - loc(BUF + j)))
+        tr.assert_zero(cont * (nxt(CAP + j) - loc(CAP + j)))
+    fl = flush - gend                                              # the next row starts the group's next block
+    tr.assert_zero(fl * (nptr[0] - 1))
+    for j in range(1, 16):
+        tr.assert_zero(fl * (nxt(BUF + j) - loc(OUT + j)))
+    return PTR, BUF, OUT, FLUSH, GEND, BATCH
+
+
+def fri_reduce_air(shape, slots, ext_w=p3.EXT_W, sponge=False):
+    """the reduce table (module docstring).  Every constraint has degree <= 3.  sponge: False, or the batch of every slot
+    (None for the single row of a round without a matrix): reduce'' of raiko_amd.fri_open, SPONGE_COLS more columns."""
     M = len(slots)
     c = ReduceCols(M)
-    b = AirBuilder(c.width, 8 + 16 * M, ext_w)
+    b = AirBuilder(c.width + (SPONGE_COLS if sponge else 0), 8 + 16 * M, ext_w)
     loc, nxt = b.local, b.next
     ext = lambda at, f=loc: ExtExpr([f(at + k) for k in range(4)], ext_w % P)
     pub = lambda at: ExtExpr([b.public(at + k) for k in range(4)], ext_w % P)
@@ -156,7 +204,12 @@ def fri_reduce_air(shape, slots, ext_w=p3.EXT_W):
     for k in range(4):                                             # the round's reduced opening: starts anew behind a receiving row
         first.assert_eq(rop.c[k], quots[0].c[k] + quots[1].c[k])
         tr.assert_eq(nrop.c[k], (1 - rcv) * rop.c[k] + nquots[0].c[k] + nquots[1].c[k])
+    if sponge:
+        PTR, BUF, OUT, FLUSH, GEND, BATCH = _sponge_constraints(b, c, slots, list(sponge), pick, nsel)
     b.receive(BUS_FRI_CLAIM, [c.Q, c.RD, c.IDX, c.X] + list(range(c.ROP, c.ROP + 4)), mult=c.RCV, mult_is_const=False)
+    if sponge:
+        b.send(BUS_POSEIDON2_STATE, list(range(BUF, BUF + 32)), mult=FLUSH, mult_is_const=False)
+        b.send(BUS_IN_LEAF, [c.Q, BATCH, c.RD, c.IDX] + list(range(OUT, OUT + 8)), mult=GEND, mult_is_const=False)
     return b.build()
 
 

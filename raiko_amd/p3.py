@@ -534,13 +534,14 @@ def last_timing(hal) -> dict:
 BUS_POSEIDON2 = 4
 
 
-def poseidon2_chip_air(params=None, bus=BUS_POSEIDON2):
+def poseidon2_chip_air(params=None, bus=BUS_POSEIDON2, n_out=8):
     """rk_p2_chip_air: one row = one Poseidon2 permutation of the parameter set's instance (params None = the SP1 preset),
     receiving (bus: in[0..W), out[0..8)) multiplicity times -- the table a recursion / compress layer looks its hashing up in.
+    n_out = 16 (rk_p2_chip_air_ex): the receive holds the whole state after the permutation, what a sponge carries on.
     The step list is written by the library; .steps is read back (rk_air_get_steps) so that a checker can evaluate it too."""
     lib = _lib.load()
     h = C.c_void_p()
-    _lib.check(None, lib.rk_p2_chip_air(C.byref(params) if params is not None else None, bus, C.byref(h)))
+    _lib.check(None, lib.rk_p2_chip_air_ex(C.byref(params) if params is not None else None, bus, n_out, C.byref(h)))
     n = C.c_size_t(0)
     lib.rk_air_get_steps(h, None, 0, C.byref(n))
     steps = np.zeros((n.value, 3), dtype=np.uint32)
@@ -548,7 +549,7 @@ def poseidon2_chip_air(params=None, bus=BUS_POSEIDON2):
     width = int(lib.rk_p2_chip_width(C.byref(params) if params is not None else None))
     w_state = 16 if width == 314 else 24
     out0 = width - 1 - w_state                      # the last external round's state: the permutation's output
-    air = Air(steps, width, 0, [Interaction(RECEIVE, bus, list(range(w_state)) + list(range(out0, out0 + 8)), width - 1)])
+    air = Air(steps, width, 0, [Interaction(RECEIVE, bus, list(range(w_state)) + list(range(out0, out0 + n_out)), width - 1)])
     air._handle = h
     air.state_width, air.out_col = w_state, out0
     return air
