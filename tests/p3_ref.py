@@ -21,6 +21,18 @@ domain.rs, p3-challenger duplex_challenger.rs, RECALLED):
 * `recombine`: quotient(zeta) = sum_j zps_j * sum_e x^e chunk_j[e](zeta), zps_j = prod_(i != j) Z_(D_i)(zeta) /
   Z_(D_i)(first point of D_j), Z_(D_i)(y) = (y / (s w^i))^n - 1; for a trace that satisfies its AIR this equals
   fold(zeta) / Z_H(zeta), with the fold taken over the opened trace values.
+
+Tables with interactions (sp1-core's LogUp argument: lookup/interaction.rs, stark/permutation.rs, RECALLED; the
+constraints are the ones raiko_amd/p3.py::_perm_constraints states):
+
+* `perm_trace`: per interaction rlc = alpha + bus + sum_j beta^(j+1) x_j and the term +-mult / rlc (send +, receive -);
+  entry b of a row = the terms of interactions 2b and 2b + 1; the last extension column is the inclusive running sum of
+  the rows' totals.  The cumulative sum is its last row.
+* the leaves of `eval_steps`: PERM_LOCAL / PERM_NEXT a = base column a of the permutation trace (embedded on the
+  quotient coset, an extension value where it is opened), CHALLENGE a = word a of [alpha | 1 | beta | beta^2 ..],
+  CUMSUM a = word a of the table's cumulative sum.
+* `open_columns_at`: the O(n) barycentric opening f(z) = (z^n - 1) / n * sum_i f_i g^i / (z - g^i), for tables too
+  tall for the dense `interpolate` (which stays, and cross-checks it at small k).
 """
 import numpy as np
 
@@ -78,6 +90,25 @@ def eval_base_poly_at(coeffs, z, W):
     """(m, 4): the extension values at z of the m columns of base coefficients (n, m)"""
     pw = F.ext_powers(z, coeffs.shape[0], W)
     return matmod(np.ascontiguousarray(pw.T), coeffs).T
+
+
+def open_columns_at(values, k, z, preset):
+    """[extension tuple per column]: the interpolants over H_n (n = 2^k) of the canonical base columns `values` (n, m)
+    at the extension point z outside H_n, by the barycentric formula f(z) = (z^n - 1) / n * sum_i f_i g^i / (z - g^i):
+    O(n) per column, one vext_inv_many per point"""
+    W, gen = PRESETS[preset][:2]
+    n = 1 << k
+    values = np.asarray(values, dtype=np.uint64).reshape(n, -1)
+    gi = powers(F.root(k, gen), n)
+    den = np.empty((n, 4), dtype=np.uint64)
+    den[:, 0] = F.vsub(int(z[0]) % P, gi)
+    den[:, 1:] = np.array([int(c) % P for c in z[1:]], dtype=np.uint64)
+    wgt = F.vext_scale(F.vext_inv_many(den, W), gi)                       # g^i / (z - g^i)
+    acc = np.zeros((values.shape[1], 4), dtype=np.uint64)
+    for at in range(0, n, 1 << 12):                                          # matmod's inner dimension stays <= 2^12
+        acc = F.vadd(acc, matmod(np.ascontiguousarray(values[at:at + (1 << 12)].T), wgt[at:at + (1 << 12)]))
+    scale = F.ext_scale(F.ext_sub(F.ext_pow(tuple(int(c) for c in z), n, W), (1, 0, 0, 0)), F.inv(n))
+    return [tuple(int(c) for c in r) for r in F.vext_mul(acc, np.array(scale, dtype=np.uint64), W)]
 
 
 # ---------------------------------------------------------------- transcript
@@ -162,9 +193,10 @@ def transcript(preset, tables, init_canonical, pf):
 
 
 # ---------------------------------------------------------------- the AIR over extension arrays
-def eval_steps(air, local, nxt, public, sel, alpha, W):
+def eval_steps(air, local, nxt, public, sel, alpha, W, perm=None):
     """folded constraints: local / nxt (m, width, 4), public canonical, sel = (is_first, is_last, is_trans) (m, 4) each;
-    -> (m, 4).  Main-trace AIRs only."""
+    perm (AIRs with interactions) = (permutation local (m, perm_width, 4), next, challenge words, cumulative sum words);
+    -> (m, 4)"""
     m = local.shape[0]
     embed = lambda v: np.broadcast_to(np.array([v % P, 0, 0, 0], dtype=np.uint64), (m, 4))
     vals, acc = [], np.zeros((m, 4), dtype=np.uint64)
@@ -180,6 +212,14 @@ def eval_steps(air, local, nxt, public, sel, alpha, W):
             vals.append(embed(int(public[a])))
         elif op in (p3.IS_FIRST_ROW, p3.IS_LAST_ROW, p3.IS_TRANSITION):
             vals.append(sel[op - p3.IS_FIRST_ROW])
+        elif op == p3.PERM_LOCAL:
+            vals.append(perm[0][:, a])
+        elif op == p3.PERM_NEXT:
+            vals.append(perm[1][:, a])
+        elif op == p3.CHALLENGE:
+            vals.append(embed(int(perm[2][a])))
+        elif op == p3.CUMSUM:
+            vals.append(embed(int(perm[3][a])))
         elif op == p3.ADD:
             vals.append(F.vadd(vals[a], vals[b]))
         elif op == p3.SUB:
@@ -191,7 +231,7 @@ def eval_steps(air, local, nxt, public, sel, alpha, W):
         elif op == p3.ASSERT_ZERO:
             acc = F.vadd(F.vext_mul(acc, a4, W), vals[a])
         else:
-            raise ValueError("eval_steps: permutation leaves are not covered (op %d)" % op)
+            raise ValueError("eval_steps: no such opcode (%d)" % op)
     return acc
 
 
@@ -202,19 +242,74 @@ def _embed_cols(v):
     return out
 
 
+# ---------------------------------------------------------------- the permutation (LogUp) argument
+MAX_VALUES = 64      # the longest tuple an interaction may hold
+
+
+def challenge_words(pch, W, n_values=MAX_VALUES):
+    """[alpha | 1 | beta | beta^2 .. beta^n_values] as canonical base words: what a CHALLENGE leaf indexes"""
+    alpha, beta = pch
+    out, cur = [int(c) for c in alpha], (1, 0, 0, 0)
+    for _ in range(n_values + 1):
+        out += [int(c) for c in cur]
+        cur = F.ext_mul(cur, tuple(int(c) for c in beta), W)
+    return out
+
+
+def perm_entries(trace, interactions, chal, W):
+    """(entries (n, nb, 4), row totals (n, 4)) of a canonical main trace (n, width): term i = +-mult_i / rlc_i,
+    rlc_i = chal[0] + chal[1] bus + sum_j chal[2 + j] x_j over the extension elements chal[e] = words 4e .. 4e + 3 (send +,
+    receive -, mult a constant or a column); entry b = terms 2b and 2b + 1; total = the sum of a row's entries"""
+    trace = np.asarray(trace, dtype=np.uint64)
+    n = trace.shape[0]
+    ch = np.array([int(c) for c in chal], dtype=np.uint64).reshape(-1, 4)
+    nb = (len(interactions) + 1) // 2
+    entries = np.zeros((n, nb, 4), dtype=np.uint64)
+    for i, it in enumerate(interactions):
+        rlc = np.broadcast_to(F.vadd(ch[0], F.vmul(ch[1], it.bus % P)), (n, 4))
+        for j, c in enumerate(it.value_cols):
+            rlc = F.vadd(rlc, F.vext_scale(ch[2 + j], trace[:, c]))
+        m = np.full(n, it.mult % P, dtype=np.uint64) if it.mult_is_const else trace[:, it.mult]
+        if it.kind == p3.RECEIVE:
+            m = F.vsub(0, m)
+        entries[:, i // 2] = F.vadd(entries[:, i // 2], F.vext_scale(F.vext_inv_many(rlc, W), m))
+    return entries, entries.sum(axis=1) % np.uint64(P)                    # nb <= 2^11 terms below 2^31 each
+
+
+def perm_trace(table, pch, preset):
+    """the permutation trace of a table with interactions under the challenges pch = (alpha, beta): canonical uint64
+    (n, 4 (nb + 1)), nb = ceil(L / 2): the nb batch entries, then the inclusive running sum of the row totals"""
+    W = PRESETS[preset][0]
+    its = table.air.interactions
+    assert its and table.log_height <= 32 and len(its) <= 4096
+    entries, totals = perm_entries(F.from_mont(table.trace), its, challenge_words(pch, W, max(len(it.value_cols) for it in its)), W)
+    n = totals.shape[0]
+    phi = np.cumsum(totals, axis=0) % np.uint64(P)                        # canonical terms: below 2^(31 + log_n) <= 2^63
+    return np.concatenate([entries.reshape(n, -1), phi], axis=1)
+
+
 # ---------------------------------------------------------------- the checks
-def trace_openings(table, zeta, preset):
-    """(local, next): the trace interpolants at zeta and zeta * g_n, lists of extension tuples"""
+def openings(values, k, zeta, preset, tall=False):
+    """(at zeta, at zeta * g_n) of canonical base columns (n, m), lists of extension tuples: the dense interpolation, or
+    the O(n) form when tall"""
     W, gen = PRESETS[preset][:2]
-    k = table.log_height
-    C = interpolate(F.from_mont(table.trace), k, gen)
     zn = F.ext_scale(zeta, F.root(k, gen))
+    if tall:
+        return open_columns_at(values, k, zeta, preset), open_columns_at(values, k, zn, preset)
+    C = interpolate(values, k, gen)
     rows = lambda z: [tuple(int(c) for c in r) for r in eval_base_poly_at(C, z, W)]
     return rows(zeta), rows(zn)
 
 
-def quotient_chunks(table, alpha, zeta, preset, blowup_log2):
-    """[chunk j: 4 extension tuples (one per base component)] of the exact quotient"""
+def trace_openings(table, zeta, preset, tall=False):
+    """(local, next): the trace interpolants at zeta and zeta * g_n, lists of extension tuples"""
+    return openings(F.from_mont(table.trace), table.log_height, zeta, preset, tall)
+
+
+def quotient_chunks(table, alpha, zeta, preset, blowup_log2, perm=None):
+    """[chunk j: 4 extension tuples (one per base component)] of the exact quotient.  perm (a table with interactions) =
+    (its permutation trace (n, perm_width) canonical, challenge words, cumulative sum words): on the quotient coset the
+    permutation rows are the interpolants of that trace's base columns, the next row (cyclically) those at x * g"""
     W, gen, s = PRESETS[preset][:3]
     air, k = table.air, table.log_height
     lqd = air.log_quotient_degree()
@@ -231,8 +326,12 @@ def quotient_chunks(table, alpha, zeta, preset, blowup_log2):
     zh = F.vsub(F.vmul(pq[(i * n) % nq], pow(s, n, P)), 1)
     g_inv = F.inv(F.root(k, gen))
     sel = [F.vmul(zh, F.batch_inv(F.vsub(xs, 1))), F.vmul(zh, F.batch_inv(F.vsub(xs, g_inv))), F.vsub(xs, g_inv)]
+    pv = None
+    if perm is not None:
+        pl = matmod(A, interpolate(perm[0], k, gen))
+        pv = (_embed_cols(pl), _embed_cols(np.roll(pl, -qd, axis=0)), perm[1], perm[2])
     acc = eval_steps(air, _embed_cols(local), _embed_cols(nxt), F.from_mont(table.public_values),
-                     [_embed_cols(v) for v in sel], alpha, W)
+                     [_embed_cols(v) for v in sel], alpha, W, pv)
     q = F.vext_scale(acc, F.batch_inv(zh))
     out = []
     for c in range(qd):
@@ -261,8 +360,9 @@ def recombine(chunks, zeta, log_n, lqd, preset):
     return tot
 
 
-def folded_at_zeta(table, local, nxt, alpha, zeta, preset):
-    """fold(zeta) / Z_H(zeta) over opened rows"""
+def folded_at_zeta(table, local, nxt, alpha, zeta, preset, perm=None):
+    """fold(zeta) / Z_H(zeta) over opened rows.  perm = (opened perm_local, opened perm_next, challenge words, cumulative
+    sum words) for a table with interactions"""
     W, gen = PRESETS[preset][:2]
     n = 1 << table.log_height
     one = (1, 0, 0, 0)
@@ -271,27 +371,51 @@ def folded_at_zeta(table, local, nxt, alpha, zeta, preset):
     zg = F.ext_sub(zeta, (g_inv, 0, 0, 0))
     sel = [F.ext_mul(zh, F.ext_inv(F.ext_sub(zeta, one), W), W), F.ext_mul(zh, F.ext_inv(zg, W), W), zg]
     arr = lambda rows: np.array([rows], dtype=np.uint64)
+    pv = None if perm is None else (arr(perm[0]), arr(perm[1]), perm[2], perm[3])
     acc = eval_steps(table.air, arr(local), arr(nxt), F.from_mont(table.public_values),
-                     [np.array([v], dtype=np.uint64) for v in sel], alpha, W)
+                     [np.array([v], dtype=np.uint64) for v in sel], alpha, W, pv)
     return F.ext_mul(tuple(int(v) for v in acc[0]), F.ext_inv(zh, W), W)
 
 
-def check_proof(preset, blowup_log2, tables, init_mont, words, quotient=True):
-    """every check above on one proof; raises AssertionError naming what differs.  quotient=False (or a table with
-    interactions): the trace openings only.  -> (alpha, zeta)"""
+def check_proof(preset, blowup_log2, tables, init_mont, words, quotient=True, tall=False, perm_out=None):
+    """every check above on one proof; raises AssertionError naming what differs.  Tables with interactions: the
+    cumulative sum, then the permutation openings in every base column, and their quotient like any other table's.
+    quotient=False: no quotient chunks.  tall=True (tables too tall for the dense matrices): every opening by the O(n)
+    formula and no quotient; the transcript, trace openings, cumulative sums and permutation openings are still checked.
+    perm_out: a dict that receives {table index: the reference permutation trace}.  -> (alpha, zeta)"""
+    W = PRESETS[preset][0]
     pf = parse(tables, words)
     assert pf["log_n"] == [t.log_height for t in tables]
-    alpha, zeta, _ = transcript(preset, tables, F.from_mont(np.asarray(init_mont, dtype=np.uint64)), pf)
+    alpha, zeta, pch = transcript(preset, tables, F.from_mont(np.asarray(init_mont, dtype=np.uint64)), pf)
+    # the cumulative sums first: they depend on the permutation challenges alone, every later challenge depends on them
+    ptraces, chal = {}, None
+    if pch is not None:
+        chal = challenge_words(pch, W)
+        for pi, ti in enumerate(i for i, t in enumerate(tables) if t.air.perm_width):
+            ptraces[ti] = perm_trace(tables[ti], pch, preset)
+            assert ptraces[ti].shape[1] == tables[ti].air.perm_width
+            assert pf["cumsums"][pi] == [int(v) for v in ptraces[ti][-1, -4:]], "table %d: cumulative sum" % ti
+        if perm_out is not None:
+            perm_out.update(ptraces)
     for ti, (t, op) in enumerate(zip(tables, pf["tables"])):
-        loc, nxt = trace_openings(t, zeta, preset)
+        loc, nxt = trace_openings(t, zeta, preset, tall)
         assert op["local"] == loc, "table %d: trace_local" % ti
         assert op["next"] == nxt, "table %d: trace_next" % ti
-        if not quotient or t.air.perm_width:
+        perm_q = perm_z = None
+        if t.air.perm_width:
+            ploc, pnxt = openings(ptraces[ti], t.log_height, zeta, preset, tall)
+            for what, got, exp in (("perm_local", op["perm_local"], ploc), ("perm_next", op["perm_next"], pnxt)):
+                assert len(got) == len(exp) == t.air.perm_width
+                for c, (g, e) in enumerate(zip(got, exp)):
+                    assert g == e, "table %d: %s column %d of %d" % (ti, what, c, t.air.perm_width)
+            cs = [int(v) for v in ptraces[ti][-1, -4:]]
+            perm_q, perm_z = (ptraces[ti], chal, cs), (ploc, pnxt, chal, cs)
+        if not quotient or tall:
             continue
         lqd = t.air.log_quotient_degree()
-        want = quotient_chunks(t, alpha, zeta, preset, blowup_log2)
+        want = quotient_chunks(t, alpha, zeta, preset, blowup_log2, perm_q)
         for j, (got, exp) in enumerate(zip(op["chunks"], want)):
             assert got == exp, "table %d: quotient chunk %d of %d" % (ti, j, 1 << lqd)
-        assert recombine(want, zeta, t.log_height, lqd, preset) == folded_at_zeta(t, loc, nxt, alpha, zeta, preset), \
+        assert recombine(want, zeta, t.log_height, lqd, preset) == folded_at_zeta(t, loc, nxt, alpha, zeta, preset, perm_z), \
             "table %d: zps recombination" % ti
     return alpha, zeta

@@ -268,3 +268,39 @@ def test_permutation_trace_lane_by_lane(orc, emu, n, w):
         assert ext_mul(chal[0], ext_inv(chal[0])).tolist() == [int(o.to_mont(np.array([1], dtype=np.uint64))[0]), 0, 0, 0]
     finally:
         o.oracle_set_params()
+
+
+@pytest.mark.parametrize("n,L,n_used", [(2, 3, 7), (128, 1, 1), (128, 3, 63), (128, 2, 64), (128, 3, 65), (128, 16, 120),
+                                        (256, 1, 1), (256, 3, 63), (256, 2, 64), (256, 3, 65), (256, 16, 120), (300, 3, 7), (513, 2, 120)])
+def test_permutation_trace_every_row_against_the_exact_reference(emu, n, L, n_used):
+    """p3k::perm_stage / perm_row on every row against tests/p3_ref.py::perm_entries (numpy integers, nothing of the
+    oracle): all batch entries and the row totals.  Half a workgroup and exactly one (128 and 256 rows: the staging's
+    clamp to row n - 1 and its last wave), 1 / 63 / 64 / 65 / 120 used columns (lanes 0..63 alone, the second load per
+    lane from slot 64 on, the cap), a last batch of one, column and constant multiplicities 0, 1, 2, p - 1, a tuple of
+    no values, bus p - 1; 300 and 513 rows: the rows of a partial last workgroup"""
+    import p3_lookup_cases as LC
+    import p3_ref as R
+    log_n = max(1, (n - 1).bit_length())
+    table = LC.edge_table(log_n, L, n_used, seed=n)
+    trace = np.ascontiguousarray(table.trace[:n])
+    its = table.air.interactions
+    kmax = max(len(it.value_cols) for it in its)
+    pch = ((3, P - 1, 0, 9), (P - 5, 2, 77, 1))
+    chal = R.challenge_words(pch, 11, kmax)
+    assert len(chal) == 4 * (kmax + 2)
+    used, flat = [], []
+    slot = lambda c: used.index(c) if c in used else (used.append(c) or len(used) - 1)
+    mont = lambda v: int(o.to_mont(np.array([v], dtype=np.uint64))[0])
+    for it in its:
+        flat += [it.kind, mont(it.bus), int(it.mult_is_const), mont(it.mult) if it.mult_is_const else slot(it.mult), len(it.value_cols)]
+        flat += [slot(c) for c in it.value_cols]
+    assert len(used) == n_used
+    desc = np.concatenate([o.to_mont(np.array(chal, dtype=np.uint64)), np.array(flat, dtype=np.uint32), np.array(used, dtype=np.uint32)]).astype(np.uint32)
+    nb = (L + 1) // 2
+    got = np.full((4 * (nb + 1), n), 0xFFFFFFFF, dtype=np.uint32)
+    emu.emul_perm_entries(got.ctypes.data, trace.ctypes.data, desc.ctypes.data, n, trace.shape[1], len(chal), L, mont(11), n_used, len(chal) + len(flat))
+    entries, totals = R.perm_entries(R.F.from_mont(trace), its, chal, 11)
+    want = np.concatenate([entries.reshape(n, 4 * nb), totals], axis=1)
+    assert int(got.max()) < P
+    bad = np.argwhere(o.from_mont(got).T.astype(np.uint64) != want)
+    assert bad.size == 0, "first differing (row, column): %s" % bad[:4].tolist()

@@ -52,8 +52,9 @@ def test_generated_kernel_gives_the_committed_digest(hal, case):
 
 @pytest.mark.parametrize("case", REF_CASES)
 def test_exact_reference_matches_the_gpu_proof(hal, case):
-    """transcript, trace openings, quotient chunks (tables without lookups) and the zps recombination of tests/p3_ref.py
-    against the GPU's proof words, interpreter and generated kernel"""
+    """transcript, trace openings, quotient chunks and the zps recombination of tests/p3_ref.py against the GPU's proof
+    words, interpreter and generated kernel; tables with lookups: their cumulative sums, permutation openings and
+    quotients as well (tests/test_gpu_p3_lookups.py runs those cases under the generated kernel too)"""
     preset, over, _, _ = P3_CASES[case]
     hal.set_params(preset, **over)
     o.oracle_set_params(preset, **over)          # the Merkle-path case builds its chip rows under the case's parameter set

@@ -382,7 +382,7 @@ def test_power_air_degree(D, lqd):
 @pytest.mark.parametrize("case", REF_CASES)
 def test_exact_reference_matches_the_oracle_proof(params, case):
     """transcript, trace openings, quotient chunks and the zps recombination of tests/p3_ref.py against the oracle's
-    proof words (lookup tables: the trace openings)"""
+    proof words (lookup tables: their cumulative sums, permutation openings and quotients too)"""
     import p3_ref as R
     preset, over, _, _ = P3_CASES[case]
     R.p2_tables(preset)                    # read the preset's constants before the parameter set changes
@@ -433,3 +433,188 @@ def test_exact_reference_notices_a_changed_opening(params):
         s[at] = (int(s[at]) + 1) % P
         with pytest.raises(AssertionError, match=what):
             R.check_proof(preset, 4, tables, init, s)
+
+
+# ---------------------------------------------------------------- the exact reference on tables with interactions
+LOOKUP_REF_CASES = [c for c in REF_CASES if any(perm for _, _, perm in shapes(c))]
+
+
+def test_lookup_cases_of_the_exact_reference():
+    assert {"sp1_lookup_k6", "sp1_lookup_two_rows", "sp1_selfperm_k5", "risc0_lookup_k7_blow2", "sp1_merkle_paths_poseidon2_chip",
+            "sp1_blow4_lookup_beside_deg9", "risc0_blow3_powerperm_deg5", "sp1_blow4_powerperm_deg9", "sp1_lookup_beside_plain",
+            "sp1_wide_tuples_k9"} == set(LOOKUP_REF_CASES)
+
+
+@pytest.mark.parametrize("case", LOOKUP_REF_CASES)
+def test_exact_reference_checks_the_lookups_of_the_oracle_proof(params, case):
+    """every table with interactions of every seeded case: the oracle's cumulative sums, permutation openings (all
+    4 (nb + 1) base columns, at zeta and zeta g) and quotient chunks are the reference's; so are they in the O(n) mode
+    for tall tables (barycentric openings, no dense quotient), which the GPU tests rely on above 2^11 rows"""
+    import p3_ref as R
+    preset, over, _, _ = P3_CASES[case]
+    R.p2_tables(preset)
+    params(preset, **over)
+    tables, init = tables_of(case), init_of(case)
+    pf = o.oracle_p3_prove(tables, init)
+    seen = {}
+    R.check_proof(preset, _blowup(preset, over), tables, init, pf, perm_out=seen)
+    assert sorted(seen) == [i for i, t in enumerate(tables) if t.air.perm_width] != []
+    for ti, pt in seen.items():
+        assert pt.shape == (1 << tables[ti].log_height, tables[ti].air.perm_width)
+    assert R.check_proof(preset, _blowup(preset, over), tables, init, pf, tall=True) == R.check_proof(preset, _blowup(preset, over), tables, init, pf, quotient=False)
+
+
+def test_eval_steps_covers_every_opcode():
+    """no opcode of raiko_amd/p3.py is left to raise, and no table is skipped for having interactions"""
+    import inspect
+    import p3_ref as R
+    src = inspect.getsource(R.eval_steps)
+    for name in ("CONST", "LOCAL", "NEXT", "PUBLIC", "IS_FIRST_ROW", "IS_LAST_ROW", "IS_TRANSITION", "ADD", "SUB", "MUL", "NEG",
+                 "ASSERT_ZERO", "PERM_LOCAL", "PERM_NEXT", "CHALLENGE", "CUMSUM"):
+        assert "p3." + name in src, name
+    assert max(p3.PERM_LOCAL, p3.PERM_NEXT, p3.CHALLENGE, p3.CUMSUM) == 15
+    with pytest.raises(ValueError):
+        R.eval_steps(p3.Air(np.array([[16, 0, 0]], dtype=np.uint32), 1, 0), np.zeros((1, 1, 4), dtype=np.uint64), np.zeros((1, 1, 4), dtype=np.uint64),
+                     [], [np.zeros((1, 4), dtype=np.uint64)] * 3, (1, 0, 0, 0), 11)
+
+
+@pytest.mark.parametrize("log_n,L,n_used,unbalanced", [(1, 3, 7, False), (4, 1, 1, False), (5, 2, 6, True), (6, 3, 7, True), (5, 16, 8, False),
+                                                       (3, 3, 63, False), (3, 2, 64, False), (3, 3, 65, True), (3, 16, 120, False)])
+def test_reference_permutation_trace_satisfies_the_definition(log_n, L, n_used, unbalanced):
+    """tests/p3_ref.py::perm_trace against eval_permutation_constraints row by row, in plain integers, without any proof:
+    per batch entry * prod rlc = sum +-mult * prod_(j != i) rlc_j; phi[0] = sum entries[0]; phi[r + 1] - phi[r] = sum
+    entries[r + 1]; on the edge tables of tests/p3_lookup_cases.py (last batch of one, column and constant multiplicities
+    0, 1, 2, p - 1, both kinds, tuples of 0 to 59 values, bus p - 1), whose own asserts hold"""
+    import field_ref as F
+    import p3_lookup_cases as LC
+    import p3_ref as R
+    W = 11
+    t = LC.edge_table(log_n, L, n_used, seed=3, unbalanced=unbalanced)
+    pch = ((5, 0, P - 1, 77), (P - 2, 1, 0, 12345))
+    pt = R.perm_trace(t, pch, 1)
+    LC.assert_edges(t, pt)
+    its, n, nb = t.air.interactions, 1 << log_n, (L + 1) // 2
+    assert pt.shape == (n, 4 * (nb + 1)) and pt.dtype == np.uint64 and int(pt.max()) < P
+    tr = [[int(v) for v in row] for row in F.from_mont(t.trace)]
+    beta_pow = [(1, 0, 0, 0)]
+    for _ in range(max(len(it.value_cols) for it in its)):
+        beta_pow.append(F.ext_mul(beta_pow[-1], pch[1], W))
+    ext_row = lambda r, b: tuple(int(v) for v in pt[r, 4 * b:4 * b + 4])
+    rows = range(n) if n <= 16 else sorted({0, 1, 2, n // 2 - 1, n // 2, n - 2, n - 1} | {int(v) for v in np.random.default_rng(log_n).integers(0, n, 6)})
+    for r in rows:
+        total = (0, 0, 0, 0)
+        for b in range(nb):
+            pair = its[2 * b:2 * b + 2]
+            rlc, sm = [], []
+            for it in pair:
+                acc = F.ext_add(pch[0], (it.bus % P, 0, 0, 0))
+                for j, c in enumerate(it.value_cols):
+                    acc = F.ext_add(acc, F.ext_scale(beta_pow[j + 1], tr[r][c]))
+                rlc.append(acc)
+                m = it.mult if it.mult_is_const else tr[r][it.mult]
+                sm.append(m % P if it.kind == p3.SEND else -m % P)
+            lhs, rhs = ext_row(r, b), (0, 0, 0, 0)
+            for i in range(len(pair)):
+                lhs = F.ext_mul(lhs, rlc[i], W)
+                term = (sm[i], 0, 0, 0)
+                for j in range(len(pair)):
+                    if j != i:
+                        term = F.ext_mul(term, rlc[j], W)
+                rhs = F.ext_add(rhs, term)
+            assert lhs == rhs, (r, b)
+            total = F.ext_add(total, ext_row(r, b))
+        assert F.ext_sub(ext_row(r, nb), ext_row(r - 1, nb) if r else (0, 0, 0, 0)) == total, r
+
+
+def test_edge_tables_are_proven_by_the_oracle_and_checked_by_the_reference(params):
+    """the edge tables before they judge the GPU: the oracle proves them, both verifiers accept the balanced table and
+    refuse its unbalanced twin with reason 8 (nonzero cumulative sum), and the exact reference reproduces cumulative sums,
+    permutation openings and quotient chunks of both"""
+    import p3_lookup_cases as LC
+    import p3_ref as R
+    R.p2_tables(1)
+    over = dict(queries=3, pow_bits=1)
+    params(1, **over)
+    blob = hal.make_params(1, **over)
+    init = p3.to_mont([4, 2])
+    for log_n, L, n_used in ((1, 3, 7), (7, 3, 7), (5, 1, 1), (4, 2, 64), (6, 16, 8)):
+        for unbalanced in (False, True):
+            t = [LC.edge_table(log_n, L, n_used, seed=9, unbalanced=unbalanced)]
+            pf = o.oracle_p3_prove(t, init)
+            seen = {}
+            R.check_proof(1, 1, t, init, pf, perm_out=seen)
+            LC.assert_edges(t[0], seen[0])
+            want = 8 if unbalanced else 0
+            assert o.oracle_p3_verify(t, pf, init) == want == p3.verify(t, pf, init, params=blob), (log_n, L, n_used, unbalanced)
+
+
+def test_exact_reference_notices_a_changed_lookup_word(params):
+    """one word at a time in each class of words that only tables with interactions have: a cumulative sum, a perm_local
+    word, a perm_next word, a chunk word of such a table -- each is reported under its own name"""
+    import p3_ref as R
+    case = "sp1_lookup_k6"
+    preset, over, _, _ = P3_CASES[case]
+    R.p2_tables(preset)
+    params(preset, **over)
+    tables, init = tables_of(case), init_of(case)
+    pf = o.oracle_p3_prove(tables, init)
+    R.check_proof(preset, 1, tables, init, pf)
+    nt = len(tables)
+    cums = 1 + nt + 16
+    head = cums + 4 * nt + 8                  # ... | the cumulative sums | quotient root | table 0: local, next, perm_local, perm_next, chunks
+    t0, t1 = tables[0].air, tables[1].air
+    pl0 = head + 8 * t0.width
+    size0 = 8 * t0.width + 8 * t0.perm_width + (16 << t0.log_quotient_degree())
+    pn1 = head + size0 + 8 * t1.width + 4 * t1.perm_width
+    assert t0.perm_width == 12 and t1.perm_width == 8
+    for at, what in ((cums + 4 * 2 + 1, "table 2: cumulative sum"), (cums, "table 0: cumulative sum"),
+                     (pl0 + 4 * 9 + 2, "table 0: perm_local column 9 of 12"), (pl0, "table 0: perm_local column 0 of 12"),
+                     (pn1 + 4 * 7 + 3, "table 1: perm_next column 7 of 8"),
+                     (pl0 + 8 * t0.perm_width + 4 * 2 + 1, "table 0: quotient chunk 0 of 2"),
+                     (pl0 + 8 * t0.perm_width + 16 + 4 * 3, "table 0: quotient chunk 1 of 2")):
+        s = pf.copy()
+        s[at] = (int(s[at]) + 1) % P
+        with pytest.raises(AssertionError, match=what):
+            R.check_proof(preset, 1, tables, init, s)
+
+
+@pytest.mark.parametrize("k", [3, 8, 10])
+def test_barycentric_opening_equals_the_dense_one(k):
+    """tests/p3_ref.py::open_columns_at (O(n)) against interpolate + eval_base_poly_at (dense), both presets: columns of
+    random values, a constant column, an impulse, all p - 1; at a random point and at that point times g"""
+    import field_ref as F
+    import p3_ref as R
+    n = 1 << k
+    for preset in (0, 1):
+        W, gen = R.PRESETS[preset][:2]
+        rng = np.random.default_rng(10 * k + preset)
+        v = rng.integers(0, P, size=(n, 7), dtype=np.uint64)
+        v[:, 3], v[:, 4], v[:, 5] = 5, 0, P - 1
+        v[n - 1, 4] = 1
+        C = R.interpolate(v, k, gen)
+        z = tuple(int(c) for c in rng.integers(0, P, 4))
+        for pt in (z, F.ext_scale(z, F.root(k, gen)), (int(z[0]), 0, 0, 0)):
+            want = [tuple(int(c) for c in r) for r in R.eval_base_poly_at(C, pt, W)]
+            assert R.open_columns_at(v, k, pt, preset) == want
+            assert want[3] == (5, 0, 0, 0)
+        a, b = R.openings(v, k, z, preset, tall=True), R.openings(v, k, z, preset)
+        assert a == b
+
+
+def test_more_than_120_used_columns_are_refused():
+    """the staged tile holds 120 columns: 121 distinct columns read by the interactions are refused where the AIR is
+    created, with the library's constraints or the front end's; 120 are taken"""
+    import p3_lookup_cases as LC
+    for L, n_used, fine in ((2, 120, True), (3, 121, False), (2, 122, False)):
+        air, _ = LC.edge_air(L, n_used)
+        own = air.steps[:int(np.flatnonzero(air.steps[:, 0] == p3.ASSERT_ZERO)[0]) + 1]        # the flag's constraint alone
+        if fine:
+            assert air.handle() is not None
+            assert p3.Air(own, air.width, 0, air.interactions, append_lookup_constraints_w=11).n_constraints == air.n_constraints
+            continue
+        with pytest.raises(_lib.RkError) as ei:
+            air.handle()
+        assert ei.value.status == _lib.RK_ERR_INVALID
+        with pytest.raises(_lib.RkError) as ei:
+            p3.Air(own, air.width, 0, air.interactions, append_lookup_constraints_w=11)
+        assert ei.value.status == _lib.RK_ERR_INVALID
