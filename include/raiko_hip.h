@@ -265,7 +265,9 @@ typedef struct {
                                     * ([1], [2]; valid in `accumulate` only, NULL otherwise) */
     const uint32_t* d_lde[3];      /* device, column-major 4*2^po2 x group_size[g]: evaluations on the coset
                                     * 3*w^i, natural order (PolyGroup::evaluated); NULL until committed.
-                                    * (4 = 2^blowup_log2, 3 = coset_shift of the context's rk_params) */
+                                    * (4 = 2^blowup_log2, 3 = coset_shift of the context's rk_params).
+                                    * READ-ONLY, as the type says: d_lde[1] may be the LDE of a code-cache entry
+                                    * (rk_code_cache_configure) that other proofs in flight read too */
     const uint32_t* globals;       /* host */
     uint32_t n_globals;
     const uint32_t* mix;           /* host: the n_accum_mix elements drawn before the accum commit */
@@ -457,6 +459,21 @@ const char* rk_session_last_error(int device);
 /* how many segments `device` proved in the last session it took part in (the balance of the work queue) */
 int rk_session_last_proven(int device, size_t* count);
 int rk_session_release(void);
+/* ---- the code group's commitment, cached per device ----
+ * The code (control) columns depend on the circuit and po2 alone, so every segment of one size commits the same code
+ * group.  rk_prove_segment (and with it every session entry point) fingerprints the code input it is given where it
+ * lies in device memory -- every word, on every call: a keyed 123-bit hash, never the address -- and when the device
+ * already holds the group committed from the same words under the same po2, column count, blow-up, query count, field
+ * and Poseidon2 instance, it reuses coefficients, LDE, Merkle tree and top layer: the seal is word for word the one a
+ * recomputation gives.  An entry costs 36 * cols * 2^po2 + 256 * 2^po2 bytes at blow-up 4 (576 MiB for 16 columns at
+ * po2 20) of device memory outside every context's pool, is shared by all contexts of the device and outlives them;
+ * least recently used entries go when max_bytes would be exceeded.  With the cache on, an on_device = 2 code buffer is
+ * left untouched.  Inputs with a word >= p or of more than 2^28 words are committed the ordinary way.
+ * rk_code_cache_configure: max_bytes of `device` (default 2 GiB, or RK_CODE_CACHE_BYTES from the environment, read
+ * once); 0 switches the cache off and frees its entries.  rk_code_cache_stats: lookups that hit / missed since the
+ * process started and the bytes held now (any pointer may be NULL).  rk_session_release drops the entries too. */
+int rk_code_cache_configure(int device, size_t max_bytes);
+int rk_code_cache_stats(int device, uint64_t* hits, uint64_t* misses, uint64_t* bytes);
 /* Test switch: with RK_TEST_LOGICAL_DEVICES=k in the environment the session entry points see k devices, logical
  * device d running on physical GPU d mod (number of GPUs) -- the multi-device path (a pool, a feeder and `inflight`
  * provers per device, session-wide claim flags, pinning of device-resident segments to the first device of the GPU

@@ -520,6 +520,8 @@ extern "C" {
     pub fn rk_session_last_error(device: c_int) -> *const c_char;
     pub fn rk_session_last_proven(device: c_int, count: *mut usize) -> c_int;
     pub fn rk_session_release() -> c_int;
+    pub fn rk_code_cache_configure(device: c_int, max_bytes: usize) -> c_int;
+    pub fn rk_code_cache_stats(device: c_int, hits: *mut u64, misses: *mut u64, bytes: *mut u64) -> c_int;
     pub fn rk_comm_unique_id(id: *mut u8) -> c_int;
     pub fn rk_comm_create(id: *const u8, rank: c_int, world: c_int, device: c_int, out: *mut *mut rk_comm) -> c_int;
     pub fn rk_comm_destroy(comm: *mut rk_comm) -> c_int;

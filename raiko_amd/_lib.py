@@ -196,6 +196,8 @@ SYMBOLS = {
     "rk_stream_close": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "rk_session_release": (C.c_int, []),
     "rk_session_last_proven": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "rk_code_cache_configure": (C.c_int, [C.c_int, C.c_size_t]),
+    "rk_code_cache_stats": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rk_abi_version": (C.c_int, []),
     "rk_strerror": (C.c_char_p, [C.c_int]),
     "rk_last_error": (C.c_char_p, [_vp]),

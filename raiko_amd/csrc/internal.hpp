@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -192,5 +194,39 @@ int pcs_coset_lde_cols(rk_ctx* ctx, uint32_t* d_cols, const uint32_t* d_in, size
 int ext_sub_at(rk_ctx* ctx, uint32_t* d_ext, const uint32_t* h_idx, const bb::Ext* h_delta, size_t n);
 // p3.hip: the contexts rk_p3_prove_shards keeps per device (freed by rk_session_release)
 void p3_release_pools();
+
+// code_cache.hip: the committed code group of a segment, kept per device and looked up by content
+struct CodeKey {
+    uint32_t fp[4];                    // keyed fingerprint of the code input's words
+    uint32_t po2, cols, blowup_log2, queries;
+    uint32_t root27m, shiftm;          // the field parameters the transforms depend on
+    uint32_t p2[8];                    // digest of the Poseidon2 instance
+    bool operator==(const CodeKey& o) const { return std::memcmp(this, &o, sizeof(CodeKey)) == 0; }
+};
+struct CodeEntry {                     // what commit_group leaves behind for the code group; device memory of its own
+    CodeKey key{};
+    int device = 0;
+    uint32_t* coeffs = nullptr;        // interpolated, zk-shifted, bit-reversed
+    uint32_t* evaluated = nullptr;     // the LDE
+    uint32_t* nodes = nullptr;         // the Merkle heap over its rows
+    std::vector<uint32_t> top;         // MerkleDev::top
+    hipEvent_t ready = nullptr;        // recorded on the building stream once the tree is complete
+    size_t bytes = 0;
+    CodeEntry() = default;
+    CodeEntry(const CodeEntry&) = delete;
+    CodeEntry& operator=(const CodeEntry&) = delete;
+    ~CodeEntry();
+};
+// the cache of `device` is on, an input of `words` words can be fingerprinted and an entry of entry_bytes fits
+bool code_cache_usable(int device, size_t words, size_t entry_bytes);
+// fp = the fingerprint of d_src[0 .. words) (waits for the stream); *canonical: every word was < p
+int code_fingerprint(rk_ctx* ctx, const uint32_t* d_src, size_t words, uint32_t fp[4], bool* canonical);
+// the entry of `key` (a hit) or null (a miss)
+std::shared_ptr<CodeEntry> code_cache_lookup(int device, const CodeKey& key);
+// an entry with buffers of the given sizes, not yet in the cache; null when the device has no room for it
+std::shared_ptr<CodeEntry> code_cache_new_entry(int device, const CodeKey& key, size_t coeff_bytes, size_t eval_bytes, size_t node_bytes);
+// after `ready` was recorded; dropped when the key is already there (two contexts missed at once)
+void code_cache_insert(const std::shared_ptr<CodeEntry>& e);
+void code_cache_release();
 
 }  // namespace rk

@@ -83,7 +83,7 @@ struct MerkleDev {
     const uint32_t* matrix = nullptr;  // device, column-major rows x cols
     std::vector<uint32_t> top;         // host copy of nodes[1 .. 2*top_size)
 
-    int build(rk_ctx* ctx, const uint32_t* d_matrix, size_t r, size_t c, size_t queries) {
+    void shape(const uint32_t* d_matrix, size_t r, size_t c, size_t queries) {
         rows = r;
         cols = c;
         matrix = d_matrix;
@@ -94,7 +94,10 @@ struct MerkleDev {
             top_layer = i;
         }
         top_size = (size_t)1 << top_layer;
-        RK_TRY(nodes.alloc(ctx, 2 * rows * p2::OUT * 4));
+    }
+    int build(rk_ctx* ctx, const uint32_t* d_matrix, size_t r, size_t c, size_t queries) {
+        shape(d_matrix, r, c, queries);
+        if (!nodes.p) RK_TRY(nodes.alloc(ctx, 2 * rows * p2::OUT * 4));  // else: adopted (an entry of the code cache)
         return rk::merkle_build(ctx, nodes.u32(), d_matrix, rows, cols);
     }
     // MerkleTreeProver::commit: send the top layer, absorb the root
@@ -102,9 +105,13 @@ struct MerkleDev {
         top.assign(2 * top_size * p2::OUT, 0);
         // nodes[1 .. 2*top_size) in one copy (index 0 unused)
         RK_TRY(d2h_sync(ctx, top.data() + p2::OUT, nodes.u32() + p2::OUT, (2 * top_size - 1) * p2::OUT * 4));
+        commit_top(iop);
+        return RK_OK;
+    }
+    // the same from a host copy of the top layer that is already there: no device round trip
+    void commit_top(Transcript& iop) const {
         iop.write(top.data() + top_size * p2::OUT, top_size * p2::OUT);
         iop.commit(top.data() + p2::OUT);
-        return RK_OK;
     }
     size_t path_len() const { return layers - top_layer; }
 };
@@ -192,7 +199,7 @@ struct PolyGroup {
         size = sz;
         const unsigned blow = ctx->sys.blowup_log2;
         size_t domain = sz << blow;
-        RK_TRY(evaluated.alloc(ctx, cnt * domain * 4));
+        if (!evaluated.p) RK_TRY(evaluated.alloc(ctx, cnt * domain * 4));  // else: adopted (an entry of the code cache)
         RK_TRY(rk::ntt_forward(ctx, evaluated.u32(), coeffs.u32(), sz, cnt, blow));
         // risc0 bit-reverses the coefficients here (PolyGroup::new) because its later users
         // index them in natural order.  The device pipeline instead keeps them bit-reversed:
@@ -304,6 +311,9 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
     ctx->timing = rk_timing{};
     StageClock sw(ctx);
     std::vector<Ext> rems;  // filled by a download that is only waited for later: must outlive `finish_on_exit`
+    // the code-cache entry this proof reads or builds: held until the stream has drained, so like `rems` it is declared
+    // before `finish_on_exit` (an evicted entry frees its buffers when the last reference goes)
+    std::shared_ptr<rk::CodeEntry> code_ref;
     sw.start("segment");
     const size_t total_bracket = sw.used.size() - 1;
     struct Finish {  // also on the error returns
@@ -370,10 +380,8 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         from = d_raw[g];
         return dst.alloc(ctx, words * 4);
     };
-    // Prover::commit_group; `preloaded`: pg.coeffs already holds the trace (written by a hook)
-    auto commit_group = [&](int g, PolyGroup& pg, const uint32_t* trace, size_t count, bool preloaded = false) -> int {
-        const uint32_t* from = nullptr;
-        if (!preloaded) RK_TRY(load_group(g, pg.coeffs, trace, count * N, from));
+    // the part of commit_group that follows the loading: `from` as in load_group
+    auto commit_loaded = [&](PolyGroup& pg, const uint32_t* from, size_t count) -> int {
         sw.start("ntt");
         RK_TRY(rk::ntt_reverse_from(ctx, pg.coeffs.u32(), from ? from : pg.coeffs.u32(), N, count, /*fuse_zk_shift=*/true));
         RK_TRY(pg.build(ctx, count, N));
@@ -383,9 +391,83 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         sw.stop(&ctx->timing.hash);
         return pg.merkle.commit(ctx, iop);
     };
+    // Prover::commit_group; `preloaded`: pg.coeffs already holds the trace (written by a hook)
+    auto commit_group = [&](int g, PolyGroup& pg, const uint32_t* trace, size_t count, bool preloaded = false) -> int {
+        const uint32_t* from = nullptr;
+        if (!preloaded) RK_TRY(load_group(g, pg.coeffs, trace, count * N, from));
+        return commit_loaded(pg, from, count);
+    };
+    // The code group through the device's cache (code_cache.hip): its input is fingerprinted where it lies in device
+    // memory -- every word, on every call; the address is no part of the key -- and when the group committed from the
+    // same words under the same parameters is there, coefficients, LDE, tree and top layer are borrowed from the
+    // entry.  Everything later only reads them (tap evaluation, DEEP mix, openings, a hook's d_lde[1]).  On a miss the
+    // group is committed as ever, into buffers of a new entry; the caller's buffer stays untouched in either case.
+    auto commit_code = [&](PolyGroup& pg) -> int {
+        const size_t count = taps.group_size[1], words = count * N;
+        const size_t coeff_bytes = words * 4, eval_bytes = count * D * 4, node_bytes = 2 * D * p2::OUT * 4;
+        if (!rk::code_cache_usable(ctx->device, words, coeff_bytes + eval_bytes + node_bytes))
+            return commit_group(1, pg, seg->group[1], count);
+        const uint32_t* src = seg->group[1];
+        if (!seg->on_device) {
+            RK_TRY(raw[1].alloc(ctx, words * 4));
+            RK_HIP_TRY(ctx, hipMemcpyAsync(raw[1].p, src, words * 4, hipMemcpyHostToDevice, ctx->stream));
+            src = raw[1].u32();
+        }
+        if (hook_accum) d_raw[1] = src;  // the raw code witness reaches `accumulate` as before
+        rk::CodeKey key{};
+        bool canonical = false;
+        RK_TRY(rk::code_fingerprint(ctx, src, words, key.fp, &canonical));
+        std::shared_ptr<rk::CodeEntry> hit;
+        if (canonical) {
+            key.po2 = seg->po2;
+            key.cols = (uint32_t)count;
+            key.blowup_log2 = BLOW;
+            key.queries = (uint32_t)QUERIES;  // MerkleDev::top_layer depends on it
+            key.root27m = ctx->sys.root27m;
+            key.shiftm = ctx->sys.shiftm;
+            std::vector<uint32_t> inst{bb::encode((uint32_t)kc.kind), bb::encode(kc.pad_free ? 1u : 0u)};
+            inst.insert(inst.end(), kc.rc_ext(), kc.rc_ext() + 8 * kc.cells());
+            inst.insert(inst.end(), kc.rc_int(), kc.rc_int() + kc.rounds_partial());
+            inst.insert(inst.end(), kc.diag(), kc.diag() + kc.cells());
+            kc.hash_elems(inst.data(), inst.size(), key.p2);
+            hit = rk::code_cache_lookup(ctx->device, key);
+        }
+        pg.count = count;
+        pg.size = N;
+        if (hit) {
+            code_ref = hit;
+            RK_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, hit->ready, 0));
+            pg.coeffs.adopt(ctx, hit->coeffs);
+            pg.evaluated.adopt(ctx, hit->evaluated);
+            pg.merkle.shape(hit->evaluated, D, count, QUERIES);
+            pg.merkle.nodes.adopt(ctx, hit->nodes);
+            pg.merkle.top = hit->top;
+            pg.merkle.commit_top(iop);
+        } else {
+            // a word >= p (no collision bound for it) or no room for an entry: the context's own buffers
+            std::shared_ptr<rk::CodeEntry> fresh;
+            if (canonical) fresh = rk::code_cache_new_entry(ctx->device, key, coeff_bytes, eval_bytes, node_bytes);
+            if (fresh) {
+                code_ref = fresh;
+                pg.coeffs.adopt(ctx, fresh->coeffs);
+                pg.evaluated.adopt(ctx, fresh->evaluated);
+                pg.merkle.nodes.adopt(ctx, fresh->nodes);
+            } else {
+                RK_TRY(pg.coeffs.alloc(ctx, words * 4));
+            }
+            RK_TRY(commit_loaded(pg, src, count));
+            if (fresh) {
+                fresh->top = pg.merkle.top;
+                RK_HIP_TRY(ctx, hipEventRecord(fresh->ready, ctx->stream));
+                rk::code_cache_insert(fresh);
+            }
+        }
+        if (!hook_accum) raw[1].release();
+        return RK_OK;
+    };
 
     PolyGroup groups[3], check;
-    RK_TRY(commit_group(1, groups[1], seg->group[1], taps.group_size[1]));  // code
+    RK_TRY(commit_code(groups[1]));  // code
     RK_TRY(commit_group(2, groups[2], seg->group[2], taps.group_size[2]));  // data
     // the accum mix: drawn once code and data are bound (rv32im prove_segment)
     std::vector<uint32_t> accum_mix(seg->n_accum_mix);

@@ -473,6 +473,18 @@ def session_release():
     _lib.check(None, _lib.load().rk_session_release())
 
 
+def code_cache_configure(device: int, max_bytes: int):
+    """rk_code_cache_configure: byte limit of the device's cache of committed code groups; 0 switches it off and frees it"""
+    _lib.check(None, _lib.load().rk_code_cache_configure(device, max_bytes))
+
+
+def code_cache_stats(device: int) -> dict:
+    """{hits, misses, bytes}: lookups since the process started and the bytes the device's code cache holds now"""
+    h, m, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _lib.check(None, _lib.load().rk_code_cache_stats(device, C.byref(h), C.byref(m), C.byref(b)))
+    return {"hits": int(h.value), "misses": int(m.value), "bytes": int(b.value)}
+
+
 def session_set_kernel_timing(device: int, enabled: bool):
     """hipEvent brackets around every launch class of rk_prove_session's contexts of `device`"""
     lib = _lib.load()
