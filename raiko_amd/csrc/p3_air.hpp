@@ -1,8 +1,10 @@
-// Shared by p3_air.hip (the AIR front end: rk_air_*, the lookup constraints, the Poseidon2 chip) and p3.hip (prover,
-// verifier, shards): what an rk_air holds, and the scoped device buffer both use.
+// Shared by p3_air.hip (the AIR front end: rk_air_*, the lookup constraints, the Poseidon2 chip), fri_tables.hip (the rows
+// of the FRI lookup tables) and p3.hip (prover, verifier, shards): what an rk_air holds, the scoped device buffer all
+// three use, and the Poseidon2 chip as the FRI tables feed it.
 #pragma once
 #include "internal.hpp"
 #include "circuit_program.hpp"
+#include "p3_kernels.hpp"
 
 #include <vector>
 
@@ -47,5 +49,24 @@ struct DevBuf {  // dev_alloc'd block released with the scope
     }
     uint32_t* u32() const { return (uint32_t*)p; }
 };
+
+// the Poseidon2 chip of an instance: where its columns are, and the constants its lanes read
+inline p3k::P2ChipLayout p2_chip_layout(const p2::Any& k) {
+    p3k::P2ChipLayout L;
+    L.W = (uint32_t)k.cells();
+    L.RP = (uint32_t)k.rounds_partial();
+    L.width = L.W + 16 * L.W + 2 * L.RP - 1 + L.W + 1;
+    return L;
+}
+inline std::vector<uint32_t> p2_chip_tab(const p2::Any& k) {   // rc_ext | rc_int | diag: what p3k::chip_permute reads
+    const p3k::P2ChipLayout L = p2_chip_layout(k);
+    std::vector<uint32_t> tab(k.rc_ext(), k.rc_ext() + 8 * L.W);
+    tab.insert(tab.end(), k.rc_int(), k.rc_int() + L.RP);
+    tab.insert(tab.end(), k.diag(), k.diag() + L.W);
+    return tab;
+}
+// rk_p2_chip_trace behind its argument checks (0 < n <= 2^24, the context's device current), reading the constants from
+// d_tab: p2_chip_tab of the context's instance, uploaded by the caller (p3_air.hip)
+int p2_chip_trace(rk_ctx* ctx, const uint32_t* d_tab, const p3k::P2ChipLayout& L, const uint32_t* d_in, const uint32_t* d_mult, size_t n, uint32_t* d_out);
 
 }  // namespace rk

@@ -1,4 +1,4 @@
-// Lane-level bodies of the uni-stark path's own kernels (p3.hip, p3_air.hip) as host/device functions: the GPU kernels are
+// Lane-level bodies of the uni-stark path's own kernels (p3.hip, p3_air.hip, fri_tables.hip) as host/device functions: the GPU kernels are
 // these phases with __syncthreads() between them; tests/emul runs the same code on the CPU one emulated lane at a time.
 #pragma once
 #include "bb.hpp"

@@ -34,6 +34,7 @@ import re
 import numpy as np
 
 from . import _lib, p3
+from . import fri_tables as T
 from .p3 import P, AirBuilder, ExtExpr
 
 BUS_FRI_OPEN, BUS_FRI_CLAIM = 5, 6
@@ -505,9 +506,21 @@ def witness(st):
     return [fold, path, claims, chip_rows(chip_in, consts, chip_mult)]
 
 
+TABLE_NAMES = ("fold", "path", "claims", "chip")
+
+
+def _lead(shape):
+    return shape.log_max, shape.blowup_log2, shape.queries
+
+
+def device_inputs(st):
+    """the two host arrays rk_fri_chip_rows_device reads, in argument order"""
+    return st.publics, st.records
+
+
 def tables_from_rows(st, rows):
     """p3 tables over canonical rows (the witness or a variation of it)"""
-    return [p3.Table(air, p3.to_mont(r), pv) for air, r, pv in zip(airs(st), rows, public_values(st))]
+    return T.tables_from_rows(airs(st), rows, public_values(st))
 
 
 def host_tables(st):
@@ -516,44 +529,25 @@ def host_tables(st):
 
 
 def _pinned_tables(st):
-    out = []
-    for air, pv, h in zip(airs(st), public_values(st), heights(st.shape)):
-        t = p3.Table(air, None, pv)
-        t.log_height = h
-        out.append(t)
-    return out
+    return T.pinned_tables(airs(st), public_values(st), heights(st.shape))
 
 
 # ---------------------------------------------------------------------------------------------- GPU rows and proof
 def sizes(shape):
     """rk_fri_chip_sizes -> dict"""
-    out = _lib.RkFriChipSizeInfo()
-    _lib.check(None, _lib.load().rk_fri_chip_sizes(shape.log_max, shape.blowup_log2, shape.queries, C.byref(out)))
-    return {n: int(getattr(out, n)) for n, _ in out._fields_ if n != "reserved"}
+    return T.sizes(_lib.RkFriChipSizeInfo, "rk_fri_chip_sizes", _lead(shape))
 
 
 def device_tables(hal, st):
     """rk_fri_chip_rows_device under hal's parameter set -> [(DeviceBuffer, log_height)] for fold, path, claims, chip:
     the rows stay in HBM, ready as on_device tables"""
-    from .hal import _ptr
-    sz = sizes(st.shape)
-    d_pub, d_rec = hal.copy_from_elem(st.publics), hal.copy_from_elem(st.records)
-    bufs = [hal.alloc_elem(sz[n + "_width"] << sz[n + "_log_height"]) for n in ("fold", "path", "claims", "chip")]
-    args = []
-    for b in bufs:
-        args += [_ptr(b), b.size()]
-    _lib.check(hal._ctx, _lib.load().rk_fri_chip_rows_device(hal._ctx, st.shape.log_max, st.shape.blowup_log2, st.shape.queries,
-                                                              _ptr(d_pub), _ptr(d_rec), *args))
-    hal.sync()
-    return [(b, sz[n + "_log_height"]) for b, n in zip(bufs, ("fold", "path", "claims", "chip"))]
+    return T.device_tables(hal, TABLE_NAMES, sizes(st.shape), "rk_fri_chip_rows_device", _lead(st.shape), device_inputs(st))
 
 
 def prove(hal, st, device=None):
     """the FRI statement's proof by rk_p3_prove over the four on_device tables (device: device_tables' result, kept by
     the caller, or None to write the rows now)"""
-    from .hal import _ptr
-    device = device if device is not None else device_tables(hal, st)
-    return p3.prove(hal, _pinned_tables(st), st.init, device_traces=[(_ptr(b), h) for b, h in device])
+    return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
 def verify_fri_statement(tables, shard_proof, init, fri_proof, params=None) -> int:

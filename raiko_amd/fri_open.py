@@ -45,6 +45,7 @@ import numpy as np
 from . import _lib, p3
 from . import fri_chip as F
 from . import fri_reduce as G
+from . import fri_tables as T
 from .fri_reduce import BUS_IN_LEAF, BUS_POSEIDON2_STATE, SPONGE_COLS
 from .p3 import P, AirBuilder
 
@@ -370,35 +371,6 @@ def witness(st, records=None, paths=None, bits=None, swapped=()):
     return [G.fold_rows(st.red, fold), path, reduce, ipath, chip, F.chip_rows(sin, consts, smult)]
 
 
-def tables_from_rows(st, rows):
-    """p3 tables over canonical rows (the witness or a variation of it)"""
-    return [p3.Table(air, p3.to_mont(r), pv) for air, r, pv in zip(airs(st), rows, public_values(st))]
-
-
-def host_tables(st):
-    """the six tables with the numpy witness as host traces"""
-    return tables_from_rows(st, witness(st))
-
-
-def _pinned_tables(st):
-    out = []
-    for air, pv, h in zip(airs(st), public_values(st), heights(st)):
-        t = p3.Table(air, None, pv)
-        t.log_height = h
-        out.append(t)
-    return out
-
-
-# ---------------------------------------------------------------------------------------------- GPU rows and proof
-def sizes(st):
-    """rk_fri_open_sizes -> dict"""
-    out = _lib.RkFriOpenSizeInfo()
-    lw = st.layout_words
-    _lib.check(None, _lib.load().rk_fri_open_sizes(st.shape.log_max, st.shape.blowup_log2, st.shape.queries, lw.ctypes.data_as(_lib.u32p),
-                                                   len(st.layout), C.byref(out)))
-    return {n: int(getattr(out, n)) for n, _ in out._fields_ if n != "reserved"}
-
-
 TABLE_NAMES = ("fold", "path", "reduce", "ipath", "chip", "state")
 
 
@@ -407,29 +379,36 @@ def device_inputs(st):
     return (st.fold.publics, st.fold.records, st.red.reduce_publics, st.red.in_records, st.in_roots, st.in_paths)
 
 
+def tables_from_rows(st, rows):
+    """p3 tables over canonical rows (the witness or a variation of it)"""
+    return T.tables_from_rows(airs(st), rows, public_values(st))
+
+
+def host_tables(st):
+    """the six tables with the numpy witness as host traces"""
+    return tables_from_rows(st, witness(st))
+
+
+def _pinned_tables(st):
+    return T.pinned_tables(airs(st), public_values(st), heights(st))
+
+
+# ---------------------------------------------------------------------------------------------- GPU rows and proof
+def sizes(st):
+    """rk_fri_open_sizes -> dict"""
+    return T.sizes(_lib.RkFriOpenSizeInfo, "rk_fri_open_sizes", G._lead(st))
+
+
 def device_tables(hal, st):
     """rk_fri_open_rows_device under hal's parameter set -> [(DeviceBuffer, log_height)] for the six tables: the rows stay
     in HBM, ready as on_device tables"""
-    from .hal import _ptr
-    sz = sizes(st)
-    ins = [hal.copy_from_elem(a) for a in device_inputs(st)]
-    bufs = [hal.alloc_elem(sz[n + "_width"] << sz[n + "_log_height"]) for n in TABLE_NAMES]
-    args = []
-    for b in bufs:
-        args += [_ptr(b), b.size()]
-    lw = st.layout_words
-    _lib.check(hal._ctx, _lib.load().rk_fri_open_rows_device(hal._ctx, st.shape.log_max, st.shape.blowup_log2, st.shape.queries,
-                                                              lw.ctypes.data_as(_lib.u32p), len(st.layout), *[_ptr(b) for b in ins], *args))
-    hal.sync()
-    return [(b, sz[n + "_log_height"]) for b, n in zip(bufs, TABLE_NAMES)]
+    return T.device_tables(hal, TABLE_NAMES, sizes(st), "rk_fri_open_rows_device", G._lead(st), device_inputs(st))
 
 
 def prove(hal, st, device=None):
     """the statement's proof by rk_p3_prove over the six on_device tables (device: device_tables' result, kept by the
     caller, or None to write the rows now)"""
-    from .hal import _ptr
-    device = device if device is not None else device_tables(hal, st)
-    return p3.prove(hal, _pinned_tables(st), st.init, device_traces=[(_ptr(b), h) for b, h in device])
+    return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
 def verify_open_statement(tables, shard_proof, init, fri_proof, params=None) -> int:

@@ -34,6 +34,7 @@ import numpy as np
 
 from . import _lib, p3
 from . import fri_chip as F
+from . import fri_tables as T
 from .fri_chip import BUS_FRI_CLAIM, Shape
 from .p3 import P, AirBuilder, ExtExpr
 
@@ -404,9 +405,21 @@ def witness(st):
     return [fold_rows(st, fold), path, reduce_rows(st), chip]
 
 
+TABLE_NAMES = ("fold", "path", "reduce", "chip")
+
+
+def _lead(st):
+    return F._lead(st.shape) + (st.layout_words.ctypes.data_as(_lib.u32p), len(st.layout))
+
+
+def device_inputs(st):
+    """the four host arrays rk_fri_reduce_rows_device reads, in argument order"""
+    return st.fold.publics, st.fold.records, st.reduce_publics, st.in_records
+
+
 def tables_from_rows(st, rows):
     """p3 tables over canonical rows (the witness or a variation of it)"""
-    return [p3.Table(air, p3.to_mont(r), pv) for air, r, pv in zip(airs(st), rows, public_values(st))]
+    return T.tables_from_rows(airs(st), rows, public_values(st))
 
 
 def host_tables(st):
@@ -415,50 +428,25 @@ def host_tables(st):
 
 
 def _pinned_tables(st):
-    out = []
-    for air, pv, h in zip(airs(st), public_values(st), heights(st)):
-        t = p3.Table(air, None, pv)
-        t.log_height = h
-        out.append(t)
-    return out
+    return T.pinned_tables(airs(st), public_values(st), heights(st))
 
 
 # ---------------------------------------------------------------------------------------------- GPU rows and proof
 def sizes(st):
     """rk_fri_reduce_sizes -> dict"""
-    out = _lib.RkFriReduceSizeInfo()
-    lw = st.layout_words
-    _lib.check(None, _lib.load().rk_fri_reduce_sizes(st.shape.log_max, st.shape.blowup_log2, st.shape.queries, lw.ctypes.data_as(_lib.u32p),
-                                                     len(st.layout), C.byref(out)))
-    return {n: int(getattr(out, n)) for n, _ in out._fields_}
-
-
-TABLE_NAMES = ("fold", "path", "reduce", "chip")
+    return T.sizes(_lib.RkFriReduceSizeInfo, "rk_fri_reduce_sizes", _lead(st))
 
 
 def device_tables(hal, st):
     """rk_fri_reduce_rows_device under hal's parameter set -> [(DeviceBuffer, log_height)] for fold', path, reduce, chip:
     the rows stay in HBM, ready as on_device tables"""
-    from .hal import _ptr
-    sz = sizes(st)
-    ins = [hal.copy_from_elem(a) for a in (st.fold.publics, st.fold.records, st.reduce_publics, st.in_records)]
-    bufs = [hal.alloc_elem(sz[n + "_width"] << sz[n + "_log_height"]) for n in TABLE_NAMES]
-    args = []
-    for b in bufs:
-        args += [_ptr(b), b.size()]
-    lw = st.layout_words
-    _lib.check(hal._ctx, _lib.load().rk_fri_reduce_rows_device(hal._ctx, st.shape.log_max, st.shape.blowup_log2, st.shape.queries,
-                                                                lw.ctypes.data_as(_lib.u32p), len(st.layout), *[_ptr(b) for b in ins], *args))
-    hal.sync()
-    return [(b, sz[n + "_log_height"]) for b, n in zip(bufs, TABLE_NAMES)]
+    return T.device_tables(hal, TABLE_NAMES, sizes(st), "rk_fri_reduce_rows_device", _lead(st), device_inputs(st))
 
 
 def prove(hal, st, device=None):
     """the statement's proof by rk_p3_prove over the four on_device tables (device: device_tables' result, kept by the
     caller, or None to write the rows now)"""
-    from .hal import _ptr
-    device = device if device is not None else device_tables(hal, st)
-    return p3.prove(hal, _pinned_tables(st), st.init, device_traces=[(_ptr(b), h) for b, h in device])
+    return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
 def verify_reduce_statement(tables, shard_proof, init, fri_proof, params=None) -> int:

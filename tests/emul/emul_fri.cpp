@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: the lane bodies of rk_fri_chip_rows_device (p3k::fri_fold_lane / fri_path_lane / chip_row,
 // raiko_amd/csrc/p3_kernels.hpp) run on the CPU one emulated lane at a time, in the order of the launches of
-// p3_air.hip: every fold lane, every path lane, every chip lane.  Buffers must arrive zeroed, as the library clears them.
+// fri_tables.hip: every fold lane, every path lane, every chip lane.  Buffers must arrive zeroed, as the library clears them.
 #include <cstring>
 #include <vector>
 

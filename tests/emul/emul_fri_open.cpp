@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: the three new lane bodies of rk_fri_open_rows_device (p3k::fri_open_sponge_lane, fri_open_fill_lane,
 // fri_open_ipath_lane; raiko_amd/csrc/p3_kernels.hpp) and chip_row run on the CPU in the order of the launches of
-// p3_air.hip.  `reduce` arrives as the earlier kernels leave it -- the reduce table's own columns at the wider stride, the
+// fri_tables.hip.  `reduce` arrives as the earlier kernels leave it -- the reduce table's own columns at the wider stride, the
 // sponge columns zero --, chip_in / chip_mult with the commit-phase inputs (rows below chip_base) filled in; everything
 // else must arrive zeroed, as the library clears it.
 #include <vector>

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: the lane bodies of rk_fri_reduce_rows_device (p3k::fri_fold_lane with the X column, fri_path_lane,
 // fri_reduce_term / fri_reduce_join / fri_reduce_row, chip_row; raiko_amd/csrc/p3_kernels.hpp) run on the CPU in the
-// order of the launches of p3_air.hip.  The reduce kernel's workgroup is emulated as it runs: FRI_REDUCE_TPB lanes in
+// order of the launches of fri_tables.hip.  The reduce kernel's workgroup is emulated as it runs: FRI_REDUCE_TPB lanes in
 // waves of 64, every scan step reading the sums the lanes `d` further down held before the step (a shuffle), the waves'
 // totals and the round's running reduced opening passed through arrays that stand for LDS, the barriers where the
 // kernel has them.  Buffers must arrive zeroed, as the library clears them.

@@ -1,7 +1,7 @@
 """rk_fri_open_rows_device on the GPU (raiko_amd/fri_open.py): the rows of fold', path, reduce'', ipath, chip and the state chip
 equal the numpy witness word for word; the tables stay in HBM and go to rk_p3_prove as on_device tables, whose proof is the
 oracle's over the witness; verify_open_statement accepts it; undersized or wrong-parameter calls are refused with nothing
-written.
+written; the tables the chip, the reduce and the open statement share hold the same words whichever of them wrote the rows.
 
 Every GPU step runs in a child process of its own under a time limit of its own (this file run as a script: `python
 tests/test_gpu_fri_open.py STEP [CASE]`), once: a step that fails is not started again, and after a step that ended by a
@@ -48,6 +48,10 @@ def test_gpu_proves_the_statement_from_device_tables():
 
 def test_gpu_bad_arguments_are_refused_with_nothing_written():
     assert "refusals ok" in run_step("refuse", "sp1_mixed_fib8_cubic4")
+
+
+def test_gpu_shared_tables_are_the_same_words_in_every_statement():
+    assert "shared ok" in run_step("shared", "sp1_mixed_fib8_cubic4")
 
 
 # ---------------------------------------------------------------------------------------------- the steps (child process)
@@ -153,6 +157,29 @@ def step_refuse(h, case):
     print("refusals ok")
 
 
+def step_shared(h, case):
+    """the rows of the chip, the reduce and the open statement written one after the other on one context: what two
+    statements share is written by one stage of the library (csrc/fri_tables.hip), so it is the same words in both --
+    compared table against table, without the numpy witness"""
+    import numpy as np
+    from raiko_amd import fri_chip as F, fri_open as H, fri_reduce as G
+    blob, tables, init, pf = _shard(h, case)
+    st = H.statement(tables, pf, init, blob)
+    rows = lambda names, dev: {n: b.to_host().reshape(1 << lh, -1) for n, (b, lh) in zip(names, dev)}
+    chip = rows(F.TABLE_NAMES, F.device_tables(h, st.fold))
+    red = rows(G.TABLE_NAMES, G.device_tables(h, st.red))
+    opn = rows(H.TABLE_NAMES, H.device_tables(h, st))
+    assert chip["path"].any() and red["fold"].any() and red["reduce"].any()
+    assert np.array_equal(red["path"], chip["path"]) and np.array_equal(opn["path"], chip["path"])
+    assert np.array_equal(opn["fold"], red["fold"])
+    assert np.array_equal(red["fold"][:, :-1], chip["fold"])              # fold' = fold | X
+    assert np.array_equal(red["chip"], chip["chip"])                       # one chip feed, one chip trace
+    w = red["reduce"].shape[1]
+    assert opn["reduce"].shape == (red["reduce"].shape[0], w + G.SPONGE_COLS)
+    assert np.array_equal(opn["reduce"][:, :w], red["reduce"])           # reduce'' = reduce | the sponge columns
+    print("shared ok")
+
+
 def main(step, case):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -160,7 +187,7 @@ def main(step, case):
     from raiko_amd import hal
     h = hal.HipHal(0)
     try:
-        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse}[step](h, case)
+        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse, "shared": step_shared}[step](h, case)
     finally:
         o.oracle_set_params()
         h.close()
