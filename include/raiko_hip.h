@@ -915,6 +915,53 @@ int rk_fri_open_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2,
                             const uint32_t* d_inputs, const uint32_t* d_roots, const uint32_t* d_paths, uint32_t* d_fold, size_t fold_capacity,
                             uint32_t* d_path, size_t path_capacity, uint32_t* d_reduce, size_t reduce_capacity, uint32_t* d_ipath,
                             size_t ipath_capacity, uint32_t* d_chip, size_t chip_capacity, uint32_t* d_state, size_t state_capacity);
+/* The Fiat-Shamir transcript of the FRI query check as lookup tables: a fourth statement beside the three above (AIRs and
+ * host witness: raiko_amd/fri_transcript.py; the scope of rk_fri_open_* and pow_bits <= 27).  Eight tables: fold'' (fold'
+ * with one more column FIRST, with which a query's first row receives (query, index) from the bits table), path,
+ * reduce'', ipath, transcript (one row per duplex permutation of rk_p3_verify's challenger: what it absorbs and what is
+ * sampled from it are public values, every cell it keeps is the row before's output), bits (one row per sample_bits: the
+ * canonical 31-bit form of the sampled cell, its low bits the proof-of-work check and the query indices), the chip and the
+ * state chip, which now also holds the transcript's permutations.
+ * rk_p3_fri_transcript: rk_p3_verify (same arguments, same verdict) that on verdict 0 also hands back, as Montgomery words,
+ *   ops:      the challenger's calls in order as pairs (kind, count): 0 observe `count` words (an empty observe is left
+ *             out), 1 sample `count` field elements, 2 sample_bits(count)
+ *   observed: every observed word, concatenated
+ *   sampled:  every sampled field element in order, those behind sample_bits included
+ * with the capacity protocol of rk_p3_fri_inputs. */
+int rk_p3_fri_transcript(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                         const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* ops, size_t ops_capacity, uint32_t* observed,
+                         size_t observed_capacity, uint32_t* sampled, size_t sampled_capacity, size_t* ops_words, size_t* observed_words,
+                         size_t* sampled_words);
+/* The eight tables for a shape, a layout and the challenger's calls (n_ops pairs, as rk_p3_fri_transcript wrote them; host
+ * memory).  The calls must end in queries + 1 sample_bits with nothing between them: the proof of work (pow_bits <= 27),
+ * then one of log_max bits per query.  n_steps = the duplex permutations = transcript_rows; bits_rows = queries + 1;
+ * state_rows = those of the open statement + n_steps; transcript_publics_words = observed_words + the field elements
+ * sampled by kind 1. */
+typedef struct {
+    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, n_steps, pow_bits, reserved;
+    uint32_t fold_width, path_width, reduce_width, ipath_width, transcript_width, bits_width, chip_width, state_width;
+    uint32_t fold_log_height, path_log_height, reduce_log_height, ipath_log_height, transcript_log_height, bits_log_height, chip_log_height,
+        state_log_height;
+    uint64_t fold_rows, path_rows, reduce_rows, ipath_rows, transcript_rows, bits_rows, chip_rows, state_rows, rows_per_query;
+    uint64_t fold_publics_words, fold_records_words, reduce_publics_words, inputs_words, roots_words, paths_words, observed_words,
+        transcript_publics_words;
+} rk_fri_transcript_size_info;
+int rk_fri_transcript_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                            const uint32_t* ops, uint32_t n_ops, rk_fri_transcript_size_info* out);
+/* The rows of all eight tables on the GPU: the kernels of rk_fri_open_rows_device (the fold rows with FIRST), then a chain
+ * kernel (one wave: a half-wave walks the challenger's permutations one after the other, one lane per state cell, over
+ * d_observed; it writes IN and OUT of every transcript row, the state chip's inputs behind the sponge's, and the cells
+ * sample_bits consumed), a fill kernel (one lane per transcript row: step one-hot and helpers; one lane per bits row) and
+ * rk_p2_chip_trace twice.  Refusals as rk_fri_open_rows_device, and calls that do not fit the shape are RK_ERR_INVALID;
+ * all before anything is launched. */
+int rk_fri_transcript_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout,
+                                  uint32_t n_matrices, const uint32_t* ops, uint32_t n_ops, const uint32_t* d_fold_publics,
+                                  const uint32_t* d_fold_records, const uint32_t* d_reduce_publics, const uint32_t* d_inputs,
+                                  const uint32_t* d_roots, const uint32_t* d_paths, const uint32_t* d_observed, uint32_t* d_fold,
+                                  size_t fold_capacity, uint32_t* d_path, size_t path_capacity, uint32_t* d_reduce, size_t reduce_capacity,
+                                  uint32_t* d_ipath, size_t ipath_capacity, uint32_t* d_transcript, size_t transcript_capacity,
+                                  uint32_t* d_bits, size_t bits_capacity, uint32_t* d_chip, size_t chip_capacity, uint32_t* d_state,
+                                  size_t state_capacity);
 /* exact proof size for the tables' shapes (log_height, width, air); 0 for shapes rk_p3_prove rejects */
 size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables);
 /* Many independent proofs -- the shards of one SP1 execution -- with `batch` of them in flight per GPU: what SP1's

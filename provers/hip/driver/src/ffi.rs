@@ -396,6 +396,52 @@ pub struct rk_fri_open_size_info {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct rk_fri_transcript_size_info {
+    pub n_rounds: u32,
+    pub n_slots: u32,
+    pub n_groups: u32,
+    pub n_batches: u32,
+    pub log_pmax: u32,
+    pub n_steps: u32,
+    pub pow_bits: u32,
+    pub reserved: u32,
+    pub fold_width: u32,
+    pub path_width: u32,
+    pub reduce_width: u32,
+    pub ipath_width: u32,
+    pub transcript_width: u32,
+    pub bits_width: u32,
+    pub chip_width: u32,
+    pub state_width: u32,
+    pub fold_log_height: u32,
+    pub path_log_height: u32,
+    pub reduce_log_height: u32,
+    pub ipath_log_height: u32,
+    pub transcript_log_height: u32,
+    pub bits_log_height: u32,
+    pub chip_log_height: u32,
+    pub state_log_height: u32,
+    pub fold_rows: u64,
+    pub path_rows: u64,
+    pub reduce_rows: u64,
+    pub ipath_rows: u64,
+    pub transcript_rows: u64,
+    pub bits_rows: u64,
+    pub chip_rows: u64,
+    pub state_rows: u64,
+    pub rows_per_query: u64,
+    pub fold_publics_words: u64,
+    pub fold_records_words: u64,
+    pub reduce_publics_words: u64,
+    pub inputs_words: u64,
+    pub roots_words: u64,
+    pub paths_words: u64,
+    pub observed_words: u64,
+    pub transcript_publics_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct rk_p3_shard {
     pub tables: *const rk_p3_table,
     pub n_tables: u32,
@@ -570,6 +616,9 @@ extern "C" {
     pub fn rk_p3_fri_input_paths(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
     pub fn rk_fri_open_sizes(log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, out: *mut rk_fri_open_size_info) -> c_int;
     pub fn rk_fri_open_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, d_fold_publics: *const u32, d_fold_records: *const u32, d_reduce_publics: *const u32, d_inputs: *const u32, d_roots: *const u32, d_paths: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_reduce: *mut u32, reduce_capacity: usize, d_ipath: *mut u32, ipath_capacity: usize, d_chip: *mut u32, chip_capacity: usize, d_state: *mut u32, state_capacity: usize) -> c_int;
+    pub fn rk_p3_fri_transcript(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, ops: *mut u32, ops_capacity: usize, observed: *mut u32, observed_capacity: usize, sampled: *mut u32, sampled_capacity: usize, ops_words: *mut usize, observed_words: *mut usize, sampled_words: *mut usize) -> c_int;
+    pub fn rk_fri_transcript_sizes(log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, ops: *const u32, n_ops: u32, out: *mut rk_fri_transcript_size_info) -> c_int;
+    pub fn rk_fri_transcript_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, ops: *const u32, n_ops: u32, d_fold_publics: *const u32, d_fold_records: *const u32, d_reduce_publics: *const u32, d_inputs: *const u32, d_roots: *const u32, d_paths: *const u32, d_observed: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_reduce: *mut u32, reduce_capacity: usize, d_ipath: *mut u32, ipath_capacity: usize, d_transcript: *mut u32, transcript_capacity: usize, d_bits: *mut u32, bits_capacity: usize, d_chip: *mut u32, chip_capacity: usize, d_state: *mut u32, state_capacity: usize) -> c_int;
     pub fn rk_p3_proof_bound_words(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
     pub fn rk_p3_prove_shards(opts: *const rk_p3_session_opts, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
     pub fn rk_p3_last_timing(ctx: *mut rk_ctx, out: *mut rk_p3_timing) -> c_int;

@@ -149,6 +149,17 @@ class RkP3Table(C.Structure):
                 ("public_values", u32p), ("n_public", C.c_uint32), ("on_device", C.c_uint32)]
 
 
+class RkFriTranscriptSizeInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "n_steps", "pow_bits", "reserved",
+                                          "fold_width", "path_width", "reduce_width", "ipath_width", "transcript_width", "bits_width",
+                                          "chip_width", "state_width", "fold_log_height", "path_log_height", "reduce_log_height",
+                                          "ipath_log_height", "transcript_log_height", "bits_log_height", "chip_log_height",
+                                          "state_log_height")] + \
+               [(n, C.c_uint64) for n in ("fold_rows", "path_rows", "reduce_rows", "ipath_rows", "transcript_rows", "bits_rows", "chip_rows",
+                                          "state_rows", "rows_per_query", "fold_publics_words", "fold_records_words", "reduce_publics_words",
+                                          "inputs_words", "roots_words", "paths_words", "observed_words", "transcript_publics_words")]
+
+
 class RkFriChipSizeInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "fold_width", "path_width", "claims_width", "chip_width", "fold_log_height",
                                           "path_log_height", "claims_log_height", "chip_log_height", "reserved")] + \
@@ -312,6 +323,11 @@ SYMBOLS = {
     "rk_fri_open_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, C.POINTER(RkFriOpenSizeInfo)]),
     "rk_fri_open_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
                                           _vp, _sz, _vp, _sz]),
+    "rk_p3_fri_transcript": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz, u32p,
+                                       _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_fri_transcript_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, u32p, _u32, C.POINTER(RkFriTranscriptSizeInfo)]),
+    "rk_fri_transcript_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                                _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "rk_p3_last_timing": (C.c_int, [_vp, C.POINTER(RkP3Timing)]),
     "rk_p3_prove_shards": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
     "rk_comm_unique_id": (C.c_int, [C.c_char_p]),

@@ -1,9 +1,11 @@
-// The rows of the FRI lookup tables on the GPU (include/raiko_hip.h: rk_fri_chip_*, rk_fri_reduce_*, rk_fri_open_*): three
-// statements about the FRI queries of a shard proof, each containing the one before -- the commit phase (fold, path,
-// claims, chip), the reduced openings (fold', path, reduce, chip), the input-batch openings (fold', path, reduce'', ipath,
-// chip, state).  Here: the kernels (lane bodies: p3_kernels.hpp), the size plans, and the row writing as stages the three
-// entry points share -- commit, reduce, open, and the Poseidon2 chip (p3_air.hip) fed by their lanes.  AIRs and numpy
-// witnesses: raiko_amd/fri_chip.py, fri_reduce.py, fri_open.py.
+// The rows of the FRI lookup tables on the GPU (include/raiko_hip.h: rk_fri_chip_*, rk_fri_reduce_*, rk_fri_open_*,
+// rk_fri_transcript_*): four statements about the FRI queries of a shard proof, each containing the one before -- the
+// commit phase (fold, path, claims, chip), the reduced openings (fold', path, reduce, chip), the input-batch openings
+// (fold', path, reduce'', ipath, chip, state), the transcript (fold'', path, reduce'', ipath, transcript, bits, chip,
+// state).  Here: the kernels (lane bodies: p3_kernels.hpp), the size plans, and the row writing as stages the four entry
+// points share -- commit, reduce, open, transcript, and the Poseidon2 chip (p3_air.hip) fed by their lanes.  AIRs and
+// numpy witnesses: raiko_amd/fri_chip.py, fri_reduce.py, fri_open.py, fri_transcript.py.
+#include "cell_perm.hpp"
 #include "p3_air.hpp"
 
 #include <algorithm>
@@ -257,6 +259,101 @@ int fri_open_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint3
     return RK_OK;
 }
 
+// the transcript (rk_fri_transcript_rows_device).  The challenger is ONE chain of dependent permutations, so a lane per
+// chain would leave 63 lanes idle for the latency of every permutation; the chain kernel is one wave with one lane per
+// state cell instead (CellPerm, cell_perm.hpp): the first half-wave's 16 cells hold the state, the second half-wave
+// follows with its results dropped (hash_fold_cells_kernel's idle half-waves), every lane executes every permutation.
+// Lane-per-chain form of the same steps: p3k::fri_transcript_chain_lane.
+template <class C>
+__global__ void __launch_bounds__(64) fri_transcript_chain_kernel(p3k::FriTranscriptArgs a, const typename C::Consts* __restrict__ kc) {
+    const typename C::Consts& k = *kc;
+    const unsigned lane = threadIdx.x, cell = lane & 31u;
+    const bool writes = lane < 16;
+    CellPerm<C> cp;
+    cp.init(k, cell);
+    uint32_t x = 0;
+    for (uint32_t s = 0; s < a.N; s++) {
+        const uint32_t* st = a.steps + p3k::FRI_TRANSCRIPT_STEP_WORDS * s;
+        uint32_t* row = a.transcript + (size_t)s * a.width();
+        if (cell < st[0]) x = a.observed[st[1] + cell];
+        if (writes) row[cell] = a.state_in[(a.state_base + s) * 16 + cell] = x;
+        if (lane == 0) a.state_mult[a.state_base + s] = bb::ONE;
+        x = cp.permute(x, k);
+        if (writes) row[16 + cell] = x;
+        if (lane < 8 && st[2 + lane]) a.samples[st[2 + lane] - 1] = x;
+    }
+}
+__global__ void __launch_bounds__(64) fri_transcript_fill_kernel(p3k::FriTranscriptArgs a) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.N) p3k::fri_transcript_fill_lane(a, t);
+    else if (t - a.N <= a.Q) p3k::fri_bits_fill_lane(a, t - a.N);
+}
+
+struct FriTranscriptPlan {
+    FriOpenPlan open;
+    rk_fri_transcript_size_info sz;
+    std::vector<uint32_t> steps;      // FRI_TRANSCRIPT_STEP_WORDS per duplex permutation
+};
+// the duplex permutations from the challenger's calls (Montgomery pairs, rk_p3_fri_transcript): p3.hip's Challenger replayed
+// without hashing -- which step absorbs which observed words, which output cell every sample pops
+int fri_transcript_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint32_t* layout, uint32_t n_matrices, const uint32_t* ops,
+                        uint32_t n_ops, FriTranscriptPlan* plan) {
+    RK_TRY(fri_open_plan(log_max, blow, queries, layout, n_matrices, &plan->open));
+    if (!ops || n_ops == 0 || n_ops > (1u << 16)) return RK_ERR_INVALID;
+    std::vector<uint32_t>& steps = plan->steps;
+    steps.clear();
+    uint32_t n_in = 0, n_out = 0, n_bits = 0, pow_bits = 0;
+    uint64_t n_obs = 0, n_pub = 0;
+    auto duplex = [&] {
+        steps.insert(steps.end(), {n_in, (uint32_t)(n_obs - n_in), 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u});
+        n_in = 0, n_out = 8;
+    };
+    for (uint32_t i = 0; i < n_ops; i++) {
+        if (ops[2 * i] >= bb::P || ops[2 * i + 1] >= bb::P) return RK_ERR_INVALID;
+        const uint32_t kind = bb::decode(ops[2 * i]), count = bb::decode(ops[2 * i + 1]);
+        if (kind > 2 || (kind < 2 && (count == 0 || count > (1u << 20) || n_bits))) return RK_ERR_INVALID;   // the sample_bits come last
+        if (kind == 0) {
+            for (uint32_t j = 0; j < count; j++) {
+                n_out = 0, n_in++, n_obs++;
+                if (n_in == 8) duplex();
+            }
+            continue;
+        }
+        for (uint32_t j = 0; j < (kind == 1 ? count : 1u); j++) {
+            if (n_in != 0 || n_out == 0) duplex();
+            --n_out;
+            if (kind == 1) {
+                n_pub++;
+            } else {
+                if (n_bits ? count != log_max : count > 27) return RK_ERR_INVALID;
+                if (!n_bits) pow_bits = count;
+                steps[steps.size() - p3k::FRI_TRANSCRIPT_STEP_WORDS + 2 + n_out] = ++n_bits;   // slot + 1
+            }
+        }
+        if (steps.size() > (size_t)p3k::FRI_TRANSCRIPT_STEP_WORDS * p3k::FRI_TRANSCRIPT_MAX_STEPS) return RK_ERR_INVALID;
+    }
+    if (n_bits != queries + 1 || steps.size() > (size_t)p3k::FRI_TRANSCRIPT_STEP_WORDS * p3k::FRI_TRANSCRIPT_MAX_STEPS) return RK_ERR_INVALID;
+    const rk_fri_open_size_info& p = plan->open.sz;
+    const uint32_t N = (uint32_t)(steps.size() / p3k::FRI_TRANSCRIPT_STEP_WORDS);
+    rk_fri_transcript_size_info& o = plan->sz;
+    o = rk_fri_transcript_size_info{};
+    o.n_rounds = p.n_rounds, o.n_slots = p.n_slots, o.n_groups = p.n_groups, o.n_batches = p.n_batches, o.log_pmax = p.log_pmax;
+    o.n_steps = N, o.pow_bits = pow_bits;
+    o.fold_width = p.fold_width + 1, o.path_width = p.path_width, o.reduce_width = p.reduce_width, o.ipath_width = p.ipath_width;
+    o.transcript_width = p3k::FRI_TRANSCRIPT_FIXED + N, o.bits_width = p3k::FRI_BITS_WIDTH, o.chip_width = p.chip_width, o.state_width = p.state_width;
+    o.fold_rows = p.fold_rows, o.path_rows = p.path_rows, o.reduce_rows = p.reduce_rows, o.ipath_rows = p.ipath_rows;
+    o.transcript_rows = N, o.bits_rows = (uint64_t)queries + 1, o.chip_rows = p.chip_rows, o.state_rows = p.state_rows + N;
+    o.rows_per_query = p.rows_per_query;
+    if (o.state_rows > ((uint64_t)1 << 24)) return RK_ERR_INVALID;
+    o.fold_log_height = p.fold_log_height, o.path_log_height = p.path_log_height, o.reduce_log_height = p.reduce_log_height;
+    o.ipath_log_height = p.ipath_log_height, o.chip_log_height = p.chip_log_height;
+    o.transcript_log_height = log_height(N), o.bits_log_height = log_height(o.bits_rows), o.state_log_height = log_height(o.state_rows);
+    o.fold_publics_words = p.fold_publics_words, o.fold_records_words = p.fold_records_words, o.reduce_publics_words = p.reduce_publics_words;
+    o.inputs_words = p.inputs_words, o.roots_words = p.roots_words, o.paths_words = p.paths_words;
+    o.observed_words = n_obs, o.transcript_publics_words = n_obs + n_pub;
+    return RK_OK;
+}
+
 // ---------------------------------------------------------------- the row writing, as stages
 template <class... P, class... A>
 int launch(rk_ctx* ctx, const char* name, void (*kernel)(P...), dim3 grid, dim3 block, A... args) {
@@ -335,13 +432,16 @@ struct FriCall {
     int chip_trace(const ChipFeed& f, uint32_t* d_out) { return rk::p2_chip_trace(ctx, d_tab, L, f.in, f.mult, f.n, d_out); }
 
     // the commit phase: the fold chain of every query, then the Merkle path of every (query, round).  xcol: the fold
-    // rows end in the point X (fold'); d_claims: the claims table, or null where a reduce table takes its place
-    int commit(const uint32_t* d_publics, const uint32_t* d_records, uint32_t* d_fold, uint32_t* d_path, uint32_t* d_claims, bool xcol, const ChipFeed& chip) {
+    // rows end in the point X (fold'), firstcol: and behind it in FIRST (fold''); d_claims: the claims table, or null where
+    // a reduce table takes its place
+    int commit(const uint32_t* d_publics, const uint32_t* d_records, uint32_t* d_fold, uint32_t* d_path, uint32_t* d_claims, bool xcol, const ChipFeed& chip,
+               bool firstcol = false) {
         p3k::FriArgs a{};
         a.L = log_max, a.R = n_rounds, a.Q = queries, a.gen_l = gen_l, a.wm = ctx->sys.wm;
         a.pub = d_publics, a.rec = d_records;
         a.fold = d_fold, a.path = d_path, a.claims = d_claims, a.chip_in = chip.in, a.chip_mult = chip.mult;
         if (xcol) a.xcol = 1, a.shiftm = ctx->sys.shiftm;
+        if (firstcol) a.firstcol = 1;
         RK_TRY(launch(ctx, "fri_fold_kernel", fri_fold_kernel, dim3((queries + 63) / 64), dim3(64), a));
         const dim3 grid((unsigned)(((uint64_t)queries * n_rounds + 63) / 64));
         return launch_m4(ctx, "fri_path_kernel", fri_path_kernel<0>, fri_path_kernel<1>, grid, dim3(64), a, d_tab, L);
@@ -382,6 +482,24 @@ struct FriCall {
         RK_TRY(launch_m4(ctx, "fri_open_sponge_kernel", fri_open_sponge_kernel<0>, fri_open_sponge_kernel<1>, sgrid, block, o, d_tab, L));
         RK_TRY(launch(ctx, "fri_open_fill_kernel", fri_open_fill_kernel, dim3((unsigned)((sz.reduce_rows + 255) / 256)), dim3(256), o));
         return launch_m4(ctx, "fri_open_ipath_kernel", fri_open_ipath_kernel<0>, fri_open_ipath_kernel<1>, igrid, block, o, d_tab, L);
+    }
+    // the transcript: the chain of the challenger's permutations (one wave), whose inputs join the state chip's behind the
+    // sponge's, then the cells of the transcript and bits rows that follow from the plan and the sampled cells
+    int transcript(const FriTranscriptPlan& plan, const uint32_t* d_observed, uint32_t* d_transcript, uint32_t* d_bits, const ChipFeed& state) {
+        const rk_fri_transcript_size_info& sz = plan.sz;
+        uint32_t *steps, *samples;
+        RK_TRY(dev(plan.steps.size(), &steps, plan.steps.data()));
+        RK_TRY(dev((size_t)queries + 1, &samples));
+        p3k::FriTranscriptArgs t{};
+        t.N = sz.n_steps, t.Q = queries, t.L = log_max, t.pow_bits = sz.pow_bits, t.state_base = (size_t)plan.open.sz.state_rows;
+        t.steps = steps, t.observed = d_observed, t.transcript = d_transcript, t.bits = d_bits;
+        t.state_in = state.in, t.state_mult = state.mult, t.samples = samples;
+        if (ctx->h_p2.m4()) {
+            RK_TRY(launch(ctx, "fri_transcript_chain_kernel", fri_transcript_chain_kernel<p2::K3>, dim3(1), dim3(64), t, (const p2::K3::Consts*)ctx->d_p2));
+        } else {
+            RK_TRY(launch(ctx, "fri_transcript_chain_kernel", fri_transcript_chain_kernel<p2::K2>, dim3(1), dim3(64), t, (const p2::K2::Consts*)ctx->d_p2));
+        }
+        return launch(ctx, "fri_transcript_fill_kernel", fri_transcript_fill_kernel, dim3((sz.n_steps + queries + 1 + 63) / 64), dim3(64), t);
     }
 };
 
@@ -492,6 +610,56 @@ int rk_fri_open_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2,
     RK_TRY(c.commit(d_fold_publics, d_fold_records, d_fold, d_path, nullptr, /*xcol=*/true, chip));
     RK_TRY(c.reduce(plan.red, d_reduce_publics, d_inputs, d_reduce, /*stride=*/sz.reduce_width));
     RK_TRY(c.open(plan, d_inputs, d_paths, d_reduce, d_ipath, chip, state));
+    RK_TRY(c.chip_trace(chip, d_chip));
+    return c.chip_trace(state, d_state);
+    RK_GUARD_END
+}
+
+int rk_fri_transcript_sizes(uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout, uint32_t n_matrices,
+                            const uint32_t* ops, uint32_t n_ops, rk_fri_transcript_size_info* out) {
+    RK_GUARD_BEGIN
+    if (!out) return RK_ERR_INVALID;
+    FriTranscriptPlan plan;
+    RK_TRY(fri_transcript_plan(log_max, blowup_log2, queries, layout, n_matrices, ops, n_ops, &plan));
+    *out = plan.sz;
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_fri_transcript_rows_device(rk_ctx* ctx, uint32_t log_max, uint32_t blowup_log2, uint32_t queries, const uint32_t* layout,
+                                  uint32_t n_matrices, const uint32_t* ops, uint32_t n_ops, const uint32_t* d_fold_publics,
+                                  const uint32_t* d_fold_records, const uint32_t* d_reduce_publics, const uint32_t* d_inputs,
+                                  const uint32_t* d_roots, const uint32_t* d_paths, const uint32_t* d_observed, uint32_t* d_fold,
+                                  size_t fold_capacity, uint32_t* d_path, size_t path_capacity, uint32_t* d_reduce, size_t reduce_capacity,
+                                  uint32_t* d_ipath, size_t ipath_capacity, uint32_t* d_transcript, size_t transcript_capacity,
+                                  uint32_t* d_bits, size_t bits_capacity, uint32_t* d_chip, size_t chip_capacity, uint32_t* d_state,
+                                  size_t state_capacity) {
+    RK_GUARD_BEGIN
+    if (!ctx || !d_fold_publics || !d_fold_records || !d_reduce_publics || !d_inputs || !d_roots || !d_paths || !d_observed || !d_fold ||
+        !d_path || !d_reduce || !d_ipath || !d_transcript || !d_bits || !d_chip || !d_state)
+        return RK_ERR_INVALID;
+    FriTranscriptPlan plan;
+    RK_TRY(fri_transcript_plan(log_max, blowup_log2, queries, layout, n_matrices, ops, n_ops, &plan));
+    const rk_fri_transcript_size_info& sz = plan.sz;
+    RK_TRY(fri_scope(ctx, blowup_log2, /*sponge=*/true));
+    const OutTable outs[] = {{d_fold, fold_capacity, sz.fold_width, sz.fold_log_height},
+                             {d_path, path_capacity, sz.path_width, sz.path_log_height},
+                             {d_reduce, reduce_capacity, sz.reduce_width, sz.reduce_log_height},
+                             {d_ipath, ipath_capacity, sz.ipath_width, sz.ipath_log_height},
+                             {d_transcript, transcript_capacity, sz.transcript_width, sz.transcript_log_height},
+                             {d_bits, bits_capacity, sz.bits_width, sz.bits_log_height},
+                             {d_chip, chip_capacity, sz.chip_width, sz.chip_log_height},
+                             {d_state, state_capacity, sz.state_width, sz.state_log_height}};
+    RK_TRY(check_outputs(outs, 8));
+    FriCall c{ctx, log_max, sz.n_rounds, queries};
+    ChipFeed chip, state;
+    RK_TRY(c.begin());
+    RK_TRY(clear_outputs(ctx, outs, 6));
+    RK_TRY(c.chip_feed(sz.chip_log_height, &chip));
+    RK_TRY(c.chip_feed(sz.state_log_height, &state));
+    RK_TRY(c.commit(d_fold_publics, d_fold_records, d_fold, d_path, nullptr, /*xcol=*/true, chip, /*firstcol=*/true));
+    RK_TRY(c.reduce(plan.open.red, d_reduce_publics, d_inputs, d_reduce, /*stride=*/sz.reduce_width));
+    RK_TRY(c.open(plan.open, d_inputs, d_paths, d_reduce, d_ipath, chip, state));
+    RK_TRY(c.transcript(plan, d_observed, d_transcript, d_bits, state));
     RK_TRY(c.chip_trace(chip, d_chip));
     return c.chip_trace(state, d_state);
     RK_GUARD_END

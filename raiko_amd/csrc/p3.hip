@@ -51,10 +51,19 @@ using rk::NEXT_BACK;
 constexpr uint32_t MAX_TABLES = 32, MAX_QD_LOG = 4;
 
 // ---------------------------------------------------------------- p3-challenger DuplexChallenger (host)
+// rk_p3_fri_transcript: the challenger's calls in order, every word it observed and every field element it sampled
+struct FriTranscript {
+    uint32_t log_max = 0, n_rounds = 0, blowup_log2 = 0, queries = 0;
+    std::vector<uint32_t> ops;        // (kind, count) pairs: 0 observe n words, 1 sample n field elements, 2 sample_bits(b)
+    std::vector<uint32_t> observed;   // Montgomery
+    std::vector<uint32_t> sampled;    // Montgomery, those behind sample_bits included
+    void op(uint32_t kind, uint32_t n) { ops.push_back(kind), ops.push_back(n); }
+};
 struct Challenger {
     const p2::Any* k;
     uint32_t state[p2::MAX_CELLS], in[p2::MAX_CELLS], out[p2::MAX_CELLS];
     unsigned n_in = 0, n_out = 0;
+    FriTranscript* log = nullptr;
     explicit Challenger(const p2::Any* kk) : k(kk) { std::memset(state, 0, sizeof state); }
     unsigned rate() const { return (unsigned)k->rate(); }
     void duplex() {
@@ -70,20 +79,27 @@ struct Challenger {
         if (n_in == rate()) duplex();
     }
     void observe(const uint32_t* v, size_t n) {
+        if (log && n) log->op(0, (uint32_t)n), log->observed.insert(log->observed.end(), v, v + n);
         for (size_t i = 0; i < n; i++) observe(v[i]);
     }
     uint32_t sample() {
         if (n_in != 0 || n_out == 0) duplex();
+        if (log) log->sampled.push_back(out[n_out - 1]);
         return out[--n_out];
     }
     Ext sample_ext() {
+        if (log) log->op(1, 4);
         Ext r;
         for (int i = 0; i < 4; i++) r.c[i] = sample();
         return r;
     }
-    uint32_t sample_bits(unsigned bits) { return bb::decode(sample()) & (uint32_t)(((uint64_t)1 << bits) - 1); }
+    uint32_t sample_bits(unsigned bits) {
+        if (log) log->op(2, bits);
+        return bb::decode(sample()) & (uint32_t)(((uint64_t)1 << bits) - 1);
+    }
     bool check_witness(unsigned bits, uint32_t w) {
-        observe(bb::encode(w));
+        const uint32_t wm = bb::encode(w);
+        observe(&wm, 1);
         return sample_bits(bits) == 0;
     }
 };
@@ -771,7 +787,7 @@ struct FriPaths {
 };
 int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init,
               const uint32_t* proof, size_t words, bool one_thread = false, FriCapture* cap = nullptr,
-              FriInputs* inp = nullptr, FriPaths* pth = nullptr) {
+              FriInputs* inp = nullptr, FriPaths* pth = nullptr, FriTranscript* trn = nullptr) {
     rk_params def;
     rk::params_preset(&def, RK_PRESET_SP1);
     const rk_params& par = params ? *params : def;
@@ -799,6 +815,7 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         log_max = std::max(log_max, log_n[t] + blow);
     }
     Challenger ch(k.get());
+    ch.log = trn;
     ch.observe(init, n_init);
     const uint32_t* troot = r.take(8);
     if (!troot) return 1;
@@ -1066,6 +1083,7 @@ int p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tab
         inp->per_record = 1 + trow + prow + qrow;
         inp->records.assign(inp->per_record * sys.queries, 0);
     }
+    if (trn) trn->log_max = log_max, trn->n_rounds = n_rounds, trn->blowup_log2 = blow, trn->queries = sys.queries;
     if (pth) {
         pth->log_max = log_max, pth->n_rounds = n_rounds, pth->blowup_log2 = blow, pth->queries = sys.queries;
         pth->publics.assign(25, 0);
@@ -1496,6 +1514,33 @@ int rk_p3_fri_input_paths(const rk_params* params, const rk_p3_table* tables, ui
     shape[0] = bb::encode(pth.log_max), shape[1] = bb::encode(pth.n_rounds), shape[2] = bb::encode(pth.blowup_log2), shape[3] = bb::encode(pth.queries);
     std::memcpy(publics, pth.publics.data(), pth.publics.size() * 4);
     std::memcpy(records, pth.records.data(), pth.records.size() * 4);
+    return 0;
+    RK_GUARD_END
+}
+
+int rk_p3_fri_transcript(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                         const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* ops, size_t ops_capacity, uint32_t* observed,
+                         size_t observed_capacity, uint32_t* sampled, size_t sampled_capacity, size_t* ops_words, size_t* observed_words,
+                         size_t* sampled_words) {
+    RK_GUARD_BEGIN
+    if (!shape || !ops_words || !observed_words || !sampled_words || (ops_capacity && !ops) || (observed_capacity && !observed) ||
+        (sampled_capacity && !sampled))
+        return RK_ERR_INVALID;
+    *ops_words = *observed_words = *sampled_words = 0;
+    rk_params def;
+    rk::params_preset(&def, RK_PRESET_SP1);
+    const rk_params& par = params ? *params : def;
+    // the bits table tells a proof-of-work sample from its low bits by the canonical 31-bit form: pow_bits <= 27
+    if (par.p2_width != 16 || par.fri_fold_log2 != 1 || par.p2_pad_free != 1 || par.pow_bits > 27) return RK_ERR_INVALID;
+    FriTranscript trn;
+    const int verdict = p3_verify(&par, tables, n_tables, init_words, n_init, proof, proof_words, false, nullptr, nullptr, nullptr, &trn);
+    if (verdict != 0) return verdict;
+    *ops_words = trn.ops.size(), *observed_words = trn.observed.size(), *sampled_words = trn.sampled.size();
+    if (trn.ops.size() > ops_capacity || trn.observed.size() > observed_capacity || trn.sampled.size() > sampled_capacity) return RK_ERR_CAPACITY;
+    shape[0] = bb::encode(trn.log_max), shape[1] = bb::encode(trn.n_rounds), shape[2] = bb::encode(trn.blowup_log2), shape[3] = bb::encode(trn.queries);
+    for (size_t i = 0; i < trn.ops.size(); i++) ops[i] = bb::encode(trn.ops[i]);
+    std::memcpy(observed, trn.observed.data(), trn.observed.size() * 4);
+    std::memcpy(sampled, trn.sampled.data(), trn.sampled.size() * 4);
     return 0;
     RK_GUARD_END
 }

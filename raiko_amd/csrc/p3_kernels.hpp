@@ -172,11 +172,12 @@ struct FriArgs {
     const uint32_t *pub, *rec;
     uint32_t *fold, *path, *claims, *chip_in, *chip_mult;
     uint32_t xcol, shiftm;      // xcol = 1: the fold rows end in X = shift (1 - 2 bit) x0 (rk_fri_reduce_rows_device); claims may then be null
+    uint32_t firstcol;          // 1: behind X the column FIRST = the row is a query's first (rk_fri_transcript_rows_device)
     RK_HD uint32_t lfh(uint32_t rd) const { return L - 1 - rd; }
     RK_HD size_t per_record() const { return 1 + 8 * (size_t)R + 8 * steps_before(R); }
     RK_HD size_t steps_before(uint32_t rd) const { return (size_t)rd * (L - 1) - (size_t)rd * (rd - 1) / 2; }   // sum of lfh(r), r < rd
     RK_HD size_t rec_round(uint32_t rd) const { return 1 + 8 * (size_t)rd + 8 * steps_before(rd); }
-    RK_HD uint32_t fold_width() const { return 41 + R + 2 * (L - 1) + xcol; }
+    RK_HD uint32_t fold_width() const { return 41 + R + 2 * (L - 1) + xcol + firstcol; }
     RK_HD uint32_t path_width() const { return 48 + R; }
 };
 constexpr uint32_t FRI_CLAIMS_WIDTH = 8;
@@ -221,7 +222,8 @@ RK_HD void fri_fold_lane(const FriArgs& a, uint32_t q) {
         row[30] = x0, row[31] = bb::sqr(x0);
         row[41 + rd] = bb::ONE;
         for (uint32_t j = 0; j < lfh; j++) row[41 + a.R + j] = (pidx >> j) & 1u ? bb::ONE : 0u;
-        if (a.xcol) row[fw - 1] = bb::mul(a.shiftm, bit ? bb::neg(x0) : x0);   // the point of the height-(L - rd) coset at idx
+        if (a.xcol) row[fw - 1 - a.firstcol] = bb::mul(a.shiftm, bit ? bb::neg(x0) : x0);   // the point of the height-(L - rd) coset at idx
+        if (a.firstcol) row[fw - 1] = rd == 0 ? bb::ONE : 0u;
         if (a.claims) {
             uint32_t* cl = a.claims + ((size_t)q * a.R + rd) * FRI_CLAIMS_WIDTH;
             cl[0] = qm, cl[1] = rdm, cl[2] = idxm, cl[7] = bb::ONE;
@@ -491,6 +493,65 @@ RK_HD void fri_open_ipath_lane(const FriOpenArgs& a, uint32_t t, const uint32_t*
         for (uint32_t j = 0; j < a.NB; j++) row[FRI_OPEN_IPATH_FIXED + j] = j == k ? bb::ONE : 0u;
         pos >>= 1;
     }
+}
+
+// ---- the transcript (rk_fri_transcript_rows_device; column plans: raiko_amd/fri_transcript.py).  steps = 10 plain words per
+// duplex permutation of the challenger: words absorbed | their offset in `observed` | per output cell 0..7 the sample_bits
+// slot that consumes it + 1 (0: none; slot 0 = the proof of work, slot q + 1 = query q).
+// transcript columns: IN 16 | OUT 16 | step one-hot N | real | per output cell: consumed by a sample_bits 8 | its slot 8.
+// bits columns: slot | value | 31 bits | b30 b29 b28 | real | slot - 1 | idx | is the proof of work | is a query.
+// `samples` = one word per slot, the output cell the chain kernel saw consumed there.
+constexpr uint32_t FRI_TRANSCRIPT_STEP_WORDS = 10, FRI_TRANSCRIPT_FIXED = 49, FRI_BITS_WIDTH = 39, FRI_TRANSCRIPT_MAX_STEPS = 1024;
+struct FriTranscriptArgs {
+    uint32_t N, Q, L, pow_bits;     // duplex permutations, queries, log_max
+    size_t state_base;              // the state chip's first input row behind the sponge's
+    const uint32_t *steps, *observed;
+    uint32_t *transcript, *bits, *state_in, *state_mult, *samples;
+    RK_HD uint32_t width() const { return FRI_TRANSCRIPT_FIXED + N; }
+};
+// The chain as one lane walks it, all 16 cells in its registers: what fri_transcript_chain_kernel (fri_tables.hip) does
+// with one lane per cell, and what the CPU emulation runs.  Step s overwrites the first n_in cells with observed words,
+// permutes, and leaves IN | OUT in row s, IN in the state chip's inputs, the consumed cells in `samples`.
+template <int M4>
+RK_HD void fri_transcript_chain_lane(const FriTranscriptArgs& a, const uint32_t* tab, const P2ChipLayout& L) {
+    uint32_t c[16];
+    for (int i = 0; i < 16; i++) c[i] = 0;
+    for (uint32_t s = 0; s < a.N; s++) {
+        const uint32_t* st = a.steps + FRI_TRANSCRIPT_STEP_WORDS * s;
+        uint32_t* row = a.transcript + (size_t)s * a.width();
+        uint32_t* sin = a.state_in + (a.state_base + s) * 16;
+        for (uint32_t i = 0; i < st[0]; i++) c[i] = a.observed[st[1] + i];
+        for (int i = 0; i < 16; i++) row[i] = sin[i] = c[i];
+        a.state_mult[a.state_base + s] = bb::ONE;
+        chip_permute<16, 13, M4, false>(c, nullptr, tab, L);
+        for (int i = 0; i < 16; i++) row[16 + i] = c[i];
+        for (int i = 0; i < 8; i++)
+            if (st[2 + i]) a.samples[st[2 + i] - 1] = c[i];
+    }
+}
+// One lane per transcript row: everything but IN and OUT (the chain writes those)
+RK_HD void fri_transcript_fill_lane(const FriTranscriptArgs& a, uint32_t s) {
+    uint32_t* row = a.transcript + (size_t)s * a.width();
+    const uint32_t* st = a.steps + FRI_TRANSCRIPT_STEP_WORDS * s;
+    for (uint32_t j = 0; j < a.N; j++) row[32 + j] = j == s ? bb::ONE : 0u;
+    row[32 + a.N] = bb::ONE;
+    for (uint32_t j = 0; j < 8; j++) {
+        row[33 + a.N + j] = st[2 + j] ? bb::ONE : 0u;
+        row[41 + a.N + j] = st[2 + j] ? bb::encode(st[2 + j] - 1) : 0u;
+    }
+}
+// One lane per bits row (slot): the canonical form of the sampled cell and what the checks read of it
+RK_HD void fri_bits_fill_lane(const FriTranscriptArgs& a, uint32_t slot) {
+    uint32_t* row = a.bits + (size_t)slot * FRI_BITS_WIDTH;
+    const uint32_t vm = a.samples[slot], v = bb::decode(vm);
+    const uint32_t nb = slot ? a.L : a.pow_bits;
+    row[0] = bb::encode(slot), row[1] = vm;
+    for (uint32_t i = 0; i < 31; i++) row[2 + i] = (v >> i) & 1u ? bb::ONE : 0u;
+    row[33] = ((v >> 28) & 7u) == 7u ? bb::ONE : 0u;
+    row[34] = bb::ONE;
+    row[35] = slot ? bb::encode(slot - 1) : 0u;
+    row[36] = bb::encode(v & (uint32_t)(((uint64_t)1 << nb) - 1));
+    row[37] = slot ? 0u : bb::ONE, row[38] = slot ? bb::ONE : 0u;
 }
 
 }  // namespace p3k

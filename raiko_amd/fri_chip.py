@@ -38,6 +38,7 @@ from . import fri_tables as T
 from .p3 import P, AirBuilder, ExtExpr
 
 BUS_FRI_OPEN, BUS_FRI_CLAIM = 5, 6
+BUS_FRI_SAMPLE, BUS_FRI_INDEX = 11, 12      # raiko_amd.fri_transcript
 SP1_ROOT_2_27 = 0x1A427A41
 
 Shape = collections.namedtuple("Shape", "log_max n_rounds blowup_log2 queries root_2_27", defaults=(SP1_ROOT_2_27,))
@@ -102,7 +103,7 @@ def _gen(shape, bits):
     return pow(shape.root_2_27, 1 << (27 - bits), P)
 
 
-def fri_fold_air(shape, ext_w=p3.EXT_W, coset_shift=None):
+def fri_fold_air(shape, ext_w=p3.EXT_W, coset_shift=None, index_bus=False):
     """One row per (query, round), the rounds of a query on consecutive rows.  Enforced per row (degree <= 3):
       pair order      (e0, e1) = (cur, sib) ordered by bit; cur = the joining reduced opening in round 0, afterwards the
                       previous row's folded + this row's joining reduced opening
@@ -115,12 +116,15 @@ def fri_fold_air(shape, ext_w=p3.EXT_W, coset_shift=None):
     and three sends with multiplicity `real` (0 on padding rows).
     coset_shift = s (raiko_amd.fri_reduce): one more column X = s (1 - 2 bit) x0 behind the others, the point of the
     height-(L - rd) coset at idx [bitrev(2 p + b, n) = b 2^(n-1) + bitrev(p, n-1), gen(n)^(2^(n-1)) = -1]; the claim sent
-    becomes (query, round, idx, X, reduced opening).  None: the AIR without it."""
+    becomes (query, round, idx, X, reduced opening).  None: the AIR without it.
+    index_bus (raiko_amd.fri_transcript): one more column FIRST = REAL SEL[0] behind the others, with which a query's first
+    row receives (query, idx) from BUS_FRI_INDEX: the index is the one the bits table cut from the transcript."""
     L, R = shape.log_max, shape.n_rounds
     nb = L - 1
     c = FoldCols(shape)
     with_x = coset_shift is not None
-    b = AirBuilder(c.width + (1 if with_x else 0), 12 * R + 4, ext_w)
+    first_col = c.width + (1 if with_x else 0)
+    b = AirBuilder(first_col + (1 if index_bus else 0), 12 * R + 4, ext_w)
     loc, nxt = b.local, b.next
     ext = lambda at, f=loc: ExtExpr([f(at + k) for k in range(4)], ext_w % P)
     real, bit = loc(c.REAL), loc(c.BIT)
@@ -178,6 +182,9 @@ def fri_fold_air(shape, ext_w=p3.EXT_W, coset_shift=None):
     b.send(p3.BUS_POSEIDON2, pair + [c.ZERO] * 8 + list(range(c.DIG, c.DIG + 8)), mult=c.REAL, mult_is_const=False)
     b.send(BUS_FRI_OPEN, [c.Q, c.RD] + list(range(c.DIG, c.DIG + 8)) + [c.PIDX], mult=c.REAL, mult_is_const=False)
     b.send(BUS_FRI_CLAIM, [c.Q, c.RD, c.IDX] + ([c.width] if with_x else []) + list(range(c.RO, c.RO + 4)), mult=c.REAL, mult_is_const=False)
+    if index_bus:
+        b.assert_eq(loc(first_col), real * sel[0])
+        b.receive(BUS_FRI_INDEX, [c.Q, c.IDX], mult=first_col, mult_is_const=False)
     return b.build()
 
 
