@@ -294,7 +294,7 @@ struct FriTranscriptPlan {
     rk_fri_transcript_size_info sz;
     std::vector<uint32_t> steps;      // FRI_TRANSCRIPT_STEP_WORDS per duplex permutation
 };
-// the duplex permutations from the challenger's calls (Montgomery pairs, rk_p3_fri_transcript): p3.hip's Challenger replayed
+// the duplex permutations from the challenger's calls (Montgomery pairs, rk_p3_fri_transcript): p3_host.hpp's Challenger replayed
 // without hashing -- which step absorbs which observed words, which output cell every sample pops
 int fri_transcript_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint32_t* layout, uint32_t n_matrices, const uint32_t* ops,
                         uint32_t n_ops, FriTranscriptPlan* plan) {

@@ -192,7 +192,7 @@ int pcs_reduce_openings(rk_ctx* ctx, uint32_t* d_ro_ext, const uint32_t* d_lde, 
                         const uint32_t* h_points, const uint32_t* h_ys, const bb::Ext& alpha, uint64_t alpha_offset, bool cols = false);
 int pcs_coset_lde_cols(rk_ctx* ctx, uint32_t* d_cols, const uint32_t* d_in, size_t h, size_t w);
 int ext_sub_at(rk_ctx* ctx, uint32_t* d_ext, const uint32_t* h_idx, const bb::Ext* h_delta, size_t n);
-// p3.hip: the contexts rk_p3_prove_shards keeps per device (freed by rk_session_release)
+// p3_shards.hip: the contexts rk_p3_prove_shards keeps per device (freed by rk_session_release)
 void p3_release_pools();
 
 // code_cache.hip: the committed code group of a segment, kept per device and looked up by content

@@ -2,7 +2,7 @@
 // translation of the step list into an rk_program for the GPU evaluator, sp1-core's eval_permutation_constraints written
 // as steps (PermStepGen) -- and the Poseidon2 chip: its AIR written from the configured instance's constants and its rows
 // written on the GPU (rk_p2_chip_*; layout, constants and the trace behind its checks: p3_air.hpp, for the FRI tables too).
-// Prover and verifier are in p3.hip.  Reference call site of the path:
+// Prover and verifier are in p3.hip and p3_verify.hip.  Reference call site of the path:
 // provers/sp1/driver/src/lib.rs:44-57; p3-uni-stark symbolic_builder.rs / symbolic_expression.rs, sp1-core
 // stark/permutation.rs, sp1-recursion-core's Poseidon2 wide chip: outside the reference tree, RECALLED.
 #include "p3_air.hpp"

@@ -1,5 +1,5 @@
 // Shared by p3_air.hip (the AIR front end: rk_air_*, the lookup constraints, the Poseidon2 chip), fri_tables.hip (the rows
-// of the FRI lookup tables) and p3.hip (prover, verifier, shards): what an rk_air holds, the scoped device buffer all
+// of the FRI lookup tables) and p3.hip / p3_verify.hip (prover, verifier): what an rk_air holds, the scoped device buffer all
 // three use, and the Poseidon2 chip as the FRI tables feed it.
 #pragma once
 #include "internal.hpp"

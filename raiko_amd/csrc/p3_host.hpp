@@ -1,0 +1,118 @@
+// What the uni-stark prover (p3.hip) and its host verifier (p3_verify.hip) share: the limits of a statement, the
+// DuplexChallenger both run the transcript on, the checks both make on the tables, "the caller's parameter set or the
+// SP1 preset", and the layout of a proof -- the one place its size is worked out.
+#pragma once
+#include "p3_air.hpp"
+
+#include <algorithm>
+
+namespace p3h {
+
+using bb::Ext;
+constexpr uint32_t MAX_TABLES = 32, MAX_QD_LOG = 4;
+
+inline rk_params params_or_sp1(const rk_params* params) {
+    rk_params def;
+    rk::params_preset(&def, RK_PRESET_SP1);
+    return params ? *params : def;
+}
+
+// ---------------------------------------------------------------- p3-challenger DuplexChallenger (host)
+// rk_p3_fri_transcript: the challenger's calls in order, every word it observed and every field element it sampled
+struct Transcript {
+    std::vector<uint32_t> ops;        // (kind, count) pairs: 0 observe n words, 1 sample n field elements, 2 sample_bits(b)
+    std::vector<uint32_t> observed;   // Montgomery
+    std::vector<uint32_t> sampled;    // Montgomery, those behind sample_bits included
+    void op(uint32_t kind, uint32_t n) { ops.push_back(kind), ops.push_back(n); }
+};
+struct Challenger {
+    const p2::Any* k;
+    uint32_t state[p2::MAX_CELLS], in[p2::MAX_CELLS], out[p2::MAX_CELLS];
+    unsigned n_in = 0, n_out = 0;
+    Transcript* log = nullptr;
+    explicit Challenger(const p2::Any* kk) : k(kk) { std::memset(state, 0, sizeof state); }
+    unsigned rate() const { return (unsigned)k->rate(); }
+    void duplex() {
+        for (unsigned i = 0; i < n_in; i++) state[i] = in[i];
+        n_in = 0;
+        k->permute(state);
+        for (unsigned i = 0; i < rate(); i++) out[i] = state[i];
+        n_out = rate();
+    }
+    void observe(uint32_t v) {
+        n_out = 0;
+        in[n_in++] = v;
+        if (n_in == rate()) duplex();
+    }
+    void observe(const uint32_t* v, size_t n) {
+        if (log && n) log->op(0, (uint32_t)n), log->observed.insert(log->observed.end(), v, v + n);
+        for (size_t i = 0; i < n; i++) observe(v[i]);
+    }
+    uint32_t sample() {
+        if (n_in != 0 || n_out == 0) duplex();
+        if (log) log->sampled.push_back(out[n_out - 1]);
+        return out[--n_out];
+    }
+    Ext sample_ext() {
+        if (log) log->op(1, 4);
+        Ext r;
+        for (int i = 0; i < 4; i++) r.c[i] = sample();
+        return r;
+    }
+    uint32_t sample_bits(unsigned bits) {
+        if (log) log->op(2, bits);
+        return bb::decode(sample()) & (uint32_t)(((uint64_t)1 << bits) - 1);
+    }
+    bool check_witness(unsigned bits, uint32_t w) {
+        const uint32_t wm = bb::encode(w);
+        observe(&wm, 1);
+        return sample_bits(bits) == 0;
+    }
+};
+
+inline int check_tables(const rk_params& par, const rk_p3_table* tables, uint32_t n_tables, bool prover, uint32_t* lqd) {
+    if (!tables || n_tables == 0 || n_tables > MAX_TABLES) return RK_ERR_INVALID;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const rk_p3_table& tb = tables[t];
+        if (!tb.air || tb.width != tb.air->width || tb.n_public != tb.air->n_public || (tb.n_public && !tb.public_values)) return RK_ERR_INVALID;
+        for (uint32_t i = 0; i < tb.n_public; i++)
+            if (tb.public_values[i] >= bb::P) return RK_ERR_INVALID;
+        lqd[t] = tb.air->info.log_quotient_degree;
+        if (lqd[t] > par.blowup_log2 || lqd[t] > MAX_QD_LOG) return RK_ERR_INVALID;  // the LDE must cover the quotient domain
+        if (prover && (!tb.trace || tb.log_height < 1 || tb.log_height + par.blowup_log2 > ntt::LAMBDA || tb.on_device > 1)) return RK_ERR_INVALID;
+    }
+    return RK_OK;
+}
+
+// The words of a proof, from the blow-up, the tables' widths, permutation widths and log quotient degrees (lqd) and their
+// log heights (log_n: the prover's own, or the ones the verifier read from the header):
+//   head   table count, heights | trace root | [permutation root, 4 words of cumulative sum per table with lookups] |
+//          quotient root | per table: local 4w, next 4w, [perm local 4pw, perm next 4pw], chunks 16 each | round count,
+//          8 words of root per round, final polynomial 4, witness
+//   query  trace rows, path 8 log_max | [permutation rows, path 8 log_pmax] | quotient rows, path 8 log_max |
+//          per round: sibling 4, path 8 (log_max - 1 - round)
+struct Layout {
+    unsigned log_max = 0, log_pmax = 0, n_rounds = 0;
+    size_t trow = 0, prow = 0, qrow = 0;   // words of one opened row of the trace, permutation and quotient batch
+    size_t head_words = 0, query_words = 0;
+    Layout() = default;
+    Layout(unsigned blow, const rk_p3_table* t, uint32_t n, const uint32_t* lqd, const unsigned* log_n) {
+        head_words = 1 + n + 16;
+        for (uint32_t i = 0; i < n; i++) {
+            const size_t pw = t[i].air->perm_width;
+            head_words += 8 * (size_t)t[i].width + 8 * pw + (pw ? 4 : 0) + ((size_t)16 << lqd[i]);
+            log_max = std::max(log_max, log_n[i] + blow);
+            if (pw) log_pmax = std::max(log_pmax, log_n[i] + blow);
+            trow += t[i].width;
+            prow += pw;
+            qrow += (size_t)4 << lqd[i];
+        }
+        n_rounds = log_max - blow;
+        head_words += 1 + 8 * (size_t)n_rounds + 4 + 1 + (prow ? 8 : 0);
+        query_words = trow + qrow + 16 * (size_t)log_max + (prow ? prow + 8 * (size_t)log_pmax : 0);
+        for (unsigned r = 0; r < n_rounds; r++) query_words += 4 + 8 * (size_t)(log_max - 1 - r);
+    }
+    size_t words(uint32_t queries) const { return head_words + query_words * queries; }
+};
+
+}  // namespace p3h

@@ -17,7 +17,7 @@ using K2 = Core<16, 13, 0>;
 using K3 = Core<16, 13, 1>;  // SP1 / Plonky3 shape
 constexpr int MAX_CELLS = 24;
 
-// rk_p3_verify_hashes: while set on the calling thread, every host permutation appends its input state here (what a
+// rk_p3_verify_hashes (p3_verify.hip): while set on the calling thread, every host permutation appends its input state here (what a
 // recursion layer's Poseidon2 chip has to prove for the proof being checked).  Host only.
 inline thread_local std::vector<uint32_t>* g_permute_log = nullptr;
 

@@ -26,7 +26,6 @@ pidx = idx_rd >> 1, bit = idx_rd & 1.
 statement / airs / host_tables / device_tables / prove / verify_fri_statement are the calls; host_tables is a numpy
 witness of all four tables (Poseidon2 restated here), device_tables the same rows written on the GPU
 (rk_fri_chip_rows_device)."""
-import collections
 import ctypes as C
 import os
 import re
@@ -39,9 +38,7 @@ from .p3 import P, AirBuilder, ExtExpr
 
 BUS_FRI_OPEN, BUS_FRI_CLAIM = 5, 6
 BUS_FRI_SAMPLE, BUS_FRI_INDEX = 11, 12      # raiko_amd.fri_transcript
-SP1_ROOT_2_27 = 0x1A427A41
-
-Shape = collections.namedtuple("Shape", "log_max n_rounds blowup_log2 queries root_2_27", defaults=(SP1_ROOT_2_27,))
+SP1_ROOT_2_27, Shape = T.SP1_ROOT_2_27, T.Shape     # the shape every FRI statement carries (fri_tables)
 
 
 def lfh(shape, rd):
@@ -256,29 +253,7 @@ def _check_scope(params):
 def fri_openings(tables, proof, init=(), params=None):
     """rk_p3_fri_openings -> (verdict, Shape or None, publics, records): Montgomery words; nothing but the verdict
     unless it is 0"""
-    lib = _lib.load()
-    arr, keep = p3._c_tables(tables)
-    iw = np.ascontiguousarray(init, dtype=np.uint32)
-    pf = np.ascontiguousarray(proof, dtype=np.uint32)
-    par = C.byref(params) if params is not None else None
-    shape = np.zeros(4, dtype=np.uint32)
-    n_pub, n_rec = C.c_size_t(0), C.c_size_t(0)
-    pub, rec = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-    while True:
-        rc = lib.rk_p3_fri_openings(par, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
-                                    shape.ctypes.data_as(_lib.u32p), pub.ctypes.data_as(_lib.u32p) if pub.size else None, pub.size,
-                                    rec.ctypes.data_as(_lib.u32p) if rec.size else None, rec.size, C.byref(n_pub), C.byref(n_rec))
-        if rc != _lib.RK_ERR_CAPACITY:
-            break
-        pub, rec = np.zeros(n_pub.value, dtype=np.uint32), np.zeros(n_rec.value, dtype=np.uint32)
-    del keep
-    if rc < 0:
-        _lib.check(None, rc)
-    if rc != 0:
-        return rc, None, None, None
-    s = [int(v) for v in p3.from_mont(shape)]
-    root = int(params.root_2_27) if params is not None else SP1_ROOT_2_27
-    return 0, Shape(s[0], s[1], s[2], s[3], root), pub, rec
+    return T.capture("rk_p3_fri_openings", 2, tables, proof, init, params)
 
 
 _CONSTS_INC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "poseidon2_consts.inc")

@@ -162,29 +162,7 @@ def fri_ipath_air(shape, trees, ext_w=p3.EXT_W):
 def fri_input_paths(tables, proof, init=(), params=None):
     """rk_p3_fri_input_paths -> (verdict, Shape or None, publics, records): Montgomery words; nothing but the verdict
     unless it is 0"""
-    lib = _lib.load()
-    arr, keep = p3._c_tables(tables)
-    iw = np.ascontiguousarray(init, dtype=np.uint32)
-    pf = np.ascontiguousarray(proof, dtype=np.uint32)
-    par = C.byref(params) if params is not None else None
-    shape = np.zeros(4, dtype=np.uint32)
-    n_pub, n_rec = C.c_size_t(0), C.c_size_t(0)
-    pub, rec = np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-    while True:
-        rc = lib.rk_p3_fri_input_paths(par, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
-                                       shape.ctypes.data_as(_lib.u32p), pub.ctypes.data_as(_lib.u32p) if pub.size else None, pub.size,
-                                       rec.ctypes.data_as(_lib.u32p) if rec.size else None, rec.size, C.byref(n_pub), C.byref(n_rec))
-        if rc != _lib.RK_ERR_CAPACITY:
-            break
-        pub, rec = np.zeros(n_pub.value, dtype=np.uint32), np.zeros(n_rec.value, dtype=np.uint32)
-    del keep
-    if rc < 0:
-        _lib.check(None, rc)
-    if rc != 0:
-        return rc, None, None, None
-    s = [int(v) for v in p3.from_mont(shape)]
-    root = int(params.root_2_27) if params is not None else F.SP1_ROOT_2_27
-    return 0, F.Shape(s[0], s[1], s[2], s[3], root), pub, rec
+    return T.capture("rk_p3_fri_input_paths", 2, tables, proof, init, params)
 
 
 class Statement:

@@ -218,31 +218,10 @@ def fri_reduce_air(shape, slots, ext_w=p3.EXT_W, sponge=False):
 def fri_inputs(tables, proof, init=(), params=None):
     """rk_p3_fri_inputs -> (verdict, Shape or None, layout [Matrix], publics, records): Montgomery words; nothing but the
     verdict unless it is 0"""
-    lib = _lib.load()
-    arr, keep = p3._c_tables(tables)
-    iw = np.ascontiguousarray(init, dtype=np.uint32)
-    pf = np.ascontiguousarray(proof, dtype=np.uint32)
-    par = C.byref(params) if params is not None else None
-    shape = np.zeros(4, dtype=np.uint32)
-    n = [C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)]
-    bufs = [np.zeros(0, dtype=np.uint32)] * 3
-    ptr = lambda a: a.ctypes.data_as(_lib.u32p) if a.size else None
-    while True:
-        rc = lib.rk_p3_fri_inputs(par, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
-                                  shape.ctypes.data_as(_lib.u32p), ptr(bufs[0]), bufs[0].size, ptr(bufs[1]), bufs[1].size, ptr(bufs[2]), bufs[2].size,
-                                  C.byref(n[0]), C.byref(n[1]), C.byref(n[2]))
-        if rc != _lib.RK_ERR_CAPACITY:
-            break
-        bufs = [np.zeros(v.value, dtype=np.uint32) for v in n]
-    del keep
-    if rc < 0:
-        _lib.check(None, rc)
+    rc, shape, layout, pub, rec = T.capture("rk_p3_fri_inputs", 3, tables, proof, init, params)
     if rc != 0:
         return rc, None, None, None, None
-    s = [int(v) for v in p3.from_mont(shape)]
-    root = int(params.root_2_27) if params is not None else F.SP1_ROOT_2_27
-    layout = [Matrix(*[int(v) for v in row]) for row in p3.from_mont(bufs[0]).reshape(-1, 5)]
-    return 0, Shape(s[0], s[1], s[2], s[3], root), layout, bufs[1], bufs[2]
+    return 0, shape, [Matrix(*[int(v) for v in row]) for row in p3.from_mont(layout).reshape(-1, 5)], pub, rec
 
 
 class Statement:

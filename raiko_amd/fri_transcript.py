@@ -7,7 +7,7 @@ polynomial and the proof-of-work witness are the words that chain absorbs and gi
   fold''      fri_chip.fri_fold_air(..., index_bus=True): fold' plus the column FIRST = REAL SEL[0], with which a query's
               first row receives (Q, IDX) from BUS_FRI_INDEX.
   path, reduce'', ipath   as in fri_open, unchanged.
-  transcript  transcript_air: one row per duplex permutation of the DuplexChallenger (csrc/p3.hip), N rows.  IN 16 | OUT 16 |
+  transcript  transcript_air: one row per duplex permutation of the DuplexChallenger (csrc/p3_host.hpp), N rows.  IN 16 | OUT 16 |
               STEP one-hot N | REAL | BM 8 | SLOT 8.  STEP is pinned to step 0 on the first row, shifts by one per row and
               is all zero behind N rows; REAL = sum STEP.  The PLAN -- a function of the challenger's calls alone, no
               hashing (plan_of) -- says per step how many words the duplex absorbs and which output cells the samples
@@ -182,31 +182,7 @@ def bits_air(log_max, pow_bits, ext_w=p3.EXT_W):
 def fri_transcript(tables, proof, init=(), params=None):
     """rk_p3_fri_transcript -> (verdict, Shape or None, ops, observed, sampled): Montgomery words; nothing but the verdict
     unless it is 0"""
-    lib = _lib.load()
-    arr, keep = p3._c_tables(tables)
-    iw = np.ascontiguousarray(init, dtype=np.uint32)
-    pf = np.ascontiguousarray(proof, dtype=np.uint32)
-    par = C.byref(params) if params is not None else None
-    shape = np.zeros(4, dtype=np.uint32)
-    n = [C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)]
-    out = [np.zeros(0, dtype=np.uint32)] * 3
-    while True:
-        bufs = []
-        for a in out:
-            bufs += [a.ctypes.data_as(_lib.u32p) if a.size else None, a.size]
-        rc = lib.rk_p3_fri_transcript(par, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
-                                      shape.ctypes.data_as(_lib.u32p), *bufs, *[C.byref(v) for v in n])
-        if rc != _lib.RK_ERR_CAPACITY:
-            break
-        out = [np.zeros(v.value, dtype=np.uint32) for v in n]
-    del keep
-    if rc < 0:
-        _lib.check(None, rc)
-    if rc != 0:
-        return rc, None, None, None, None
-    s = [int(v) for v in p3.from_mont(shape)]
-    root = int(params.root_2_27) if params is not None else F.SP1_ROOT_2_27
-    return 0, F.Shape(s[0], s[1], s[2], s[3], root), out[0], out[1], out[2]
+    return T.capture("rk_p3_fri_transcript", 3, tables, proof, init, params)
 
 
 def _check_scope(params):

@@ -54,7 +54,7 @@ def setup(params, case, queries, init, more=()):
 
 
 def challenger_replay(ops, observed, consts):
-    """csrc/p3.hip's DuplexChallenger in plain Python over canonical words -> (sampled, absorbed words per duplex)"""
+    """csrc/p3_host.hpp's DuplexChallenger in plain Python over canonical words -> (sampled, absorbed words per duplex)"""
     state, buf, out, at, sampled, duplexes = [0] * 16, [], [], 0, [], []
 
     def duplex():

@@ -233,6 +233,27 @@ def test_lookups_that_do_not_balance_are_rejected_by_both_verifiers(params, pres
     s = pf.copy()
     s[at] = (int(s[at]) + 5) % P
     assert o.oracle_p3_verify(tables, s, init) == 8 == p3.verify(tables, s, init, params=blob)
+    # two defects at once: both verifiers report the same one (the stages of the check run in one order)
+    summed = pf.copy()
+    summed[at] = (int(summed[at]) + 5) % P
+    forged = summed.copy()
+    forged[at + 4] = (int(forged[at + 4]) - 5) % P
+    for base, reason in ((summed, 8), (forged, 3)):
+        for two in (base[:-3], np.concatenate([base, [0]]).astype(np.uint32)):      # ... and the last 3 words cut off / one trailing word
+            assert o.oracle_p3_verify(tables, two, init) == reason == p3.verify(tables, two, init, params=blob)
+    two = summed.copy()
+    two[-1] = P                                      # ... and a word that is no field element
+    assert o.oracle_p3_verify(tables, two, init) == 1 == p3.verify(tables, two, init, params=blob)
+    high = [p3.Table(t.air, None, t.public_values) for t in tables]
+    high[3].log_height = tables[3].log_height + 1    # ... and a pinned height the proof does not have
+    assert o.oracle_p3_verify(high, summed, init) == 2 == p3.verify(high, summed, init, params=blob)
+    for n in range(400):                             # every cut inside the header, the roots, the sums and the opened values
+        assert o.oracle_p3_verify(tables, pf[:n], init) == p3.verify(tables, pf[:n], init, params=blob) != 0, n
+    # the one known difference: the product checks the total length before any query, the oracle query by query -- a
+    # changed last word (6 from both on its own) AND a trailing word (1 from both on its own) give 6 from the oracle
+    two = np.concatenate([pf, [0]]).astype(np.uint32)
+    two[pf.size - 1] = (int(two[pf.size - 1]) + 1) % P
+    assert p3.verify(tables, two, init, params=blob) == 1
     # a verifier can pin a table's height (the range table must hold ALL values): the proof's own height word is not enough
     free = [p3.Table(t.air, None, t.public_values) for t in tables]
     assert p3.verify(free, pf, init, params=blob) == 0 == o.oracle_p3_verify(free, pf, init)       # heights from the proof
