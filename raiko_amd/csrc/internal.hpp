@@ -161,11 +161,26 @@ int bit_reverse_ext(rk_ctx* ctx, uint32_t* d_io_ext, size_t size, size_t count);
 // every level from the one with top_output_size (<= HASH_FOLD_TOP_MAX, a power of two) parents up to the root
 constexpr size_t HASH_FOLD_TOP_MAX = 4096;
 int hash_fold_top(rk_ctx* ctx, uint32_t* d_nodes, size_t top_output_size);
-// d_out_ext[e] = sum_k coeffs[which[e]*size + k] * pw[pw_sel[e]*size + k]
-int eval_dot(rk_ctx* ctx, uint32_t* d_out_ext, const uint32_t* d_coeffs, size_t size, const uint32_t* d_which,
-             const uint32_t* d_pw_ext, const uint32_t* d_pw_sel, size_t eval_count);
-int mix_poly_coeffs(rk_ctx* ctx, uint32_t* d_out_ext, const bb::Ext& mix_start, const bb::Ext& mix,
-                    const uint32_t* d_in, const uint32_t* h_combos, size_t input_size, size_t count);
+// d_out_ext[e] = sum_k coeffs[which[e]*size + k] * pw[pw_sel[e]*size + k], one launch over several coefficient buffers:
+// the evaluations are numbered through the sources in order, the first srcs[0].n of them read srcs[0].d_coeffs, ...
+// h_which / h_sel (host, one word per evaluation) are arbitrary: repeats, any order
+struct EvalSrc {
+    const uint32_t* d_coeffs;
+    size_t n;
+};
+int eval_dot(rk_ctx* ctx, uint32_t* d_out_ext, size_t size, const EvalSrc* srcs, size_t n_srcs, const uint32_t* h_which,
+             const uint32_t* h_sel, const uint32_t* d_pw_ext);
+// out[h_combos[i]*count + idx] += mix_start * mix^i * in[i*count + idx], the columns i numbered through the sources in
+// order (srcs[g].n columns of `count` words at srcs[g].d_in, their combos at srcs[g].h_combos).
+// fresh_combos != 0: instead of adding to `out`, every combo below fresh_combos is written once (zero where no column
+// names it) and none may be named at or above it
+struct MixSrc {
+    const uint32_t* d_in;
+    const uint32_t* h_combos;
+    size_t n;
+};
+int mix_poly_coeffs(rk_ctx* ctx, uint32_t* d_out_ext, const bb::Ext& mix_start, const bb::Ext& mix, const MixSrc* srcs,
+                    size_t n_srcs, size_t count, size_t fresh_combos);
 int poly_divide(rk_ctx* ctx, uint32_t* d_poly_ext, size_t count, const bb::Ext& z, bb::Ext* h_rem);
 // n_items polynomials of `count` ext coefficients at d_base_ext + h_offsets[i] (in ext elements), each divided
 // by (x - h_z[i]) in one batch of launches; remainders to h_rems (may be null)

@@ -3,6 +3,7 @@
 // device form of core/poly.rs poly_divide.  All are HBM-bound streaming kernels:
 // one lane per coefficient index, consecutive lanes on consecutive addresses.
 #include "internal.hpp"
+#include "poly_lazy.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -21,6 +22,11 @@ inline unsigned grid_for(size_t n, unsigned cap = 16384) {
 __device__ __forceinline__ Ext load_ext(const uint32_t* p) {
     uint4 v = *reinterpret_cast<const uint4*>(p);
     return Ext{{v.x, v.y, v.z, v.w}};
+}
+// for a pointer that was itself read from device memory: the compiler cannot tell that it points to global memory and
+// would use the slower generic (flat) load
+__device__ __forceinline__ uint32_t load_global(const uint32_t* p) {
+    return *(const __attribute__((address_space(1))) uint32_t*)p;
 }
 __device__ __forceinline__ void store_ext(uint32_t* p, const Ext& e) {
     *reinterpret_cast<uint4*>(p) = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
@@ -157,43 +163,82 @@ __global__ void bit_reverse_ext_kernel(uint32_t* io, size_t total, size_t size, 
     }
 }
 
-// partial[e][blk] = sum over this block's slice of coeffs[which[e]][k] * pw[sel[e]][k]
+// partial[e][blk] = sum over this block's slice of column_e[k] * pw[sel][k], for the up to DOT_BATCH evaluations e of
+// one batch: they share the power table, so a lane loads the table element once per k and one coefficient word per
+// evaluation.  The products are accumulated lazily (poly_lazy.hpp) and reduced once per lane.
 constexpr int DOT_BLOCKS = 64;
-__global__ __launch_bounds__(TPB) void eval_dot_kernel(uint32_t* __restrict__ partial, const uint32_t* __restrict__ coeffs,
-                                                       size_t size, const uint32_t* __restrict__ which,
-                                                       const uint32_t* __restrict__ pw, const uint32_t* __restrict__ sel) {
-    __shared__ uint32_t red[TPB * 4];
-    size_t e = blockIdx.y;
-    const uint32_t* c = coeffs + (size_t)which[e] * size;
-    const uint32_t* p = pw + (size_t)sel[e] * size * 4;
-    Ext acc = bb::ext_zero();
-    // four independent (coefficient, table element) loads in flight per lane
-    constexpr size_t STEP = (size_t)DOT_BLOCKS * TPB;
+constexpr int DOT_BATCH = 8;
+constexpr int DOT_RED_STRIDE = TPB + 8;   // words per row of the reduction tile: 8 lanes of 4 rows fill the 32 banks once
+constexpr size_t DOT_STEP = (size_t)DOT_BLOCKS * TPB;
+struct EvalBatch {
+    const uint32_t* col[DOT_BATCH];   // the coefficient columns
+    uint32_t out[DOT_BATCH];          // the evaluations' positions in the caller's order
+    uint32_t sel, nb;                 // power table; evaluations in this batch: 1, 2, 4 or 8
+};
+template <int NB>
+__device__ __forceinline__ void eval_dot_body(uint32_t* __restrict__ partial, const EvalBatch* __restrict__ bp,
+                                              const uint32_t* __restrict__ pw, size_t size, uint32_t* red) {
+    const EvalBatch& b = *bp;
+    const uint32_t* p = pw + (size_t)b.sel * size * 4;
+    pl::Acc acc[NB];
+#pragma unroll
+    for (int e = 0; e < NB; e++) acc[e] = pl::zero();
     size_t k = (size_t)blockIdx.x * TPB + threadIdx.x;
-    for (; k + 3 * STEP < size; k += 4 * STEP) {
-        uint32_t v[4];
+    // one fold interval per trip: its table elements and coefficient words are loaded together
+    static_assert(pl::FOLD_TERMS == 4, "the trip below is one fold interval");
+    for (; k + 3 * DOT_STEP < size; k += 4 * DOT_STEP) {
         Ext t[4];
+        uint32_t v[4][NB];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            v[u] = c[k + u * STEP];
-            t[u] = load_ext(p + (k + u * STEP) * 4);
+            t[u] = load_ext(p + (k + u * DOT_STEP) * 4);
+#pragma unroll
+            for (int e = 0; e < NB; e++) v[u][e] = load_global(b.col[e] + k + u * DOT_STEP);
         }
 #pragma unroll
-        for (int u = 0; u < 4; u++) acc = bb::add(acc, bb::scale(t[u], v[u]));
-    }
-    for (; k < size; k += STEP) acc = bb::add(acc, bb::scale(load_ext(p + k * 4), c[k]));
+        for (int e = 0; e < NB; e++) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) red[threadIdx.x * 4 + j] = acc.c[j];
+            for (int u = 0; u < 4; u++) pl::mac(acc[e], v[u][e], t[u]);
+            pl::fold(acc[e]);
+        }
+    }
+    // at most three terms on top of a folded value
+    for (; k < size; k += DOT_STEP) {
+        const Ext t = load_ext(p + k * 4);
+#pragma unroll
+        for (int e = 0; e < NB; e++) pl::mac(acc[e], load_global(b.col[e] + k), t);
+    }
+#pragma unroll
+    for (int e = 0; e < NB; e++) {
+        const Ext r = pl::finish(acc[e]);
+#pragma unroll
+        for (int j = 0; j < 4; j++) red[(e * 4 + j) * DOT_RED_STRIDE + threadIdx.x] = r.c[j];
+    }
     __syncthreads();
-    for (int s = TPB / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                red[threadIdx.x * 4 + j] = bb::add(red[threadIdx.x * 4 + j], red[(threadIdx.x + s) * 4 + j]);
-        }
-        __syncthreads();
+    // row = (evaluation, component); eight lanes per row sum 32 lanes' words each (< 32 p < 2^36), then combine
+    const unsigned row = threadIdx.x >> 3, s = threadIdx.x & 7;
+    uint32_t val = 0;
+    if (row < NB * 4) {
+        uint64_t sum = 0;
+#pragma unroll 8
+        for (int i = 0; i < TPB / 8; i++) sum += red[row * DOT_RED_STRIDE + i * 8 + s];
+        val = (uint32_t)(sum % bb::P);
     }
-    if (threadIdx.x < 4) partial[(e * DOT_BLOCKS + blockIdx.x) * 4 + threadIdx.x] = red[threadIdx.x];
+    val = bb::add(val, __shfl_xor(val, 1));
+    val = bb::add(val, __shfl_xor(val, 2));
+    val = bb::add(val, __shfl_xor(val, 4));
+    if (row < NB * 4 && s == 0) partial[((size_t)bp->out[row >> 2] * DOT_BLOCKS + blockIdx.x) * 4 + (row & 3)] = val;
+}
+__global__ __launch_bounds__(TPB) void eval_dot_kernel(uint32_t* __restrict__ partial, const EvalBatch* __restrict__ batches,
+                                                       size_t size, const uint32_t* __restrict__ pw) {
+    __shared__ uint32_t red[DOT_BATCH * 4 * DOT_RED_STRIDE];
+    const EvalBatch* bp = batches + blockIdx.y;
+    switch (bp->nb) {
+        case 8: eval_dot_body<8>(partial, bp, pw, size, red); break;
+        case 4: eval_dot_body<4>(partial, bp, pw, size, red); break;
+        case 2: eval_dot_body<2>(partial, bp, pw, size, red); break;
+        default: eval_dot_body<1>(partial, bp, pw, size, red); break;
+    }
 }
 __global__ void eval_reduce_kernel(uint32_t* out, const uint32_t* partial, size_t n_eval) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -204,34 +249,45 @@ __global__ void eval_reduce_kernel(uint32_t* out, const uint32_t* partial, size_
     out[i] = acc;
 }
 
-// one grid.y slot per distinct combo: out[combo][idx] += sum_t pows[t] * in[cols[t]][idx].
-// A slot can hold a couple of hundred columns (every register read at the current row only); the
-// loads of eight of them are issued together so that a lane keeps eight coefficient loads in
-// flight instead of one.
-__global__ void mix_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, size_t count,
-                           const uint32_t* __restrict__ slot_combo, const uint32_t* __restrict__ slot_off,
-                           const uint32_t* __restrict__ cols, const uint32_t* __restrict__ pows) {
-    constexpr unsigned U = 8;
+// one grid.y slot per destination combo: out[combo][idx] = (ACCUM ? out[combo][idx] : 0) + sum_t pows[t] * cols[t][idx].
+// A slot can hold a couple of hundred columns (every register read at the current row only).  A lane keeps the four
+// lazy accumulators (poly_lazy.hpp) of its (combo, idx) in registers over all of them; the multipliers are the same
+// for every lane and arrive through scalar loads; the loads of eight columns are issued together so that a lane keeps
+// eight coefficient loads in flight instead of one.
+template <bool ACCUM>
+__global__ void mix_kernel(uint32_t* __restrict__ out, size_t count, const uint32_t* __restrict__ slot_combo,
+                           const uint32_t* __restrict__ slot_off, const uint32_t* const* __restrict__ cols,
+                           const uint32_t* __restrict__ pows) {
+    constexpr unsigned U = 2 * pl::FOLD_TERMS;
     unsigned slot = blockIdx.y;
     size_t combo = slot_combo[slot];
     unsigned t0 = slot_off[slot], t1 = slot_off[slot + 1];
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, st = (size_t)gridDim.x * blockDim.x;
     for (; idx < count; idx += st) {
         uint32_t* o = out + (combo * count + idx) * 4;
-        Ext acc = load_ext(o);
+        pl::Acc acc = pl::zero();
         unsigned t = t0;
         for (; t + U <= t1; t += U) {
             uint32_t v[U];
 #pragma unroll
-            for (unsigned u = 0; u < U; u++) v[u] = in[(size_t)cols[t + u] * count + idx];
+            for (unsigned u = 0; u < U; u++) v[u] = load_global(cols[t + u] + idx);
 #pragma unroll
-            for (unsigned u = 0; u < U; u++) acc = bb::add(acc, bb::scale(load_ext(pows + (size_t)(t + u) * 4), v[u]));
+            for (unsigned u = 0; u < U; u++) {
+                pl::mac(acc, v[u], load_ext(pows + (size_t)(t + u) * 4));
+                if ((u + 1) % pl::FOLD_TERMS == 0) pl::fold(acc);
+            }
         }
-        for (; t < t1; t++) {
-            Ext pw = load_ext(pows + (size_t)t * 4);
-            acc = bb::add(acc, bb::scale(pw, in[(size_t)cols[t] * count + idx]));
+        // up to U - 1 columns left, the accumulators folded on entry
+        for (unsigned n = 0; t < t1; t++) {
+            pl::mac(acc, load_global(cols[t] + idx), load_ext(pows + (size_t)t * 4));
+            if (++n == (unsigned)pl::FOLD_TERMS) {
+                pl::fold(acc);
+                n = 0;
+            }
         }
-        store_ext(o, acc);
+        Ext r = pl::finish(acc);
+        if (ACCUM) r = bb::add(load_ext(o), r);
+        store_ext(o, r);
     }
 }
 
@@ -471,15 +527,49 @@ int bit_reverse_ext(rk_ctx* ctx, uint32_t* d_io_ext, size_t size, size_t count) 
                        log2u(size));
     return post_launch(ctx, "bit_reverse_ext_kernel");
 }
-int eval_dot(rk_ctx* ctx, uint32_t* d_out_ext, const uint32_t* d_coeffs, size_t size, const uint32_t* d_which,
-             const uint32_t* d_pw_ext, const uint32_t* d_pw_sel, size_t eval_count) {
+int eval_dot(rk_ctx* ctx, uint32_t* d_out_ext, size_t size, const EvalSrc* srcs, size_t n_srcs, const uint32_t* h_which,
+             const uint32_t* h_sel, const uint32_t* d_pw_ext) {
+    size_t eval_count = 0;
+    for (size_t g = 0; g < n_srcs; g++) eval_count += srcs[g].n;
     if (eval_count == 0) return RK_OK;
-    if (eval_count > 65535) return RK_ERR_INVALID;
+    if (eval_count > 65535 || size == 0) return RK_ERR_INVALID;
+    // per coefficient buffer, the evaluations that share a power table go into batches of 8, 4, 2 or 1; every
+    // evaluation keeps its position in the caller's order
+    std::vector<EvalBatch> batches;
+    std::vector<uint32_t> order;
+    size_t first = 0;
+    for (size_t g = 0; g < n_srcs; first += srcs[g].n, g++) {
+        const size_t n = srcs[g].n;
+        order.resize(n);
+        for (size_t i = 0; i < n; i++) order[i] = (uint32_t)(first + i);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h_sel[a] < h_sel[b]; });
+        for (size_t i = 0; i < n;) {
+            size_t run = 1;
+            while (i + run < n && h_sel[order[i + run]] == h_sel[order[i]]) run++;
+            for (size_t end = i + run; i < end;) {
+                size_t nb = DOT_BATCH;
+                while (nb > end - i) nb >>= 1;
+                EvalBatch bt{};
+                for (size_t e = 0; e < nb; e++) {
+                    bt.col[e] = srcs[g].d_coeffs + (size_t)h_which[order[i + e]] * size;
+                    bt.out[e] = order[i + e];
+                }
+                bt.sel = h_sel[order[i]];
+                bt.nb = (uint32_t)nb;
+                batches.push_back(bt);
+                i += nb;
+            }
+        }
+    }
+    void* d_batches = nullptr;
+    RK_TRY(scratch(ctx, batches.size() * sizeof(EvalBatch), &d_batches));
+    RK_TRY(upload(ctx, d_batches, batches.data(), batches.size() * sizeof(EvalBatch)));
     void* partial = nullptr;
     RK_TRY(dev_alloc(ctx, eval_count * DOT_BLOCKS * 16, &partial));
-    KTimer kt(ctx, RK_KCLASS_POLY, (double)eval_count * size * 20);
-    hipLaunchKernelGGL(eval_dot_kernel, dim3(DOT_BLOCKS, (unsigned)eval_count), dim3(TPB), 0, ctx->stream,
-                       (uint32_t*)partial, d_coeffs, size, d_which, d_pw_ext, d_pw_sel);
+    // every input read once: a column per evaluation, a power table per batch
+    KTimer kt(ctx, RK_KCLASS_POLY, (double)size * (eval_count * 4 + batches.size() * 16));
+    hipLaunchKernelGGL(eval_dot_kernel, dim3(DOT_BLOCKS, (unsigned)batches.size()), dim3(TPB), 0, ctx->stream,
+                       (uint32_t*)partial, (const EvalBatch*)d_batches, size, d_pw_ext);
     int st = post_launch(ctx, "eval_dot_kernel");
     if (st == RK_OK) {
         hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)((eval_count * 4 + TPB - 1) / TPB)), dim3(TPB), 0,
@@ -491,48 +581,78 @@ int eval_dot(rk_ctx* ctx, uint32_t* d_out_ext, const uint32_t* d_coeffs, size_t 
     return st;
 }
 
-int mix_poly_coeffs(rk_ctx* ctx, uint32_t* d_out_ext, const bb::Ext& mix_start, const bb::Ext& mix,
-                    const uint32_t* d_in, const uint32_t* h_combos, size_t input_size, size_t count) {
-    if (input_size == 0 || count == 0) return RK_OK;
+int mix_poly_coeffs(rk_ctx* ctx, uint32_t* d_out_ext, const bb::Ext& mix_start, const bb::Ext& mix, const MixSrc* srcs,
+                    size_t n_srcs, size_t count, size_t fresh_combos) {
+    size_t input_size = 0;
+    for (size_t g = 0; g < n_srcs; g++) input_size += srcs[g].n;
+    if (count == 0 || (input_size == 0 && fresh_combos == 0)) return RK_OK;
+    // column i of the concatenated inputs: its combo, its address, its power of mix
+    std::vector<uint32_t> combo_of(input_size);
+    std::vector<const uint32_t*> col_of(input_size);
+    {
+        size_t i = 0;
+        for (size_t g = 0; g < n_srcs; g++)
+            for (size_t c = 0; c < srcs[g].n; c++, i++) {
+                combo_of[i] = srcs[g].h_combos[c];
+                col_of[i] = srcs[g].d_in + c * count;
+                if (fresh_combos && combo_of[i] >= fresh_combos) return RK_ERR_INVALID;
+            }
+    }
     // bucket the input columns by destination combo; each bucket is one grid.y slot
     std::vector<uint32_t> order(input_size);
     for (size_t i = 0; i < input_size; i++) order[i] = (uint32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h_combos[a] < h_combos[b]; });
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return combo_of[a] < combo_of[b]; });
     std::vector<bb::Ext> pw(input_size);
     bb::Ext cur = mix_start;
     for (size_t i = 0; i < input_size; i++) {
         pw[i] = cur;
         cur = bb::mul(cur, mix, ctx->sys.wm);
     }
-    std::vector<uint32_t> slot_combo, slot_off, cols(input_size), pows(input_size * 4);
+    std::vector<uint32_t> slot_combo, slot_off, pows(input_size * 4);
+    std::vector<const uint32_t*> cols(input_size);
+    auto open_slot = [&](uint32_t combo, size_t t) {
+        slot_combo.push_back(combo);
+        slot_off.push_back((uint32_t)t);
+    };
     for (size_t t = 0; t < input_size; t++) {
         uint32_t i = order[t];
-        if (t == 0 || h_combos[i] != h_combos[order[t - 1]]) {
-            slot_combo.push_back(h_combos[i]);
-            slot_off.push_back((uint32_t)t);
+        // fresh: a slot for every combo below fresh_combos, the ones without a column included (they come out zero)
+        if (fresh_combos) {
+            while (slot_combo.size() <= combo_of[i]) open_slot((uint32_t)slot_combo.size(), t);
+        } else if (t == 0 || combo_of[i] != combo_of[order[t - 1]]) {
+            open_slot(combo_of[i], t);
         }
-        cols[t] = i;
+        cols[t] = col_of[i];
         std::memcpy(&pows[t * 4], pw[i].c, 16);
     }
+    while (slot_combo.size() < fresh_combos) open_slot((uint32_t)slot_combo.size(), input_size);
     slot_off.push_back((uint32_t)input_size);
     size_t n_slots = slot_combo.size();
-    // pack: [slot_combo | slot_off | cols | pows(16B aligned)]
-    size_t o_combo = 0, o_off = o_combo + n_slots, o_cols = o_off + n_slots + 1;
-    size_t o_pows = (o_cols + input_size + 3) & ~(size_t)3;
-    size_t words = o_pows + input_size * 4;
+    if (n_slots > 65535) return RK_ERR_INVALID;
+    // pack: [cols (8-byte items) | pows (16-byte items) | slot_combo | slot_off]
+    size_t o_cols = 0, o_pows = (o_cols + input_size * 2 + 3) & ~(size_t)3;
+    size_t o_combo = o_pows + input_size * 4, o_off = o_combo + n_slots;
+    size_t words = o_off + n_slots + 1;
     std::vector<uint32_t> pack(words, 0);
+    if (input_size) {
+        std::memcpy(&pack[o_cols], cols.data(), input_size * 8);
+        std::memcpy(&pack[o_pows], pows.data(), input_size * 16);
+    }
     std::memcpy(&pack[o_combo], slot_combo.data(), n_slots * 4);
     std::memcpy(&pack[o_off], slot_off.data(), (n_slots + 1) * 4);
-    std::memcpy(&pack[o_cols], cols.data(), input_size * 4);
-    std::memcpy(&pack[o_pows], pows.data(), input_size * 16);
     void* d = nullptr;
     RK_TRY(scratch(ctx, words * 4, &d));
     // the previous user of the scratch area may still be running: the copy is ordered behind it on the stream
     RK_TRY(upload(ctx, d, pack.data(), words * 4));
     const uint32_t* dp = (const uint32_t*)d;
-    KTimer kt(ctx, RK_KCLASS_POLY, (double)count * (input_size * 4 + n_slots * 32));
-    hipLaunchKernelGGL(mix_kernel, dim3(grid_for(count, 4096), (unsigned)n_slots), dim3(TPB), 0, ctx->stream, d_out_ext,
-                       d_in, count, dp + o_combo, dp + o_off, dp + o_cols, dp + o_pows);
+    KTimer kt(ctx, RK_KCLASS_POLY, (double)count * (input_size * 4 + n_slots * (fresh_combos ? 16 : 32)));
+    const dim3 grid(grid_for(count, 4096), (unsigned)n_slots), blk(TPB);
+    if (fresh_combos)
+        hipLaunchKernelGGL(mix_kernel<false>, grid, blk, 0, ctx->stream, d_out_ext, count, dp + o_combo, dp + o_off,
+                           (const uint32_t* const*)(dp + o_cols), dp + o_pows);
+    else
+        hipLaunchKernelGGL(mix_kernel<true>, grid, blk, 0, ctx->stream, d_out_ext, count, dp + o_combo, dp + o_off,
+                           (const uint32_t* const*)(dp + o_cols), dp + o_pows);
     return post_launch(ctx, "mix_kernel");
 }
 
@@ -694,24 +814,18 @@ int rk_batch_evaluate_any(rk_ctx* ctx, const uint32_t* d_coeffs, size_t poly_cou
     }
     void *d_pw = nullptr, *d_small = nullptr;
     RK_TRY(rk::dev_alloc(ctx, pts.size() * size * 16, &d_pw));
-    int st = rk::dev_alloc(ctx, eval_count * (4 + 4 + 16) + 32, &d_small);
+    int st = rk::dev_alloc(ctx, eval_count * 16, &d_small);
     if (st != RK_OK) {
         rk::dev_free(ctx, d_pw);
         return st;
     }
-    uint32_t* d_which = (uint32_t*)d_small;
-    uint32_t* d_sel = d_which + eval_count;
-    uint32_t* d_out = d_sel + eval_count;
-    // keep d_out 16-byte aligned
-    if (((uintptr_t)d_out & 15) != 0) d_out += (16 - ((uintptr_t)d_out & 15)) / 4;
+    uint32_t* d_out = (uint32_t*)d_small;
     do {
-        hipError_t e1 = hipMemcpyAsync(d_which, h_which, eval_count * 4, hipMemcpyHostToDevice, ctx->stream);
-        hipError_t e2 = hipMemcpyAsync(d_sel, sel.data(), eval_count * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e1 != hipSuccess || e2 != hipSuccess) { st = RK_ERR_HIP; ctx->last_error = "evaluate_any h2d"; break; }
         for (size_t j = 0; j < pts.size() && st == RK_OK; j++)
             st = rk::ext_powers(ctx, (uint32_t*)d_pw + j * size * 4, pts[j], size, false);
         if (st != RK_OK) break;
-        st = rk::eval_dot(ctx, d_out, d_coeffs, size, d_which, (const uint32_t*)d_pw, d_sel, eval_count);
+        const rk::EvalSrc src{d_coeffs, eval_count};
+        st = rk::eval_dot(ctx, d_out, size, &src, 1, h_which, sel.data(), (const uint32_t*)d_pw);
         if (st != RK_OK) break;
         hipError_t e3 = hipMemcpyAsync(h_out, d_out, eval_count * 16, hipMemcpyDeviceToHost, ctx->stream);
         if (e3 == hipSuccess) e3 = hipStreamSynchronize(ctx->stream);
@@ -731,7 +845,9 @@ int rk_mix_poly_coeffs(rk_ctx* ctx, uint32_t* d_out_ext, const uint32_t mix_star
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
     bb::Ext ms{{mix_start[0], mix_start[1], mix_start[2], mix_start[3]}};
     bb::Ext mx{{mix[0], mix[1], mix[2], mix[3]}};
-    return rk::mix_poly_coeffs(ctx, d_out_ext, ms, mx, d_in, h_combos, input_size, count);
+    if (input_size == 0 || count == 0) return RK_OK;
+    const rk::MixSrc src{d_in, h_combos, input_size};
+    return rk::mix_poly_coeffs(ctx, d_out_ext, ms, mx, &src, 1, count, 0);
     RK_GUARD_END
 }
 

@@ -590,18 +590,12 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         }
         first[4] = pos + CHECK_SIZE;
         const size_t n_ev = first[4];
-        RK_TRY(d_small.alloc(ctx, n_ev * (4 + 4 + 16) + 32));
-        uint32_t* d_which = d_small.u32();
-        uint32_t* d_sel = d_which + n_ev;
-        uint32_t* d_out = d_sel + n_ev;
-        if (((uintptr_t)d_out & 15) != 0) d_out += (16 - ((uintptr_t)d_out & 15)) / 4;
-        RK_TRY(rk::upload(ctx, d_which, which.data(), n_ev * 4));
-        RK_TRY(rk::upload(ctx, d_sel, sel.data(), n_ev * 4));
-        for (uint32_t gid = 0; gid < 4; gid++) {
-            const PolyGroup& pg = gid < 3 ? groups[gid] : check;
-            const size_t a = first[gid], n = first[gid + 1] - a;
-            if (n) RK_TRY(rk::eval_dot(ctx, d_out + a * 4, pg.coeffs.u32(), N, d_which + a, d_pw.u32(), d_sel + a, n));
-        }
+        RK_TRY(d_small.alloc(ctx, n_ev * 16));
+        uint32_t* d_out = d_small.u32();
+        rk::EvalSrc srcs[4];
+        for (uint32_t gid = 0; gid < 4; gid++)
+            srcs[gid] = rk::EvalSrc{(gid < 3 ? groups[gid] : check).coeffs.u32(), first[gid + 1] - first[gid]};
+        RK_TRY(rk::eval_dot(ctx, d_out, N, srcs, 4, which.data(), sel.data(), d_pw.u32()));
         RK_TRY(d2h_sync(ctx, eval_u.data(), d_out, n_ev * 16));
         // registers -> coefficients of their interpolating polynomials
         size_t p = 0;
@@ -622,20 +616,20 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
     const size_t combo_count = taps.n_combos;
     DevBuf combos;
     RK_TRY(combos.alloc(ctx, (combo_count + 1) * N * 16));
-    RK_HIP_TRY(ctx, hipMemsetAsync(combos.p, 0, (combo_count + 1) * N * 16, ctx->stream));
     {
-        Ext cur_mix = bb::ext_one();
-        uint32_t reg = 0;
-        std::vector<uint32_t> which;
-        for (uint32_t gid = 0; gid < 3; gid++) {
-            uint32_t gs = taps.group_size[gid];
-            which.assign(gs, 0);
-            for (uint32_t i = 0; i < gs; i++, reg++) which[i] = taps.reg_combo[reg];
-            RK_TRY(rk::mix_poly_coeffs(ctx, combos.u32(), cur_mix, mix, groups[gid].coeffs.u32(), which.data(), gs, N));
-            cur_mix = bb::mul(cur_mix, bb::pow(mix, gs, wm), wm);
+        // one pass over the four coefficient buffers writes every (combo, coefficient) once; the check columns mix
+        // into a combo of their own behind the tap set's
+        std::vector<uint32_t> which(taps.n_regs + CHECK_SIZE, (uint32_t)combo_count);
+        for (uint32_t r = 0; r < taps.n_regs; r++) which[r] = taps.reg_combo[r];
+        rk::MixSrc srcs[4];
+        size_t at = 0;
+        for (uint32_t gid = 0; gid < 4; gid++) {
+            const size_t n = gid < 3 ? taps.group_size[gid] : CHECK_SIZE;
+            srcs[gid] = rk::MixSrc{(gid < 3 ? groups[gid] : check).coeffs.u32(), which.data() + at, n};
+            at += n;
         }
-        which.assign(CHECK_SIZE, (uint32_t)combo_count);
-        RK_TRY(rk::mix_poly_coeffs(ctx, combos.u32(), cur_mix, mix, check.coeffs.u32(), which.data(), CHECK_SIZE, N));
+        if (at != which.size()) return RK_ERR_INVALID;
+        RK_TRY(rk::mix_poly_coeffs(ctx, combos.u32(), bb::ext_one(), mix, srcs, 4, N, combo_count + 1));
         // inputs were bit-reversed, so are the mixed polynomials: natural order for the division
         RK_TRY(rk::bit_reverse_ext(ctx, combos.u32(), N, combo_count + 1));
     }
