@@ -688,6 +688,7 @@ int rk_exec_free(rk_exec* ex);
  *   PERM_LOCAL a / PERM_NEXT a   base column a of the table's permutation trace (rk_air_create_lookup), current / next row
  *   CHALLENGE a          base component a of the permutation challenges [alpha | beta^0 | beta^1 | ...] (4 words each)
  *   CUMSUM a             base component a of the table's cumulative sum
+ *   PREP_LOCAL a / PREP_NEXT a   preprocessed column a (rk_air_create_prep), current / next row; symbolic degree 1
  * rk_air_create validates, derives the quotient degree from the symbolic degrees (get_log_quotient_degree: a cell and
  * is_first_row / is_last_row count 1, is_transition and constants 0) and translates the list into an rk_program whose
  * taps are the columns of the LDE, so the quotient is evaluated by the same GPU evaluator as risc0's eval_check;
@@ -695,7 +696,8 @@ int rk_exec_free(rk_exec* ex);
 typedef enum {
     RK_AIR_CONST = 0, RK_AIR_LOCAL = 1, RK_AIR_NEXT = 2, RK_AIR_PUBLIC = 3, RK_AIR_IS_FIRST_ROW = 4, RK_AIR_IS_LAST_ROW = 5,
     RK_AIR_IS_TRANSITION = 6, RK_AIR_ADD = 7, RK_AIR_SUB = 8, RK_AIR_MUL = 9, RK_AIR_NEG = 10, RK_AIR_ASSERT_ZERO = 11,
-    RK_AIR_PERM_LOCAL = 12, RK_AIR_PERM_NEXT = 13, RK_AIR_CHALLENGE = 14, RK_AIR_CUMSUM = 15
+    RK_AIR_PERM_LOCAL = 12, RK_AIR_PERM_NEXT = 13, RK_AIR_CHALLENGE = 14, RK_AIR_CUMSUM = 15,
+    RK_AIR_PREP_LOCAL = 16, RK_AIR_PREP_NEXT = 17
 } rk_air_op;
 typedef struct { uint32_t op, a, b; } rk_air_step;
 typedef struct rk_air rk_air;
@@ -729,6 +731,18 @@ int rk_air_create(const rk_air_step* steps, size_t n_steps, uint32_t width, uint
  * list back.  A proof without any interaction keeps the bytes it had before this entry point existed. */
 int rk_air_create_lookup(const rk_air_step* steps, size_t n_steps, uint32_t width, uint32_t n_public,
                          const uint32_t* interaction_words, uint32_t n_interactions, size_t n_words, uint32_t ext_w, rk_air** out);
+/* An AIR over `width` trace columns and `prep_width` PREPROCESSED columns: columns fixed before any witness exists (a
+ * range table's values, a program's instructions), committed once by rk_p3_setup and read by the steps through
+ * PREP_LOCAL / PREP_NEXT a, a < prep_width.  Interactions as in rk_air_create_lookup (n_interactions = 0: none), over the
+ * union of both: a column number c >= width in the flat words -- a value or a `mult` that is a column -- means
+ * preprocessed column c - width; the limits (64 values per tuple, 120 distinct columns per table) count the union, and
+ * the appended permutation constraints read such a column through PREP_LOCAL.  rk_air_create and rk_air_create_lookup
+ * are this call with prep_width = 0, where PREP_* steps are refused.  Tables of such an AIR are proven with
+ * rk_p3_prove_key and checked with rk_p3_verify_key only (see there). */
+int rk_air_create_prep(const rk_air_step* steps, size_t n_steps, uint32_t width, uint32_t prep_width, uint32_t n_public,
+                       const uint32_t* interaction_words, uint32_t n_interactions, size_t n_words, uint32_t ext_w, rk_air** out);
+/* the AIR's preprocessed columns (0: none, or air NULL) */
+uint32_t rk_air_prep_width(const rk_air* air);
 /* the AIR's complete step list (with the appended lookup constraints); RK_ERR_CAPACITY with *n_steps set when it does not fit */
 int rk_air_get_steps(const rk_air* air, rk_air_step* out, size_t capacity, size_t* n_steps);
 int rk_air_destroy(rk_air* air);
@@ -781,6 +795,55 @@ typedef struct {
  * yields a proof (as in Plonky3's release builds); rk_p3_verify rejects it with reason 3. */
 int rk_p3_prove(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
                 uint32_t* h_proof, size_t capacity_words, size_t* proof_words);
+/* PREPROCESSED COLUMNS: setup once, prove with a key -- the shape of SP1's `client.setup(ELF)` -> `prove(&pk, ..)` ->
+ * `verify(.., &vk)` (provers/sp1/driver/src/lib.rs:44-57,116-120).  A fourth committed batch beside trace, permutation
+ * and quotient: the preprocessed matrices of the tables whose AIR has prep_width > 0, committed ONCE, their root part of
+ * the statement (the verifying key = that root plus the heights of those tables), opened at zeta and zeta * g like the
+ * main trace and readable by the AIR and the interactions.  The protocol, as prover, verifier and the tests' reference
+ * state it (this project's choice, modelled on sp1-core's machine, RECALLED; the pinned Plonky3 revision has no
+ * preprocessed trace in uni-stark, so there is no upstream parity to pin):
+ *   transcript   observe(init_words), observe(preprocessed root) IF the key has one, then the trace root and everything
+ *                after it as in rk_p3_prove
+ *   proof words  header, trace root, permutation part, quotient root unchanged -- the preprocessed root is NOT in the
+ *                proof, the verifier's caller supplies it; per table the opened values are
+ *                  local 4w | next 4w | [prep local 4c | prep next 4c] | [perm local | perm next] | chunks
+ *                per query: the trace batch, [the preprocessed batch: every preprocessed table's LDE row in table order,
+ *                then the Merkle path of its own tree, whose height is that of its tallest member], [the permutation
+ *                batch], the quotient batch, the FRI rounds
+ *   order of the opened matrices (batches hashed, powers of the PCS's alpha in the reduced openings): trace,
+ *                preprocessed, permutation, quotient
+ * A proof of tables without any preprocessed column keeps every byte rk_p3_prove gives it.
+ *
+ * rk_p3_setup: prep_traces[t] = the row-major 2^log_height x prep_width Montgomery matrix of table t (host memory, or
+ * device memory where tables[t].on_device), NULL where the table's AIR has prep_width = 0; of `tables` the air,
+ * log_height and on_device are read.  The key holds in the memory of the context's GPU (its own allocations, alive until
+ * rk_p3_key_destroy, usable by any context of that GPU under the same parameter set): the column LDE of every
+ * preprocessed matrix (2^(log_height + blowup_log2) x prep_width words), the tree over them (one rk_mmcs_commit in table
+ * order), the root, the row-major matrix itself for the tables whose interactions read a preprocessed column, and every
+ * table's (prep_width, log_height): a table with preprocessed columns has its height fixed by the key.  A key over
+ * tables without any preprocessed column is legal and has no root (rk_p3_key_root: RK_ERR_INVALID). */
+typedef struct rk_p3_key rk_p3_key;
+int rk_p3_setup(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* const* prep_traces, rk_p3_key** key);
+int rk_p3_key_root(const rk_p3_key* key, uint32_t out[8]);
+size_t rk_p3_key_bytes(const rk_p3_key* key);   /* device memory the key holds */
+int rk_p3_key_destroy(rk_p3_key* key);
+/* rk_p3_prove with a key (NULL: none -- rk_p3_prove is exactly that, and refuses AIRs with prep_width > 0).  The key must
+ * come from a context of the same GPU under the same parameter set and from tables of the same count, prep_width and --
+ * where prep_width > 0 -- log_height: anything else is RK_ERR_INVALID before a kernel is launched.  The quotient reads
+ * the key's LDE in place (a fourth column group of the evaluator), the permutation trace its rows, the queries its tree:
+ * nothing of the preprocessed data is copied or recomputed per proof. */
+int rk_p3_prove_key(rk_ctx* ctx, const rk_p3_key* key, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                    uint32_t* h_proof, size_t capacity_words, size_t* proof_words);
+/* exact proof size of rk_p3_prove_key for the tables' shapes; = rk_p3_proof_bound_words without preprocessed columns */
+size_t rk_p3_proof_bound_words_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables);
+/* rk_p3_verify against a verifying key: prep_root = the 8 words of rk_p3_key_root, NULL when no table has preprocessed
+ * columns (then this is rk_p3_verify); every table with prep_width > 0 must come with its pinned log_height != 0.  A root
+ * without such a table, such a table without a root or without its height: RK_ERR_INVALID.  A proof carrying another
+ * height: reason 2; a preprocessed opening that does not lead to the caller's root: reason 5.
+ * rk_p3_verify, rk_p3_verify_hashes, the four rk_p3_fri_* captures, rk_p3_prove and rk_p3_prove_shards refuse tables with
+ * prep_width > 0 with RK_ERR_INVALID: their statements do not know the fourth batch yet. */
+int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                     const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words);
 /* p3-uni-stark `verify` on the host (no GPU): params NULL = the SP1 preset; trace / on_device of the tables are ignored;
  * log_height = 0 takes the table's height from the proof, any other value PINS it (the proof must carry that height: what
  * a statement with a fixed-size table -- all 2^16 values of a range check -- needs).  0 = accepted, RK_ERR_INVALID for malformed arguments, otherwise a reason: 1 malformed proof (short,

@@ -58,6 +58,8 @@ pub const RK_AIR_PERM_LOCAL: rk_air_op = 12;
 pub const RK_AIR_PERM_NEXT: rk_air_op = 13;
 pub const RK_AIR_CHALLENGE: rk_air_op = 14;
 pub const RK_AIR_CUMSUM: rk_air_op = 15;
+pub const RK_AIR_PREP_LOCAL: rk_air_op = 16;
+pub const RK_AIR_PREP_NEXT: rk_air_op = 17;
 
 pub type rk_kclass = c_int;
 pub const RK_KCLASS_HASH_ROWS: rk_kclass = 0;
@@ -103,6 +105,11 @@ pub struct rk_ctx {
 
 #[repr(C)]
 pub struct rk_exec {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct rk_p3_key {
     _private: [u8; 0],
 }
 
@@ -596,6 +603,8 @@ extern "C" {
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;
     pub fn rk_air_create_lookup(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, interaction_words: *const u32, n_interactions: u32, n_words: usize, ext_w: u32, out: *mut *mut rk_air) -> c_int;
+    pub fn rk_air_create_prep(steps: *const rk_air_step, n_steps: usize, width: u32, prep_width: u32, n_public: u32, interaction_words: *const u32, n_interactions: u32, n_words: usize, ext_w: u32, out: *mut *mut rk_air) -> c_int;
+    pub fn rk_air_prep_width(air: *const rk_air) -> u32;
     pub fn rk_air_get_steps(air: *const rk_air, out: *mut rk_air_step, capacity: usize, n_steps: *mut usize) -> c_int;
     pub fn rk_air_destroy(air: *mut rk_air) -> c_int;
     pub fn rk_air_get_info(air: *const rk_air, out: *mut rk_air_info) -> c_int;
@@ -605,6 +614,13 @@ extern "C" {
     pub fn rk_p2_chip_air_ex(params: *const rk_params, bus: u32, n_out: u32, out: *mut *mut rk_air) -> c_int;
     pub fn rk_p2_chip_trace(ctx: *mut rk_ctx, d_inputs: *const u32, d_mult: *const u32, n: usize, d_trace: *mut u32) -> c_int;
     pub fn rk_p3_prove(ctx: *mut rk_ctx, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, h_proof: *mut u32, capacity_words: usize, proof_words: *mut usize) -> c_int;
+    pub fn rk_p3_setup(ctx: *mut rk_ctx, tables: *const rk_p3_table, n_tables: u32, prep_traces: *const *const u32, key: *mut *mut rk_p3_key) -> c_int;
+    pub fn rk_p3_key_root(key: *const rk_p3_key, out: *mut u32) -> c_int;
+    pub fn rk_p3_key_bytes(key: *const rk_p3_key) -> usize;
+    pub fn rk_p3_key_destroy(key: *mut rk_p3_key) -> c_int;
+    pub fn rk_p3_prove_key(ctx: *mut rk_ctx, key: *const rk_p3_key, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, h_proof: *mut u32, capacity_words: usize, proof_words: *mut usize) -> c_int;
+    pub fn rk_p3_proof_bound_words_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
+    pub fn rk_p3_verify_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize) -> c_int;
     pub fn rk_p3_verify(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize) -> c_int;
     pub fn rk_p3_verify_hashes(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, states: *mut u32, capacity_permutations: usize, n_permutations: *mut usize) -> c_int;
     pub fn rk_p3_fri_openings(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;

@@ -298,6 +298,15 @@ SYMBOLS = {
     "rk_program_poly_ext": (C.c_int, [_vp, _u32, u32p, u32p, _sz, u32p, _u32, u32p, _u32, u32p]),
     "rk_air_create": (C.c_int, [_vp, _sz, _u32, _u32, C.POINTER(_vp)]),
     "rk_air_create_lookup": (C.c_int, [_vp, _sz, _u32, _u32, u32p, _u32, _sz, _u32, C.POINTER(_vp)]),
+    "rk_air_create_prep": (C.c_int, [_vp, _sz, _u32, _u32, _u32, u32p, _u32, _sz, _u32, C.POINTER(_vp)]),
+    "rk_air_prep_width": (_u32, [_vp]),
+    "rk_p3_setup": (C.c_int, [_vp, C.POINTER(RkP3Table), _u32, C.POINTER(_vp), C.POINTER(_vp)]),
+    "rk_p3_key_root": (C.c_int, [_vp, u32p]),
+    "rk_p3_key_bytes": (_sz, [_vp]),
+    "rk_p3_key_destroy": (C.c_int, [_vp]),
+    "rk_p3_prove_key": (C.c_int, [_vp, _vp, C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, C.POINTER(_sz)]),
+    "rk_p3_proof_bound_words_key": (_sz, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32]),
+    "rk_p3_verify_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz]),
     "rk_p2_chip_width": (_u32, [C.POINTER(RkParams)]),
     "rk_p2_chip_air": (C.c_int, [C.POINTER(RkParams), _u32, C.POINTER(_vp)]),
     "rk_p2_chip_air_ex": (C.c_int, [C.POINTER(RkParams), _u32, _u32, C.POINTER(_vp)]),

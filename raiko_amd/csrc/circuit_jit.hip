@@ -136,16 +136,20 @@ void cache_write(const std::string& path, const uint8_t key[32], const std::vect
     if (!ok || std::rename(tmp.c_str(), path.c_str()) != 0) (void)std::remove(tmp.c_str());
 }
 
-// what the generated kernel receives (same layout as `struct Args` in the source below)
+// what the generated kernel receives (same layout as `struct Args` in the source below).  NG = the column groups the
+// kernel carries bases for: 3 for every list whose taps stay in groups 0..2 (risc0's circuits, AIRs without preprocessed
+// columns: the argument block, and so the kernel's scalar registers, are what they were before group 3 existed), 4 for a
+// list that reads the preprocessed LDE of an rk_p3_key (two more 64-bit scalars and a stride)
+template <int NG>
 struct JitArgs {
-    const uint32_t* lde[3];
-    uint64_t len[3];     // words per column of each group
+    const uint32_t* lde[NG];
+    uint64_t len[NG];    // words per column of each group
     uint64_t tab;        // globals | accum mix | powers (4 words each)
     uint32_t* check;
     uint64_t d;
     uint32_t glob_base, mix_base, pw_base, wm;
     uint32_t blow, split;   // log2 (domain / trace rows); the result leaves in 2^split chunks (rk::EvalDomain)
-    uint32_t str[3], one;   // point i of the domain is element i << str[g] of a column of group g; one = 1 (see below)
+    uint32_t str[NG], one;  // point i of the domain is element i << str[g] of a column of group g; one = 1 (see below)
     uint32_t inv_base, pad; // the 1 / (x^n - 1) values sit in the table too: indexing an ARRAY inside the kernel arguments by
                             // the lane's point makes the compiler copy the whole argument block to scratch and read
                             // every argument back from there with vector loads
@@ -199,14 +203,14 @@ RK_FI Acc eqz(const Acc& x, const Ext& pw, u32 v) {
 using bb::Ext;
 using bb::Acc;
 struct Args {
-    const u32* lde[3];
-    u64 len[3];
+    const u32* lde[RK_NG];
+    u64 len[RK_NG];
     u64 tab;
     u32* check;
     u64 d;
     u32 glob_base, mix_base, pw_base, wm;
     u32 blow, split;
-    u32 str[3], one;
+    u32 str[RK_NG], one;
     u32 inv_base, pad;
 };
 RK_FI Ext load_pw(const_u32 tab, u32 base, u32 j) {
@@ -234,7 +238,7 @@ constexpr u128 FOLDED = (u128)0xffffffffu * bb::ONE + 0xffffffffu;              
 constexpr u128 REDC_OK = ((u128)bb::P << 32) - 1;                                    // bb::redc's precondition
 
 // the source of the kernel; *powers: the exponents its table holds
-std::string generate(const rk_program& pg, std::vector<uint32_t>* powers_out) {
+std::string generate(const rk_program& pg, std::vector<uint32_t>* powers_out, uint32_t* n_groups) {
     const auto& steps = pg.steps;
     std::vector<Fp> fp;
     std::vector<Mx> mx;
@@ -481,8 +485,12 @@ std::string generate(const rk_program& pg, std::vector<uint32_t>* powers_out) {
         blocks << "    {\n    u32 flag = a.one;\n    asm volatile(\"\" : \"+v\"(flag));\n    const u32 sf = __builtin_amdgcn_readfirstlane(flag);\n"
                << "    if (sf) {\n" << body.str() << "    }\n    }\n";
     }
+    // the column groups the kernel carries: three, or four when a live tap names the preprocessed group
+    uint32_t ng = 3;
+    for (const auto& o : offs) ng = std::max(ng, o.second + 1);
+    *n_groups = ng;
     std::ostringstream src;
-    src << PRELUDE;
+    src << "#define RK_NG " << ng << "\n" << PRELUDE;
     src << "extern \"C\" __global__ __attribute__((amdgpu_flat_work_group_size(1, 256))) void rk_jit_eval_check(Args a) {\n"
         << "    const u32 i = blockIdx.x * 256u + threadIdx.x, d = (u32)a.d;\n"
         << "    if (i >= d) return;\n"
@@ -493,7 +501,7 @@ std::string generate(const rk_program& pg, std::vector<uint32_t>* powers_out) {
         else src << "((i + d - (" << o.first << "u << a.blow)) & (d - 1u))";   // back = 2^32 - 1: one row ahead, modulo d
         src << ") << a.str[" << o.second << "]) << 2;\n";
     }
-    for (uint32_t g = 0; g < 3; g++)
+    for (uint32_t g = 0; g < ng; g++)
         src << "    const char* const gb" << g << " = (const char*)a.lde[" << g << "];\n    const u64 lb" << g << " = a.len[" << g << "] * 4;\n";
     for (uint32_t k = 0; k < next_fp; k++) src << "    u32 c" << k << " = 0;\n";
     for (uint32_t k = 0; k < next_mx; k++)
@@ -512,22 +520,12 @@ std::string generate(const rk_program& pg, std::vector<uint32_t>* powers_out) {
     return src.str();
 }
 
-}  // namespace
-
-namespace rk {
-
-// the generated kernel for the context's device, or nullptr when rk_program_compile has not run for it
-const JitEntry* program_jit(rk_program* pg, int device) {
-    std::lock_guard<std::mutex> lk(pg->mu);
-    auto it = pg->jit.find(device);
-    return it == pg->jit.end() ? nullptr : &it->second;
-}
-
-int program_jit_launch(rk_ctx* ctx, const JitEntry& je, const EvalDomain& v, const uint32_t* d_tab, uint32_t glob_base,
-                       uint32_t mix_base, uint32_t pw_base, uint32_t* d_check, uint32_t inv_base) {
+template <int NG>
+int jit_launch(rk_ctx* ctx, const rk::JitEntry& je, const rk::EvalDomain& v, const uint32_t* d_tab, uint32_t glob_base, uint32_t mix_base,
+               uint32_t pw_base, uint32_t* d_check, uint32_t inv_base) {
     const unsigned blow = v.ratio_log2;
-    JitArgs a{};
-    for (int g = 0; g < 3; g++) {
+    JitArgs<NG> a{};
+    for (int g = 0; g < NG; g++) {
         a.lde[g] = v.d_cols[g];
         a.len[g] = v.col_len[g];
         a.str[g] = v.stride_log2[g];
@@ -549,6 +547,23 @@ int program_jit_launch(rk_ctx* ctx, const JitEntry& je, const EvalDomain& v, con
     return RK_OK;
 }
 
+}  // namespace
+
+namespace rk {
+
+// the generated kernel for the context's device, or nullptr when rk_program_compile has not run for it
+const JitEntry* program_jit(rk_program* pg, int device) {
+    std::lock_guard<std::mutex> lk(pg->mu);
+    auto it = pg->jit.find(device);
+    return it == pg->jit.end() ? nullptr : &it->second;
+}
+
+int program_jit_launch(rk_ctx* ctx, const JitEntry& je, const EvalDomain& v, const uint32_t* d_tab, uint32_t glob_base,
+                       uint32_t mix_base, uint32_t pw_base, uint32_t* d_check, uint32_t inv_base) {
+    if (je.n_groups == 4) return jit_launch<4>(ctx, je, v, d_tab, glob_base, mix_base, pw_base, d_check, inv_base);
+    return jit_launch<3>(ctx, je, v, d_tab, glob_base, mix_base, pw_base, d_check, inv_base);
+}
+
 }  // namespace rk
 
 extern "C" {
@@ -562,7 +577,7 @@ int rk_program_compile(rk_program* pg, rk_ctx* ctx) {
         if (pg->jit.count(ctx->device)) return RK_OK;
     }
     rk::JitEntry je;
-    const std::string src = generate(*pg, &je.powers);
+    const std::string src = generate(*pg, &je.powers, &je.n_groups);
     je.n_powers = (uint32_t)je.powers.size();
     hipDeviceProp_t props;
     RK_HIP_TRY(ctx, hipGetDeviceProperties(&props, ctx->device));
@@ -639,7 +654,8 @@ int rk_program_source(const rk_program* pg, char* out, size_t capacity, size_t* 
     RK_GUARD_BEGIN
     if (!pg || !length) return RK_ERR_INVALID;
     std::vector<uint32_t> powers;
-    const std::string src = generate(*pg, &powers);
+    uint32_t n_groups = 0;
+    const std::string src = generate(*pg, &powers, &n_groups);
     *length = src.size();
     if (!out || capacity < src.size() + 1) return RK_ERR_CAPACITY;
     std::memcpy(out, src.c_str(), src.size() + 1);

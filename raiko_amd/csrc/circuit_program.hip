@@ -549,7 +549,7 @@ int program_eval_domain(const rk_program* cprog, const EvalDomain& v, const uint
     if (v.n_globals < pg->need_globals || v.n_mix < pg->need_mix) return RK_ERR_INVALID;
     if ((v.n_globals && !v.globals) || (v.n_mix && !v.mix)) return RK_ERR_INVALID;
     const size_t n = (size_t)1 << v.po2, d = n << blow;
-    for (int g = 0; g < 3; g++)
+    for (uint32_t g = 0; g < MAX_GROUPS; g++)
         if (pg->group_min[g] && (!v.d_cols[g] || v.group_size[g] < pg->group_min[g] || v.stride_log2[g] > 8 ||
                                  v.col_len[g] < (d << v.stride_log2[g])))
             return RK_ERR_INVALID;
@@ -591,12 +591,12 @@ int program_eval_domain(const rk_program* cprog, const EvalDomain& v, const uint
     for (size_t t = 0; t < ntap; t++) {  // a tap `back` rows behind is back << blow points behind
         const Tap& tp = pg->taps[t];
         uint64_t col = 0;
-        if (tp.group < 3 && v.d_cols[tp.group] && tp.offset < v.group_size[tp.group])
+        if (tp.group < MAX_GROUPS && v.d_cols[tp.group] && tp.offset < v.group_size[tp.group])
             col = (uint64_t)(uintptr_t)(v.d_cols[tp.group] + (size_t)tp.offset * v.col_len[tp.group]);
         pack[o_tap + 4 * t] = (uint32_t)col;
         pack[o_tap + 4 * t + 1] = (uint32_t)(col >> 32);
         pack[o_tap + 4 * t + 2] = (uint32_t)((((size_t)tp.back) << blow) & (d - 1));
-        pack[o_tap + 4 * t + 3] = tp.group < 3 ? v.stride_log2[tp.group] : 0u;
+        pack[o_tap + 4 * t + 3] = tp.group < MAX_GROUPS ? v.stride_log2[tp.group] : 0u;
     }
     void* d_pack = nullptr;
     RK_TRY(scratch(ctx, words * 4 + 16, &d_pack));

@@ -10,6 +10,11 @@
 
 namespace rk {
 constexpr uint32_t PROGRAM_NONE = 0xffffffffu;
+// column groups a tap may name.  risc0's circuits and the uni-stark AIRs without preprocessed columns use groups 0..2;
+// group 3 is the preprocessed LDE of an rk_p3_key, a buffer of its own.  The interpreter reads absolute column addresses
+// from its tap table, so its kernel is the same for any count; the generated kernel carries the bases of the groups its
+// list names and no more (circuit_jit.hip: three unless a tap names group 3).
+constexpr uint32_t MAX_GROUPS = 4;
 struct Tap {
     uint32_t group, offset, back;
 };
@@ -18,6 +23,7 @@ struct JitEntry {
     hipModule_t module = nullptr;
     hipFunction_t kernel = nullptr;
     uint32_t n_powers = 0;
+    uint32_t n_groups = 3;          // column bases in the kernel's argument block
     std::vector<uint32_t> powers;   // exponents of poly_mix the kernel's table holds, ascending
 };
 }  // namespace rk
@@ -32,10 +38,10 @@ namespace rk {
 struct EvalDomain {
     rk_ctx* ctx = nullptr;
     unsigned po2 = 0, ratio_log2 = 0, split_log2 = 0;
-    const uint32_t* d_cols[3] = {nullptr, nullptr, nullptr};
-    uint32_t group_size[3] = {0, 0, 0};
-    uint64_t col_len[3] = {0, 0, 0};
-    uint32_t stride_log2[3] = {0, 0, 0};
+    const uint32_t* d_cols[MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t group_size[MAX_GROUPS] = {0, 0, 0, 0};
+    uint64_t col_len[MAX_GROUPS] = {0, 0, 0, 0};
+    uint32_t stride_log2[MAX_GROUPS] = {0, 0, 0, 0};
     const uint32_t* globals = nullptr;
     uint32_t n_globals = 0;
     const uint32_t* mix = nullptr;
@@ -60,7 +66,7 @@ struct rk_program {
     // other way round -- acc = acc * mix + c_k, Plonky3's ConstraintFolder -- so constraint k carries mix^(K - 1 - k)
     bool horner = false;
     std::vector<rk::Tap> taps;
-    uint32_t group_min[3] = {0, 0, 0};  // columns a view must have per group
+    uint32_t group_min[rk::MAX_GROUPS] = {0, 0, 0, 0};  // columns a view must have per group
 
     std::vector<uint4> code;
     std::vector<uint32_t> consts;   // Montgomery

@@ -1,4 +1,4 @@
-// rk_p3_prove (include/raiko_hip.h; the AIR front end rk_air_* is in p3_air.hip, the host verifier rk_p3_verify in p3_verify.hip, the
+// rk_p3_prove, rk_p3_setup / rk_p3_prove_key (include/raiko_hip.h; the AIR front end rk_air_* is in p3_air.hip, the host verifier rk_p3_verify in p3_verify.hip, the
 // shards in flight rk_p3_prove_shards in p3_shards.hip, what prover and verifier share in p3_host.hpp): a univariate STARK over the two-adic FRI PCS for AIRs
 // handed over as data -- the proof system behind SP1's `client.setup(ELF)` / `client.prove(&pk, stdin)` (reference
 // provers/sp1/driver/src/lib.rs:44-57, shard knobs docs/README_Sp1.md:19-32) as far as it exists without SP1's chips:
@@ -27,6 +27,11 @@
 //   chunk LDE      iNTT, coefficient i of chunk j times w_(N qd)^(-j i) (chunk_shift_kernel), expanding NTT, to rows
 //   openings       rk_pcs_eval_at_many / rk_pcs_reduce_openings, FRI commit phase rk_fri_fold_evals + rk_mmcs_commit
 //   queries        every opened row and sibling digest of the proof in ONE gather launch and one download
+//   preprocessed   columns fixed before any witness (rk_air_create_prep) are committed ONCE by rk_p3_setup into an rk_p3_key
+//                  (p3_host.hpp): their LDE, their tree, their rows.  rk_p3_prove_key observes the key's root after the init
+//                  words and reads all three in place: the LDE as the evaluator's fourth column group and in the opening
+//                  round (between the traces and the permutation traces), the rows in perm_entries_kernel, the tree in
+//                  the queries' gather.  rk_p3_prove is rk_p3_prove_key without a key
 // The transcript (DuplexChallenger) runs on the host between those steps; the proof of work on the GPU.
 #include "p3_host.hpp"
 #include "p3_kernels.hpp"
@@ -182,8 +187,11 @@ struct TableState {
     DevBuf lde;                   // w columns of H natural-order evaluations (rk_matrix layout 2: committed row r at index bitrev(r))
     DevBuf chunks;                // 4 qd columns of H: the qd chunk LDEs side by side (as one matrix they hash, open and
                                   // reduce exactly like qd matrices of width 4 that follow each other in the batch)
-    std::vector<uint32_t> y;      // opened values: local 4w | next 4w | [perm local 4pw | perm next 4pw] | chunks 16 each
+    std::vector<uint32_t> y;      // opened values: local 4w | next 4w | [prep local 4cw | prep next 4cw] | [perm local 4pw | perm next 4pw] | chunks 16 each
     size_t pw = 0;                // base columns of the permutation trace (0: the table has no lookups)
+    size_t cw = 0;                // preprocessed columns (0: none); their LDE and rows are the key's, read in place
+    const uint32_t* prep_lde = nullptr;    // cw columns of H, laid out like lde
+    const uint32_t* prep_rows = nullptr;   // row-major n x cw, there when the interactions read it
     DevBuf staged;                // a host trace's copy in HBM, kept for the permutation trace
     const uint32_t* d_trace = nullptr;
     DevBuf perm;                  // pw columns of H, laid out like lde
@@ -212,6 +220,7 @@ struct ProofRun {
     rk_ctx* ctx;
     const rk_p3_table* tables;
     uint32_t n_tables;
+    const rk_p3_key* key = nullptr;      // the preprocessed batch (rk_p3_prove_key), committed at setup
     rk_params par;
     unsigned blow = 0;
     uint32_t lqd[MAX_TABLES];
@@ -265,6 +274,11 @@ int ProofRun::commit_traces() {
         s.w = tb.width;
         pf.push_back(tb.log_height);
         s.pw = tb.air->perm_width;
+        s.cw = tb.air->prep_width;
+        if (s.cw) {
+            s.prep_lde = key->tables[t].lde.u32();
+            s.prep_rows = key->tables[t].rows.u32();
+        }
         s.d_trace = tb.trace;
         if (!tb.on_device) {
             RK_TRY(s.staged.alloc(ctx, s.n * s.w * 4));
@@ -317,7 +331,8 @@ int ProofRun::permutation_traces() {
             RK_TRY(d_desc.alloc(ctx, desc.size() * 4));
             RK_TRY(rk::upload(ctx, d_desc.p, desc.data(), desc.size() * 4));
             RK_TRY(cols.alloc(ctx, s.n * s.pw * 4));
-            PermArgs a{cols.u32(), s.d_trace, d_desc.u32(), s.n, s.w, air.n_chal, air.n_lookups, ctx->sys.wm, (uint32_t)air.used.size(), desc_words};
+            PermArgs a{cols.u32(), s.d_trace, d_desc.u32(), s.n, s.w, air.n_chal, air.n_lookups, ctx->sys.wm, (uint32_t)air.used.size(), desc_words,
+                       air.perm_reads_prep ? s.prep_rows : nullptr, s.cw};
             const size_t lds = std::max<size_t>(air.used.size(), 1) * PERM_LD * 4;
             if (lds > 64 * 1024)
                 RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)perm_entries_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -397,6 +412,12 @@ int ProofRun::quotients(const Ext& alpha) {
         dom.group_size[2] = (uint32_t)s.w;
         dom.col_len[2] = s.H;
         dom.stride_log2[2] = blow - s.lqd;
+        if (s.cw) {   // the key's LDE where it lies: a column group of its own
+            dom.d_cols[3] = s.prep_lde;
+            dom.group_size[3] = (uint32_t)s.cw;
+            dom.col_len[3] = s.H;
+            dom.stride_log2[3] = blow - s.lqd;
+        }
         dom.globals = tb.public_values;
         dom.n_globals = tb.n_public;
         std::vector<uint32_t> globals;   // lookups: public values | challenges | cumulative sum
@@ -450,15 +471,17 @@ int ProofRun::open() {
     };
     std::vector<Opening> openings;
     size_t y_words = 0;
-    for (TableState& s : ts) s.y.resize(8 * s.w + 8 * s.pw + ((size_t)16 << s.lqd));
+    for (TableState& s : ts) s.y.resize(8 * s.w + 8 * s.cw + 8 * s.pw + ((size_t)16 << s.lqd));
     auto add_opening = [&](TableState& s, const uint32_t* mat, size_t w, size_t n_points, size_t y_at) {
         openings.push_back(Opening{&s, mat, w, n_points, y_at, y_words});
         y_words += 4 * w * n_points;
     };
     for (TableState& s : ts) add_opening(s, s.lde.u32(), s.w, 2, 0);                       // round 0: every trace at zeta and zeta * g
     for (TableState& s : ts)
-        if (s.pw) add_opening(s, s.perm.u32(), s.pw, 2, 8 * s.w);                          // round 1 (lookups): the permutation traces, likewise
-    for (TableState& s : ts) add_opening(s, s.chunks.u32(), (size_t)4 << s.lqd, 1, 8 * s.w + 8 * s.pw);   // last round: every quotient chunk at zeta
+        if (s.cw) add_opening(s, s.prep_lde, s.cw, 2, 8 * s.w);                            // the preprocessed batch (the key's), likewise
+    for (TableState& s : ts)
+        if (s.pw) add_opening(s, s.perm.u32(), s.pw, 2, 8 * s.w + 8 * s.cw);               // (lookups): the permutation traces, likewise
+    for (TableState& s : ts) add_opening(s, s.chunks.u32(), (size_t)4 << s.lqd, 1, 8 * s.w + 8 * s.cw + 8 * s.pw);   // last round: every quotient chunk at zeta
     DevBuf d_ys;
     RK_TRY(d_ys.alloc(ctx, y_words * 4));
     auto points_of = [&](const TableState& s, uint32_t pts[8]) {
@@ -555,6 +578,7 @@ int ProofRun::queries(uint32_t* h_proof, size_t capacity, size_t* proof_words) {
     for (uint32_t qi = 0; qi < par.queries; qi++) {
         const uint32_t index = ch.sample_bits(log_max);
         open_batch(tmats, tnodes.u32(), Ht, index >> (log_max - log2u(Ht)));
+        if (key && key->has_root()) open_batch(key->mats, key->nodes.u32(), key->H, index >> (log_max - log2u(key->H)));
         if (!pmats.empty()) open_batch(pmats, pnodes.u32(), Hp, index >> (log_max - log2u(Hp)));
         open_batch(qmats, qnodes.u32(), Hq, index >> (log_max - log2u(Hq)));
         for (unsigned rd = 0; rd < n_rounds; rd++) {
@@ -580,11 +604,31 @@ int ProofRun::queries(uint32_t* h_proof, size_t capacity, size_t* proof_words) {
     return RK_OK;
 }
 
-int p3_prove(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init, uint32_t* h_proof,
-             size_t capacity, size_t* proof_words) {
+// the parameters a key's LDEs and tree depend on (queries and pow_bits may differ between setup and proof)
+bool same_commitment_params(rk_ctx* ctx, const rk_params& a, const rk_p3_key& key) {
+    const rk_params& b = key.par;
+    return a.ext_w == b.ext_w && a.root_2_27 == b.root_2_27 && a.coset_shift == b.coset_shift && a.p2_width == b.p2_width && a.p2_m4 == b.p2_m4 &&
+           a.p2_pad_free == b.p2_pad_free && a.blowup_log2 == b.blowup_log2 && rk::p2_chip_tab(ctx->h_p2) == key.p2_tab;
+}
+// the key against the context and the tables: all of it before anything is launched
+int check_key(rk_ctx* ctx, const rk_params& par, const rk_p3_key& key, const rk_p3_table* tables, uint32_t n_tables) {
+    if (key.device != ctx->device || !same_commitment_params(ctx, par, key) || key.tables.size() != n_tables) return RK_ERR_INVALID;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const rk_p3_key::Table& kt = key.tables[t];
+        if (kt.prep_width != tables[t].air->prep_width) return RK_ERR_INVALID;
+        if (kt.prep_width && kt.log_height != tables[t].log_height) return RK_ERR_INVALID;
+        if (tables[t].air->perm_reads_prep && !kt.rows.p) return RK_ERR_INVALID;
+    }
+    return RK_OK;
+}
+
+int p3_prove(rk_ctx* ctx, const rk_p3_key* key, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init, size_t n_init,
+             uint32_t* h_proof, size_t capacity, size_t* proof_words) {
     ProofRun run(ctx, tables, n_tables);
+    run.key = key;
     RK_TRY(rk_get_params(ctx, &run.par));
-    RK_TRY(check_tables(run.par, tables, n_tables, true, run.lqd));
+    RK_TRY(check_tables(run.par, tables, n_tables, true, run.lqd, /*keyed=*/key != nullptr));
+    if (key) RK_TRY(check_key(ctx, run.par, *key, tables, n_tables));
     for (size_t i = 0; i < n_init; i++)
         if (init[i] >= bb::P) return RK_ERR_INVALID;
     const size_t bound = proof_bound(run.par, tables, n_tables, run.lqd);
@@ -598,6 +642,7 @@ int p3_prove(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const ui
     run.t_mark = t_start;
     run.pf.reserve(bound);
     run.ch.observe(init, n_init);
+    if (key && key->has_root()) run.ch.observe(key->root, 8);   // the verifying key binds the statement before any witness
     RK_TRY(run.commit_traces());
     RK_TRY(run.permutation_traces());     // nothing of it without interactions
     const Ext alpha = run.ch.sample_ext();
@@ -610,30 +655,125 @@ int p3_prove(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const ui
     return RK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables) {
+size_t bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, bool keyed) {
     const rk_params par = p3h::params_or_sp1(params);
     rk::Sys sys;
     auto k = std::make_unique<p2::Any>();
     if (rk::resolve_params(&par, &sys, k.get()) != RK_OK) return 0;
     uint32_t lqd[MAX_TABLES];
-    if (check_tables(par, tables, n_tables, false, lqd) != RK_OK) return 0;
+    if (check_tables(par, tables, n_tables, false, lqd, keyed) != RK_OK) return 0;
     for (uint32_t t = 0; t < n_tables; t++)
         if (tables[t].log_height < 1 || tables[t].log_height + par.blowup_log2 > ntt::LAMBDA) return 0;
     return proof_bound(par, tables, n_tables, lqd);
 }
 
+// rk_p3_setup: the preprocessed matrices' LDEs and their commitment, once.  The same two calls a proof spends on its
+// trace (pcs_coset_lde_cols, rk_mmcs_commit), off the per-proof path.
+int key_alloc(rk_ctx* ctx, rk_p3_key& key, rk_p3_key::Buf& b, size_t bytes) {
+    RK_HIP_TRY(ctx, hipMalloc(&b.p, bytes));
+    key.bytes += bytes;
+    return RK_OK;
+}
+int p3_setup(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* const* prep_traces, rk_p3_key** out) {
+    std::unique_ptr<rk_p3_key> key(new rk_p3_key);
+    RK_TRY(rk_get_params(ctx, &key->par));
+    key->par.p2_rc_ext = key->par.p2_rc_int = key->par.p2_diag = nullptr;   // the context's own storage
+    key->p2_tab = rk::p2_chip_tab(ctx->h_p2);
+    uint32_t lqd[MAX_TABLES];
+    RK_TRY(check_tables(key->par, tables, n_tables, false, lqd, /*keyed=*/true));
+    const unsigned blow = key->par.blowup_log2;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        if (!tables[t].air->prep_width) continue;
+        if (!prep_traces || !prep_traces[t] || tables[t].log_height < 1 || tables[t].log_height + blow > ntt::LAMBDA || tables[t].on_device > 1)
+            return RK_ERR_INVALID;
+    }
+    key->device = ctx->device;
+    key->tables = std::vector<rk_p3_key::Table>(n_tables);
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const rk_air& air = *tables[t].air;
+        if (!air.prep_width) continue;
+        rk_p3_key::Table& kt = key->tables[t];
+        kt.prep_width = air.prep_width;
+        kt.log_height = tables[t].log_height;
+        const size_t n = (size_t)1 << kt.log_height, H = n << blow, cw = kt.prep_width;
+        const uint32_t* d_rows = prep_traces[t];
+        DevBuf staged;
+        if (!tables[t].on_device || air.perm_reads_prep) {   // rows the key keeps, or a host matrix on its way through HBM
+            void* dst = nullptr;
+            if (air.perm_reads_prep) {
+                RK_TRY(key_alloc(ctx, *key, kt.rows, n * cw * 4));
+                dst = kt.rows.p;
+            } else {
+                RK_TRY(staged.alloc(ctx, n * cw * 4));
+                dst = staged.p;
+            }
+            RK_HIP_TRY(ctx, hipMemcpyAsync(dst, prep_traces[t], n * cw * 4, tables[t].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            d_rows = (const uint32_t*)dst;
+        }
+        RK_TRY(key_alloc(ctx, *key, kt.lde, H * cw * 4));
+        RK_TRY(rk::pcs_coset_lde_cols(ctx, kt.lde.u32(), d_rows, n, cw));
+        RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the caller's matrix and the staging block are free again
+        key->mats.push_back(rk_matrix{kt.lde.u32(), (uint32_t)H, (uint32_t)cw, 2});
+        key->H = std::max(key->H, H);
+    }
+    if (key->has_root()) {
+        RK_TRY(key_alloc(ctx, *key, key->nodes, 2 * key->H * p2::OUT * 4));
+        RK_TRY(rk_mmcs_commit(ctx, key->mats.data(), (uint32_t)key->mats.size(), key->nodes.u32(), key->root));
+        RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *out = key.release();
+    return RK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rk_p3_proof_bound_words(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables) {
+    return bound_words(params, tables, n_tables, /*keyed=*/false);
+}
+size_t rk_p3_proof_bound_words_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables) {
+    return bound_words(params, tables, n_tables, /*keyed=*/true);
+}
+
 int rk_p3_prove(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init, uint32_t* h_proof,
                 size_t capacity_words, size_t* proof_words) {
+    return rk_p3_prove_key(ctx, nullptr, tables, n_tables, init_words, n_init, h_proof, capacity_words, proof_words);
+}
+int rk_p3_prove_key(rk_ctx* ctx, const rk_p3_key* key, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
+                    uint32_t* h_proof, size_t capacity_words, size_t* proof_words) {
     RK_GUARD_BEGIN
     if (!ctx || !h_proof || !proof_words || (n_init && !init_words)) return RK_ERR_INVALID;
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int rc = p3_prove(ctx, tables, n_tables, init_words, n_init, h_proof, capacity_words, proof_words);
+    const int rc = p3_prove(ctx, key, tables, n_tables, init_words, n_init, h_proof, capacity_words, proof_words);
     if (rc != RK_OK) (void)hipStreamSynchronize(ctx->stream);   // scoped buffers are back in the pool: nothing may still read them
     return rc;
+    RK_GUARD_END
+}
+
+int rk_p3_setup(rk_ctx* ctx, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* const* prep_traces, rk_p3_key** out) {
+    RK_GUARD_BEGIN
+    if (!out) return RK_ERR_INVALID;
+    *out = nullptr;
+    if (!ctx) return RK_ERR_INVALID;
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = p3_setup(ctx, tables, n_tables, prep_traces, out);
+    if (rc != RK_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+    RK_GUARD_END
+}
+int rk_p3_key_root(const rk_p3_key* key, uint32_t out[8]) {
+    if (!key || !out || !key->has_root()) return RK_ERR_INVALID;
+    std::memcpy(out, key->root, 32);
+    return RK_OK;
+}
+size_t rk_p3_key_bytes(const rk_p3_key* key) { return key ? key->bytes : 0; }
+int rk_p3_key_destroy(rk_p3_key* key) {
+    RK_GUARD_BEGIN
+    if (!key) return RK_OK;
+    (void)hipSetDevice(key->device);
+    delete key;
+    return RK_OK;
     RK_GUARD_END
 }
 

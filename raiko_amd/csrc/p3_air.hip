@@ -21,7 +21,7 @@ using rk::p2_chip_layout;
 using rk::p2_chip_tab;
 
 // ---------------------------------------------------------------- AIR: checks, symbolic degree, host evaluation
-int air_scan(const rk_air_step* steps, size_t n, uint32_t width, uint32_t n_public, uint32_t perm_width, uint32_t n_chal, rk_air_info* info) {
+int air_scan(const rk_air_step* steps, size_t n, uint32_t width, uint32_t prep_width, uint32_t n_public, uint32_t perm_width, uint32_t n_chal, rk_air_info* info) {
     std::vector<uint32_t> deg;
     deg.reserve(n);
     uint32_t max_deg = 0, n_con = 0;
@@ -31,6 +31,7 @@ int air_scan(const rk_air_step* steps, size_t n, uint32_t width, uint32_t n_publ
         switch (st.op) {
             case RK_AIR_CONST: if (st.a >= bb::P) return RK_ERR_INVALID; deg.push_back(0); break;
             case RK_AIR_LOCAL: case RK_AIR_NEXT: if (st.a >= width) return RK_ERR_INVALID; deg.push_back(1); break;
+            case RK_AIR_PREP_LOCAL: case RK_AIR_PREP_NEXT: if (st.a >= prep_width) return RK_ERR_INVALID; deg.push_back(1); break;
             case RK_AIR_PUBLIC: if (st.a >= n_public) return RK_ERR_INVALID; deg.push_back(0); break;
             case RK_AIR_IS_FIRST_ROW: case RK_AIR_IS_LAST_ROW: deg.push_back(1); break;
             case RK_AIR_IS_TRANSITION: deg.push_back(0); break;
@@ -69,6 +70,7 @@ struct PermStepGen {
     std::vector<rk_air_step>& steps;
     uint32_t nv, w;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> memo;
+    uint32_t main_w = 0xffffffffu;   // an interaction's column c >= main_w is preprocessed column c - main_w
     using E = std::array<uint32_t, 4>;
     uint32_t push(uint32_t op, uint32_t a = 0, uint32_t b = 0) {
         const auto key = std::make_tuple(op, a, b);
@@ -83,7 +85,7 @@ struct PermStepGen {
     uint32_t sub(uint32_t a, uint32_t b) { return push(RK_AIR_SUB, a, b); }
     uint32_t mul(uint32_t a, uint32_t b) { return push(RK_AIR_MUL, a, b); }
     uint32_t cst(uint32_t canon) { return push(RK_AIR_CONST, canon); }
-    uint32_t col(uint32_t c) { return push(RK_AIR_LOCAL, c); }
+    uint32_t col(uint32_t c) { return c < main_w ? push(RK_AIR_LOCAL, c) : push(RK_AIR_PREP_LOCAL, c - main_w); }
     E leaf(uint32_t op, uint32_t at) { return E{push(op, 4 * at), push(op, 4 * at + 1), push(op, 4 * at + 2), push(op, 4 * at + 3)}; }
     E add(const E& x, const E& y) { return E{push(RK_AIR_ADD, x[0], y[0]), push(RK_AIR_ADD, x[1], y[1]), push(RK_AIR_ADD, x[2], y[2]), push(RK_AIR_ADD, x[3], y[3])}; }
     E sub(const E& x, const E& y) { return E{push(RK_AIR_SUB, x[0], y[0]), push(RK_AIR_SUB, x[1], y[1]), push(RK_AIR_SUB, x[2], y[2]), push(RK_AIR_SUB, x[3], y[3])}; }
@@ -119,11 +121,11 @@ struct PermStepGen {
         const E alpha = leaf(RK_AIR_CHALLENGE, 0);
         auto rlc = [&](const Ix& it) {
             E acc = add(alpha, scale(leaf(RK_AIR_CHALLENGE, 1), push(RK_AIR_CONST, it.bus)));
-            for (uint32_t j = 0; j < it.nv; j++) acc = add(acc, scale(leaf(RK_AIR_CHALLENGE, 2 + j), push(RK_AIR_LOCAL, it.cols[j])));
+            for (uint32_t j = 0; j < it.nv; j++) acc = add(acc, scale(leaf(RK_AIR_CHALLENGE, 2 + j), col(it.cols[j])));
             return acc;
         };
         auto signed_mult = [&](const Ix& it) {
-            const uint32_t m = it.is_const ? push(RK_AIR_CONST, it.mult) : push(RK_AIR_LOCAL, it.mult);
+            const uint32_t m = it.is_const ? push(RK_AIR_CONST, it.mult) : col(it.mult);
             return it.kind == 0 ? m : push(RK_AIR_NEG, m);
         };
         std::vector<E> el, en;
@@ -246,20 +248,25 @@ int rk::p2_chip_trace(rk_ctx* ctx, const uint32_t* d_tab, const P2ChipLayout& L,
 extern "C" {
 
 int rk_air_create(const rk_air_step* steps, size_t n_steps, uint32_t width, uint32_t n_public, rk_air** out) {
-    return rk_air_create_lookup(steps, n_steps, width, n_public, nullptr, 0, 0, 0, out);
+    return rk_air_create_prep(steps, n_steps, width, 0, n_public, nullptr, 0, 0, 0, out);
 }
-int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_t width, uint32_t n_public, const uint32_t* iw,
+int rk_air_create_lookup(const rk_air_step* steps, size_t n_steps, uint32_t width, uint32_t n_public, const uint32_t* iw,
                          uint32_t n_interactions, size_t n_words, uint32_t ext_w, rk_air** out) {
+    return rk_air_create_prep(steps, n_steps, width, 0, n_public, iw, n_interactions, n_words, ext_w, out);
+}
+int rk_air_create_prep(const rk_air_step* steps_in, size_t n_steps_in, uint32_t width, uint32_t prep_width, uint32_t n_public, const uint32_t* iw,
+                       uint32_t n_interactions, size_t n_words, uint32_t ext_w, rk_air** out) {
     RK_GUARD_BEGIN
     if (!out) return RK_ERR_INVALID;
     *out = nullptr;
     const rk_air_step* steps = steps_in;
     size_t n_steps = n_steps_in;
     // a table that only takes part in lookups has no constraints of its own: an empty list is fine when the library writes the rest
-    if (((!steps || n_steps == 0) && !(ext_w && n_steps == 0)) || n_steps > ((size_t)1 << 27) || width == 0 || width > (1u << 16) || n_public > (1u << 20)) return RK_ERR_INVALID;
+    if (((!steps || n_steps == 0) && !(ext_w && n_steps == 0)) || n_steps > ((size_t)1 << 27) || width == 0 || width > (1u << 16) || prep_width > (1u << 16) || n_public > (1u << 20)) return RK_ERR_INVALID;
     if (n_interactions > 4096 || (n_interactions && !iw) || (!n_interactions && n_words)) return RK_ERR_INVALID;
     if (ext_w >= bb::P || (ext_w && !n_interactions)) return RK_ERR_INVALID;
     std::unique_ptr<rk_air> air(new rk_air);
+    const uint32_t n_cols = width + prep_width;   // an interaction's column c >= width is preprocessed column c - width
     {   // the interactions: kind, bus, mult_is_const, mult, n_values, columns...
         size_t at = 0;
         uint32_t max_values = 0;
@@ -267,7 +274,7 @@ int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_
             if (at + 5 > n_words) return RK_ERR_INVALID;
             const uint32_t kind = iw[at], bus = iw[at + 1], is_const = iw[at + 2], mult = iw[at + 3], nv = iw[at + 4];
             if (kind > 1 || bus >= bb::P || is_const > 1 || nv > 64 || at + 5 + nv > n_words) return RK_ERR_INVALID;
-            if (is_const ? mult >= bb::P : mult >= width) return RK_ERR_INVALID;
+            if (is_const ? mult >= bb::P : mult >= n_cols) return RK_ERR_INVALID;
             auto slot = [&](uint32_t col) {
                 auto it = std::find(air->used.begin(), air->used.end(), col);
                 if (it == air->used.end()) {
@@ -278,7 +285,7 @@ int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_
             };
             air->lookups.insert(air->lookups.end(), {kind, bb::encode(bus), is_const, is_const ? bb::encode(mult) : slot(mult), nv});
             for (uint32_t j = 0; j < nv; j++) {
-                if (iw[at + 5 + j] >= width) return RK_ERR_INVALID;
+                if (iw[at + 5 + j] >= n_cols) return RK_ERR_INVALID;
                 air->lookups.push_back(slot(iw[at + 5 + j]));
             }
             max_values = std::max(max_values, nv);
@@ -287,6 +294,7 @@ int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_
         if (at != n_words) return RK_ERR_INVALID;
         if (air->used.size() > 120) return RK_ERR_INVALID;   // the staged tile (120 x 257 words of LDS)
         air->n_lookups = n_interactions;
+        for (uint32_t c : air->used) air->perm_reads_prep = air->perm_reads_prep || c >= width;
         if (n_interactions) {
             air->perm_width = 4 * ((n_interactions + 1) / 2 + 1);
             air->n_chal = 4 * (max_values + 2);
@@ -295,28 +303,32 @@ int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_
     const uint32_t pw = air->perm_width, n_chal = air->n_chal;
     std::vector<rk_air_step> extended;
     if (ext_w) {   // the caller's list holds the main constraints only: append eval_permutation_constraints for x^4 - ext_w
-        if (n_steps) RK_TRY(air_scan(steps, n_steps, width, n_public, 0, 0, &air->info));   // ... and may not name the permutation trace itself
+        if (n_steps) RK_TRY(air_scan(steps, n_steps, width, prep_width, n_public, 0, 0, &air->info));   // ... and may not name the permutation trace itself
         if (n_steps) extended.assign(steps, steps + n_steps);
         uint32_t nv = 0;
         for (const rk_air_step& st : extended) nv += st.op != RK_AIR_ASSERT_ZERO;
-        PermStepGen gen{extended, nv, ext_w, {}};
+        PermStepGen gen{extended, nv, ext_w, {}, width};
         gen.run(iw, n_interactions);
         steps = extended.data();
         n_steps = extended.size();
     }
-    RK_TRY(air_scan(steps, n_steps, width, n_public, pw, n_chal, &air->info));
+    RK_TRY(air_scan(steps, n_steps, width, prep_width, n_public, pw, n_chal, &air->info));
     air->steps.assign(steps, steps + n_steps);
     air->width = width;
     air->n_public = n_public;
+    air->prep_width = prep_width;
     // the list as an rk_program: taps 0..2 = the selector columns (group 0), 3 + c = LOCAL c, 3 + width + c = NEXT c
-    // (group 2), then PERM_LOCAL / PERM_NEXT c (group 1); PUBLIC / CHALLENGE / CUMSUM = GET_GLOBAL of the proof's globals
-    // (public values | challenges | cumulative sum); NEG a = 0 - a; the asserts one AND_EQZ chain
+    // (group 2), then PERM_LOCAL / PERM_NEXT c (group 1), then PREP_LOCAL / PREP_NEXT c (group 3: the key's LDE, a buffer
+    // of its own; an AIR without preprocessed columns has no such tap); PUBLIC / CHALLENGE / CUMSUM = GET_GLOBAL of the
+    // proof's globals (public values | challenges | cumulative sum); NEG a = 0 - a; the asserts one AND_EQZ chain
     std::vector<rk::Tap> taps;
     for (uint32_t c = 0; c < 3; c++) taps.push_back(rk::Tap{0, c, 0});
     for (uint32_t c = 0; c < width; c++) taps.push_back(rk::Tap{2, c, 0});
     for (uint32_t c = 0; c < width; c++) taps.push_back(rk::Tap{2, c, NEXT_BACK});
     for (uint32_t c = 0; c < pw; c++) taps.push_back(rk::Tap{1, c, 0});
     for (uint32_t c = 0; c < pw; c++) taps.push_back(rk::Tap{1, c, NEXT_BACK});
+    for (uint32_t c = 0; c < prep_width; c++) taps.push_back(rk::Tap{3, c, 0});
+    for (uint32_t c = 0; c < prep_width; c++) taps.push_back(rk::Tap{3, c, NEXT_BACK});
     std::vector<rk_poly_step> ps;
     ps.reserve(n_steps + 2);
     std::vector<uint32_t> fp_of;   // AIR value -> position in the program's field-value list
@@ -333,6 +345,8 @@ int rk_air_create_lookup(const rk_air_step* steps_in, size_t n_steps_in, uint32_
             case RK_AIR_PUBLIC: ps.push_back(rk_poly_step{RK_STEP_GET_GLOBAL, 0, st.a, 0}); fp_of.push_back(n_fp++); break;
             case RK_AIR_PERM_LOCAL: ps.push_back(rk_poly_step{RK_STEP_GET, 3 + 2 * width + st.a, 0, 0}); fp_of.push_back(n_fp++); break;
             case RK_AIR_PERM_NEXT: ps.push_back(rk_poly_step{RK_STEP_GET, 3 + 2 * width + pw + st.a, 0, 0}); fp_of.push_back(n_fp++); break;
+            case RK_AIR_PREP_LOCAL: ps.push_back(rk_poly_step{RK_STEP_GET, 3 + 2 * width + 2 * pw + st.a, 0, 0}); fp_of.push_back(n_fp++); break;
+            case RK_AIR_PREP_NEXT: ps.push_back(rk_poly_step{RK_STEP_GET, 3 + 2 * width + 2 * pw + prep_width + st.a, 0, 0}); fp_of.push_back(n_fp++); break;
             case RK_AIR_CHALLENGE: ps.push_back(rk_poly_step{RK_STEP_GET_GLOBAL, 0, n_public + st.a, 0}); fp_of.push_back(n_fp++); break;
             case RK_AIR_CUMSUM: ps.push_back(rk_poly_step{RK_STEP_GET_GLOBAL, 0, n_public + n_chal + st.a, 0}); fp_of.push_back(n_fp++); break;
             case RK_AIR_IS_FIRST_ROW: case RK_AIR_IS_LAST_ROW: case RK_AIR_IS_TRANSITION:
@@ -423,6 +437,7 @@ int rk_air_destroy(rk_air* air) {
     return RK_OK;
     RK_GUARD_END
 }
+uint32_t rk_air_prep_width(const rk_air* air) { return air ? air->prep_width : 0; }
 int rk_air_get_info(const rk_air* air, rk_air_info* out) {
     if (!air || !out) return RK_ERR_INVALID;
     *out = air->info;

@@ -11,9 +11,11 @@
 struct rk_air {
     std::vector<rk_air_step> steps;
     std::vector<uint32_t> lookups;   // flat interactions (rk_air_create_lookup): constants as Montgomery words, columns as slots of `used`
-    std::vector<uint32_t> used;      // the distinct main-trace columns the interactions read
+    std::vector<uint32_t> used;      // the distinct columns the interactions read: c < width main trace, else preprocessed column c - width
     uint32_t n_lookups = 0, perm_width = 0, n_chal = 0;   // base columns of the permutation trace, words of the challenge vector
     uint32_t width = 0, n_public = 0;
+    uint32_t prep_width = 0;         // preprocessed columns (rk_air_create_prep): committed once in an rk_p3_key, not part of the trace
+    bool perm_reads_prep = false;    // an interaction names a preprocessed column: the permutation trace needs the key's rows
     rk_air_info info{};
     uint32_t sel_mask = 0;   // bit c: selector column c (is_first_row, is_last_row, is_transition) is named by the list
     rk_program* prog = nullptr;

@@ -8,7 +8,8 @@ namespace p3k {
 // ---- lookups: the permutation trace (sp1-core generate_permutation_trace, RECALLED).  desc = the challenge vector
 // [alpha | beta^0 | beta^1 ..] (4 words each, n_chal words), the flat interactions (kind, bus, mult_is_const, mult, n_values,
 // slots...; constants as Montgomery words; columns renumbered to slots of the `used` list), then the n_used distinct
-// main-trace columns the interactions read.  A workgroup takes PERM_ROWS rows of the row-major trace: first every wave
+// columns the interactions read (c < w: column c of the main trace; otherwise column c - w of the row-major preprocessed
+// matrix `prep`, pw words a row).  A workgroup takes PERM_ROWS rows of the row-major trace: first every wave
 // stages the used columns of its rows in LDS -- one row per load instruction, the lanes along the used columns, so a row's
 // cache lines are fetched once instead of once per interaction --, then one lane per row walks the interactions out of LDS
 // (slot-major: conflict-free).  out = 4 (nb + 1) columns of n words: the nb batch entries, then the row totals (the
@@ -20,6 +21,8 @@ struct PermArgs {
     const uint32_t* desc;
     size_t n, w;
     uint32_t n_chal, n_lookups, wm, n_used, desc_words;
+    const uint32_t* prep = nullptr;   // preprocessed rows (an rk_p3_key's), null when no interaction reads one
+    size_t pw = 0;
 };
 // phase 1: lane `tid` of workgroup `blk` stages its share of the tile (n_used x PERM_LD words).  A wave takes 64 rows, eight
 // at a time: the loads of eight rows are issued before the first LDS store waits for any of them (one row per iteration
@@ -36,9 +39,12 @@ RK_HD void perm_stage(const PermArgs& a, size_t blk, unsigned tid, uint32_t* til
 #pragma unroll
         for (int j = 0; j < GROUP; j++) {
             const size_t r = r0 + wave * 64 + i + j;
-            const uint32_t* row = a.trace + (r < a.n ? r : a.n - 1) * a.w;    // past the end: a valid row, never stored
+            const size_t rr = r < a.n ? r : a.n - 1;                          // past the end: a valid row, never stored
+            const uint32_t* row = a.trace + rr * a.w;
+            const uint32_t* prow = a.prep + rr * a.pw;                        // only read for columns >= w, which need a.prep
 #pragma unroll
-            for (int q = 0; q < PER_LANE; q++) v[j][q] = lane + 64 * q < a.n_used ? row[col[q]] : 0;
+            for (int q = 0; q < PER_LANE; q++)
+                v[j][q] = lane + 64 * q < a.n_used ? (col[q] < a.w ? row[col[q]] : prow[col[q] - a.w]) : 0;
         }
 #pragma unroll
         for (int j = 0; j < GROUP; j++) {

@@ -53,6 +53,12 @@ int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t 
     if (!opts || (n && !shards) || opts->batch < 1 || opts->batch > 16) return RK_ERR_INVALID;
     if (opts->n_devices < 0 || opts->n_devices > 64 || (opts->n_devices > 0 && !opts->devices)) return RK_ERR_INVALID;
     if (n == 0) return RK_OK;
+    for (size_t i = 0; i < n; i++)   // a shard carries no key: tables with preprocessed columns are rk_p3_prove_key's
+        for (uint32_t t = 0; shards[i].tables && t < shards[i].n_tables; t++)
+            if (rk_air_prep_width(shards[i].tables[t].air)) {
+                if (failed_index) *failed_index = i;
+                return RK_ERR_INVALID;
+            }
     std::vector<int> devices;
     if (opts->n_devices > 0) devices.assign(opts->devices, opts->devices + opts->n_devices);
     else devices.push_back(opts->device);

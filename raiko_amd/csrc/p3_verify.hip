@@ -10,7 +10,8 @@
 //                      cumulative sums, alpha, zeta, the opened values
 //   check_constraints  the quotient recombined from its chunks against the AIR folded at zeta, per table
 //   open_fri           commit-phase roots and betas, final polynomial, proof of work, total length, query indices
-//   check_query        one query: the three input openings, the reduced openings, the fold rounds
+//   check_query        one query: the input openings (three batches, four with preprocessed columns), the reduced
+//                      openings, the fold rounds
 // Verdicts: 0 accept; 1 malformed / short / trailing / non-canonical word, 2 shape mismatch, 3 constraint identity
 // (OodEvaluationMismatch), 4 proof of work, 5 input opening, 6 commit-phase opening, 7 final polynomial, 8 the lookups'
 // cumulative sums do not cancel.  The total length is checked before any query: a proof with trailing words AND a
@@ -61,6 +62,7 @@ void put(std::vector<uint32_t>& v, const uint32_t* w, size_t n) { v.insert(v.end
 struct PermView {   // the verifier's view of a table's lookup argument (all null without one)
     const Ext *local = nullptr, *next = nullptr;
     const uint32_t *chal = nullptr, *cumsum = nullptr;
+    const Ext *prep_local = nullptr, *prep_next = nullptr;   // and of its preprocessed columns (null without any)
 };
 Ext air_fold(const rk_air& air, const Ext* local, const Ext* next, const uint32_t* pub, const Ext& is_first, const Ext& is_last,
              const Ext& is_trans, const Ext& alpha, uint32_t wm, const PermView& pv) {
@@ -80,6 +82,8 @@ Ext air_fold(const rk_air& air, const Ext* local, const Ext* next, const uint32_
             case RK_AIR_PERM_NEXT: v.push_back(pv.next[st.a]); break;
             case RK_AIR_CHALLENGE: v.push_back(bb::ext_from(pv.chal[st.a])); break;
             case RK_AIR_CUMSUM: v.push_back(bb::ext_from(pv.cumsum[st.a])); break;
+            case RK_AIR_PREP_LOCAL: v.push_back(pv.prep_local[st.a]); break;
+            case RK_AIR_PREP_NEXT: v.push_back(pv.prep_next[st.a]); break;
             case RK_AIR_ADD: v.push_back(bb::add(v[st.a], v[st.b])); break;
             case RK_AIR_SUB: v.push_back(bb::sub(v[st.a], v[st.b])); break;
             case RK_AIR_MUL: v.push_back(bb::mul(v[st.a], v[st.b], wm)); break;
@@ -126,8 +130,13 @@ struct Statement {   // the arguments of rk_p3_verify
     size_t n_init;
     const uint32_t* proof;
     size_t words;
+    bool keyed = false;                    // rk_p3_verify_key: the caller knows the preprocessed batch
+    const uint32_t* prep_root = nullptr;   // the verifying key's root, null when no table has preprocessed columns
 };
-enum { TRACE = 0, PERM = 1, QUOTIENT = 2 };   // the three input batches
+// the input batches.  The numbers are what the captures index by; the ORDER of a proof and of the reduced openings is
+// trace, preprocessed, permutation, quotient (BATCH_ORDER)
+enum { TRACE = 0, PERM = 1, QUOTIENT = 2, PREP = 3, N_BATCHES = 4 };
+constexpr int BATCH_ORDER[N_BATCHES] = {TRACE, PREP, PERM, QUOTIENT};
 struct OpenedMatrix {
     uint32_t batch;
     unsigned log_n, lh;        // log2 of the trace's rows and of the LDE's
@@ -146,19 +155,19 @@ struct Opened {
     Reader r{nullptr, 0};
     Layout lay;
     // pointers into the proof, and the challenges in between
-    const uint32_t* root[3] = {nullptr, nullptr, nullptr};
+    const uint32_t* root[N_BATCHES] = {nullptr, nullptr, nullptr, nullptr};   // PREP: the caller's, not the proof's
     const uint32_t* cumsum[MAX_TABLES] = {nullptr};
     std::vector<uint32_t> pchal;   // lookups: [alpha | beta^0 | .. | beta^K], every table reads a prefix
     struct TableY {
-        const uint32_t *local, *next, *plocal, *pnext, *chunks;
+        const uint32_t *local, *next, *klocal, *knext, *plocal, *pnext, *chunks;   // k..: the preprocessed columns
     } y[MAX_TABLES];
     Ext alpha, zeta, alpha2, final_poly;
     const uint32_t *commits = nullptr, *fp = nullptr;
     std::vector<Ext> betas;
-    // every opened matrix in the verifier's order -- traces, permutation traces, quotient chunks, by table in each: the
+    // every opened matrix in the verifier's order -- traces, preprocessed, permutation traces, quotient chunks, by table in each: the
     // order the batches are hashed in, the reduced openings take their powers of alpha in and rk_p3_fri_inputs lays out
     std::vector<OpenedMatrix> mats;
-    std::vector<uint32_t> heights[3], widths[3];   // the same per batch, as rk_mmcs_verify reads them
+    std::vector<uint32_t> heights[N_BATCHES], widths[N_BATCHES];   // the same per batch, as rk_mmcs_verify reads them
     std::vector<uint32_t> indices;
 
     uint32_t gen(unsigned bits) const { return bb::pow(sys.root27m, (uint64_t)1 << (27 - bits)); }
@@ -176,8 +185,20 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
     RK_TRY(rk::resolve_params(&o.par, &o.sys, o.k.get()));
     const rk_p3_table* tables = o.tables = st.tables;
     const uint32_t n_tables = o.n_tables = st.n_tables;
-    RK_TRY(p3h::check_tables(o.par, tables, n_tables, false, o.lqd));
+    RK_TRY(p3h::check_tables(o.par, tables, n_tables, false, o.lqd, st.keyed));
     if (!st.proof || (st.n_init && !st.init)) return RK_ERR_INVALID;
+    {   // the verifying key: the root and the pinned height of every table with preprocessed columns, both or neither
+        bool any = false;
+        for (uint32_t t = 0; t < n_tables; t++) {
+            if (!tables[t].air->prep_width) continue;
+            any = true;
+            if (!tables[t].log_height) return RK_ERR_INVALID;
+        }
+        if (any != (st.prep_root != nullptr)) return RK_ERR_INVALID;
+        for (int i = 0; any && i < 8; i++)
+            if (st.prep_root[i] >= bb::P) return RK_ERR_INVALID;
+        o.root[PREP] = st.prep_root;
+    }
     for (size_t i = 0; i < st.n_init; i++)
         if (st.init[i] >= bb::P) return RK_ERR_INVALID;
     for (size_t i = 0; i < st.words; i++)
@@ -195,6 +216,7 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
     Challenger& ch = o.ch;
     ch.log = log;
     ch.observe(st.init, st.n_init);
+    if (o.root[PREP]) ch.observe(o.root[PREP], 8);
     if (!(o.root[TRACE] = r.take(8))) return 1;
     ch.observe(o.root[TRACE], 8);
     for (uint32_t t = 0; t < n_tables; t++) ch.observe(tables[t].public_values, tables[t].n_public);
@@ -226,18 +248,22 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
     ch.observe(o.root[QUOTIENT], 8);
     o.zeta = ch.sample_ext();
     for (uint32_t t = 0; t < n_tables; t++) {
-        const size_t w = tables[t].width, pw = tables[t].air->perm_width;
+        const size_t w = tables[t].width, pw = tables[t].air->perm_width, cw = tables[t].air->prep_width;
         Opened::TableY& y = o.y[t];
         y.local = r.take(4 * w);
         y.next = r.take(4 * w);
+        y.klocal = cw ? r.take(4 * cw) : nullptr;
+        y.knext = cw ? r.take(4 * cw) : nullptr;
         y.plocal = pw ? r.take(4 * pw) : nullptr;
         y.pnext = pw ? r.take(4 * pw) : nullptr;
         y.chunks = r.take((size_t)16 << o.lqd[t]);
         if (r.bad) return 1;
     }
     // every table is in the trace and the quotient batch: both trees have the global maximum height; the permutation
-    // batch only holds the tables with lookups
+    // batch only holds the tables with lookups, the preprocessed batch those with preprocessed columns
     for (uint32_t t = 0; t < n_tables; t++) o.add_matrix(TRACE, t, tables[t].width, 2, o.y[t].local, o.y[t].next);
+    for (uint32_t t = 0; t < n_tables; t++)
+        if (tables[t].air->prep_width) o.add_matrix(PREP, t, tables[t].air->prep_width, 2, o.y[t].klocal, o.y[t].knext);
     for (uint32_t t = 0; t < n_tables; t++)
         if (tables[t].air->perm_width) o.add_matrix(PERM, t, tables[t].air->perm_width, 2, o.y[t].plocal, o.y[t].pnext);
     for (uint32_t t = 0; t < n_tables; t++)
@@ -270,7 +296,7 @@ int check_constraints(const Opened& o) {
         }
         const Selectors s = selectors_at(o.zeta, o.log_n[t], o.sys.root27m, wm);
         const Opened::TableY& y = o.y[t];
-        const PermView pv{(const Ext*)y.plocal, (const Ext*)y.pnext, o.pchal.data(), o.cumsum[t]};
+        const PermView pv{(const Ext*)y.plocal, (const Ext*)y.pnext, o.pchal.data(), o.cumsum[t], (const Ext*)y.klocal, (const Ext*)y.knext};
         const Ext folded = air_fold(*o.tables[t].air, (const Ext*)y.local, (const Ext*)y.next, o.tables[t].public_values, s.is_first, s.is_last,
                                     s.is_trans, o.alpha, wm, pv);
         if (!bb::eq(bb::mul(folded, s.inv_zeroifier, wm), quotient)) return 3;
@@ -310,7 +336,7 @@ int open_fri(Opened& o) {
 // round the sibling, its path and the reduced opening that joined (zero where no matrix has that height)
 struct QueryView {
     uint32_t index;
-    const uint32_t *rows[3], *paths[3];
+    const uint32_t *rows[N_BATCHES], *paths[N_BATCHES];
     const uint32_t *sib[ntt::LAMBDA], *path[ntt::LAMBDA];
     Ext joined[ntt::LAMBDA];
 };
@@ -319,16 +345,16 @@ int check_query(const Opened& o, uint32_t index, Reader r, QueryView& q) {
     const Layout& lay = o.lay;
     const unsigned log_max = lay.log_max;
     const uint32_t wm = o.sys.wm;
-    const size_t row_words[3] = {lay.trow, lay.prow, lay.qrow};
-    const unsigned tree[3] = {log_max, lay.log_pmax, log_max};
+    const size_t row_words[N_BATCHES] = {lay.trow, lay.prow, lay.qrow, lay.krow};
+    const unsigned tree[N_BATCHES] = {log_max, lay.log_pmax, log_max, lay.log_kmax};
     q.index = index;
-    for (int b = 0; b < 3; b++) {
-        const bool there = b != PERM || lay.prow;
+    for (int b : BATCH_ORDER) {
+        const bool there = (b != PERM || lay.prow) && (b != PREP || lay.krow);
         q.rows[b] = there ? r.take(row_words[b]) : nullptr;
         q.paths[b] = there ? r.take(8 * (size_t)tree[b]) : nullptr;
     }
     if (r.bad) return 1;
-    for (int b = 0; b < 3; b++)
+    for (int b : BATCH_ORDER)   // the preprocessed batch against the caller's root
         if (q.rows[b] && rk_mmcs_verify(&o.par, o.heights[b].data(), o.widths[b].data(), (uint32_t)o.heights[b].size(), index >> (log_max - tree[b]),
                                         q.rows[b], q.paths[b], o.root[b]) != 0)
             return 5;
@@ -534,6 +560,16 @@ int rk_p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_
                  const uint32_t* proof, size_t proof_words) {
     RK_GUARD_BEGIN
     return p3_verify({params, tables, n_tables, init_words, n_init, proof, proof_words});
+    RK_GUARD_END
+}
+
+int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root, const uint32_t* init_words,
+                     size_t n_init, const uint32_t* proof, size_t proof_words) {
+    RK_GUARD_BEGIN
+    Statement st{params, tables, n_tables, init_words, n_init, proof, proof_words};
+    st.keyed = true;
+    st.prep_root = prep_root;
+    return p3_verify(st);
     RK_GUARD_END
 }
 

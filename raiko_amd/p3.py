@@ -17,6 +17,10 @@ Tables of one proof may look values up in each other (sp1-core's LogUp permutati
 -- leaves them to rk_air_create_lookup.  `poseidon2_chip_air` / `poseidon2_chip_trace` are the Poseidon2 permutation as a
 table (rows written on the GPU), `merkle_path_air` a table that verifies Merkle paths by looking its compressions up in it,
 `verify_hashes` the list of permutations one verification performs: pieces of a recursion / compress layer.
+Columns fixed before any witness exists are PREPROCESSED: `AirBuilder(.., prep_width=c)` reads them with `prep_local` /
+`prep_next`, interactions name them as column `width + c` (`b.prep(c)`), `setup(hal, tables)` commits them once into a
+`Key`, `prove(.., key=key)` proves under it and `verify(.., prep_root=key.root)` checks against it (`p3_range_air_prep`:
+a range table whose values are preprocessed).
 `prove` / `prove_shards` / `verify` are the calls; `lookup_demo_airs`, `fibonacci_air`, `cubic_air`, `wide_air`, `local_air`
 the example AIRs the tests and benches use.
 """
@@ -32,6 +36,8 @@ CONST, LOCAL, NEXT, PUBLIC, IS_FIRST_ROW, IS_LAST_ROW, IS_TRANSITION, ADD, SUB, 
 # the permutation (LogUp) argument's leaves: a base column of the permutation trace (this / next row), a base
 # component of the challenge vector [alpha | beta^0 | beta^1 | ...], a base component of the table's cumulative sum
 PERM_LOCAL, PERM_NEXT, CHALLENGE, CUMSUM = 12, 13, 14, 15
+# a preprocessed column (rk_air_create_prep), this / next row
+PREP_LOCAL, PREP_NEXT = 16, 17
 SEND, RECEIVE = 0, 1
 EXT_W = 11          # x^4 - 11: the quartic extension of the SP1 / Plonky3 preset (risc0's is x^4 + 11: ext_w = P - 11)
 
@@ -102,7 +108,8 @@ class ExtExpr:
 
 class Interaction:
     """one side of a lookup: the tuple (bus, local[value_cols]...) sent (kind SEND) or received (RECEIVE) `mult` times
-    per row -- mult a column of the main trace, or a constant when mult_is_const (sp1-core lookup/interaction.rs, RECALLED)"""
+    per row -- mult a column, or a constant when mult_is_const (sp1-core lookup/interaction.rs, RECALLED).  A column
+    number c >= the AIR's width names preprocessed column c - width, in value_cols and in mult alike."""
 
     def __init__(self, kind, bus, value_cols, mult, mult_is_const=False):
         self.kind, self.bus, self.value_cols = int(kind), int(bus), [int(c) for c in value_cols]
@@ -126,11 +133,12 @@ class _When:
 class Air:
     """steps: (n, 3) uint32 array of (op, a, b)"""
 
-    def __init__(self, steps, width, n_public, interactions=(), append_lookup_constraints_w=0):
+    def __init__(self, steps, width, n_public, interactions=(), append_lookup_constraints_w=0, prep_width=0):
         """append_lookup_constraints_w = W: `steps` holds the table's own constraints only and rk_air_create_lookup appends
-        the permutation constraints for the extension x^4 - W (self.steps is then read back from the library)"""
+        the permutation constraints for the extension x^4 - W (self.steps is then read back from the library).
+        prep_width: preprocessed columns (rk_air_create_prep)"""
         self.steps = np.ascontiguousarray(steps, dtype=np.uint32).reshape(-1, 3)
-        self.width, self.n_public = int(width), int(n_public)
+        self.width, self.n_public, self.prep_width = int(width), int(n_public), int(prep_width)
         self.interactions = list(interactions)
         self._handle = None
         if append_lookup_constraints_w:
@@ -138,9 +146,9 @@ class Air:
             lib = _lib.load()
             h = C.c_void_p()
             iw = self.interaction_words()
-            _lib.check(None, lib.rk_air_create_lookup(self.steps.ctypes.data if self.steps.size else None, self.steps.shape[0], self.width,
-                                                      self.n_public, iw.ctypes.data_as(_lib.u32p), len(self.interactions), iw.size,
-                                                      int(append_lookup_constraints_w) % P, C.byref(h)))
+            _lib.check(None, lib.rk_air_create_prep(self.steps.ctypes.data if self.steps.size else None, self.steps.shape[0], self.width,
+                                                    self.prep_width, self.n_public, iw.ctypes.data_as(_lib.u32p), len(self.interactions), iw.size,
+                                                    int(append_lookup_constraints_w) % P, C.byref(h)))
             self._handle = h
             n = C.c_size_t(0)
             lib.rk_air_get_steps(h, None, 0, C.byref(n))
@@ -166,7 +174,12 @@ class Air:
         if self._handle is None:
             lib = _lib.load()
             h = C.c_void_p()
-            if self.interactions:
+            if self.prep_width:
+                iw = self.interaction_words()
+                _lib.check(None, lib.rk_air_create_prep(self.steps.ctypes.data, self.steps.shape[0], self.width, self.prep_width, self.n_public,
+                                                        iw.ctypes.data_as(_lib.u32p) if iw.size else None, len(self.interactions), iw.size, 0,
+                                                        C.byref(h)))
+            elif self.interactions:
                 iw = self.interaction_words()
                 _lib.check(None, lib.rk_air_create_lookup(self.steps.ctypes.data, self.steps.shape[0], self.width, self.n_public,
                                                           iw.ctypes.data_as(_lib.u32p), len(self.interactions), iw.size, 0, C.byref(h)))
@@ -203,7 +216,7 @@ class Air:
         for op, a, b in self.steps.tolist():
             if op in (CONST, PUBLIC, IS_TRANSITION, CHALLENGE, CUMSUM):
                 deg.append(0)
-            elif op in (LOCAL, NEXT, IS_FIRST_ROW, IS_LAST_ROW, PERM_LOCAL, PERM_NEXT):
+            elif op in (LOCAL, NEXT, IS_FIRST_ROW, IS_LAST_ROW, PERM_LOCAL, PERM_NEXT, PREP_LOCAL, PREP_NEXT):
                 deg.append(1)
             elif op in (ADD, SUB):
                 deg.append(max(deg[a], deg[b]))
@@ -216,12 +229,15 @@ class Air:
         d = max(mx, 2) - 1
         return (d - 1).bit_length()
 
-    def check_trace(self, trace, public_values=()):
+    def check_trace(self, trace, public_values=(), prep=None):
         """every constraint on every row of a canonical-integer trace (rows wrap around); -> list of (row, constraint).
+        prep: the canonical preprocessed matrix of an AIR with prep_width > 0.
         Main-trace constraints only: the asserts over the permutation trace of an AIR with lookups are skipped (they
         are checked by proving)."""
         t = np.asarray(trace, dtype=object)
         n = t.shape[0]
+        pt = None if prep is None else np.asarray(prep, dtype=object)
+        assert (pt is not None and pt.shape == (n, self.prep_width)) or not self.prep_width
         bad = []
         for r in range(n):
             vals, k = [], 0
@@ -234,6 +250,10 @@ class Air:
                     vals.append(int(t[(r + 1) % n][a]))
                 elif op == PUBLIC:
                     vals.append(int(public_values[a]))
+                elif op == PREP_LOCAL:
+                    vals.append(int(pt[r][a]))
+                elif op == PREP_NEXT:
+                    vals.append(int(pt[(r + 1) % n][a]))
                 elif op == IS_FIRST_ROW:
                     vals.append(1 if r == 0 else 0)
                 elif op == IS_LAST_ROW:
@@ -255,10 +275,11 @@ class Air:
 
 
 class AirBuilder:
-    def __init__(self, width, n_public=0, ext_w=EXT_W):
+    def __init__(self, width, n_public=0, ext_w=EXT_W, prep_width=0):
         """ext_w: the W of the parameter set's extension x^4 - W the proofs will be made under (it is written into the
-        lookup constraints; an AIR without interactions does not depend on it)"""
-        self.width, self.n_public, self.ext_w = width, n_public, ext_w % P
+        lookup constraints; an AIR without interactions does not depend on it).  prep_width: preprocessed columns, read
+        with prep_local / prep_next; send / receive name preprocessed column c as column number width + c = prep(c)"""
+        self.width, self.n_public, self.ext_w, self.prep_width = width, n_public, ext_w % P, prep_width
         self.steps, self.nv = [], 0
         self._memo = {}
         self.interactions = []
@@ -288,6 +309,23 @@ class AirBuilder:
     def public(self, i):
         assert 0 <= i < self.n_public
         return self._push(PUBLIC, i)
+
+    def prep_local(self, c):
+        assert 0 <= c < self.prep_width
+        return self._push(PREP_LOCAL, c)
+
+    def prep_next(self, c):
+        assert 0 <= c < self.prep_width
+        return self._push(PREP_NEXT, c)
+
+    def prep(self, c):
+        """the column number send / receive take for preprocessed column c (in value_cols, or as a mult that is a column)"""
+        assert 0 <= c < self.prep_width
+        return self.width + c
+
+    def _cell(self, c):
+        """an interaction's column: main trace below width, preprocessed from there"""
+        return self.local(c) if c < self.width else self.prep_local(c - self.width)
 
     def is_first_row(self):
         return self._push(IS_FIRST_ROW)
@@ -339,11 +377,11 @@ class AirBuilder:
         def rlc(it):
             acc = alpha + self._ext_leaf(CHALLENGE, 1).scale(self.const(it.bus))
             for j, col in enumerate(it.value_cols):
-                acc = acc + self._ext_leaf(CHALLENGE, 2 + j).scale(self.local(col))
+                acc = acc + self._ext_leaf(CHALLENGE, 2 + j).scale(self._cell(col))
             return acc
 
         def signed_mult(it):
-            m = self.const(it.mult) if it.mult_is_const else self.local(it.mult)
+            m = self.const(it.mult) if it.mult_is_const else self._cell(it.mult)
             return m if it.kind == SEND else -m
 
         entries_l = [self._ext_leaf(PERM_LOCAL, b) for b in range(nb)]
@@ -376,11 +414,11 @@ class AirBuilder:
         if self.interactions and library_constraints:
             assert not getattr(self, "_perm_done", False)
             return Air(np.array(self.steps, dtype=np.uint32).reshape(-1, 3), self.width, self.n_public, self.interactions,
-                       append_lookup_constraints_w=self.ext_w)
+                       append_lookup_constraints_w=self.ext_w, prep_width=self.prep_width)
         if self.interactions and not getattr(self, "_perm_done", False):
             self._perm_constraints()
             self._perm_done = True
-        return Air(np.array(self.steps, dtype=np.uint32), self.width, self.n_public, self.interactions)
+        return Air(np.array(self.steps, dtype=np.uint32), self.width, self.n_public, self.interactions, prep_width=self.prep_width)
 
 
 _R_MOD_P = (1 << 32) % P
@@ -398,10 +436,12 @@ def from_mont(x):
 
 
 class Table:
-    """one table of a proof: a row-major trace (Montgomery words, as every buffer of the ABI), its AIR, its public values"""
+    """one table of a proof: a row-major trace (Montgomery words, as every buffer of the ABI), its AIR, its public values,
+    and -- an AIR with preprocessed columns -- the preprocessed matrix (rows x prep_width), which setup() commits"""
 
-    def __init__(self, air, trace_mont, public_mont=()):
+    def __init__(self, air, trace_mont, public_mont=(), prep=None):
         self.air = air
+        self.prep = None if prep is None else np.ascontiguousarray(prep, dtype=np.uint32).reshape(-1, air.prep_width)
         self.trace = None if trace_mont is None else np.ascontiguousarray(trace_mont, dtype=np.uint32)
         self.public_values = np.ascontiguousarray(public_mont, dtype=np.uint32).reshape(-1)
         if self.trace is not None:
@@ -409,10 +449,15 @@ class Table:
             assert w == air.width and n >= 2 and n & (n - 1) == 0
             self.log_height = n.bit_length() - 1
         assert self.public_values.size == air.n_public
+        if self.prep is not None:
+            assert air.prep_width and self.prep.shape[0] & (self.prep.shape[0] - 1) == 0
+            if self.trace is None:
+                self.log_height = self.prep.shape[0].bit_length() - 1
+            assert self.prep.shape[0] == 1 << self.log_height
 
     @classmethod
-    def from_canonical(cls, air, trace, public_values=()):
-        return cls(air, to_mont(trace), to_mont(np.array(list(public_values), dtype=np.uint64)))
+    def from_canonical(cls, air, trace, public_values=(), prep=None):
+        return cls(air, to_mont(trace), to_mont(np.array(list(public_values), dtype=np.uint64)), None if prep is None else to_mont(prep))
 
 
 def _c_tables(tables, device_traces=None):
@@ -436,21 +481,63 @@ def _c_tables(tables, device_traces=None):
     return arr, keep
 
 
-def prove(hal, tables, init=(), device_traces=None):
+class Key:
+    """rk_p3_setup's result: the preprocessed columns of `tables` committed once on hal's GPU.  .root: the 8 Montgomery
+    words a verifier needs (None when no table has preprocessed columns); .bytes: the device memory held; close() frees
+    it (and so does dropping the object)."""
+
+    def __init__(self, handle):
+        self._handle = handle
+        lib = _lib.load()
+        root = np.zeros(8, dtype=np.uint32)
+        self.root = root if lib.rk_p3_key_root(handle, root.ctypes.data_as(_lib.u32p)) == 0 else None
+        self.bytes = int(lib.rk_p3_key_bytes(handle))
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None and _lib is not None:
+            try:
+                _lib.load().rk_p3_key_destroy(self._handle)
+            except Exception:
+                pass
+        self._handle = None
+
+    __del__ = close
+
+
+def setup(hal, tables):
+    """rk_p3_setup on hal's context under its current parameter set: commits the .prep matrices of the tables whose AIR
+    has preprocessed columns -> Key (the traces are not read)"""
+    lib = _lib.load()
+    arr, keep = _c_tables(tables)
+    preps = (C.c_void_p * len(tables))()
+    for i, t in enumerate(tables):
+        if t.air.prep_width:
+            assert t.prep is not None, "table %d: the AIR has preprocessed columns, the table no matrix" % i
+            preps[i] = t.prep.ctypes.data
+            arr[i].log_height = t.log_height
+    h = C.c_void_p()
+    _lib.check(hal._ctx, lib.rk_p3_setup(hal._ctx, arr, len(tables), preps, C.byref(h)))
+    del keep
+    return Key(h)
+
+
+def prove(hal, tables, init=(), device_traces=None, key=None):
     """rk_p3_prove on hal's context under its current parameter set -> proof words.  device_traces: optional list of
-    (device pointer, log_height) per table for traces already in HBM."""
+    (device pointer, log_height) per table for traces already in HBM.  key: a Key from setup() -- rk_p3_prove_key, the
+    only way to prove tables with preprocessed columns."""
     lib = _lib.load()
     arr, keep = _c_tables(tables, device_traces)
     iw = np.ascontiguousarray(init, dtype=np.uint32)
     par = _lib.RkParams()
     _lib.check(hal._ctx, lib.rk_get_params(hal._ctx, C.byref(par)))
-    cap = lib.rk_p3_proof_bound_words(C.byref(par), arr, len(tables))
+    bound = lib.rk_p3_proof_bound_words if key is None else lib.rk_p3_proof_bound_words_key
+    cap = bound(C.byref(par), arr, len(tables))
     if cap == 0:
         raise _lib.RkError(_lib.RK_ERR_INVALID, "rk_p3_proof_bound_words: shapes the prover rejects")
     out = np.zeros(cap, dtype=np.uint32)
     n = C.c_size_t(0)
-    _lib.check(hal._ctx, lib.rk_p3_prove(hal._ctx, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size,
-                                        out.ctypes.data_as(_lib.u32p), cap, C.byref(n)))
+    args = (arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, out.ctypes.data_as(_lib.u32p), cap, C.byref(n))
+    _lib.check(hal._ctx, lib.rk_p3_prove(hal._ctx, *args) if key is None else lib.rk_p3_prove_key(hal._ctx, key._handle, *args))
     del keep
     return out[: n.value].copy()
 
@@ -488,14 +575,22 @@ def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, d
     return [bufs[i][: arr[i].proof_words].copy() for i in range(n)]
 
 
-def verify(tables, proof, init=(), params=None) -> int:
-    """rk_p3_verify (host only).  params: an RkParams blob (raiko_amd.hal.make_params) or None for the SP1 preset"""
+def verify(tables, proof, init=(), params=None, prep_root=None) -> int:
+    """rk_p3_verify (host only).  params: an RkParams blob (raiko_amd.hal.make_params) or None for the SP1 preset.
+    prep_root: the verifying key's root (Key.root) -- rk_p3_verify_key; the tables with preprocessed columns then need
+    their pinned log_height"""
     lib = _lib.load()
     arr, keep = _c_tables(tables)
     iw = np.ascontiguousarray(init, dtype=np.uint32)
     pf = np.ascontiguousarray(proof, dtype=np.uint32)
-    rc = lib.rk_p3_verify(C.byref(params) if params is not None else None, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size,
-                          pf.ctypes.data_as(_lib.u32p), pf.size)
+    par = C.byref(params) if params is not None else None
+    args = (iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size)
+    if prep_root is None:
+        rc = lib.rk_p3_verify(par, arr, len(tables), *args)
+    else:
+        kr = np.ascontiguousarray(prep_root, dtype=np.uint32)
+        assert kr.size == 8
+        rc = lib.rk_p3_verify_key(par, arr, len(tables), kr.ctypes.data_as(_lib.u32p), *args)
     del keep
     return rc
 
@@ -801,3 +896,21 @@ def lookup_demo_tables(log_cpu, log_range=4, seed=0, ext_w=EXT_W, airs=None):
     rng = np.stack([np.arange(1 << log_range, dtype=np.uint64), np.bincount(live[:, 0].astype(np.int64), minlength=1 << log_range).astype(np.uint64)], axis=1)
     return [Table.from_canonical(cpu_air, cpu), Table.from_canonical(add_air, add), Table.from_canonical(mul_air, mul),
             Table.from_canonical(rng_air, rng)]
+
+
+# ---------------------------------------------------------------------------------------------- preprocessed columns
+def p3_range_air_prep(ext_w=EXT_W):
+    """lookup_demo_airs' range table with its values PREPROCESSED: the value column 0 .. 2^k - 1 is committed once by
+    setup() (prep_width 1), the main trace is the multiplicity column alone (width 1), there are no counter constraints
+    -- a counter that is a constant needs none --, and the table receives (RANGE: prep 0) main[0] times"""
+    rng = AirBuilder(1, 0, ext_w, prep_width=1)
+    rng.receive(BUS_RANGE, [rng.prep(0)], mult=0, mult_is_const=False)
+    return rng.build()
+
+
+def lookup_demo_tables_prep(log_cpu, log_range=4, seed=0, ext_w=EXT_W):
+    """lookup_demo_tables with the range table replaced by p3_range_air_prep's: the same cpu, add and mul tables (same
+    seed, same rows), the range values in Table.prep and the multiplicities as the only trace column"""
+    cpu, add, mul, rng = lookup_demo_tables(log_cpu, log_range, seed, ext_w)
+    t = from_mont(rng.trace)
+    return [cpu, add, mul, Table.from_canonical(p3_range_air_prep(ext_w), t[:, 1:2], (), prep=t[:, 0:1])]
