@@ -3,7 +3,9 @@
 // which interprets the guest and cuts the run into segments of at most 2^segment_limit_po2 cycles
 // (bonsai.rs:249) that `session.prove()` (bonsai.rs:271) then proves one by one.
 //
-// Host code (no GPU work: the reference's executor is CPU code too, single-threaded).  What is
+// Host code only (the reference's executor is CPU code too, single-threaded): the machine, the ELF loader, the
+// segmenter and the host-side witness of the stand-in trace circuit.  The witness written on the GPU -- the same columns
+// and the tables of the rv32 chip sets -- is rv32_shards.hip, which reads a recorded segment through executor.hpp.  What is
 // restated is the public part: the RV32IM instruction set (RISC-V unprivileged spec 2.2: RV32I +
 // M), a little-endian paged memory, an ELF32 loader, and the cut into power-of-two segments.
 // What is NOT risc0's (its executor lives in risc0-zkvm / risc0-circuit-rv32im 1.0.1, outside the
@@ -23,7 +25,9 @@
 #include <vector>
 
 #include "../../include/raiko_hip.h"
+#include "executor.hpp"
 #include "internal.hpp"
+#include "rv32_rows.hpp"
 
 namespace {
 
@@ -100,11 +104,6 @@ void state_digest(const p2::Any& k, const Machine& m, uint32_t* out8) {
 }
 
 }  // namespace
-
-// one executed cycle as the witness generator needs it
-struct TraceRow {
-    uint32_t pc, ins, a, b, res, next, wr;
-};
 
 struct rk_exec {
     std::vector<rk_exec_segment> segments;
@@ -427,42 +426,12 @@ int exec_elf(const uint8_t* elf, size_t elf_bytes, const rk_exec_opts* o, rk_exe
 
 }  // namespace
 
-// The same columns written by the GPU: one lane per row, the trace rows (28 bytes per cycle) are the only upload --
-// 2.5x less over PCIe than the 18 finished columns and none of the host's time (rk_exec_witness_device).
-__global__ void exec_witness_kernel(uint32_t* __restrict__ code, uint32_t* __restrict__ data, const TraceRow* __restrict__ tr,
-                                    size_t cycles, size_t n, uint32_t end_pc, uint32_t rows_only) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const bool active = i < cycles;
-    TraceRow r{};
-    if (active) r = tr[i];
-    else r.pc = r.next = end_pc;
-    const uint32_t lo = r.pc & 0xffffu, carry = (active && lo + 4 > 0xffffu) ? 1u : 0u;
-    const uint32_t seq = (active && r.next == r.pc + 4 && r.pc <= 0xfffffffbu) ? 1u : 0u;
-    // rows_only: the 16 data columns as one row-major row per lane (64 contiguous bytes: an rk_p3_table), no code columns
-    auto put = [&](uint32_t* base, unsigned col, uint32_t canon) {
-        base[rows_only ? i * RK_TRACE_DATA_COLS + col : (size_t)col * n + i] = bb::mul(canon, bb::R2);
-    };
-    if (!rows_only) {
-        put(code, 0, i == 0 ? 1u : 0u);
-        put(code, 1, i + 1 == n ? 1u : 0u);
-    }
-    put(data, 0, lo);
-    put(data, 1, r.pc >> 16);
-    put(data, 2, r.next & 0xffffu);
-    put(data, 3, r.next >> 16);
-    put(data, 4, r.ins & 0xffffu);
-    put(data, 5, r.ins >> 16);
-    put(data, 6, seq);
-    put(data, 7, seq ? carry : 0u);
-    put(data, 8, r.a & 0xffffu);
-    put(data, 9, r.a >> 16);
-    put(data, 10, r.b & 0xffffu);
-    put(data, 11, r.b >> 16);
-    put(data, 12, r.res & 0xffffu);
-    put(data, 13, r.res >> 16);
-    put(data, 14, r.wr);
-    put(data, 15, active ? 1u : 0u);
+int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out) {
+    if (!ex || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
+    if (ex->traces[index].size() != ex->segments[index].cycles) return RK_ERR_INTERNAL;
+    *out = ExecSegmentView{&ex->segments[index], &ex->traces[index], ex->regs[index].data(), &ex->ecalls[index],
+                           ex->pc_range[index][0], ex->pc_range[index][1]};
+    return RK_OK;
 }
 
 extern "C" {
@@ -520,39 +489,22 @@ int rk_exec_journal(const rk_exec* ex, uint8_t* out, size_t capacity, size_t* le
 // 16-bit field elements; rows beyond the executed cycles repeat the final pc with active = seq = 0.
 int rk_exec_witness(const rk_exec* ex, uint32_t index, uint32_t* code, uint32_t* data) {
     RK_GUARD_BEGIN
-    if (!ex || !code || !data || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
-    const rk_exec_segment& seg = ex->segments[index];
-    const std::vector<TraceRow>& tr = ex->traces[index];
-    const size_t n = (size_t)1 << seg.po2;
-    if (tr.size() != seg.cycles || tr.size() > n) return RK_ERR_INTERNAL;
+    if (!code || !data) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    const std::vector<TraceRow>& tr = *v.trace;
+    const size_t n = (size_t)1 << v.seg->po2;
+    if (tr.size() > n) return RK_ERR_INTERNAL;
     // every cell is below 2^16 (or a bit): one Montgomery product each; rows are independent, four threads split them
-    auto put = [&](uint32_t* base, unsigned col, size_t i, uint32_t canon) { base[(size_t)col * n + i] = bb::mul(canon, bb::R2); };
+    auto put = [&](uint32_t* base, unsigned col, size_t i, uint32_t canon) { base[(size_t)col * n + i] = rv32::enc(canon); };
     auto fill = [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; i++) {
             put(code, 0, i, i == 0 ? 1u : 0u);         // first row
             put(code, 1, i, i + 1 == n ? 1u : 0u);     // last row
             const bool active = i < tr.size();
-            TraceRow r{};
-            if (active) r = tr[i];
-            else r.pc = r.next = seg.end_pc;           // padding: stay where the segment ended
-            const uint32_t lo = r.pc & 0xffffu, carry = (active && lo + 4 > 0xffffu) ? 1u : 0u;
-            const uint32_t seq = (active && r.next == r.pc + 4 && r.pc <= 0xfffffffbu) ? 1u : 0u;  // no wrap of the 32-bit pc
-            put(data, 0, i, lo);
-            put(data, 1, i, r.pc >> 16);
-            put(data, 2, i, r.next & 0xffffu);
-            put(data, 3, i, r.next >> 16);
-            put(data, 4, i, r.ins & 0xffffu);
-            put(data, 5, i, r.ins >> 16);
-            put(data, 6, i, seq);
-            put(data, 7, i, seq ? carry : 0u);
-            put(data, 8, i, r.a & 0xffffu);
-            put(data, 9, i, r.a >> 16);
-            put(data, 10, i, r.b & 0xffffu);
-            put(data, 11, i, r.b >> 16);
-            put(data, 12, i, r.res & 0xffffu);
-            put(data, 13, i, r.res >> 16);
-            put(data, 14, i, r.wr);
-            put(data, 15, i, active ? 1u : 0u);
+            uint32_t c[RK_TRACE_DATA_COLS];
+            rv32::trace_cells(active ? tr[i] : rv32::padding_row(v.seg->end_pc), active, c);
+            for (unsigned col = 0; col < RK_TRACE_DATA_COLS; col++) put(data, col, i, c[col]);
         }
     };
     const size_t n_threads = n >= (1u << 16) ? 4 : 1;
@@ -565,17 +517,17 @@ int rk_exec_witness(const rk_exec* ex, uint32_t index, uint32_t* code, uint32_t*
 }
 int rk_exec_lookup_tables(const rk_exec* ex, uint32_t index, uint32_t* range_table, uint32_t* program_table, size_t* program_rows) {
     RK_GUARD_BEGIN
-    if (!ex || !range_table || !program_rows || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
-    const std::vector<TraceRow>& tr = ex->traces[index];
-    if (tr.size() != ex->segments[index].cycles) return RK_ERR_INTERNAL;
+    if (!range_table || !program_rows) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    const std::vector<TraceRow>& tr = *v.trace;
     // one pass over the executed cycles: how often each (pc, instruction) pair ran, how often each 16-bit value occurs
     // among the ten limbs a row sends to the range table
     std::vector<uint32_t> hist((size_t)1 << 16, 0);
     std::unordered_map<uint64_t, uint32_t> seen;
     // programs run from a few KiB of text: count per word of the executed pc range; the map only for what does not fit that
     // picture (a range above 16 MiB, an address executed with two different instruction words)
-    uint32_t pc_lo = 0xffffffffu, pc_hi = 0;
-    for (const TraceRow& r : tr) pc_lo = std::min(pc_lo, r.pc), pc_hi = std::max(pc_hi, r.pc);
+    const uint32_t pc_lo = v.pc_lo, pc_hi = v.pc_hi;
     struct Slot {
         uint32_t ins, count;
     };
@@ -629,947 +581,11 @@ int rk_exec_lookup_tables(const rk_exec* ex, uint32_t index, uint32_t* range_tab
     return RK_OK;
     RK_GUARD_END
 }
-static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_code, uint32_t* d_data, bool rows_only);
-int rk_exec_witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_code, uint32_t* d_data) {
-    RK_GUARD_BEGIN
-    if (!d_code) return RK_ERR_INVALID;
-    return witness_device(ctx, ex, index, d_code, d_data, false);
-    RK_GUARD_END
-}
-int rk_exec_witness_device_rows(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_rows) {
-    RK_GUARD_BEGIN
-    return witness_device(ctx, ex, index, nullptr, d_rows, true);
-    RK_GUARD_END
-}
-static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_code, uint32_t* d_data, bool rows_only) {
-    {
-    if (!ctx || !ex || !d_data || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
-    const rk_exec_segment& seg = ex->segments[index];
-    const std::vector<TraceRow>& tr = ex->traces[index];
-    const size_t n = (size_t)1 << seg.po2;
-    if (tr.size() != seg.cycles || tr.size() > n) return RK_ERR_INTERNAL;
-    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* d_tr = nullptr;
-    RK_TRY(rk::dev_alloc(ctx, std::max<size_t>(tr.size(), 1) * sizeof(TraceRow), &d_tr));
-    int st = RK_OK;
-    if (!tr.empty()) {
-        // the trace stays valid while `ex` lives, but the caller may free `ex` right after this call: wait for the copy
-        hipError_t e = hipMemcpyAsync(d_tr, tr.data(), tr.size() * sizeof(TraceRow), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("rk_exec_witness_device h2d: ") + hipGetErrorString(e);
-            st = RK_ERR_HIP;
-        }
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(exec_witness_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_code, d_data,
-                           (const TraceRow*)d_tr, tr.size(), n, seg.end_pc, rows_only ? 1u : 0u);
-        st = rk::post_launch(ctx, "exec_witness_kernel");
-    }
-    rk::dev_free(ctx, d_tr);
-    return st;
-    }
-}
 const char* rk_exec_error(const rk_exec* ex) { return ex ? ex->error.c_str() : ""; }
 int rk_exec_free(rk_exec* ex) {
     delete ex;
     return RK_OK;
 }
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The rv32i chip set (include/raiko_hip.h rk_exec_rv32_shard_device; raiko_amd/rv32.py is the same in numpy and names
-// every column).  Per segment on the GPU: prep (decode, recompute the written value, pack the three accesses, count
-// program hits) -> block_last (last access per register per 128 rows) -> scan (exclusive max-scan of those 32-vectors)
-// -> rows (in-block resolve of each access's predecessor, the cpu row staged through LDS, RANGE16 / BYTE counts) ->
-// the program, register, byte and range tables.
-namespace rv32 {
-
-constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 for rv32i-cf / rv32im)
-constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_W = RK_RV32_REGISTER_COLS,
-                   BYTE_W = RK_RV32_BYTE_COLS, CF_CPU_W = RK_RV32CF_CPU_COLS, CF_PROG_W = RK_RV32CF_PROGRAM_COLS,
-                   SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256, IM_CPU_W = RK_RV32IM_CPU_COLS,
-                   IM_PROG_W = RK_RV32IM_PROGRAM_COLS, MD_W = RK_RV32IM_MULDIV_COLS;
-// the chip set a kernel writes: each one's tables are the previous one's with columns (and tables) appended
-enum ChipSet : int { CS_I, CS_CF, CS_IM };
-enum : unsigned {
-    PC_LO, PC_HI, NX_LO, NX_HI, INS_LO, INS_HI, SEQ, CARRY, A_LO, A_HI, B_LO, B_HI, RES_LO, RES_HI, WR, ACTIVE,
-    RS1, RS2, WREG, IMM_LO, IMM_HI, IS_ADD, IS_SUB, IS_SLT, IS_SLTU, IS_BIT, BOP, IS_IMM, IS_LUI, IS_AUIPC, IS_LINK,
-    TSA, TSB, TSW, PA_TS, PB_TS, PW_TS, PW_LO, PW_HI, DA_LO, DA_HI, DB_LO, DB_HI, DW_LO, DW_HI,
-    OB_LO, OB_HI, C0, C1, D_LO, D_HI, SA, SB, SNE, SA_CHK, SB_CHK, BA, BB = BA + 4, BR = BB + 4,
-    // rv32i-cf (raiko_amd/rv32cf.py): the twelve looked-up fields, then the branch, next-pc and shift columns
-    IS_JAL = BR + 4, IS_BEQ, IS_BNE, IS_BLT, IS_BGE, IS_BLTU, IS_BGEU, JIMM_LO, JIMM_HI, IS_SLL, IS_SRL, IS_SRA,
-    IS_BR, TAKEN, BD_LO, BD_HI, BC0, BC1, EQ, INV, M_SA, M_SB, NC0, NC1, DROP, NXH,
-    IS_SHIFT, KB, Q = KB + 3, SK = Q + 4, T, FILL, U_LO, U_HI, V_LO, V_HI, SX, SLO = SX + 4, SHI = SLO + 4,
-    // rv32im (raiko_amd/rv32im.py): the eight M selectors and their sum (looked up), the op, the multiplicity
-    IS_MUL = SHI + 4, IS_M = IS_MUL + 8, MOP, M_W
-};
-static_assert(SHI + 4 == CF_CPU_W, "rv32i-cf cpu columns");
-static_assert(M_W + 1 == IM_CPU_W, "rv32im cpu columns");
-constexpr uint32_t OPCODES[11] = {0x37, 0x17, 0x6f, 0x67, 0x63, 0x03, 0x23, 0x13, 0x33, 0x0f, 0x73};
-enum { O_LUI, O_AUIPC, O_JAL, O_JALR, O_BRANCH, O_LOAD, O_STORE, O_OPIMM, O_OP, O_FENCE, O_SYSTEM };
-
-struct Dec {
-    int opc;   // index into OPCODES, -1 for none
-    uint32_t f3, rd, rs1, rs2, wreg, imm, opr, is_add, is_sub, is_slt, is_sltu, is_bit, bop, is_imm, is_lui, is_auipc,
-        is_link, wr;
-    // rv32i-cf: bsel = the branch (0..5: BEQ BNE BLT BGE BLTU BGEU) or -1; jimm = imm_B of a branch, imm_J of JAL
-    int bsel;
-    uint32_t is_jal, jimm, is_sll, is_srl, is_sra;
-    uint32_t is_m;   // rv32im: an M word (OP, funct7 = 1); its op is f3
-};
-
-__host__ __device__ inline Dec decode(uint32_t ins) {
-    Dec d{};
-    d.opc = -1;
-    for (int k = 0; k < 11; k++)
-        if ((ins & 0x7fu) == OPCODES[k]) d.opc = k;
-    d.f3 = (ins >> 12) & 7;
-    d.rd = (ins >> 7) & 31;
-    d.rs1 = (ins >> 15) & 31;
-    d.rs2 = (ins >> 20) & 31;
-    const uint32_t b25 = (ins >> 25) & 1, b30 = (ins >> 30) & 1;
-    d.opr = d.opc == O_OP && !b25;
-    const uint32_t opimm = d.opc == O_OPIMM, alu = d.opr | opimm;
-    d.is_add = (d.f3 == 0) && ((d.opr && !b30) || opimm);
-    d.is_sub = d.opr && d.f3 == 0 && b30;
-    d.is_slt = alu && d.f3 == 2;
-    d.is_sltu = alu && d.f3 == 3;
-    d.is_bit = alu && (d.f3 == 4 || d.f3 == 6 || d.f3 == 7);
-    d.bop = !alu ? 0 : d.f3 == 4 ? 3 : d.f3 == 6 ? 2 : d.f3 == 7 ? 1 : 0;
-    d.is_imm = opimm;
-    d.is_lui = d.opc == O_LUI;
-    d.is_auipc = d.opc == O_AUIPC;
-    d.is_link = d.opc == O_JAL || d.opc == O_JALR;
-    if (opimm || d.opc == O_LOAD || d.opc == O_JALR) d.imm = (uint32_t)((int32_t)ins >> 20);
-    else if (d.is_lui || d.is_auipc) d.imm = ins & 0xfffff000u;
-    const bool writes = d.is_lui || d.is_auipc || d.is_link || d.opc == O_LOAD || opimm || d.opc == O_OP;
-    d.wr = (writes && d.rd != 0) || d.opc == O_SYSTEM;
-    d.wreg = d.rd + (d.opc == O_SYSTEM ? 10u : 0u);
-    d.is_jal = d.opc == O_JAL;
-    d.bsel = -1;
-    if (d.opc == O_BRANCH) {
-        d.bsel = d.f3 < 2 ? (int)d.f3 : d.f3 >= 4 ? (int)d.f3 - 2 : -1;
-        const uint32_t b = (ins >> 31) << 12 | ((ins >> 7) & 1) << 11 | ((ins >> 25) & 0x3f) << 5 | ((ins >> 8) & 0xf) << 1;
-        d.jimm = (uint32_t)((int32_t)(b << 19) >> 19);
-    } else if (d.is_jal) {
-        const uint32_t j = (ins >> 31) << 20 | ((ins >> 12) & 0xff) << 12 | ((ins >> 20) & 1) << 11 | ((ins >> 21) & 0x3ff) << 1;
-        d.jimm = (uint32_t)((int32_t)(j << 11) >> 11);
-    }
-    d.is_sll = alu && d.f3 == 1;
-    d.is_srl = alu && d.f3 == 5 && !b30;
-    d.is_sra = alu && d.f3 == 5 && b30;
-    d.is_m = d.opc == O_OP && (ins >> 25) == 1;
-    return d;
-}
-
-// the value a row writes: recomputed for the constrained ops, the side list's for an ecall, TraceRow.res otherwise
-__device__ inline uint32_t written(const Dec& d, const TraceRow& r, uint32_t ecall_a0) {
-    const uint32_t a = r.a, ob = d.is_imm ? d.imm : r.b;
-    if (d.is_add) return a + ob;
-    if (d.is_sub) return a - ob;
-    if (d.is_sltu) return a < ob;
-    if (d.is_slt) return (int32_t)a < (int32_t)ob;
-    if (d.is_bit) return d.f3 == 4 ? a ^ ob : d.f3 == 6 ? a | ob : a & ob;
-    if (d.is_lui) return d.imm;
-    if (d.is_auipc) return r.pc + d.imm;
-    if (d.is_link) return r.pc + 4;
-    if (d.opc == O_SYSTEM) return ecall_a0;
-    return r.res;
-}
-
-__device__ inline uint32_t enc(uint32_t canon) { return bb::mul(canon, bb::R2); }
-
-// a histogram bin += 1 for every lane with `on`; the lanes of a wave that agree with its first active lane add once
-__device__ inline void hist_add(uint32_t* h, uint32_t v, bool on) {
-    const uint64_t act = __ballot(on);
-    if (!act) return;
-    const int first = __ffsll((unsigned long long)act) - 1;
-    const uint32_t lv = __shfl(v, first);
-    const uint64_t same = __ballot(on && v == lv);
-    if ((int)(threadIdx.x & 63) == first) atomicAdd(&h[lv], (uint32_t)__popcll(same));
-    else if (on && v != lv) atomicAdd(&h[v], 1u);
-}
-
-// the row a cpu lane writes row-major: staged in LDS (odd stride: no bank conflicts), then whole lines to HBM
-template <unsigned W>
-__device__ inline void flush_rows(uint32_t* out, const uint32_t* s, size_t r0, size_t n_rows) {
-    constexpr unsigned SW = W | 1;
-    const size_t rows = n_rows - r0 < blockDim.x ? n_rows - r0 : blockDim.x;
-    for (size_t k = threadIdx.x; k < rows * W; k += blockDim.x) out[r0 * W + k] = s[(k / W) * SW + k % W];
-}
-
-__global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
-                            uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
-                            uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
-                            uint32_t* __restrict__ err, uint32_t* __restrict__ mflag) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (i >= cycles) {
-        wval[i] = 0;
-        acc[i] = 0;
-        if (mflag) mflag[i] = 0;
-        return;
-    }
-    const TraceRow r = tr[i];
-    const Dec d = decode(r.ins);
-    if (mflag) mflag[i] = d.is_m && d.wr;   // rv32im: the rows with M_W = 1, one muldiv row each
-    uint32_t a0 = 0;
-    if (d.opc == O_SYSTEM) {   // the side list is in cycle order: binary search
-        uint32_t lo = 0, hi = n_ecalls;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) / 2;
-            if (ecalls[2 * mid] < i) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < n_ecalls && ecalls[2 * lo] == i) a0 = ecalls[2 * lo + 1];
-        else atomicOr(err, 2u);
-    }
-    wval[i] = written(d, r, a0);
-    acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16;
-    const uint32_t slot = (r.pc - pc_base) >> 2;
-    if (slot >= n_slots) {
-        atomicOr(err, 4u);
-        return;
-    }
-    atomicAdd(&prog_mult[slot], 1u);
-    const uint32_t old = atomicCAS(&prog_ins[slot], 0u, r.ins);
-    if (old != 0 && old != r.ins) atomicOr(err, 1u);    // one pc, two instruction words in one shard
-}
-
-__device__ inline void unpack(uint32_t v, uint32_t& rs1, uint32_t& rs2, uint32_t& wreg, bool& wr, bool& active) {
-    rs1 = v & 31;
-    rs2 = (v >> 5) & 31;
-    wreg = (v >> 10) & 31;
-    wr = (v >> 15) & 1;
-    active = (v >> 16) & 1;
-}
-
-__global__ void block_last_kernel(const uint32_t* __restrict__ acc, uint32_t* __restrict__ blk) {
-    __shared__ uint32_t s[32];
-    if (threadIdx.x < 32) s[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    uint32_t rs1, rs2, wreg;
-    bool wr, active;
-    unpack(acc[i], rs1, rs2, wreg, wr, active);
-    if (active) {
-        const uint32_t tsa = (uint32_t)(3 * i + 1);
-        atomicMax(&s[rs1], tsa);
-        atomicMax(&s[rs2], tsa + 1);
-        if (wr) atomicMax(&s[wreg], tsa + 2);
-    }
-    __syncthreads();
-    if (threadIdx.x < 32) blk[(size_t)blockIdx.x * 32 + threadIdx.x] = s[threadIdx.x];
-}
-
-// one workgroup of 1024: lane = register (t & 31) x chunk of blocks (t >> 5); blk becomes its exclusive prefix max
-__global__ void scan_kernel(uint32_t* __restrict__ blk, size_t nb, uint32_t* __restrict__ final_ts) {
-    __shared__ uint32_t cm[32][32];
-    const unsigned r = threadIdx.x & 31, c = threadIdx.x >> 5;
-    const size_t j0 = nb * c / 32, j1 = nb * (c + 1) / 32;
-    uint32_t m = 0;
-    for (size_t j = j0; j < j1; j++) m = max(m, blk[j * 32 + r]);
-    cm[c][r] = m;
-    __syncthreads();
-    uint32_t run = 0;
-    for (unsigned k = 0; k < c; k++) run = max(run, cm[k][r]);
-    for (size_t j = j0; j < j1; j++) {
-        const uint32_t v = blk[j * 32 + r];
-        blk[j * 32 + r] = run;
-        run = max(run, v);
-    }
-    if (c == 31) final_ts[r] = run;
-}
-
-__device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* tr, const uint32_t* wval, const uint32_t* init) {
-    if (ts == 0) return init[reg];
-    const uint32_t j = (ts - 1) / 3, k = (ts - 1) % 3;
-    return k == 0 ? tr[j].a : k == 1 ? tr[j].b : wval[j];
-}
-
-// CS_CF: the rv32i-cf row (columns 0..67 are the rv32i row, the rest rv32cf.py's) and its SHIFT counts; CS_IM: the
-// rv32i-cf row with rv32im.py's M columns appended
-template <int CS>
-__global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ tr, size_t cycles, uint32_t end_pc,
-                                                   const uint32_t* __restrict__ acc, const uint32_t* __restrict__ wval,
-                                                   const uint32_t* __restrict__ pre, const uint32_t* __restrict__ init,
-                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ hist,
-                                                   uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
-                                                   size_t n) {
-    constexpr bool CF = CS != CS_I;
-    constexpr unsigned W = CS == CS_IM ? IM_CPU_W : CF ? CF_CPU_W : CPU_W;
-    extern __shared__ uint32_t s_rows[];            // TB x (W | 1)
-    __shared__ uint32_t s_wave[32][TB / 64];
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t rs1, rs2, wreg;
-    bool wr, active;
-    unpack(acc[i], rs1, rs2, wreg, wr, active);
-    const uint32_t tsa = (uint32_t)(3 * i + 1);
-    // per register: the latest access among this wave's rows up to this one (inclusive max-scan over the lanes)
-    uint32_t incl[32];
-#pragma unroll
-    for (unsigned r = 0; r < 32; r++) {
-        uint32_t v = 0;
-        if (active) {
-            if (rs1 == r) v = tsa;
-            if (rs2 == r) v = tsa + 1;
-            if (wr && wreg == r) v = tsa + 2;
-        }
-#pragma unroll
-        for (unsigned off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(v, off);
-            if (lane >= off) v = max(v, t);
-        }
-        incl[r] = v;
-        if (lane == 63) s_wave[r][wave] = v;
-    }
-    __syncthreads();
-    uint32_t e1 = 0, e2 = 0, e3 = 0;
-#pragma unroll
-    for (unsigned r = 0; r < 32; r++) {
-        uint32_t ex = __shfl_up(incl[r], 1);
-        if (lane == 0) ex = 0;
-        for (unsigned w = 0; w < wave; w++) ex = max(ex, s_wave[r][w]);
-        ex = max(ex, pre[(size_t)blockIdx.x * 32 + r]);
-        if (rs1 == r) e1 = ex;
-        if (rs2 == r) e2 = ex;
-        if (wreg == r) e3 = ex;
-    }
-    uint32_t* row = s_rows + threadIdx.x * (W | 1);
-    for (unsigned c = 0; c < W; c++) row[c] = 0;
-    uint32_t res = 0, bop = 0, ba = 0, bb_ = 0, pa = 0, pb = 0, pw = 0, sa = 0, sb = 0, is_slt = 0, d_lo = 0, d_hi = 0;
-    bool is_br = false, is_link = false, is_shift = false, m_sa = false, m_sb = false;   // rv32i-cf multiplicities
-    if (active) {
-        const TraceRow r = tr[i];
-        const Dec d = decode(r.ins);
-        res = wval[i];
-        pa = e1;
-        pb = rs2 == rs1 ? tsa : e2;
-        pw = wr ? (wreg == rs2 ? tsa + 1 : wreg == rs1 ? tsa : e3) : 0;
-        const uint32_t pwv = wr ? value_at(pw, wreg, tr, wval, init) : 0;
-        const uint32_t ob = d.is_imm ? d.imm : r.b;
-        const uint32_t seq = (r.next == r.pc + 4 && r.pc <= 0xfffffffbu) ? 1u : 0u;
-        const uint32_t carry = ((r.pc & 0xffffu) + 4 > 0xffffu) ? 1u : 0u;
-        const bool sublt = d.is_sub || d.is_slt || d.is_sltu;
-        const uint32_t dd = sublt ? r.a - ob : 0;
-        uint32_t x = 0, y = 0;
-        if (d.is_add) x = r.a, y = ob;
-        else if (d.is_auipc) x = r.pc, y = d.imm;
-        else if (d.is_link) x = r.pc, y = 4;
-        else if (sublt) x = dd, y = ob;
-        const uint32_t c0 = ((x & 0xffffu) + (y & 0xffffu)) >> 16, c1 = ((x >> 16) + (y >> 16) + c0) >> 16;
-        sa = r.a >> 31;
-        sb = ob >> 31;
-        is_slt = d.is_slt;
-        d_lo = dd & 0xffffu;
-        d_hi = dd >> 16;
-        const uint32_t da = tsa - pa - 1, db = tsa + 1 - pb - 1, dw = wr ? tsa + 2 - pw - 1 : 0;
-        const uint32_t vals[][2] = {
-            {PC_LO, r.pc & 0xffffu}, {PC_HI, r.pc >> 16}, {NX_LO, r.next & 0xffffu}, {NX_HI, r.next >> 16},
-            {INS_LO, r.ins & 0xffffu}, {INS_HI, r.ins >> 16}, {SEQ, seq}, {CARRY, seq & carry},
-            {A_LO, r.a & 0xffffu}, {A_HI, r.a >> 16}, {B_LO, r.b & 0xffffu}, {B_HI, r.b >> 16},
-            {RES_LO, res & 0xffffu}, {RES_HI, res >> 16}, {WR, d.wr}, {ACTIVE, 1},
-            {RS1, d.rs1}, {RS2, d.rs2}, {WREG, d.wreg}, {IMM_LO, d.imm & 0xffffu}, {IMM_HI, d.imm >> 16},
-            {IS_ADD, d.is_add}, {IS_SUB, d.is_sub}, {IS_SLT, d.is_slt}, {IS_SLTU, d.is_sltu}, {IS_BIT, d.is_bit},
-            {BOP, d.bop}, {IS_IMM, d.is_imm}, {IS_LUI, d.is_lui}, {IS_AUIPC, d.is_auipc}, {IS_LINK, d.is_link},
-            {PA_TS, pa}, {PB_TS, pb}, {PW_TS, pw}, {PW_LO, pwv & 0xffffu}, {PW_HI, pwv >> 16},
-            {DA_LO, da & 0x3fffu}, {DA_HI, da >> 14}, {DB_LO, db & 0x3fffu}, {DB_HI, db >> 14},
-            {DW_LO, dw & 0x3fffu}, {DW_HI, dw >> 14}, {OB_LO, ob & 0xffffu}, {OB_HI, ob >> 16}, {C0, c0}, {C1, c1},
-            {D_LO, d_lo}, {D_HI, d_hi}, {SA, sa}, {SB, sb}, {SNE, sa ^ sb},
-            {SA_CHK, 2 * (r.a >> 16) - 65536 * sa}, {SB_CHK, 2 * (ob >> 16) - 65536 * sb}};
-        for (const auto& kv : vals) row[kv[0]] = kv[1];
-        if (d.is_bit) {
-            bop = d.bop;
-            ba = r.a;
-            bb_ = ob;
-            for (unsigned k = 0; k < 4; k++) {
-                row[BA + k] = (r.a >> (8 * k)) & 255;
-                row[BB + k] = (ob >> (8 * k)) & 255;
-                row[BR + k] = (res >> (8 * k)) & 255;
-            }
-        }
-        if constexpr (CF) {
-            const uint32_t a = r.a, b = r.b;
-            // branch decision
-            is_br = d.bsel >= 0;
-            const bool eqv = a == b, ltu = a < b, lts = (int32_t)a < (int32_t)b;
-            const bool cond[6] = {eqv, !eqv, lts, !lts, ltu, !ltu};
-            const bool taken = is_br && cond[d.bsel];
-            if (is_br) {
-                const uint32_t dd = a - b, z = (dd & 0xffffu) + (dd >> 16);
-                row[IS_BEQ + d.bsel] = 1;
-                row[BD_LO] = dd & 0xffffu;
-                row[BD_HI] = dd >> 16;
-                row[BC0] = (a & 0xffffu) < (b & 0xffffu);
-                row[BC1] = ltu;
-                row[EQ] = eqv;
-                row[INV] = z ? bb::decode(bb::inv(enc(z))) : 0u;
-            }
-            m_sb = d.bsel == 2 || d.bsel == 3;
-            m_sa = m_sb || d.is_sra;
-            row[IS_BR] = is_br;
-            row[TAKEN] = taken;
-            row[M_SA] = m_sa;
-            row[M_SB] = m_sb;
-            // next pc = base + offset (mod 2^32), JALR's low bit dropped
-            const bool jalr = d.opc == O_JALR;
-            is_link = d.is_link;
-            const uint32_t base = jalr ? a : r.pc, off = jalr ? d.imm : (taken || d.is_jal) ? d.jimm : 4u;
-            const uint32_t nc0 = ((base & 0xffffu) + (off & 0xffffu)) >> 16, nc1 = ((base >> 16) + (off >> 16) + nc0) >> 16;
-            row[IS_JAL] = d.is_jal;
-            row[JIMM_LO] = d.jimm & 0xffffu;
-            row[JIMM_HI] = d.jimm >> 16;
-            row[NC0] = nc0;
-            row[NC1] = nc1;
-            row[DROP] = jalr ? (base + off) & 1u : 0u;
-            row[NXH] = is_link ? (r.next & 0xffffu) >> 1 : 0u;
-            // shifts: s = k + 8 q; the bytes of a' (a, complemented for SRA of a negative a) through the shift table
-            row[IS_SLL] = d.is_sll;
-            row[IS_SRL] = d.is_srl;
-            row[IS_SRA] = d.is_sra;
-            is_shift = d.is_sll || d.is_srl || d.is_sra;
-            if (is_shift) {
-                const uint32_t amt = d.is_imm ? d.rs2 : b & 31u, k = amt & 7u, q = amt >> 3;
-                const bool fill = d.is_sra && (a >> 31);
-                const uint32_t ap = fill ? ~a : a, sk = d.is_sll ? k : 8u - k;
-                const uint32_t u = d.is_sll ? ap << amt : ap >> amt, v = fill ? ~u : u;
-                row[IS_SHIFT] = 1;
-                for (unsigned bit = 0; bit < 3; bit++) row[KB + bit] = (k >> bit) & 1u;
-                row[Q + q] = 1;
-                row[SK] = sk;
-                row[T] = d.is_imm ? 0u : (b & 0xffffu) >> 5;
-                row[FILL] = fill;
-                row[U_LO] = u & 0xffffu;
-                row[U_HI] = u >> 16;
-                row[V_LO] = v & 0xffffu;
-                row[V_HI] = v >> 16;
-                for (unsigned j = 0; j < 4; j++) {
-                    const uint32_t x = (ap >> (8 * j)) & 255u;
-                    row[SX + j] = x;
-                    row[SLO + j] = (x << sk) & 255u;
-                    row[SHI + j] = (x << sk) >> 8;
-                }
-            }
-        }
-        if constexpr (CS == CS_IM) {
-            if (d.is_m) {
-                row[IS_MUL + d.f3] = 1;
-                row[IS_M] = 1;
-                row[MOP] = d.f3;
-                row[M_W] = d.wr;
-            }
-        }
-    } else {
-        row[PC_LO] = row[NX_LO] = end_pc & 0xffffu;
-        row[PC_HI] = row[NX_HI] = end_pc >> 16;
-    }
-    row[TSA] = tsa;
-    row[TSB] = tsa + 1;
-    row[TSW] = tsa + 2;
-    // RANGE16: the limbs the row sends (rv32.py RANGE_SENDS), BYTE: four triples of a bitwise row
-    const unsigned rc[] = {PC_LO, PC_HI, NX_LO, NX_HI, RES_LO, RES_HI, D_LO, D_HI, DA_LO, DA_HI, DB_LO, DB_HI};
-    for (unsigned c : rc) hist_add(hist, row[c], active);
-    hist_add(hist, row[DW_LO], wr);
-    hist_add(hist, row[DW_HI], wr);
-    hist_add(hist, row[SA_CHK], is_slt);
-    hist_add(hist, row[SB_CHK], is_slt);
-    if (bop)
-        for (unsigned k = 0; k < 4; k++)
-            atomicAdd(&byte_mult[(bop - 1) << 16 | ((ba >> (8 * k)) & 255) << 8 | ((bb_ >> (8 * k)) & 255)], 1u);
-    if constexpr (CF) {   // rv32cf.py RANGE_SENDS past rv32i's, then the four SHIFT lookups (k, x) -> row k 256 + x
-        hist_add(hist, row[BD_LO], is_br);
-        hist_add(hist, row[BD_HI], is_br);
-        hist_add(hist, row[NXH], is_link);
-        hist_add(hist, row[T], is_shift);
-        hist_add(hist, row[SA_CHK], m_sa);
-        hist_add(hist, row[SB_CHK], m_sb);
-        for (unsigned j = 0; j < 4; j++) hist_add(shift_mult, row[SK] << 8 | row[SX + j], is_shift);
-    }
-    for (unsigned c = 0; c < W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<W>(out, s_rows, (size_t)blockIdx.x * TB, n);
-}
-
-// CS_CF: the rv32i-cf program row, rv32i's 77 columns and the twelve fields the cf cpu row looks up; CS_IM: then the
-// nine M fields and the funct7 test's three partial products
-template <int CS>
-__global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint32_t* __restrict__ prog_mult,
-                               uint32_t n_slots, uint32_t pc_base, size_t n_rows, uint32_t* __restrict__ out) {
-    constexpr bool CF = CS != CS_I;
-    constexpr unsigned W = CS == CS_IM ? IM_PROG_W : CF ? CF_PROG_W : PROG_W;
-    extern __shared__ uint32_t s_rows[];
-    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t* row = s_rows + threadIdx.x * (W | 1);
-    for (unsigned c = 0; c < W; c++) row[c] = 0;
-    if (s < n_rows) {   // past the executed range: the row of word 0 at pc 0, multiplicity 0
-        const bool in = s < n_slots;
-        const uint32_t pc = in ? pc_base + 4 * (uint32_t)s : 0u, ins = in ? prog_ins[s] : 0u;
-        const Dec d = decode(ins);
-        const uint32_t v[20] = {pc & 0xffffu, pc >> 16, ins & 0xffffu, ins >> 16, d.rs1, d.rs2, d.wreg, d.imm & 0xffffu,
-                                d.imm >> 16, d.is_add, d.is_sub, d.is_slt, d.is_sltu, d.is_bit, d.bop, d.is_imm,
-                                d.is_lui, d.is_auipc, d.is_link, d.wr};
-        for (unsigned c = 0; c < 20; c++) row[c] = v[c];
-        row[20] = in ? prog_mult[s] : 0u;
-        for (unsigned k = 0; k < 32; k++) row[21 + k] = (ins >> k) & 1;
-        if (d.opc >= 0) {
-            row[53 + d.opc] = 1;
-            row[64 + d.f3] = 1;
-        }
-        const uint32_t b = ins >> 7;
-        const uint32_t z1 = (~b & 1) & (~b >> 1 & 1), z2 = z1 & (~b >> 2 & 1), rdz = z2 & (~b >> 3 & 1) & (~b >> 4 & 1);
-        row[72] = d.opr;
-        row[73] = z1;
-        row[74] = z2;
-        row[75] = rdz;
-        row[76] = d.rd;
-        if constexpr (CF) {
-            uint32_t* e = row + PROG_W - IS_JAL;     // e[c]: the field of cpu column c
-            e[IS_JAL] = d.is_jal;
-            if (d.bsel >= 0) e[IS_BEQ + d.bsel] = 1;
-            e[JIMM_LO] = d.jimm & 0xffffu;
-            e[JIMM_HI] = d.jimm >> 16;
-            e[IS_SLL] = d.is_sll;
-            e[IS_SRL] = d.is_srl;
-            e[IS_SRA] = d.is_sra;
-        }
-        if constexpr (CS == CS_IM) {
-            uint32_t* m = row + CF_PROG_W;          // IS_MUL .. IS_REMU, IS_M, then op b25 !b26, !b27 !b28, !b29 !b30
-            const auto nb = [&](unsigned k) { return ((ins >> k) & 1u) ^ 1u; };
-            const uint32_t f7a = (d.opc == O_OP) & (ins >> 25) & 1u & nb(26), f7b = f7a & nb(27) & nb(28), f7c = f7b & nb(29) & nb(30);
-            if (d.is_m) m[d.f3] = 1;
-            m[8] = d.is_m;
-            m[9] = f7a;
-            m[10] = f7b;
-            m[11] = f7c;
-        }
-    }
-    for (unsigned c = 0; c < W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, n_rows);
-}
-
-// the rv32i-cf shift table (rv32cf.py shift_rows): row k 256 + x = (k, x, x 2^k mod 256, x 2^k / 256, count, bits of x,
-// k one-hot, bits of x 2^k); rows past 9 x 256 the true tuple (0, 0, 0, 0) with count 0
-__global__ void shift_kernel(const uint32_t* __restrict__ shift_mult, uint32_t* __restrict__ out) {
-    extern __shared__ uint32_t s_rows[];
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t* row = s_rows + threadIdx.x * (SHIFT_W | 1);
-    for (unsigned c = 0; c < SHIFT_W; c++) row[c] = 0;
-    const uint32_t k = r < SHIFT_USED ? (uint32_t)(r >> 8) : 0u, x = r < SHIFT_USED ? (uint32_t)(r & 255) : 0u, v = x << k;
-    row[0] = k;
-    row[1] = x;
-    row[2] = v & 255u;
-    row[3] = v >> 8;
-    row[4] = r < SHIFT_USED ? shift_mult[r] : 0u;
-    for (unsigned bit = 0; bit < 8; bit++) row[5 + bit] = (x >> bit) & 1u;
-    row[13 + k] = 1;
-    for (unsigned bit = 0; bit < 16; bit++) row[22 + bit] = (v >> bit) & 1u;
-    for (unsigned c = 0; c < SHIFT_W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<SHIFT_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32CF_SHIFT_LOG_ROWS);
-}
-
-__global__ void byte_kernel(const uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ out) {
-    extern __shared__ uint32_t s_rows[];
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t* row = s_rows + threadIdx.x * (BYTE_W | 1);
-    for (unsigned c = 0; c < BYTE_W; c++) row[c] = 0;
-    if (r < (3u << 16)) {
-        const uint32_t op = (uint32_t)(r >> 16) + 1, x = (r >> 8) & 255, y = r & 255;
-        row[0] = op;
-        row[1] = x;
-        row[2] = y;
-        row[3] = op == 1 ? (x & y) : op == 2 ? (x | y) : (x ^ y);
-        for (unsigned k = 0; k < 8; k++) {
-            row[4 + k] = (x >> k) & 1;
-            row[12 + k] = (y >> k) & 1;
-        }
-        row[19 + op] = 1;
-        row[23] = byte_mult[r];
-    }
-    for (unsigned c = 0; c < BYTE_W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<BYTE_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32_BYTE_LOG_ROWS);
-}
-
-__global__ void range_kernel(const uint32_t* __restrict__ hist, uint32_t* __restrict__ out) {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= (1u << 16)) return;
-    out[2 * v] = enc(v);
-    out[2 * v + 1] = enc(hist[v]);
-}
-
-// 32 lanes: the register table (rv32.py register_rows); fin gets the final values
-__global__ void register_kernel(const uint32_t* __restrict__ final_ts, const uint32_t* __restrict__ init,
-                                const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval,
-                                uint32_t* __restrict__ fin, uint32_t* __restrict__ out) {
-    __shared__ uint32_t s_fin[32];
-    extern __shared__ uint32_t s_rows[];
-    const unsigned r = threadIdx.x;
-    s_fin[r] = value_at(final_ts[r], r, tr, wval, init);
-    fin[r] = s_fin[r];
-    __syncthreads();
-    uint32_t* row = s_rows + r * (REG_W | 1);
-    row[0] = r;
-    row[1] = 0;
-    row[2] = final_ts[r];
-    for (unsigned j = 0; j < 32; j++) {
-        const bool in = r + j < 32;
-        row[3 + j] = in ? init[r + j] & 0xffffu : 0;
-        row[35 + j] = in ? init[r + j] >> 16 : 0;
-        row[67 + j] = in ? s_fin[r + j] & 0xffffu : 0;
-        row[99 + j] = in ? s_fin[r + j] >> 16 : 0;
-    }
-    for (unsigned c = 0; c < REG_W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<REG_W>(out, s_rows, 0, 32);
-}
-
-// ---- rv32im: the muldiv table (raiko_amd/rv32im.py muldiv_witness names every column)
-enum : unsigned {
-    D_SEL, D_MULT = 8, D_OP, D_A_LO, D_A_HI, D_B_LO, D_B_HI, D_R_LO, D_R_HI, D_ONE, D_X, D_Y = D_X + 4, D_Z = D_Y + 4,
-    D_C = D_Z + 4, D_CY = D_C + 8, D_S = D_CY + 8, D_L = D_S + 4, D_E = D_L + 4, D_AND = D_E + 4, D_BZ = D_AND + 8, D_BINV,
-    D_OVF, D_OINV, D_BM_LO, D_BM_HI, D_KB, D_RM_LO, D_RM_HI, D_KR, D_DL_LO, D_DL_HI, D_K0
-};
-static_assert(D_K0 + 1 == MD_W, "rv32im muldiv columns");
-// the byte pairs looked up as ANDs (rv32im.py BYTE_PAIRS), the top bytes looked up in the shift table (SIGN_BYTES)
-constexpr unsigned MD_PAIRS[8][2] = {{D_X, D_X + 1}, {D_X + 2, D_Y}, {D_Y + 1, D_Y + 2}, {D_Z, D_Z + 1}, {D_Z + 2, D_C},
-                                     {D_C + 1, D_C + 2}, {D_C + 4, D_C + 5}, {D_C + 6, D_C + 7}};
-constexpr unsigned MD_RANGE[14] = {D_CY, D_CY + 1, D_CY + 2, D_CY + 3, D_CY + 4, D_CY + 5, D_CY + 6, D_CY + 7,
-                                   D_BM_LO, D_BM_HI, D_RM_LO, D_RM_HI, D_DL_LO, D_DL_HI};
-
-// per block of TB cpu rows: how many have M_W = 1
-__global__ void mcount_kernel(const uint32_t* __restrict__ mflag, uint32_t* __restrict__ mblk) {
-    const int c = __syncthreads_count(mflag[(size_t)blockIdx.x * TB + threadIdx.x] != 0);
-    if (threadIdx.x == 0) mblk[blockIdx.x] = (uint32_t)c;
-}
-
-// one workgroup of 1024: mblk becomes its exclusive prefix sum, total the sum
-__global__ void mscan_kernel(uint32_t* __restrict__ mblk, size_t nb, uint32_t* __restrict__ total) {
-    __shared__ uint32_t part[1024];
-    const unsigned t = threadIdx.x;
-    const size_t j0 = nb * t / 1024, j1 = nb * (t + 1) / 1024;
-    uint32_t sum = 0;
-    for (size_t j = j0; j < j1; j++) sum += mblk[j];
-    part[t] = sum;
-    __syncthreads();
-    for (unsigned off = 1; off < 1024; off <<= 1) {   // inclusive Hillis-Steele scan of the chunk sums
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (size_t j = j0; j < j1; j++) {
-        const uint32_t v = mblk[j];
-        mblk[j] = run;
-        run += v;
-    }
-    if (t == 1023) *total = run;
-}
-
-// the muldiv index of every row with M_W = 1: its block's offset + the flagged rows before it in the block; idx[k] = the
-// cpu row of muldiv row k (k < count)
-__global__ void mcompact_kernel(const uint32_t* __restrict__ mflag, const uint32_t* __restrict__ mblk, size_t count,
-                                uint32_t* __restrict__ idx) {
-    __shared__ uint32_t s_wave[TB / 64];
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool on = mflag[i] != 0;
-    const uint64_t bal = __ballot(on);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t k = mblk[blockIdx.x] + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
-    for (unsigned w = 0; w < wave; w++) k += s_wave[w];
-    if (on && k < count) idx[k] = (uint32_t)i;
-}
-
-// one lane per muldiv row: row k < count is the witness of cpu row idx[k]'s op on its 32-bit operands (64-bit products
-// and the division's quotient / remainder, the executor's conventions), rows past count padding (ONE = 1, the rest 0);
-// the RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms
-__global__ void muldiv_kernel(const TraceRow* __restrict__ tr, size_t cycles, const uint32_t* __restrict__ wval,
-                              const uint32_t* __restrict__ idx, size_t count, size_t n_rows, uint32_t* __restrict__ out,
-                              uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
-                              uint32_t* __restrict__ err) {
-    extern __shared__ uint32_t s_rows[];
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t* row = s_rows + threadIdx.x * (MD_W | 1);
-    for (unsigned c = 0; c < MD_W; c++) row[c] = 0;
-    row[D_ONE] = 1;
-    bool on = k < count;
-    const uint32_t i = on ? idx[k] : 0u;
-    if (on && i >= cycles) {   // the device's count is not the host's (reported after the run)
-        atomicOr(err, 16u);
-        on = false;
-    }
-    if (on) {
-        const TraceRow r = tr[i];
-        const uint32_t op = (r.ins >> 12) & 7, a = r.a, b = r.b, res = wval[i];
-        const bool is_mul = op < 4, divs = op == 4 || op == 6, bz = b == 0, ovf = divs && a == 0x80000000u && b == 0xffffffffu;
-        const bool sgn_x = op == 1 || op == 2 || divs, sgn_y = op == 1 || divs;
-        uint32_t q, rm;
-        if (bz) q = 0xffffffffu, rm = a;
-        else if (ovf) q = 0x80000000u, rm = 0;
-        else if (divs) q = (uint32_t)((int32_t)a / (int32_t)b), rm = (uint32_t)((int32_t)a % (int32_t)b);
-        else q = a / b, rm = a % b;
-        const uint32_t x = is_mul ? a : q, z = is_mul ? 0u : rm;
-        uint32_t xe[8], ye[8], ze[8], cb[8];
-        const uint32_t ex = sgn_x && (x >> 31), ey = sgn_y && (b >> 31), ez = divs && (z >> 31);
-        for (unsigned j = 0; j < 4; j++) {
-            xe[j] = (x >> (8 * j)) & 255u, ye[j] = (b >> (8 * j)) & 255u, ze[j] = (z >> (8 * j)) & 255u;
-            xe[j + 4] = 255u * ex, ye[j + 4] = 255u * ey, ze[j + 4] = 255u * ez;
-            row[D_X + j] = xe[j];
-            row[D_Y + j] = ye[j];
-            row[D_Z + j] = ze[j];
-        }
-        uint32_t carry = 0;   // < 8 * 255^2 + 255 + carry < 2^20: no overflow
-        for (unsigned c = 0; c < 8; c++) {
-            uint32_t acc = ze[c] + carry;
-            for (unsigned j = 0; j <= c; j++) acc += xe[j] * ye[c - j];
-            cb[c] = acc & 255u;
-            carry = acc >> 8;
-            row[D_C + c] = cb[c];
-            row[D_CY + c] = carry;
-        }
-        const uint32_t sc = cb[3] >> 7, ec = divs && sc;
-        const uint32_t lo_w = cb[0] | cb[1] << 8 | cb[2] << 16 | cb[3] << 24, hi_w = cb[4] | cb[5] << 8 | cb[6] << 16 | cb[7] << 24;
-        const uint32_t want = op == 0 ? lo_w : is_mul ? hi_w : (op == 4 || op == 5) ? q : rm;
-        if (want != res) atomicOr(err, 8u);   // the executor's result is not the op's
-        row[D_SEL + op] = 1;
-        row[D_MULT] = 1;
-        row[D_OP] = op;
-        row[D_A_LO] = a & 0xffffu;
-        row[D_A_HI] = a >> 16;
-        row[D_B_LO] = b & 0xffffu;
-        row[D_B_HI] = b >> 16;
-        row[D_R_LO] = res & 0xffffu;
-        row[D_R_HI] = res >> 16;
-        const uint32_t sgn[4] = {x >> 31, b >> 31, z >> 31, sc}, ext[4] = {ex, ey, ez, ec},
-                       top[4] = {xe[3], ye[3], ze[3], cb[3]};
-        for (unsigned j = 0; j < 4; j++) {
-            row[D_S + j] = sgn[j];
-            row[D_L + j] = (2 * top[j]) & 255u;
-            row[D_E + j] = ext[j];
-        }
-        for (unsigned j = 0; j < 8; j++) row[D_AND + j] = row[MD_PAIRS[j][0]] & row[MD_PAIRS[j][1]];
-        if (!is_mul) {
-            const uint32_t bsum = (b & 0xffffu) + (b >> 16);
-            row[D_BZ] = bz;
-            row[D_BINV] = bsum ? bb::decode(bb::inv(enc(bsum))) : 0u;
-        }
-        if (divs) {
-            uint32_t dev = 2 * (cb[0] + cb[1] + cb[2]) + 2 * (1 - sc) + row[D_L + 3];
-            for (unsigned j = 0; j < 4; j++) dev += 2 * (255u - ye[j]);
-            row[D_OVF] = ovf;
-            row[D_OINV] = dev ? bb::decode(bb::inv(enc(dev))) : 0u;
-        }
-        const uint32_t bm = ey ? 0u - b : b, zm = ez ? 0u - z : z;   // |b|, |r| (two's complement; |-2^31| = 2^31)
-        row[D_BM_LO] = bm & 0xffffu;
-        row[D_BM_HI] = bm >> 16;
-        row[D_KB] = ey && (b & 0xffffu);
-        row[D_RM_LO] = zm & 0xffffu;
-        row[D_RM_HI] = zm >> 16;
-        row[D_KR] = ez && (z & 0xffffu);
-        if (!is_mul && !bz) {   // |r| + 1 + DL = |b|
-            const uint32_t dl = bm - zm - 1;
-            row[D_DL_LO] = dl & 0xffffu;
-            row[D_DL_HI] = dl >> 16;
-            row[D_K0] = ((zm & 0xffffu) + 1 + (dl & 0xffffu)) >> 16;
-        }
-    }
-    for (unsigned c : MD_RANGE) hist_add(hist, row[c], on);
-    for (unsigned j = 0; j < 4; j++) hist_add(shift_mult, 256u + row[D_X + 3 + 4 * j], on);   // (1, top byte) -> row 256 + x
-    // AND (op 1) of each byte pair; the wave-aggregated add, as M loops repeat their operands
-    for (unsigned j = 0; j < 8; j++) hist_add(byte_mult, row[MD_PAIRS[j][0]] << 8 | row[MD_PAIRS[j][1]], on);
-    for (unsigned c = 0; c < MD_W; c++) row[c] = enc(row[c]);
-    __syncthreads();
-    flush_rows<MD_W>(out, s_rows, (size_t)blockIdx.x * blockDim.x, n_rows);
-}
-
-}  // namespace rv32
-
-static size_t rv32_program_rows(const rk_exec* ex, uint32_t index, uint32_t* n_slots) {
-    const auto& pr = ex->pc_range[index];
-    const uint32_t slots = ex->traces[index].empty() ? 0 : (pr[1] - pr[0]) / 4 + 1;
-    size_t rows = 2;
-    while (rows < slots) rows <<= 1;
-    if (n_slots) *n_slots = slots;
-    return rows;
-}
-
-// the rows of a segment's trace with M_W = 1 (an M word writing a register other than x0): its muldiv rows
-static size_t rv32im_count(const rk_exec* ex, uint32_t index) {
-    size_t c = 0;   // decode(ins).is_m && decode(ins).wr: opcode OP, funct7 = 1, rd != 0
-    for (const TraceRow& r : ex->traces[index]) c += (r.ins & 0xfe00007fu) == 0x02000033u && (r.ins & 0xf80u);
-    return c;
-}
-
-static size_t rv32im_muldiv_rows(size_t count) {
-    size_t rows = (size_t)1 << RK_RV32IM_MULDIV_MIN_LOG_ROWS;
-    while (rows < count) rows <<= 1;
-    return rows;
-}
-
-// CS_CF: the rv32i-cf tables (d_shift the sixth); CS_IM: the rv32im tables (d_muldiv the seventh, muldiv_rows rows);
-// CS_I: rv32i's five
-template <int CS>
-static int rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
-                             size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
-                             uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows) {
-    using namespace rv32;
-    constexpr bool CF = CS != CS_I, IM = CS == CS_IM;
-    if (!ctx || !ex || !d_cpu || !d_program || !d_register || !d_byte || !d_range || (CF && !d_shift) || (IM && !d_muldiv) ||
-        index >= ex->segments.size() || index >= ex->traces.size())
-        return RK_ERR_INVALID;
-    const rk_exec_segment& seg = ex->segments[index];
-    const std::vector<TraceRow>& tr = ex->traces[index];
-    const auto& ec = ex->ecalls[index];
-    const size_t n = (size_t)1 << seg.po2, nb = n / TB;
-    if (tr.size() != seg.cycles || tr.size() > n || n % TB) return RK_ERR_INTERNAL;
-    uint32_t n_slots = 0;
-    if (rv32_program_rows(ex, index, &n_slots) != program_rows) return RK_ERR_CAPACITY;
-    if (n_slots > (1u << 22)) {
-        ctx->last_error = "rk_exec_rv32_shard_device: executed pc range wider than 2^22 words";
-        return RK_ERR_CAPACITY;
-    }
-    const size_t m_count = IM ? rv32im_count(ex, index) : 0;
-    if (IM) {   // a power of two that holds every muldiv row, no taller than the cpu table; nothing is written otherwise
-        if (muldiv_rows < rv32im_muldiv_rows(m_count)) {
-            ctx->last_error = "rk_exec_rv32im_shard_device: the muldiv table has fewer rows than the segment needs";
-            return RK_ERR_CAPACITY;
-        }
-        if (muldiv_rows & (muldiv_rows - 1) || muldiv_rows > std::max<size_t>(n, rv32im_muldiv_rows(0))) return RK_ERR_INVALID;
-    }
-    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // scratch, in one allocation: trace | ecalls | wval | acc | blk | final_ts | fin | init | err | hist | byte | prog mult / ins
-    // | shift counts | rv32im: M flags | block counts | total | muldiv row -> cpu row
-    const size_t w_tr = (std::max<size_t>(tr.size(), 1) * sizeof(TraceRow) + 3) / 4, w_ec = 2 * std::max<size_t>(ec.size(), 1);
-    size_t off[18], at = 0;
-    const size_t words[18] = {w_tr, w_ec, n, n, nb * 32, 32, 32, 32, 1, (size_t)1 << 16, (size_t)3 << 16,
-                              std::max<uint32_t>(n_slots, 1), std::max<uint32_t>(n_slots, 1), CF ? SHIFT_USED : 1u,
-                              IM ? n : 1, IM ? nb : 1, 1, std::max<size_t>(m_count, 1)};
-    for (int k = 0; k < 18; k++) off[k] = at, at += (words[k] + 63) & ~(size_t)63;
-    void* base = nullptr;
-    RK_TRY(rk::dev_alloc(ctx, at * 4, &base));
-    uint32_t* w = (uint32_t*)base;
-    const TraceRow* d_tr = (const TraceRow*)(w + off[0]);
-    uint32_t *d_ec = w + off[1], *wval = w + off[2], *acc = w + off[3], *blk = w + off[4], *final_ts = w + off[5],
-             *fin = w + off[6], *init = w + off[7], *err = w + off[8], *hist = w + off[9], *bmult = w + off[10],
-             *pmult = w + off[11], *pins = w + off[12], *smult = w + off[13], *mflag = w + off[14], *mblk = w + off[15],
-             *mtotal = w + off[16], *midx = w + off[17];
-    std::vector<uint32_t> ec_flat(2 * ec.size());
-    for (size_t k = 0; k < ec.size(); k++) ec_flat[2 * k] = ec[k][0], ec_flat[2 * k + 1] = ec[k][1];
-    uint32_t host_fin[34] = {0};
-    int st = RK_OK;
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && st == RK_OK) {
-            ctx->last_error = std::string("rk_exec_rv32_shard_device ") + what + ": " + hipGetErrorString(e);
-            st = RK_ERR_HIP;
-        }
-    };
-    auto launched = [&](const char* what) {
-        if (st == RK_OK) st = rk::post_launch(ctx, what);
-    };
-    if (!tr.empty()) hip(hipMemcpyAsync((void*)d_tr, tr.data(), tr.size() * sizeof(TraceRow), hipMemcpyHostToDevice, ctx->stream), "h2d");
-    if (!ec.empty()) hip(hipMemcpyAsync(d_ec, ec_flat.data(), ec_flat.size() * 4, hipMemcpyHostToDevice, ctx->stream), "h2d");
-    hip(hipMemcpyAsync(init, ex->regs[index].data(), 32 * 4, hipMemcpyHostToDevice, ctx->stream), "h2d");
-    hip(hipMemsetAsync(err, 0, (off[13] + words[13] - off[8]) * 4, ctx->stream), "memset");   // err .. shift counts
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, d_ec,
-                           (uint32_t)ec.size(), ex->pc_range[index][0], n_slots, wval, acc, pmult, pins, err,
-                           IM ? mflag : nullptr);
-        launched("rv32 prep_kernel");
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(block_last_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, acc, blk);
-        launched("rv32 block_last_kernel");
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, final_ts);
-        launched("rv32 scan_kernel");
-    }
-    if (st == RK_OK) {
-        const size_t lds = TB * ((IM ? IM_CPU_W : CF ? CF_CPU_W : CPU_W) | 1) * 4;
-        if (lds > 64 * 1024)   // rv32im's 133-word rows: past the default dynamic LDS limit (160 KiB per CU)
-            hip(hipFuncSetAttribute((const void*)rows_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "lds");
-        if (st == RK_OK)
-            hipLaunchKernelGGL(rows_kernel<CS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), seg.end_pc, acc,
-                               wval, blk, init, d_cpu, hist, bmult, smult, n);
-        launched("rv32 rows_kernel");
-    }
-    if (IM && st == RK_OK) {   // the muldiv rows: count per block, scan, compact, then one lane per row (before the
-                               // byte / range / shift tables: its counts go into theirs)
-        hipLaunchKernelGGL(mcount_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk);
-        launched("rv32 mcount_kernel");
-        if (st == RK_OK) {
-            hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, mblk, nb, mtotal);
-            launched("rv32 mscan_kernel");
-        }
-        if (st == RK_OK) {
-            hipLaunchKernelGGL(mcompact_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk, m_count, midx);
-            launched("rv32 mcompact_kernel");
-        }
-        if (st == RK_OK) {
-            const unsigned b = (unsigned)std::min<size_t>(muldiv_rows, TB);
-            hipLaunchKernelGGL(muldiv_kernel, dim3((unsigned)(muldiv_rows / b)), dim3(b), b * (MD_W | 1) * 4, ctx->stream, d_tr,
-                               tr.size(), wval, midx, m_count, muldiv_rows, d_muldiv, hist, bmult, smult, err);
-            launched("rv32 muldiv_kernel");
-        }
-    }
-    if (st == RK_OK) {
-        const unsigned b = (unsigned)std::min<size_t>(program_rows, TB);
-        hipLaunchKernelGGL(program_kernel<CS>, dim3((unsigned)((program_rows + b - 1) / b)), dim3(b),
-                           b * ((IM ? IM_PROG_W : CF ? CF_PROG_W : PROG_W) | 1) * 4, ctx->stream, pins, pmult, n_slots, ex->pc_range[index][0],
-                           program_rows, d_program);
-        launched("rv32 program_kernel");
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(byte_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4,
-                           ctx->stream, bmult, d_byte);
-        launched("rv32 byte_kernel");
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(range_kernel, dim3((1u << 16) / TB), dim3(TB), 0, ctx->stream, hist, d_range);
-        launched("rv32 range_kernel");
-    }
-    if (st == RK_OK) {
-        hipLaunchKernelGGL(register_kernel, dim3(1), dim3(32), 32 * (REG_W | 1) * 4, ctx->stream, final_ts, init, d_tr,
-                           wval, fin, d_register);
-        launched("rv32 register_kernel");
-    }
-    if (CF && st == RK_OK) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
-        hipLaunchKernelGGL(shift_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4,
-                           ctx->stream, smult, d_shift);
-        launched("rv32 shift_kernel");
-    }
-    // the tables are complete and the scratch can go: read back the final registers and the error flags
-    hip(hipMemcpyAsync(host_fin, fin, 32 * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
-    hip(hipMemcpyAsync(host_fin + 32, err, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
-    if (IM) hip(hipMemcpyAsync(host_fin + 33, mtotal, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
-    hip(hipStreamSynchronize(ctx->stream), "sync");
-    rk::dev_free(ctx, base);
-    if (st != RK_OK) return st;
-    if (host_fin[32] & 7) {
-        ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
-                                           : "rk_exec_rv32_shard_device: trace and side list disagree";
-        return RK_ERR_INVALID;
-    }
-    if (IM && (host_fin[32] || host_fin[33] != m_count)) {
-        ctx->last_error = "rk_exec_rv32im_shard_device: an M result or the muldiv row count is not the executor's";
-        return RK_ERR_INTERNAL;
-    }
-    if (!std::equal(host_fin, host_fin + 32, ex->regs[index].begin() + 32)) {
-        ctx->last_error = "rk_exec_rv32_shard_device: the register accesses do not end in the executor's registers";
-        return RK_ERR_INTERNAL;
-    }
-    return RK_OK;
-}
-
-extern "C" {
-
 int rk_exec_registers(const rk_exec* ex, uint32_t index, uint32_t* start, uint32_t* end) {
     if (!ex || !start || !end || index >= ex->regs.size()) return RK_ERR_INVALID;
     std::copy(ex->regs[index].begin(), ex->regs[index].begin() + 32, start);
@@ -1583,43 +599,6 @@ int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capa
     if (ec.size() > capacity || (!out && !ec.empty())) return RK_ERR_CAPACITY;
     for (size_t k = 0; k < ec.size(); k++) out[2 * k] = ec[k][0], out[2 * k + 1] = ec[k][1];
     return RK_OK;
-}
-int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows) {
-    RK_GUARD_BEGIN
-    if (!ex || !program_rows || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
-    *program_rows = rv32_program_rows(ex, index, nullptr);
-    return RK_OK;
-    RK_GUARD_END
-}
-int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
-                              size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range) {
-    RK_GUARD_BEGIN
-    return rv32_shard_device<rv32::CS_I>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, nullptr,
-                                         nullptr, 0);
-    RK_GUARD_END
-}
-int rk_exec_rv32cf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
-                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
-                                uint32_t* d_shift) {
-    RK_GUARD_BEGIN
-    return rv32_shard_device<rv32::CS_CF>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
-                                          nullptr, 0);
-    RK_GUARD_END
-}
-int rk_exec_rv32im_sizes(const rk_exec* ex, uint32_t index, size_t* muldiv_rows) {
-    RK_GUARD_BEGIN
-    if (!ex || !muldiv_rows || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
-    *muldiv_rows = rv32im_muldiv_rows(rv32im_count(ex, index));
-    return RK_OK;
-    RK_GUARD_END
-}
-int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
-                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
-                                uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows) {
-    RK_GUARD_BEGIN
-    return rv32_shard_device<rv32::CS_IM>(ctx, ex, index, d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
-                                          d_muldiv, muldiv_rows);
-    RK_GUARD_END
 }
 
 }  // extern "C"

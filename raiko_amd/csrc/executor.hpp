@@ -1,0 +1,26 @@
+// What the executor (executor.cpp) records of a segment, as the witness generators read it (rv32_shards.hip, and
+// rk_exec_witness / rk_exec_lookup_tables in executor.cpp itself).  The executor's own state stays private to it.
+#pragma once
+#include <array>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/raiko_hip.h"
+
+// one executed cycle as the witness generator needs it
+struct TraceRow {
+    uint32_t pc, ins, a, b, res, next, wr;
+};
+
+// read-only view of one segment recorded with rk_exec_opts.record_trace; valid while the rk_exec lives
+struct ExecSegmentView {
+    const rk_exec_segment* seg;
+    const std::vector<TraceRow>* trace;                   // seg->cycles rows
+    const uint32_t* regs;                                 // x0..x31 at the segment's start, then at its end
+    const std::vector<std::array<uint32_t, 2>>* ecalls;   // (cycle, a0 after the call) of every ecall row, in cycle order
+    uint32_t pc_lo, pc_hi;                                // the lowest / highest pc executed
+};
+
+// RK_ERR_INVALID: no executor, or no recorded segment `index`; RK_ERR_INTERNAL: the trace is not seg->cycles rows long.
+// Not part of the library's ABI.
+__attribute__((visibility("hidden"))) int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out);

@@ -1,0 +1,461 @@
+// The rows of the rv32 chip sets' tables (rv32i, rv32i-cf, rv32im) as lane bodies: one call fills one row with canonical
+// values, on the GPU (rv32_shards.hip: one lane per row, staged in LDS) and under plain g++ (tests/emul/emul_rv32_rows.cpp
+// walks a trace through them against numpy).  raiko_amd/rv32.py, rv32cf.py and rv32im.py are the same in numpy and name
+// every column; each chip set's rows are the previous one's with columns appended, so each row comes in pieces.
+#pragma once
+#include <type_traits>
+
+#include "bb.hpp"
+#include "executor.hpp"
+
+namespace rv32 {
+
+constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_W = RK_RV32_REGISTER_COLS,
+                   BYTE_W = RK_RV32_BYTE_COLS, CF_CPU_W = RK_RV32CF_CPU_COLS, CF_PROG_W = RK_RV32CF_PROGRAM_COLS,
+                   SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256, IM_CPU_W = RK_RV32IM_CPU_COLS,
+                   IM_PROG_W = RK_RV32IM_PROGRAM_COLS, MD_W = RK_RV32IM_MULDIV_COLS;
+// the chip set a kernel writes, and what its rows are made of
+enum ChipSet : int { CS_I, CS_CF, CS_IM };
+template <int CS>
+struct Chips {
+    static constexpr bool cf = CS != CS_I, im = CS == CS_IM;
+    static constexpr unsigned cpu_w = im ? IM_CPU_W : cf ? CF_CPU_W : CPU_W, prog_w = im ? IM_PROG_W : cf ? CF_PROG_W : PROG_W;
+};
+
+// ---- cpu columns
+enum : unsigned {
+    PC_LO, PC_HI, NX_LO, NX_HI, INS_LO, INS_HI, SEQ, CARRY, A_LO, A_HI, B_LO, B_HI, RES_LO, RES_HI, WR, ACTIVE,
+    RS1, RS2, WREG, IMM_LO, IMM_HI, IS_ADD, IS_SUB, IS_SLT, IS_SLTU, IS_BIT, BOP, IS_IMM, IS_LUI, IS_AUIPC, IS_LINK,
+    TSA, TSB, TSW, PA_TS, PB_TS, PW_TS, PW_LO, PW_HI, DA_LO, DA_HI, DB_LO, DB_HI, DW_LO, DW_HI,
+    OB_LO, OB_HI, C0, C1, D_LO, D_HI, SA, SB, SNE, SA_CHK, SB_CHK, BA, BB = BA + 4, BR = BB + 4,
+    // rv32i-cf (raiko_amd/rv32cf.py): the twelve looked-up fields, then the branch, next-pc and shift columns
+    IS_JAL = BR + 4, IS_BEQ, IS_BNE, IS_BLT, IS_BGE, IS_BLTU, IS_BGEU, JIMM_LO, JIMM_HI, IS_SLL, IS_SRL, IS_SRA,
+    IS_BR, TAKEN, BD_LO, BD_HI, BC0, BC1, EQ, INV, M_SA, M_SB, NC0, NC1, DROP, NXH,
+    IS_SHIFT, KB, Q = KB + 3, SK = Q + 4, T, FILL, U_LO, U_HI, V_LO, V_HI, SX, SLO = SX + 4, SHI = SLO + 4,
+    // rv32im (raiko_amd/rv32im.py): the eight M selectors and their sum (looked up), the op, the multiplicity
+    IS_MUL = SHI + 4, IS_M = IS_MUL + 8, MOP, M_W
+};
+static_assert(ACTIVE + 1 == RK_TRACE_DATA_COLS, "the stand-in trace's columns come first");
+static_assert(IS_JAL == CPU_W, "rv32i cpu columns");
+static_assert(SHI + 4 == CF_CPU_W, "rv32i-cf cpu columns");
+static_assert(M_W + 1 == IM_CPU_W, "rv32im cpu columns");
+// ---- program columns: 0 .. P_MULT - 1 what a cpu row looks up (rv32.py PROGRAM_TUPLE), then the decoder's own; rv32i-cf
+// appends its twelve fields at P_EXT, rv32im its nine at P_M and the funct7 test's three partial products at P_F7
+enum : unsigned {
+    P_MULT = 20, P_BITS, P_OPC = P_BITS + 32, P_F3 = P_OPC + 11, P_OPR = P_F3 + 8, P_Z1, P_Z2, P_RDZ, P_RD,
+    P_EXT, P_M = P_EXT + 12, P_F7 = P_M + 9
+};
+static_assert(P_EXT == PROG_W && P_M == CF_PROG_W && P_F7 + 3 == IM_PROG_W, "program columns");
+// ---- register, byte (ops AND = 1, OR = 2, XOR = 3) and shift columns
+enum : unsigned { R_REG, R_ZERO, R_FTS, R_IL, R_IH = R_IL + 32, R_FL = R_IH + 32, R_FH = R_FL + 32 };
+static_assert(R_FH + 32 == REG_W, "register columns");
+enum : unsigned { Y_OP, Y_X, Y_Y, Y_Z, Y_XB, Y_YB = Y_XB + 8, Y_AND = Y_YB + 8, Y_OR, Y_XOR, Y_MULT };
+static_assert(Y_MULT + 1 == BYTE_W, "byte columns");
+enum : unsigned { H_K, H_X, H_LO, H_HI, H_MULT, H_XB, H_KS = H_XB + 8, H_VB = H_KS + 9 };
+static_assert(H_VB + 16 == SHIFT_W, "shift columns");
+// ---- rv32im: the muldiv table (rv32im.py muldiv_witness)
+enum : unsigned {
+    D_SEL, D_MULT = 8, D_OP, D_A_LO, D_A_HI, D_B_LO, D_B_HI, D_R_LO, D_R_HI, D_ONE, D_X, D_Y = D_X + 4, D_Z = D_Y + 4,
+    D_C = D_Z + 4, D_CY = D_C + 8, D_S = D_CY + 8, D_L = D_S + 4, D_E = D_L + 4, D_AND = D_E + 4, D_BZ = D_AND + 8, D_BINV,
+    D_OVF, D_OINV, D_BM_LO, D_BM_HI, D_KB, D_RM_LO, D_RM_HI, D_KR, D_DL_LO, D_DL_HI, D_K0
+};
+static_assert(D_K0 + 1 == MD_W, "rv32im muldiv columns");
+// the byte pairs looked up as ANDs (rv32im.py BYTE_PAIRS), the limbs sent to RANGE16 (RANGE_COLS); the top bytes looked
+// up in the shift table (SIGN_BYTES) are D_X + 3 + 4 j
+constexpr unsigned MD_PAIRS[8][2] = {{D_X, D_X + 1}, {D_X + 2, D_Y}, {D_Y + 1, D_Y + 2}, {D_Z, D_Z + 1}, {D_Z + 2, D_C},
+                                     {D_C + 1, D_C + 2}, {D_C + 4, D_C + 5}, {D_C + 6, D_C + 7}};
+constexpr unsigned MD_RANGE[14] = {D_CY, D_CY + 1, D_CY + 2, D_CY + 3, D_CY + 4, D_CY + 5, D_CY + 6, D_CY + 7,
+                                   D_BM_LO, D_BM_HI, D_RM_LO, D_RM_HI, D_DL_LO, D_DL_HI};
+
+constexpr uint32_t OPCODES[11] = {0x37, 0x17, 0x6f, 0x67, 0x63, 0x03, 0x23, 0x13, 0x33, 0x0f, 0x73};
+enum { O_LUI, O_AUIPC, O_JAL, O_JALR, O_BRANCH, O_LOAD, O_STORE, O_OPIMM, O_OP, O_FENCE, O_SYSTEM };
+
+struct Dec {
+    int opc;   // index into OPCODES, -1 for none
+    uint32_t f3, rd, rs1, rs2, wreg, imm, opr, is_add, is_sub, is_slt, is_sltu, is_bit, bop, is_imm, is_lui, is_auipc,
+        is_link, wr;
+    // rv32i-cf: bsel = the branch (0..5: BEQ BNE BLT BGE BLTU BGEU) or -1; jimm = imm_B of a branch, imm_J of JAL
+    int bsel;
+    uint32_t is_jal, jimm, is_sll, is_srl, is_sra;
+    uint32_t is_m;   // rv32im: an M word (OP, funct7 = 1); its op is f3
+};
+
+RK_HD Dec decode(uint32_t ins) {
+    Dec d{};
+    d.opc = -1;
+    for (int k = 0; k < 11; k++)
+        if ((ins & 0x7fu) == OPCODES[k]) d.opc = k;
+    d.f3 = (ins >> 12) & 7;
+    d.rd = (ins >> 7) & 31;
+    d.rs1 = (ins >> 15) & 31;
+    d.rs2 = (ins >> 20) & 31;
+    const uint32_t b25 = (ins >> 25) & 1, b30 = (ins >> 30) & 1;
+    d.opr = d.opc == O_OP && !b25;
+    const uint32_t opimm = d.opc == O_OPIMM, alu = d.opr | opimm;
+    d.is_add = (d.f3 == 0) && ((d.opr && !b30) || opimm);
+    d.is_sub = d.opr && d.f3 == 0 && b30;
+    d.is_slt = alu && d.f3 == 2;
+    d.is_sltu = alu && d.f3 == 3;
+    d.is_bit = alu && (d.f3 == 4 || d.f3 == 6 || d.f3 == 7);
+    d.bop = !alu ? 0 : d.f3 == 4 ? 3 : d.f3 == 6 ? 2 : d.f3 == 7 ? 1 : 0;
+    d.is_imm = opimm;
+    d.is_lui = d.opc == O_LUI;
+    d.is_auipc = d.opc == O_AUIPC;
+    d.is_link = d.opc == O_JAL || d.opc == O_JALR;
+    if (opimm || d.opc == O_LOAD || d.opc == O_JALR) d.imm = (uint32_t)((int32_t)ins >> 20);
+    else if (d.is_lui || d.is_auipc) d.imm = ins & 0xfffff000u;
+    const bool writes = d.is_lui || d.is_auipc || d.is_link || d.opc == O_LOAD || opimm || d.opc == O_OP;
+    d.wr = (writes && d.rd != 0) || d.opc == O_SYSTEM;
+    d.wreg = d.rd + (d.opc == O_SYSTEM ? 10u : 0u);
+    d.is_jal = d.opc == O_JAL;
+    d.bsel = -1;
+    if (d.opc == O_BRANCH) {
+        d.bsel = d.f3 < 2 ? (int)d.f3 : d.f3 >= 4 ? (int)d.f3 - 2 : -1;
+        const uint32_t b = (ins >> 31) << 12 | ((ins >> 7) & 1) << 11 | ((ins >> 25) & 0x3f) << 5 | ((ins >> 8) & 0xf) << 1;
+        d.jimm = (uint32_t)((int32_t)(b << 19) >> 19);
+    } else if (d.is_jal) {
+        const uint32_t j = (ins >> 31) << 20 | ((ins >> 12) & 0xff) << 12 | ((ins >> 20) & 1) << 11 | ((ins >> 21) & 0x3ff) << 1;
+        d.jimm = (uint32_t)((int32_t)(j << 11) >> 11);
+    }
+    d.is_sll = alu && d.f3 == 1;
+    d.is_srl = alu && d.f3 == 5 && !b30;
+    d.is_sra = alu && d.f3 == 5 && b30;
+    d.is_m = d.opc == O_OP && (ins >> 25) == 1;
+    return d;
+}
+
+// the value a row writes: recomputed for the constrained ops, the side list's for an ecall, TraceRow.res otherwise
+RK_HD uint32_t written(const Dec& d, const TraceRow& r, uint32_t ecall_a0) {
+    const uint32_t a = r.a, ob = d.is_imm ? d.imm : r.b;
+    if (d.is_add) return a + ob;
+    if (d.is_sub) return a - ob;
+    if (d.is_sltu) return a < ob;
+    if (d.is_slt) return (int32_t)a < (int32_t)ob;
+    if (d.is_bit) return d.f3 == 4 ? a ^ ob : d.f3 == 6 ? a | ob : a & ob;
+    if (d.is_lui) return d.imm;
+    if (d.is_auipc) return r.pc + d.imm;
+    if (d.is_link) return r.pc + 4;
+    if (d.opc == O_SYSTEM) return ecall_a0;
+    return r.res;
+}
+
+RK_HD uint32_t enc(uint32_t canon) { return bb::mul(canon, bb::R2); }
+
+// the row past the executed cycles: stay where the segment ended
+RK_HD TraceRow padding_row(uint32_t end_pc) {
+    TraceRow r{};
+    r.pc = r.next = end_pc;
+    return r;
+}
+
+// the 16 cells of the stand-in trace circuit (include/raiko_hip.h), the first 16 of a cpu row: every 32-bit word as two
+// 16-bit limbs; a row past the executed cycles (padding_row) has active = seq = 0
+RK_HD void trace_cells(const TraceRow& r, bool active, uint32_t* c) {
+    const uint32_t lo = r.pc & 0xffffu, carry = (active && lo + 4 > 0xffffu) ? 1u : 0u;
+    const uint32_t seq = (active && r.next == r.pc + 4 && r.pc <= 0xfffffffbu) ? 1u : 0u;   // no wrap of the 32-bit pc
+    c[PC_LO] = lo;
+    c[PC_HI] = r.pc >> 16;
+    c[NX_LO] = r.next & 0xffffu;
+    c[NX_HI] = r.next >> 16;
+    c[INS_LO] = r.ins & 0xffffu;
+    c[INS_HI] = r.ins >> 16;
+    c[SEQ] = seq;
+    c[CARRY] = seq ? carry : 0u;
+    c[A_LO] = r.a & 0xffffu;
+    c[A_HI] = r.a >> 16;
+    c[B_LO] = r.b & 0xffffu;
+    c[B_HI] = r.b >> 16;
+    c[RES_LO] = r.res & 0xffffu;
+    c[RES_HI] = r.res >> 16;
+    c[WR] = r.wr;
+    c[ACTIVE] = active ? 1u : 0u;
+}
+
+// what an executed cpu row adds to the lookup tables' multiplicities beyond its unconditional sends
+struct Mults {
+    uint32_t is_slt = 0, bop = 0, ba = 0, bb = 0;   // SA_CHK / SB_CHK to RANGE16; the BYTE op (0: none) and its operands
+    bool is_br = false, is_link = false, is_shift = false, m_sa = false, m_sb = false;   // rv32i-cf
+};
+
+// ---- the cpu row of an executed cycle; `row` is zero on entry.  res: the value the row writes (written); tsa: its first
+// timestamp, 3 i + 1; pa / pb / pw: the timestamps of the accesses before its three (pw 0 without a write), pwv: the
+// value the written register held
+RK_HD void cpu_row_i(uint32_t* row, const TraceRow& r, const Dec& d, uint32_t res, uint32_t tsa, uint32_t pa, uint32_t pb,
+                     uint32_t pw, uint32_t pwv, Mults& m) {
+    const uint32_t ob = d.is_imm ? d.imm : r.b;
+    const bool sublt = d.is_sub || d.is_slt || d.is_sltu;
+    const uint32_t dd = sublt ? r.a - ob : 0;
+    uint32_t x = 0, y = 0;
+    if (d.is_add) x = r.a, y = ob;
+    else if (d.is_auipc) x = r.pc, y = d.imm;
+    else if (d.is_link) x = r.pc, y = 4;
+    else if (sublt) x = dd, y = ob;
+    const uint32_t c0 = ((x & 0xffffu) + (y & 0xffffu)) >> 16, c1 = ((x >> 16) + (y >> 16) + c0) >> 16;
+    const uint32_t sa = r.a >> 31, sb = ob >> 31;
+    const uint32_t da = tsa - pa - 1, db = tsa + 1 - pb - 1, dw = d.wr ? tsa + 2 - pw - 1 : 0;
+    trace_cells(r, true, row);
+    const uint32_t vals[][2] = {
+        {RES_LO, res & 0xffffu}, {RES_HI, res >> 16}, {WR, d.wr},
+        {RS1, d.rs1}, {RS2, d.rs2}, {WREG, d.wreg}, {IMM_LO, d.imm & 0xffffu}, {IMM_HI, d.imm >> 16},
+        {IS_ADD, d.is_add}, {IS_SUB, d.is_sub}, {IS_SLT, d.is_slt}, {IS_SLTU, d.is_sltu}, {IS_BIT, d.is_bit},
+        {BOP, d.bop}, {IS_IMM, d.is_imm}, {IS_LUI, d.is_lui}, {IS_AUIPC, d.is_auipc}, {IS_LINK, d.is_link},
+        {PA_TS, pa}, {PB_TS, pb}, {PW_TS, pw}, {PW_LO, pwv & 0xffffu}, {PW_HI, pwv >> 16},
+        {DA_LO, da & 0x3fffu}, {DA_HI, da >> 14}, {DB_LO, db & 0x3fffu}, {DB_HI, db >> 14},
+        {DW_LO, dw & 0x3fffu}, {DW_HI, dw >> 14}, {OB_LO, ob & 0xffffu}, {OB_HI, ob >> 16}, {C0, c0}, {C1, c1},
+        {D_LO, dd & 0xffffu}, {D_HI, dd >> 16}, {SA, sa}, {SB, sb}, {SNE, sa ^ sb},
+        {SA_CHK, 2 * (r.a >> 16) - 65536 * sa}, {SB_CHK, 2 * (ob >> 16) - 65536 * sb}};
+    for (const auto& kv : vals) row[kv[0]] = kv[1];
+    m.is_slt = d.is_slt;
+    if (d.is_bit) {
+        m.bop = d.bop;
+        m.ba = r.a;
+        m.bb = ob;
+        for (unsigned k = 0; k < 4; k++) {
+            row[BA + k] = (r.a >> (8 * k)) & 255;
+            row[BB + k] = (ob >> (8 * k)) & 255;
+            row[BR + k] = (res >> (8 * k)) & 255;
+        }
+    }
+}
+
+// rv32i-cf (rv32cf.py cpu_rows): the branch decision, the next pc and the shift columns
+RK_HD void cpu_row_cf(uint32_t* row, const TraceRow& r, const Dec& d, Mults& m) {
+    const uint32_t a = r.a, b = r.b;
+    // branch decision
+    m.is_br = d.bsel >= 0;
+    const bool eqv = a == b, ltu = a < b, lts = (int32_t)a < (int32_t)b;
+    const bool cond[6] = {eqv, !eqv, lts, !lts, ltu, !ltu};
+    const bool taken = m.is_br && cond[d.bsel];
+    if (m.is_br) {
+        const uint32_t dd = a - b, z = (dd & 0xffffu) + (dd >> 16);
+        row[IS_BEQ + d.bsel] = 1;
+        row[BD_LO] = dd & 0xffffu;
+        row[BD_HI] = dd >> 16;
+        row[BC0] = (a & 0xffffu) < (b & 0xffffu);
+        row[BC1] = ltu;
+        row[EQ] = eqv;
+        row[INV] = z ? bb::decode(bb::inv(enc(z))) : 0u;
+    }
+    m.m_sb = d.bsel == 2 || d.bsel == 3;
+    m.m_sa = m.m_sb || d.is_sra;
+    row[IS_BR] = m.is_br;
+    row[TAKEN] = taken;
+    row[M_SA] = m.m_sa;
+    row[M_SB] = m.m_sb;
+    // next pc = base + offset (mod 2^32), JALR's low bit dropped
+    const bool jalr = d.opc == O_JALR;
+    m.is_link = d.is_link;
+    const uint32_t base = jalr ? a : r.pc, off = jalr ? d.imm : (taken || d.is_jal) ? d.jimm : 4u;
+    const uint32_t nc0 = ((base & 0xffffu) + (off & 0xffffu)) >> 16, nc1 = ((base >> 16) + (off >> 16) + nc0) >> 16;
+    row[IS_JAL] = d.is_jal;
+    row[JIMM_LO] = d.jimm & 0xffffu;
+    row[JIMM_HI] = d.jimm >> 16;
+    row[NC0] = nc0;
+    row[NC1] = nc1;
+    row[DROP] = jalr ? (base + off) & 1u : 0u;
+    row[NXH] = m.is_link ? (r.next & 0xffffu) >> 1 : 0u;
+    // shifts: s = k + 8 q; the bytes of a' (a, complemented for SRA of a negative a) through the shift table
+    row[IS_SLL] = d.is_sll;
+    row[IS_SRL] = d.is_srl;
+    row[IS_SRA] = d.is_sra;
+    m.is_shift = d.is_sll || d.is_srl || d.is_sra;
+    if (m.is_shift) {
+        const uint32_t amt = d.is_imm ? d.rs2 : b & 31u, k = amt & 7u, q = amt >> 3;
+        const bool fill = d.is_sra && (a >> 31);
+        const uint32_t ap = fill ? ~a : a, sk = d.is_sll ? k : 8u - k;
+        const uint32_t u = d.is_sll ? ap << amt : ap >> amt, v = fill ? ~u : u;
+        row[IS_SHIFT] = 1;
+        for (unsigned bit = 0; bit < 3; bit++) row[KB + bit] = (k >> bit) & 1u;
+        row[Q + q] = 1;
+        row[SK] = sk;
+        row[T] = d.is_imm ? 0u : (b & 0xffffu) >> 5;
+        row[FILL] = fill;
+        row[U_LO] = u & 0xffffu;
+        row[U_HI] = u >> 16;
+        row[V_LO] = v & 0xffffu;
+        row[V_HI] = v >> 16;
+        for (unsigned j = 0; j < 4; j++) {
+            const uint32_t x = (ap >> (8 * j)) & 255u;
+            row[SX + j] = x;
+            row[SLO + j] = (x << sk) & 255u;
+            row[SHI + j] = (x << sk) >> 8;
+        }
+    }
+}
+
+// rv32im (rv32im.py cpu_rows): the M selectors; M_W = 1 sends the row to the muldiv table
+RK_HD void cpu_row_im(uint32_t* row, const Dec& d) {
+    if (d.is_m) {
+        row[IS_MUL + d.f3] = 1;
+        row[IS_M] = 1;
+        row[MOP] = d.f3;
+        row[M_W] = d.wr;
+    }
+}
+
+// ---- the program row of instruction word `ins` at `pc`, executed `mult` times; `row` is zero on entry
+RK_HD void program_row_i(uint32_t* row, uint32_t pc, uint32_t ins, const Dec& d, uint32_t mult) {
+    const uint32_t v[P_MULT] = {pc & 0xffffu, pc >> 16, ins & 0xffffu, ins >> 16, d.rs1, d.rs2, d.wreg, d.imm & 0xffffu,
+                                d.imm >> 16, d.is_add, d.is_sub, d.is_slt, d.is_sltu, d.is_bit, d.bop, d.is_imm,
+                                d.is_lui, d.is_auipc, d.is_link, d.wr};
+    for (unsigned c = 0; c < P_MULT; c++) row[c] = v[c];
+    row[P_MULT] = mult;
+    for (unsigned k = 0; k < 32; k++) row[P_BITS + k] = (ins >> k) & 1;
+    if (d.opc >= 0) {
+        row[P_OPC + d.opc] = 1;
+        row[P_F3 + d.f3] = 1;
+    }
+    const uint32_t b = ins >> 7;
+    const uint32_t z1 = (~b & 1) & (~b >> 1 & 1), z2 = z1 & (~b >> 2 & 1), rdz = z2 & (~b >> 3 & 1) & (~b >> 4 & 1);
+    row[P_OPR] = d.opr;
+    row[P_Z1] = z1;
+    row[P_Z2] = z2;
+    row[P_RDZ] = rdz;
+    row[P_RD] = d.rd;
+}
+
+// rv32i-cf: the twelve fields the cf cpu row looks up
+RK_HD void program_row_cf(uint32_t* row, const Dec& d) {
+    uint32_t* e = row + P_EXT - IS_JAL;     // e[c]: the field of cpu column c
+    e[IS_JAL] = d.is_jal;
+    if (d.bsel >= 0) e[IS_BEQ + d.bsel] = 1;
+    e[JIMM_LO] = d.jimm & 0xffffu;
+    e[JIMM_HI] = d.jimm >> 16;
+    e[IS_SLL] = d.is_sll;
+    e[IS_SRL] = d.is_srl;
+    e[IS_SRA] = d.is_sra;
+}
+
+// rv32im: IS_MUL .. IS_REMU and IS_M, then the funct7 test's partial products op b25 !b26, !b27 !b28, !b29 !b30
+RK_HD void program_row_im(uint32_t* row, uint32_t ins, const Dec& d) {
+    const auto nb = [&](unsigned k) { return ((ins >> k) & 1u) ^ 1u; };
+    const uint32_t f7a = (d.opc == O_OP) & (ins >> 25) & 1u & nb(26), f7b = f7a & nb(27) & nb(28), f7c = f7b & nb(29) & nb(30);
+    if (d.is_m) row[P_M + d.f3] = 1;
+    row[P_M + IS_M - IS_MUL] = d.is_m;
+    row[P_F7] = f7a;
+    row[P_F7 + 1] = f7b;
+    row[P_F7 + 2] = f7c;
+}
+
+// ---- row r of the rv32i-cf shift table (rv32cf.py shift_rows): row k 256 + x = (k, x, x 2^k mod 256, x 2^k / 256, count,
+// bits of x, k one-hot, bits of x 2^k); rows past 9 x 256 the true tuple (0, 0, 0, 0) with count 0
+RK_HD void shift_row(uint32_t* row, size_t r, uint32_t mult) {
+    const uint32_t k = r < SHIFT_USED ? (uint32_t)(r >> 8) : 0u, x = r < SHIFT_USED ? (uint32_t)(r & 255) : 0u, v = x << k;
+    row[H_K] = k;
+    row[H_X] = x;
+    row[H_LO] = v & 255u;
+    row[H_HI] = v >> 8;
+    row[H_MULT] = mult;
+    for (unsigned bit = 0; bit < 8; bit++) row[H_XB + bit] = (x >> bit) & 1u;
+    row[H_KS + k] = 1;
+    for (unsigned bit = 0; bit < 16; bit++) row[H_VB + bit] = (v >> bit) & 1u;
+}
+
+// ---- row r < 3 x 2^16 of the byte table (rv32.py byte_rows): (op, x, y) = (r >> 16) + 1, byte 1 of r, byte 0 of r
+RK_HD void byte_row(uint32_t* row, size_t r, uint32_t mult) {
+    const uint32_t op = (uint32_t)(r >> 16) + 1, x = (r >> 8) & 255, y = r & 255;
+    row[Y_OP] = op;
+    row[Y_X] = x;
+    row[Y_Y] = y;
+    row[Y_Z] = op == 1 ? (x & y) : op == 2 ? (x | y) : (x ^ y);
+    for (unsigned k = 0; k < 8; k++) {
+        row[Y_XB + k] = (x >> k) & 1;
+        row[Y_YB + k] = (y >> k) & 1;
+    }
+    row[Y_AND + op - 1] = 1;
+    row[Y_MULT] = mult;
+}
+
+// ---- row r of the register table (rv32.py register_rows): init / fin are the 32 registers at the shard's start and end
+RK_HD void register_row(uint32_t* row, unsigned r, uint32_t final_ts, const uint32_t* init, const uint32_t* fin) {
+    row[R_REG] = r;
+    row[R_ZERO] = 0;
+    row[R_FTS] = final_ts;
+    for (unsigned j = 0; j < 32; j++) {
+        const bool in = r + j < 32;
+        row[R_IL + j] = in ? init[r + j] & 0xffffu : 0;
+        row[R_IH + j] = in ? init[r + j] >> 16 : 0;
+        row[R_FL + j] = in ? fin[r + j] & 0xffffu : 0;
+        row[R_FH + j] = in ? fin[r + j] >> 16 : 0;
+    }
+}
+
+// ---- the muldiv row of M cycle r writing res: the witness of the op on its 32-bit operands (64-bit products and the
+// division's quotient / remainder, the executor's conventions); `row` is zero on entry but for D_ONE.  -> whether res is
+// the op's result
+RK_HD bool muldiv_row(uint32_t* row, const TraceRow& r, uint32_t res) {
+    const uint32_t op = (r.ins >> 12) & 7, a = r.a, b = r.b;
+    const bool is_mul = op < 4, divs = op == 4 || op == 6, bz = b == 0, ovf = divs && a == 0x80000000u && b == 0xffffffffu;
+    const bool sgn_x = op == 1 || op == 2 || divs, sgn_y = op == 1 || divs;
+    uint32_t q, rm;
+    if (bz) q = 0xffffffffu, rm = a;
+    else if (ovf) q = 0x80000000u, rm = 0;
+    else if (divs) q = (uint32_t)((int32_t)a / (int32_t)b), rm = (uint32_t)((int32_t)a % (int32_t)b);
+    else q = a / b, rm = a % b;
+    const uint32_t x = is_mul ? a : q, z = is_mul ? 0u : rm;
+    uint32_t xe[8], ye[8], ze[8], cb[8];
+    const uint32_t ex = sgn_x && (x >> 31), ey = sgn_y && (b >> 31), ez = divs && (z >> 31);
+    for (unsigned j = 0; j < 4; j++) {
+        xe[j] = (x >> (8 * j)) & 255u, ye[j] = (b >> (8 * j)) & 255u, ze[j] = (z >> (8 * j)) & 255u;
+        xe[j + 4] = 255u * ex, ye[j + 4] = 255u * ey, ze[j + 4] = 255u * ez;
+        row[D_X + j] = xe[j];
+        row[D_Y + j] = ye[j];
+        row[D_Z + j] = ze[j];
+    }
+    uint32_t carry = 0;   // < 8 * 255^2 + 255 + carry < 2^20: no overflow
+    for (unsigned c = 0; c < 8; c++) {
+        uint32_t acc = ze[c] + carry;
+        for (unsigned j = 0; j <= c; j++) acc += xe[j] * ye[c - j];
+        cb[c] = acc & 255u;
+        carry = acc >> 8;
+        row[D_C + c] = cb[c];
+        row[D_CY + c] = carry;
+    }
+    const uint32_t sc = cb[3] >> 7, ec = divs && sc;
+    const uint32_t lo_w = cb[0] | cb[1] << 8 | cb[2] << 16 | cb[3] << 24, hi_w = cb[4] | cb[5] << 8 | cb[6] << 16 | cb[7] << 24;
+    const uint32_t want = op == 0 ? lo_w : is_mul ? hi_w : (op == 4 || op == 5) ? q : rm;
+    row[D_SEL + op] = 1;
+    row[D_MULT] = 1;
+    row[D_OP] = op;
+    row[D_A_LO] = a & 0xffffu;
+    row[D_A_HI] = a >> 16;
+    row[D_B_LO] = b & 0xffffu;
+    row[D_B_HI] = b >> 16;
+    row[D_R_LO] = res & 0xffffu;
+    row[D_R_HI] = res >> 16;
+    const uint32_t sgn[4] = {x >> 31, b >> 31, z >> 31, sc}, ext[4] = {ex, ey, ez, ec},
+                   top[4] = {xe[3], ye[3], ze[3], cb[3]};
+    for (unsigned j = 0; j < 4; j++) {
+        row[D_S + j] = sgn[j];
+        row[D_L + j] = (2 * top[j]) & 255u;
+        row[D_E + j] = ext[j];
+    }
+    for (unsigned j = 0; j < 8; j++) row[D_AND + j] = row[MD_PAIRS[j][0]] & row[MD_PAIRS[j][1]];
+    if (!is_mul) {
+        const uint32_t bsum = (b & 0xffffu) + (b >> 16);
+        row[D_BZ] = bz;
+        row[D_BINV] = bsum ? bb::decode(bb::inv(enc(bsum))) : 0u;
+    }
+    if (divs) {
+        uint32_t dev = 2 * (cb[0] + cb[1] + cb[2]) + 2 * (1 - sc) + row[D_L + 3];
+        for (unsigned j = 0; j < 4; j++) dev += 2 * (255u - ye[j]);
+        row[D_OVF] = ovf;
+        row[D_OINV] = dev ? bb::decode(bb::inv(enc(dev))) : 0u;
+    }
+    const uint32_t bm = ey ? 0u - b : b, zm = ez ? 0u - z : z;   // |b|, |r| (two's complement; |-2^31| = 2^31)
+    row[D_BM_LO] = bm & 0xffffu;
+    row[D_BM_HI] = bm >> 16;
+    row[D_KB] = ey && (b & 0xffffu);
+    row[D_RM_LO] = zm & 0xffffu;
+    row[D_RM_HI] = zm >> 16;
+    row[D_KR] = ez && (z & 0xffffu);
+    if (!is_mul && !bz) {   // |r| + 1 + DL = |b|
+        const uint32_t dl = bm - zm - 1;
+        row[D_DL_LO] = dl & 0xffffu;
+        row[D_DL_HI] = dl >> 16;
+        row[D_K0] = ((zm & 0xffffu) + 1 + (dl & 0xffffu)) >> 16;
+    }
+    return want == res;
+}
+
+}  // namespace rv32

@@ -1,0 +1,647 @@
+// The witness of an executed segment written on the GPU (include/raiko_hip.h): the stand-in trace circuit's columns
+// (rk_exec_witness_device*) and the tables of the three rv32 chip sets (rk_exec_rv32_shard_device,
+// rk_exec_rv32cf_shard_device, rk_exec_rv32im_shard_device).  The segment is read through executor.hpp's view; what a
+// row holds is rv32_rows.hpp's lane bodies (raiko_amd/rv32.py, rv32cf.py, rv32im.py are the same in numpy and name every
+// column).  What is here: the kernels around those bodies -- the wave-level code, the atomics, the LDS staging -- and
+// the host driver.
+#include "internal.hpp"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "rv32_rows.hpp"
+
+// The stand-in trace's columns: one lane per row, the trace rows (28 bytes per cycle) are the only upload -- 2.5x less
+// over PCIe than the 18 finished columns and none of the host's time (rk_exec_witness_device).
+__global__ void exec_witness_kernel(uint32_t* __restrict__ code, uint32_t* __restrict__ data, const TraceRow* __restrict__ tr,
+                                    size_t cycles, size_t n, uint32_t end_pc, uint32_t rows_only) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool active = i < cycles;
+    // rows_only: the 16 data columns as one row-major row per lane (64 contiguous bytes: an rk_p3_table), no code columns
+    auto put = [&](uint32_t* base, unsigned col, uint32_t canon) {
+        base[rows_only ? i * RK_TRACE_DATA_COLS + col : (size_t)col * n + i] = rv32::enc(canon);
+    };
+    if (!rows_only) {
+        put(code, 0, i == 0 ? 1u : 0u);
+        put(code, 1, i + 1 == n ? 1u : 0u);
+    }
+    uint32_t c[RK_TRACE_DATA_COLS];
+    rv32::trace_cells(active ? tr[i] : rv32::padding_row(end_pc), active, c);
+    for (unsigned col = 0; col < RK_TRACE_DATA_COLS; col++) put(data, col, c[col]);
+}
+
+static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_code, uint32_t* d_data, bool rows_only) {
+    if (!ctx || !d_data) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    const std::vector<TraceRow>& tr = *v.trace;
+    const size_t n = (size_t)1 << v.seg->po2;
+    if (tr.size() > n) return RK_ERR_INTERNAL;
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* d_tr = nullptr;
+    RK_TRY(rk::dev_alloc(ctx, std::max<size_t>(tr.size(), 1) * sizeof(TraceRow), &d_tr));
+    int st = RK_OK;
+    if (!tr.empty()) {
+        // the trace stays valid while `ex` lives, but the caller may free `ex` right after this call: wait for the copy
+        hipError_t e = hipMemcpyAsync(d_tr, tr.data(), tr.size() * sizeof(TraceRow), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("rk_exec_witness_device h2d: ") + hipGetErrorString(e);
+            st = RK_ERR_HIP;
+        }
+    }
+    if (st == RK_OK) {
+        hipLaunchKernelGGL(exec_witness_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_code, d_data,
+                           (const TraceRow*)d_tr, tr.size(), n, v.seg->end_pc, rows_only ? 1u : 0u);
+        st = rk::post_launch(ctx, "exec_witness_kernel");
+    }
+    rk::dev_free(ctx, d_tr);
+    return st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The rv32 chip sets.  Per segment on the GPU: prep (decode, recompute the written value, pack the three accesses, count
+// program hits) -> block_last (last access per register per 128 rows) -> scan (exclusive max-scan of those 32-vectors)
+// -> rows (in-block resolve of each access's predecessor, the cpu row staged through LDS, RANGE16 / BYTE / SHIFT counts)
+// -> rv32im: the muldiv rows -> the program, byte, range, register and shift tables.
+namespace rv32 {
+
+constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 for rv32i-cf / rv32im)
+
+// a histogram bin += 1 for every lane with `on`; the lanes of a wave that agree with its first active lane add once
+__device__ inline void hist_add(uint32_t* h, uint32_t v, bool on) {
+    const uint64_t act = __ballot(on);
+    if (!act) return;
+    const int first = __ffsll((unsigned long long)act) - 1;
+    const uint32_t lv = __shfl(v, first);
+    const uint64_t same = __ballot(on && v == lv);
+    if ((int)(threadIdx.x & 63) == first) atomicAdd(&h[lv], (uint32_t)__popcll(same));
+    else if (on && v != lv) atomicAdd(&h[v], 1u);
+}
+
+// One tile of a row-major table, a row of W words per lane: the lane's row is zeroed in LDS (s_rows: blockDim.x x (W | 1)
+// words; the odd stride avoids bank conflicts), fill(row) writes its canonical cells, every cell goes to Montgomery form
+// and the tile's rows r0 .. of n_rows leave for HBM as whole lines.  Every lane of the block calls it.
+template <unsigned W, class F>
+__device__ __forceinline__ void row_tile(uint32_t* s_rows, uint32_t* out, size_t r0, size_t n_rows, F&& fill) {
+    constexpr unsigned SW = W | 1;
+    uint32_t* row = s_rows + threadIdx.x * SW;
+    for (unsigned c = 0; c < W; c++) row[c] = 0;
+    fill(row);
+    for (unsigned c = 0; c < W; c++) row[c] = enc(row[c]);
+    __syncthreads();
+    const size_t rows = n_rows - r0 < blockDim.x ? n_rows - r0 : blockDim.x;
+    for (size_t k = threadIdx.x; k < rows * W; k += blockDim.x) out[r0 * W + k] = s_rows[(k / W) * SW + k % W];
+}
+
+__global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
+                            uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
+                            uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
+                            uint32_t* __restrict__ err, uint32_t* __restrict__ mflag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i >= cycles) {
+        wval[i] = 0;
+        acc[i] = 0;
+        if (mflag) mflag[i] = 0;
+        return;
+    }
+    const TraceRow r = tr[i];
+    const Dec d = decode(r.ins);
+    if (mflag) mflag[i] = d.is_m && d.wr;   // rv32im: the rows with M_W = 1, one muldiv row each
+    uint32_t a0 = 0;
+    if (d.opc == O_SYSTEM) {   // the side list is in cycle order: binary search
+        uint32_t lo = 0, hi = n_ecalls;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (ecalls[2 * mid] < i) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < n_ecalls && ecalls[2 * lo] == i) a0 = ecalls[2 * lo + 1];
+        else atomicOr(err, 2u);
+    }
+    wval[i] = written(d, r, a0);
+    acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16;
+    const uint32_t slot = (r.pc - pc_base) >> 2;
+    if (slot >= n_slots) {
+        atomicOr(err, 4u);
+        return;
+    }
+    atomicAdd(&prog_mult[slot], 1u);
+    const uint32_t old = atomicCAS(&prog_ins[slot], 0u, r.ins);
+    if (old != 0 && old != r.ins) atomicOr(err, 1u);    // one pc, two instruction words in one shard
+}
+
+__device__ inline void unpack(uint32_t v, uint32_t& rs1, uint32_t& rs2, uint32_t& wreg, bool& wr, bool& active) {
+    rs1 = v & 31;
+    rs2 = (v >> 5) & 31;
+    wreg = (v >> 10) & 31;
+    wr = (v >> 15) & 1;
+    active = (v >> 16) & 1;
+}
+
+__global__ void block_last_kernel(const uint32_t* __restrict__ acc, uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s[32];
+    if (threadIdx.x < 32) s[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    uint32_t rs1, rs2, wreg;
+    bool wr, active;
+    unpack(acc[i], rs1, rs2, wreg, wr, active);
+    if (active) {
+        const uint32_t tsa = (uint32_t)(3 * i + 1);
+        atomicMax(&s[rs1], tsa);
+        atomicMax(&s[rs2], tsa + 1);
+        if (wr) atomicMax(&s[wreg], tsa + 2);
+    }
+    __syncthreads();
+    if (threadIdx.x < 32) blk[(size_t)blockIdx.x * 32 + threadIdx.x] = s[threadIdx.x];
+}
+
+// one workgroup of 1024: lane = register (t & 31) x chunk of blocks (t >> 5); blk becomes its exclusive prefix max
+__global__ void scan_kernel(uint32_t* __restrict__ blk, size_t nb, uint32_t* __restrict__ final_ts) {
+    __shared__ uint32_t cm[32][32];
+    const unsigned r = threadIdx.x & 31, c = threadIdx.x >> 5;
+    const size_t j0 = nb * c / 32, j1 = nb * (c + 1) / 32;
+    uint32_t m = 0;
+    for (size_t j = j0; j < j1; j++) m = max(m, blk[j * 32 + r]);
+    cm[c][r] = m;
+    __syncthreads();
+    uint32_t run = 0;
+    for (unsigned k = 0; k < c; k++) run = max(run, cm[k][r]);
+    for (size_t j = j0; j < j1; j++) {
+        const uint32_t v = blk[j * 32 + r];
+        blk[j * 32 + r] = run;
+        run = max(run, v);
+    }
+    if (c == 31) final_ts[r] = run;
+}
+
+__device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* tr, const uint32_t* wval, const uint32_t* init) {
+    if (ts == 0) return init[reg];
+    const uint32_t j = (ts - 1) / 3, k = (ts - 1) % 3;
+    return k == 0 ? tr[j].a : k == 1 ? tr[j].b : wval[j];
+}
+
+// the cpu table: each access's predecessor from the scans, then the chip set's row pieces and its lookups' counts
+template <int CS>
+__global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ tr, size_t cycles, uint32_t end_pc,
+                                                   const uint32_t* __restrict__ acc, const uint32_t* __restrict__ wval,
+                                                   const uint32_t* __restrict__ pre, const uint32_t* __restrict__ init,
+                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ hist,
+                                                   uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
+                                                   size_t n) {
+    using CH = Chips<CS>;
+    extern __shared__ uint32_t s_rows[];            // TB x (cpu_w | 1)
+    __shared__ uint32_t s_wave[32][TB / 64];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t rs1, rs2, wreg;
+    bool wr, active;
+    unpack(acc[i], rs1, rs2, wreg, wr, active);
+    const uint32_t tsa = (uint32_t)(3 * i + 1);
+    // per register: the latest access among this wave's rows up to this one (inclusive max-scan over the lanes)
+    uint32_t incl[32];
+#pragma unroll
+    for (unsigned r = 0; r < 32; r++) {
+        uint32_t v = 0;
+        if (active) {
+            if (rs1 == r) v = tsa;
+            if (rs2 == r) v = tsa + 1;
+            if (wr && wreg == r) v = tsa + 2;
+        }
+#pragma unroll
+        for (unsigned off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(v, off);
+            if (lane >= off) v = max(v, t);
+        }
+        incl[r] = v;
+        if (lane == 63) s_wave[r][wave] = v;
+    }
+    __syncthreads();
+    uint32_t e1 = 0, e2 = 0, e3 = 0;
+#pragma unroll
+    for (unsigned r = 0; r < 32; r++) {
+        uint32_t ex = __shfl_up(incl[r], 1);
+        if (lane == 0) ex = 0;
+        for (unsigned w = 0; w < wave; w++) ex = max(ex, s_wave[r][w]);
+        ex = max(ex, pre[(size_t)blockIdx.x * 32 + r]);
+        if (rs1 == r) e1 = ex;
+        if (rs2 == r) e2 = ex;
+        if (wreg == r) e3 = ex;
+    }
+    row_tile<CH::cpu_w>(s_rows, out, (size_t)blockIdx.x * TB, n, [&](uint32_t* row) {
+        Mults m;
+        if (active) {
+            const TraceRow r = tr[i];
+            const Dec d = decode(r.ins);
+            const uint32_t pb = rs2 == rs1 ? tsa : e2, pw = wr ? (wreg == rs2 ? tsa + 1 : wreg == rs1 ? tsa : e3) : 0;
+            cpu_row_i(row, r, d, wval[i], tsa, e1, pb, pw, wr ? value_at(pw, wreg, tr, wval, init) : 0, m);
+            if constexpr (CH::cf) cpu_row_cf(row, r, d, m);
+            if constexpr (CH::im) cpu_row_im(row, d);
+        } else {
+            trace_cells(padding_row(end_pc), false, row);
+        }
+        row[TSA] = tsa;
+        row[TSB] = tsa + 1;
+        row[TSW] = tsa + 2;
+        // RANGE16: the limbs the row sends (rv32.py RANGE_SENDS), BYTE: four triples of a bitwise row
+        const unsigned rc[] = {PC_LO, PC_HI, NX_LO, NX_HI, RES_LO, RES_HI, D_LO, D_HI, DA_LO, DA_HI, DB_LO, DB_HI};
+        for (unsigned c : rc) hist_add(hist, row[c], active);
+        hist_add(hist, row[DW_LO], wr);
+        hist_add(hist, row[DW_HI], wr);
+        hist_add(hist, row[SA_CHK], m.is_slt);
+        hist_add(hist, row[SB_CHK], m.is_slt);
+        if (m.bop)
+            for (unsigned k = 0; k < 4; k++)
+                atomicAdd(&byte_mult[(m.bop - 1) << 16 | ((m.ba >> (8 * k)) & 255) << 8 | ((m.bb >> (8 * k)) & 255)], 1u);
+        if constexpr (CH::cf) {   // rv32cf.py RANGE_SENDS past rv32i's, then the four SHIFT lookups (k, x) -> row k 256 + x
+            hist_add(hist, row[BD_LO], m.is_br);
+            hist_add(hist, row[BD_HI], m.is_br);
+            hist_add(hist, row[NXH], m.is_link);
+            hist_add(hist, row[T], m.is_shift);
+            hist_add(hist, row[SA_CHK], m.m_sa);
+            hist_add(hist, row[SB_CHK], m.m_sb);
+            for (unsigned j = 0; j < 4; j++) hist_add(shift_mult, row[SK] << 8 | row[SX + j], m.is_shift);
+        }
+    });
+}
+
+// the program table: one row per word of the executed pc range, then the row of word 0 at pc 0 with multiplicity 0
+template <int CS>
+__global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint32_t* __restrict__ prog_mult,
+                               uint32_t n_slots, uint32_t pc_base, size_t n_rows, uint32_t* __restrict__ out) {
+    using CH = Chips<CS>;
+    extern __shared__ uint32_t s_rows[];
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<CH::prog_w>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+        if (s >= n_rows) return;
+        const bool in = s < n_slots;
+        const uint32_t pc = in ? pc_base + 4 * (uint32_t)s : 0u, ins = in ? prog_ins[s] : 0u;
+        const Dec d = decode(ins);
+        program_row_i(row, pc, ins, d, in ? prog_mult[s] : 0u);
+        if constexpr (CH::cf) program_row_cf(row, d);
+        if constexpr (CH::im) program_row_im(row, ins, d);
+    });
+}
+
+__global__ void shift_kernel(const uint32_t* __restrict__ shift_mult, uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<SHIFT_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32CF_SHIFT_LOG_ROWS,
+                      [&](uint32_t* row) { shift_row(row, r, r < SHIFT_USED ? shift_mult[r] : 0u); });
+}
+
+__global__ void byte_kernel(const uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<BYTE_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32_BYTE_LOG_ROWS, [&](uint32_t* row) {
+        if (r < (3u << 16)) byte_row(row, r, byte_mult[r]);
+    });
+}
+
+__global__ void range_kernel(const uint32_t* __restrict__ hist, uint32_t* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= (1u << 16)) return;
+    out[2 * v] = enc(v);
+    out[2 * v + 1] = enc(hist[v]);
+}
+
+// 32 lanes: the register table; fin gets the final values
+__global__ void register_kernel(const uint32_t* __restrict__ final_ts, const uint32_t* __restrict__ init,
+                                const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval,
+                                uint32_t* __restrict__ fin, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_fin[32];
+    extern __shared__ uint32_t s_rows[];
+    const unsigned r = threadIdx.x;
+    s_fin[r] = value_at(final_ts[r], r, tr, wval, init);
+    fin[r] = s_fin[r];
+    __syncthreads();
+    row_tile<REG_W>(s_rows, out, 0, 32, [&](uint32_t* row) { register_row(row, r, final_ts[r], init, s_fin); });
+}
+
+// ---- rv32im: the muldiv table
+// per block of TB cpu rows: how many have M_W = 1
+__global__ void mcount_kernel(const uint32_t* __restrict__ mflag, uint32_t* __restrict__ mblk) {
+    const int c = __syncthreads_count(mflag[(size_t)blockIdx.x * TB + threadIdx.x] != 0);
+    if (threadIdx.x == 0) mblk[blockIdx.x] = (uint32_t)c;
+}
+
+// one workgroup of 1024: mblk becomes its exclusive prefix sum, total the sum
+__global__ void mscan_kernel(uint32_t* __restrict__ mblk, size_t nb, uint32_t* __restrict__ total) {
+    __shared__ uint32_t part[1024];
+    const unsigned t = threadIdx.x;
+    const size_t j0 = nb * t / 1024, j1 = nb * (t + 1) / 1024;
+    uint32_t sum = 0;
+    for (size_t j = j0; j < j1; j++) sum += mblk[j];
+    part[t] = sum;
+    __syncthreads();
+    for (unsigned off = 1; off < 1024; off <<= 1) {   // inclusive Hillis-Steele scan of the chunk sums
+        const uint32_t v = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    for (size_t j = j0; j < j1; j++) {
+        const uint32_t v = mblk[j];
+        mblk[j] = run;
+        run += v;
+    }
+    if (t == 1023) *total = run;
+}
+
+// the muldiv index of every row with M_W = 1: its block's offset + the flagged rows before it in the block; idx[k] = the
+// cpu row of muldiv row k (k < count)
+__global__ void mcompact_kernel(const uint32_t* __restrict__ mflag, const uint32_t* __restrict__ mblk, size_t count,
+                                uint32_t* __restrict__ idx) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool on = mflag[i] != 0;
+    const uint64_t bal = __ballot(on);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t k = mblk[blockIdx.x] + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+    for (unsigned w = 0; w < wave; w++) k += s_wave[w];
+    if (on && k < count) idx[k] = (uint32_t)i;
+}
+
+// one lane per muldiv row: row k < count is the witness of cpu row idx[k], rows past count padding (ONE = 1, the rest 0);
+// the RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms
+__global__ void muldiv_kernel(const TraceRow* __restrict__ tr, size_t cycles, const uint32_t* __restrict__ wval,
+                              const uint32_t* __restrict__ idx, size_t count, size_t n_rows, uint32_t* __restrict__ out,
+                              uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
+                              uint32_t* __restrict__ err) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<MD_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+        row[D_ONE] = 1;
+        bool on = k < count;
+        const uint32_t i = on ? idx[k] : 0u;
+        if (on && i >= cycles) {   // the device's count is not the host's (reported after the run)
+            atomicOr(err, 16u);
+            on = false;
+        }
+        if (on && !muldiv_row(row, tr[i], wval[i])) atomicOr(err, 8u);   // the executor's result is not the op's
+        for (unsigned c : MD_RANGE) hist_add(hist, row[c], on);
+        for (unsigned j = 0; j < 4; j++) hist_add(shift_mult, 256u + row[D_X + 3 + 4 * j], on);   // (1, top byte) -> row 256 + x
+        // AND (op 1) of each byte pair; the wave-aggregated add, as M loops repeat their operands
+        for (unsigned j = 0; j < 8; j++) hist_add(byte_mult, row[MD_PAIRS[j][0]] << 8 | row[MD_PAIRS[j][1]], on);
+    });
+}
+
+static size_t program_rows_of(const ExecSegmentView& v, uint32_t* n_slots) {
+    const uint32_t slots = v.trace->empty() ? 0 : (v.pc_hi - v.pc_lo) / 4 + 1;
+    size_t rows = 2;
+    while (rows < slots) rows <<= 1;
+    if (n_slots) *n_slots = slots;
+    return rows;
+}
+
+// the rows of a segment's trace with M_W = 1 (an M word writing a register other than x0): its muldiv rows
+static size_t m_count_of(const ExecSegmentView& v) {
+    size_t c = 0;   // decode(ins).is_m && decode(ins).wr: opcode OP, funct7 = 1, rd != 0
+    for (const TraceRow& r : *v.trace) c += (r.ins & 0xfe00007fu) == 0x02000033u && (r.ins & 0xf80u);
+    return c;
+}
+
+static size_t muldiv_rows_for(size_t count) {
+    size_t rows = (size_t)1 << RK_RV32IM_MULDIV_MIN_LOG_ROWS;
+    while (rows < count) rows <<= 1;
+    return rows;
+}
+
+namespace {
+
+// the tables a shard's driver writes: rv32i's five, d_shift the sixth of rv32i-cf, d_muldiv (muldiv_rows rows) the
+// seventh of rv32im
+struct ShardOut {
+    uint32_t *cpu, *program;
+    size_t program_rows;
+    uint32_t *reg, *byte, *range, *shift, *muldiv;
+    size_t muldiv_rows;
+};
+
+// the driver's scratch: one allocation, each part's offset in words from one take(), rounded to 64 words
+struct Scratch {
+    size_t words = 0;
+    size_t take(size_t w) {
+        const size_t at = words;
+        words += (w + 63) & ~(size_t)63;
+        return at;
+    }
+    size_t tr, ec, wval, acc, blk, final_ts, fin, init;
+    size_t err, hist, bmult, pmult, pins, smult, clear_end;   // [err, clear_end): zero before the first kernel
+    size_t mflag, mblk, mtotal, midx;                          // rv32im
+    Scratch(bool cf, bool im, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count) {
+        const size_t nb = n / TB, slots = std::max<uint32_t>(n_slots, 1), sw = cf ? SHIFT_USED : 1u;
+        tr = take((std::max<size_t>(cycles, 1) * sizeof(TraceRow) + 3) / 4);
+        ec = take(2 * std::max<size_t>(n_ecalls, 1));
+        wval = take(n);
+        acc = take(n);
+        blk = take(nb * 32);
+        final_ts = take(32);
+        fin = take(32);
+        init = take(32);
+        err = take(1);
+        hist = take((size_t)1 << 16);
+        bmult = take((size_t)3 << 16);
+        pmult = take(slots);
+        pins = take(slots);
+        smult = take(sw);
+        clear_end = smult + sw;
+        mflag = take(im ? n : 1);
+        mblk = take(im ? nb : 1);
+        mtotal = take(1);
+        midx = take(std::max<size_t>(m_count, 1));
+    }
+};
+
+}  // namespace
+
+// the copies and the launches of one shard, in stream order; returns at the first error
+template <int CS>
+static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& o, const Scratch& L, uint32_t* w,
+                         const std::vector<uint32_t>& ec_flat, uint32_t n_slots, size_t m_count) {
+    using CH = Chips<CS>;
+    const std::vector<TraceRow>& tr = *v.trace;
+    const size_t n = (size_t)1 << v.seg->po2, nb = n / TB;
+    const TraceRow* d_tr = (const TraceRow*)(w + L.tr);
+    uint32_t *wval = w + L.wval, *acc = w + L.acc, *blk = w + L.blk, *final_ts = w + L.final_ts, *init = w + L.init,
+             *err = w + L.err, *hist = w + L.hist, *bmult = w + L.bmult, *pmult = w + L.pmult, *pins = w + L.pins,
+             *smult = w + L.smult, *mflag = w + L.mflag, *mblk = w + L.mblk, *midx = w + L.midx;
+    if (!tr.empty()) RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.tr, tr.data(), tr.size() * sizeof(TraceRow), hipMemcpyHostToDevice, ctx->stream));
+    if (!ec_flat.empty()) RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.ec, ec_flat.data(), ec_flat.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemcpyAsync(init, v.regs, 32 * 4, hipMemcpyHostToDevice, ctx->stream));
+    RK_HIP_TRY(ctx, hipMemsetAsync(err, 0, (L.clear_end - L.err) * 4, ctx->stream));
+    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
+                       (uint32_t)ec_flat.size() / 2, v.pc_lo, n_slots, wval, acc, pmult, pins, err, CH::im ? mflag : nullptr);
+    RK_TRY(rk::post_launch(ctx, "rv32 prep_kernel"));
+    hipLaunchKernelGGL(block_last_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, acc, blk);
+    RK_TRY(rk::post_launch(ctx, "rv32 block_last_kernel"));
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, final_ts);
+    RK_TRY(rk::post_launch(ctx, "rv32 scan_kernel"));
+    const size_t lds = TB * (CH::cpu_w | 1) * 4;
+    if (lds > 64 * 1024)   // rv32im's 133-word rows: past the default dynamic LDS limit (160 KiB per CU)
+        RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)rows_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(rows_kernel<CS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), v.seg->end_pc, acc, wval,
+                       blk, init, o.cpu, hist, bmult, smult, n);
+    RK_TRY(rk::post_launch(ctx, "rv32 rows_kernel"));
+    if (CH::im) {   // the muldiv rows: count per block, scan, compact, then one lane per row (before the byte / range /
+                    // shift tables: its counts go into theirs)
+        hipLaunchKernelGGL(mcount_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk);
+        RK_TRY(rk::post_launch(ctx, "rv32 mcount_kernel"));
+        hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, mblk, nb, w + L.mtotal);
+        RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+        hipLaunchKernelGGL(mcompact_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, mflag, mblk, m_count, midx);
+        RK_TRY(rk::post_launch(ctx, "rv32 mcompact_kernel"));
+        const unsigned b = (unsigned)std::min<size_t>(o.muldiv_rows, TB);
+        hipLaunchKernelGGL(muldiv_kernel, dim3((unsigned)(o.muldiv_rows / b)), dim3(b), b * (MD_W | 1) * 4, ctx->stream, d_tr,
+                           tr.size(), wval, midx, m_count, o.muldiv_rows, o.muldiv, hist, bmult, smult, err);
+        RK_TRY(rk::post_launch(ctx, "rv32 muldiv_kernel"));
+    }
+    const unsigned pb = (unsigned)std::min<size_t>(o.program_rows, TB);
+    hipLaunchKernelGGL(program_kernel<CS>, dim3((unsigned)((o.program_rows + pb - 1) / pb)), dim3(pb), pb * (CH::prog_w | 1) * 4,
+                       ctx->stream, pins, pmult, n_slots, v.pc_lo, o.program_rows, o.program);
+    RK_TRY(rk::post_launch(ctx, "rv32 program_kernel"));
+    hipLaunchKernelGGL(byte_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4, ctx->stream,
+                       bmult, o.byte);
+    RK_TRY(rk::post_launch(ctx, "rv32 byte_kernel"));
+    hipLaunchKernelGGL(range_kernel, dim3((1u << 16) / TB), dim3(TB), 0, ctx->stream, hist, o.range);
+    RK_TRY(rk::post_launch(ctx, "rv32 range_kernel"));
+    hipLaunchKernelGGL(register_kernel, dim3(1), dim3(32), 32 * (REG_W | 1) * 4, ctx->stream, final_ts, init, d_tr, wval,
+                       w + L.fin, o.reg);
+    RK_TRY(rk::post_launch(ctx, "rv32 register_kernel"));
+    if (CH::cf) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
+        hipLaunchKernelGGL(shift_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4,
+                           ctx->stream, smult, o.shift);
+        RK_TRY(rk::post_launch(ctx, "rv32 shift_kernel"));
+    }
+    return RK_OK;
+}
+
+// One shard's tables.  Owns the scratch block and the host staging of the ecall list: whatever shard_enqueue returns, the
+// read-backs are queued and the stream is drained before either goes, so no queued copy outlives its host buffer and the
+// scratch is never returned with work in flight.
+template <int CS>
+static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const ShardOut& o) {
+    using CH = Chips<CS>;
+    if (!ctx || !o.cpu || !o.program || !o.reg || !o.byte || !o.range || (CH::cf && !o.shift) || (CH::im && !o.muldiv))
+        return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    const size_t cycles = v.trace->size(), n = (size_t)1 << v.seg->po2;
+    if (cycles > n || n % TB) return RK_ERR_INTERNAL;
+    uint32_t n_slots = 0;
+    if (program_rows_of(v, &n_slots) != o.program_rows) return RK_ERR_CAPACITY;
+    if (n_slots > (1u << 22)) {
+        ctx->last_error = "rk_exec_rv32_shard_device: executed pc range wider than 2^22 words";
+        return RK_ERR_CAPACITY;
+    }
+    const size_t m_count = CH::im ? m_count_of(v) : 0;
+    if (CH::im) {   // a power of two that holds every muldiv row, no taller than the cpu table; nothing is written otherwise
+        if (o.muldiv_rows < muldiv_rows_for(m_count)) {
+            ctx->last_error = "rk_exec_rv32im_shard_device: the muldiv table has fewer rows than the segment needs";
+            return RK_ERR_CAPACITY;
+        }
+        if (o.muldiv_rows & (o.muldiv_rows - 1) || o.muldiv_rows > std::max<size_t>(n, muldiv_rows_for(0))) return RK_ERR_INVALID;
+    }
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Scratch L(CH::cf, CH::im, cycles, v.ecalls->size(), n, n_slots, m_count);
+    void* base = nullptr;
+    RK_TRY(rk::dev_alloc(ctx, L.words * 4, &base));
+    uint32_t* w = (uint32_t*)base;
+    std::vector<uint32_t> ec_flat(2 * v.ecalls->size());
+    for (size_t k = 0; k < v.ecalls->size(); k++) ec_flat[2 * k] = (*v.ecalls)[k][0], ec_flat[2 * k + 1] = (*v.ecalls)[k][1];
+    int st = shard_enqueue<CS>(ctx, v, o, L, w, ec_flat, n_slots, m_count);
+    // the tables are complete and the scratch can go: read back the final registers and the error flags
+    uint32_t host_fin[34] = {0};
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && st == RK_OK) {
+            ctx->last_error = std::string("rk_exec_rv32_shard_device ") + what + ": " + hipGetErrorString(e);
+            st = RK_ERR_HIP;
+        }
+    };
+    hip(hipMemcpyAsync(host_fin, w + L.fin, 32 * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    hip(hipMemcpyAsync(host_fin + 32, w + L.err, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    if (CH::im) hip(hipMemcpyAsync(host_fin + 33, w + L.mtotal, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    hip(hipStreamSynchronize(ctx->stream), "sync");
+    rk::dev_free(ctx, base);
+    if (st != RK_OK) return st;
+    if (host_fin[32] & 7) {
+        ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
+                                           : "rk_exec_rv32_shard_device: trace and side list disagree";
+        return RK_ERR_INVALID;
+    }
+    if (CH::im && (host_fin[32] || host_fin[33] != m_count)) {
+        ctx->last_error = "rk_exec_rv32im_shard_device: an M result or the muldiv row count is not the executor's";
+        return RK_ERR_INTERNAL;
+    }
+    if (!std::equal(host_fin, host_fin + 32, v.regs + 32)) {
+        ctx->last_error = "rk_exec_rv32_shard_device: the register accesses do not end in the executor's registers";
+        return RK_ERR_INTERNAL;
+    }
+    return RK_OK;
+}
+
+}  // namespace rv32
+
+extern "C" {
+
+int rk_exec_witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_code, uint32_t* d_data) {
+    RK_GUARD_BEGIN
+    if (!d_code) return RK_ERR_INVALID;
+    return witness_device(ctx, ex, index, d_code, d_data, false);
+    RK_GUARD_END
+}
+int rk_exec_witness_device_rows(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_rows) {
+    RK_GUARD_BEGIN
+    return witness_device(ctx, ex, index, nullptr, d_rows, true);
+    RK_GUARD_END
+}
+int rk_exec_rv32_sizes(const rk_exec* ex, uint32_t index, size_t* program_rows) {
+    RK_GUARD_BEGIN
+    if (!program_rows) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    *program_rows = rv32::program_rows_of(v, nullptr);
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                              size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range) {
+    RK_GUARD_BEGIN
+    return rv32::shard_device<rv32::CS_I>(ctx, ex, index, {d_cpu, d_program, program_rows, d_register, d_byte, d_range, nullptr,
+                                                           nullptr, 0});
+    RK_GUARD_END
+}
+int rk_exec_rv32cf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
+                                uint32_t* d_shift) {
+    RK_GUARD_BEGIN
+    return rv32::shard_device<rv32::CS_CF>(ctx, ex, index, {d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
+                                                            nullptr, 0});
+    RK_GUARD_END
+}
+int rk_exec_rv32im_sizes(const rk_exec* ex, uint32_t index, size_t* muldiv_rows) {
+    RK_GUARD_BEGIN
+    if (!muldiv_rows) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    *muldiv_rows = rv32::muldiv_rows_for(rv32::m_count_of(v));
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
+                                size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
+                                uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows) {
+    RK_GUARD_BEGIN
+    return rv32::shard_device<rv32::CS_IM>(ctx, ex, index, {d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
+                                                            d_muldiv, muldiv_rows});
+    RK_GUARD_END
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The executor + segmenter in front of the proving path: binding of rk_exec_* (raiko_amd/csrc/
-executor.cpp) and `execute_and_prove`, the shape of `prove_locally` (reference
+executor.cpp the host executor, rv32_shards.hip the witness written on the GPU) and `execute_and_prove`, the shape of `prove_locally` (reference
 provers/risc0/driver/src/bonsai.rs:230-272): run the guest ELF, cut the run into segments of at
 most 2^po2 cycles, prove every segment, return the receipt.
 
@@ -610,9 +610,29 @@ CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im")
 RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im")
 
 
+# per chip set: the module with its AIRs and numpy tables, the entry point that writes a shard's tables on the GPU, the
+# fixed-height tables past rv32i's five as (module, name of its log height), whether a muldiv table (of the height the
+# segment needs) comes last
+_RV32_SETS = {"rv32i": ("rv32", "rk_exec_rv32_shard_device", (), False),
+              "rv32i-cf": ("rv32cf", "rk_exec_rv32cf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), False),
+              "rv32im": ("rv32im", "rk_exec_rv32im_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True)}
+
+
+def _rv32_set(chips):
+    """-> (the chip set's module, its C entry point, the pinned log heights of its tables from the register table on,
+    whether a muldiv table follows them)"""
+    from importlib import import_module
+    if chips not in _RV32_SETS:
+        raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
+    module, entry, fixed, muldiv = _RV32_SETS[chips]
+    mod = lambda name: import_module("." + name, __package__)
+    pinned = (5, mod("rv32").BYTE_LOG_ROWS, 16) + tuple(getattr(mod(m), name) for m, name in fixed)
+    return mod(module), entry, pinned, muldiv
+
+
 def _rv32_airs_of(chips, ext_w=None):
     """the AIRs of one shard of chip set `chips`, in table order"""
-    return {"rv32i": p3_rv32_airs, "rv32i-cf": p3_rv32cf_airs, "rv32im": p3_rv32im_airs}[chips](ext_w)
+    return _rv32_set(chips)[0].airs(ext_w)
 
 
 def _rv32_side(lib, handle, index):
@@ -629,22 +649,19 @@ def _rv32_side(lib, handle, index):
 
 def p3_rv32_airs(ext_w=None):
     """(cpu, program, register, byte, range): the AIRs of one rv32i shard, in table order (raiko_amd/rv32.py)"""
-    from . import rv32
-    return rv32.airs(ext_w)
+    return _rv32_airs_of("rv32i", ext_w)
 
 
 def p3_rv32cf_airs(ext_w=None):
     """(cpu, program, register, byte, range, shift): the AIRs of one rv32i-cf shard, in table order
     (raiko_amd/rv32cf.py)"""
-    from . import rv32cf
-    return rv32cf.airs(ext_w)
+    return _rv32_airs_of("rv32i-cf", ext_w)
 
 
 def p3_rv32im_airs(ext_w=None):
     """(cpu, program, register, byte, range, shift, muldiv): the AIRs of one rv32im shard, in table order
     (raiko_amd/rv32im.py)"""
-    from . import rv32im
-    return rv32im.airs(ext_w)
+    return _rv32_airs_of("rv32im", ext_w)
 
 
 def _rv32_publics(seg, start, end):
@@ -654,93 +671,66 @@ def _rv32_publics(seg, start, end):
     return pub_cpu, to_mont(rv32.register_publics(start, end))
 
 
-def p3_rv32_shards(ex: Execution, ext_w=None, airs=None):
-    """one rv32i shard per executed segment, every table built in numpy from ex.witness and ex.rv32 -> [(tables, init
-    words)]: tables = cpu, program, register, byte, range (p3_rv32_airs), init = the state digests as in p3_shards.
-    The yardstick for the tables rk_exec_rv32_shard_device writes on the GPU."""
-    from . import p3, rv32
+def _rv32_shards(chips, ex, ext_w, airs):
+    """one shard of chip set `chips` per executed segment, every table built in numpy (the set's shard_tables) from
+    ex.witness and ex.rv32 -> [(tables, init words)], init = the state digests as in p3_shards"""
+    from . import p3
     if ex.witness is None or ex.rv32 is None:
         raise ValueError("execute(..., record_trace=True) first")
-    airs = airs or p3_rv32_airs(ext_w)
+    module = _rv32_set(chips)[0]
+    airs = airs or module.airs(ext_w)
     out = []
     for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
-        canon, _pc, _regs = rv32.shard_tables(s, data, start, end, ecalls)
+        canon, _pc, _regs = module.shard_tables(s, data, start, end, ecalls)
         pub_cpu, pub_reg = _rv32_publics(s, start, end)
-        pubs = [pub_cpu, (), pub_reg, (), ()]
+        pubs = [pub_cpu, (), pub_reg] + [()] * (len(canon) - 3)
         tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
         out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
     return out
+
+
+def p3_rv32_shards(ex: Execution, ext_w=None, airs=None):
+    """rv32i shards in numpy: tables = cpu, program, register, byte, range (p3_rv32_airs).  The yardstick for the tables
+    rk_exec_rv32_shard_device writes on the GPU."""
+    return _rv32_shards("rv32i", ex, ext_w, airs)
 
 
 def p3_rv32cf_shards(ex: Execution, ext_w=None, airs=None):
-    """one rv32i-cf shard per executed segment, every table built in numpy (rv32cf.shard_tables) -> [(tables, init
-    words)]: tables = cpu, program, register, byte, range, shift (p3_rv32cf_airs).  The yardstick for the tables
-    rk_exec_rv32cf_shard_device writes on the GPU."""
-    from . import p3, rv32cf
-    if ex.witness is None or ex.rv32 is None:
-        raise ValueError("execute(..., record_trace=True) first")
-    airs = airs or p3_rv32cf_airs(ext_w)
-    out = []
-    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
-        canon, _pc, _regs = rv32cf.shard_tables(s, data, start, end, ecalls)
-        pub_cpu, pub_reg = _rv32_publics(s, start, end)
-        pubs = [pub_cpu, (), pub_reg, (), (), ()]
-        tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
-        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
-    return out
+    """rv32i-cf shards in numpy: tables = cpu, program, register, byte, range, shift (p3_rv32cf_airs).  The yardstick for
+    the tables rk_exec_rv32cf_shard_device writes on the GPU."""
+    return _rv32_shards("rv32i-cf", ex, ext_w, airs)
 
 
 def p3_rv32im_shards(ex: Execution, ext_w=None, airs=None):
-    """one rv32im shard per executed segment, every table built in numpy (rv32im.shard_tables) -> [(tables, init
-    words)]: tables = cpu, program, register, byte, range, shift, muldiv (p3_rv32im_airs).  The yardstick for the tables
-    rk_exec_rv32im_shard_device writes on the GPU."""
-    from . import p3, rv32im
-    if ex.witness is None or ex.rv32 is None:
-        raise ValueError("execute(..., record_trace=True) first")
-    airs = airs or p3_rv32im_airs(ext_w)
-    out = []
-    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
-        canon, _pc, _regs = rv32im.shard_tables(s, data, start, end, ecalls)
-        pub_cpu, pub_reg = _rv32_publics(s, start, end)
-        pubs = [pub_cpu, (), pub_reg, (), (), (), ()]
-        tables = [p3.Table(a, p3.to_mont(t), pv) for a, t, pv in zip(airs, canon, pubs)]
-        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
-    return out
-
-
-# per chip set: the entry point that writes a shard's tables on the GPU and the fixed tables' log heights past rv32i's
-_RV32_DEVICE = {"rv32i": ("rk_exec_rv32_shard_device", ()), "rv32i-cf": ("rk_exec_rv32cf_shard_device", ("shift",)),
-                "rv32im": ("rk_exec_rv32im_shard_device", ("shift", "muldiv"))}
+    """rv32im shards in numpy: tables = cpu, program, register, byte, range, shift, muldiv (p3_rv32im_airs).  The
+    yardstick for the tables rk_exec_rv32im_shard_device writes on the GPU."""
+    return _rv32_shards("rv32im", ex, ext_w, airs)
 
 
 def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
     rk_exec_rv32im_shard_device ("rv32im"): segment `index` of an open executor as the tables of a shard of that chip
     set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per table, init words)"""
-    from . import p3, rv32, rv32cf
-    if chips not in RV32_CHIPS:
-        raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
+    from . import p3
+    _module, entry, pinned, muldiv = _rv32_set(chips)
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
     _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
-    logs = [seg.po2, rows.value.bit_length() - 1, 5, rv32.BYTE_LOG_ROWS, 16]
-    entry, extra = _RV32_DEVICE[chips]
+    logs = [seg.po2, rows.value.bit_length() - 1, *pinned]
     md_rows = C.c_size_t(0)
-    if "shift" in extra:
-        logs.append(rv32cf.SHIFT_LOG_ROWS)
-    if "muldiv" in extra:
+    if muldiv:
         _lib.check(None, lib.rk_exec_rv32im_sizes(handle, index, C.byref(md_rows)))
         logs.append(md_rows.value.bit_length() - 1)
     if len(airs) != len(logs):
         raise ValueError("%d AIRs for the %d tables of %s" % (len(airs), len(logs), chips))
     bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
     ptrs = [C.c_void_p(b.ptr) for b in bufs]
-    args = ptrs[:2] + [rows.value] + ptrs[2:] + ([md_rows.value] if "muldiv" in extra else [])
+    args = ptrs[:2] + [rows.value] + ptrs[2:] + ([md_rows.value] if muldiv else [])
     _lib.check(hal._ctx, getattr(lib, entry)(hal._ctx, handle, index, *args))
     pub_cpu, pub_reg = _rv32_publics(seg, start, end)
     tables = []
-    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg, (), (), (), ()]):
+    for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg] + [()] * (len(logs) - 3)):
         t = p3.Table(a, None, pv)
         t.log_height = lg
         tables.append(t)
@@ -754,8 +744,6 @@ def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_
     trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device
     traces], [[(device buffer, log_height)]] to free)"""
     from .hal import _ptr
-    if chips not in RV32_CHIPS:
-        raise ValueError("chips must be one of %s" % (RV32_CHIPS,))
     airs = airs or _rv32_airs_of(chips, ext_w)
     st = Stepper(elf, input_words, shard_po2)
     shards, dev, metas = [], [], []
@@ -821,16 +809,22 @@ def verify_rv32_shard(tables, proof, init, params=None) -> int:
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
     verifier's reason"""
-    from . import p3, rv32, rv32cf
+    from . import p3
+    # the chip set is the one with this many tables; the program table's height (0) is the proof's, as the muldiv table's
+    sets = [_rv32_set(c)[2:] for c in RV32_CHIPS]
+    pinned = next((p for p, muldiv in sets if 2 + len(p) + muldiv == len(tables)), None)
+    if pinned is None:
+        raise ValueError("%d tables are no rv32 chip set's shard" % len(tables))
+    pinned = (tables[0].log_height, 0, *pinned)
     vt = []
     for i, t in enumerate(tables):
         v = p3.Table(t.air, None, t.public_values)
-        if i == 6:
+        if i < len(pinned):
+            v.log_height = pinned[i]
+        else:
             lg = int(proof[1 + i]) if len(proof) > 1 + i else 0
             if not 0 < lg <= tables[0].log_height:
                 return 2
             v.log_height = lg
-        else:
-            v.log_height = (t.log_height, 0, 5, rv32.BYTE_LOG_ROWS, 16, rv32cf.SHIFT_LOG_ROWS)[i]
         vt.append(v)
     return p3.verify(vt, proof, init, params)

@@ -485,26 +485,36 @@ def program_table_for(pcs, inss, pc_lo, pc_hi):
     return program_rows(slot_pc, word, cnt, n_rows)
 
 
+def trace_of(seg, data):
+    """the 16 data columns of a segment's stand-in trace (Montgomery, (16, n)) -> (tr: dict of int64 arrays over the
+    executed cycles (pc, next, ins, a, b, res, wr), n, the lowest and the highest pc executed: 0, 0 without cycles)"""
+    from . import p3
+    vals = p3.from_mont(data).astype(np.int64)            # (16, n) canonical
+    cyc = int(seg.cycles)
+    tr = {k: vals[c, :cyc] | vals[c + 1, :cyc] << 16 for k, c in
+          (("pc", PC_LO), ("next", NX_LO), ("ins", INS_LO), ("a", A_LO), ("b", B_LO), ("res", RES_LO))}
+    tr["wr"] = vals[WR, :cyc]
+    return tr, vals.shape[1], int(tr["pc"].min()) if cyc else 0, int(tr["pc"].max()) if cyc else 0
+
+
+def shard_publics(seg, init, final, final_expected):
+    """what every chip set's shard_tables ends with: the final registers are the executor's (final_expected, unless None)
+    -> (cpu public values, register public values)"""
+    if final_expected is not None and not np.array_equal(final, _u(final_expected)):
+        raise ValueError("segment %d: the register accesses do not end in the executor's registers" % seg.index)
+    pub_cpu = np.array([seg.start_pc & 0xFFFF, seg.start_pc >> 16, seg.end_pc & 0xFFFF, seg.end_pc >> 16], dtype=np.int64)
+    return pub_cpu, register_publics(init, final)
+
+
 def shard_tables(seg, data, init, final_expected, ecalls):
     """the five canonical tables of one executed segment -> ([cpu, program, register, byte, range] canonical int64 arrays,
     cpu public values, register public values)"""
-    from . import p3
-    vals = p3.from_mont(data).astype(np.int64)            # (16, n) canonical
-    n = vals.shape[1]
-    cyc = int(seg.cycles)
-    tr = dict(pc=vals[0, :cyc] | vals[1, :cyc] << 16, next=vals[2, :cyc] | vals[3, :cyc] << 16,
-              ins=vals[4, :cyc] | vals[5, :cyc] << 16, a=vals[8, :cyc] | vals[9, :cyc] << 16,
-              b=vals[10, :cyc] | vals[11, :cyc] << 16, res=vals[12, :cyc] | vals[13, :cyc] << 16)
+    tr, n, pc_lo, pc_hi = trace_of(seg, data)
     cpu, final, final_ts, hist, byte_mult = cpu_rows(tr, n, seg.end_pc, init, ecalls)
-    if final_expected is not None and not np.array_equal(final, _u(final_expected)):
-        raise ValueError("segment %d: the register accesses do not end in the executor's registers" % seg.index)
-    pcs = tr["pc"]
-    prog = program_table_for(pcs, tr["ins"], int(pcs.min()) if cyc else 0, int(pcs.max()) if cyc else 0)
-    reg = register_rows(init, final, final_ts)
-    byte = byte_rows(byte_mult)
+    pubs = shard_publics(seg, init, final, final_expected)
+    prog = program_table_for(tr["pc"], tr["ins"], pc_lo, pc_hi)
     rng = np.stack([np.arange(1 << 16, dtype=np.int64), hist], axis=1)
-    pub_cpu = np.array([seg.start_pc & 0xFFFF, seg.start_pc >> 16, seg.end_pc & 0xFFFF, seg.end_pc >> 16], dtype=np.int64)
-    return [cpu, prog, reg, byte, rng], pub_cpu, register_publics(init, final)
+    return ([cpu, prog, register_rows(init, final, final_ts), byte_rows(byte_mult), rng],) + pubs
 
 
 def bus_balance(tables_canon, airs_):

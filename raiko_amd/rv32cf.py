@@ -354,20 +354,10 @@ def cpu_rows(tr, n, end_pc, init, ecalls, strict=True):
 def shard_tables(seg, data, init, final_expected, ecalls):
     """the six canonical tables of one executed segment -> ([cpu, program, register, byte, range, shift] canonical int64
     arrays, cpu public values, register public values)"""
-    from . import p3
-    vals = p3.from_mont(data).astype(np.int64)
-    n = vals.shape[1]
-    cyc = int(seg.cycles)
-    tr = dict(pc=vals[0, :cyc] | vals[1, :cyc] << 16, next=vals[2, :cyc] | vals[3, :cyc] << 16,
-              ins=vals[4, :cyc] | vals[5, :cyc] << 16, a=vals[8, :cyc] | vals[9, :cyc] << 16,
-              b=vals[10, :cyc] | vals[11, :cyc] << 16, res=vals[12, :cyc] | vals[13, :cyc] << 16)
+    tr, n, pc_lo, pc_hi = rv32.trace_of(seg, data)
     cpu, final, final_ts, hist, byte_mult, shift_mult = cpu_rows(tr, n, seg.end_pc, init, ecalls)
-    if final_expected is not None and not np.array_equal(final, np.asarray(final_expected, dtype=np.int64)):
-        raise ValueError("segment %d: the register accesses do not end in the executor's registers" % seg.index)
-    pcs = tr["pc"]
-    prog = program_table_for(pcs, tr["ins"], int(pcs.min()) if cyc else 0, int(pcs.max()) if cyc else 0)
-    reg = rv32.register_rows(init, final, final_ts)
+    pubs = rv32.shard_publics(seg, init, final, final_expected)
+    prog = program_table_for(tr["pc"], tr["ins"], pc_lo, pc_hi)
     rng = np.stack([np.arange(1 << 16, dtype=np.int64), hist], axis=1)
-    pub_cpu = np.array([seg.start_pc & 0xFFFF, seg.start_pc >> 16, seg.end_pc & 0xFFFF, seg.end_pc >> 16], dtype=np.int64)
-    return ([cpu, prog, reg, rv32.byte_rows(byte_mult), rng, shift_rows(shift_mult)], pub_cpu,
-            rv32.register_publics(init, final))
+    return ([cpu, prog, rv32.register_rows(init, final, final_ts), rv32.byte_rows(byte_mult), rng,
+             shift_rows(shift_mult)],) + pubs

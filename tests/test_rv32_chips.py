@@ -9,7 +9,9 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import or_rv32  # noqa: E402
+import rv32_cf_programs as CP  # noqa: E402
 import rv32_chip_programs as RP  # noqa: E402
+import rv32_m_programs as MP  # noqa: E402
 from raiko_amd import p3, rv32  # noqa: E402
 from raiko_amd import executor as X  # noqa: E402
 
@@ -189,3 +191,58 @@ def test_padding_rows_cannot_cancel_lookups():
         assert bad == [] if build is F.honest else [row for row, _ in bad] == [1], build.__name__
     tables, _pc, pub_reg = F.forged()
     assert tables[0][0, rv32.RES_LO] == 0xFE and pub_reg[64 + 2 * 3] == 0xFE
+
+
+# ---- the lane bodies the GPU writes the tables with (raiko_amd/csrc/rv32_rows.hpp), walked over a trace on the CPU
+_ROWS_SETS = {"rv32i": 0, "rv32i-cf": 1, "rv32im": 2}
+_ROWS_PROGRAMS = {"alu1": lambda: RP.alu_program(1), "cf1": lambda: CP.cf_program(1), "m1": lambda: MP.m_program(1),
+                  "mixed400": lambda: MP.mixed_program(400), "alu200": lambda: RP.alu_program(200)}
+_ROWS_CASES = [(p, c) for p in ("alu1", "cf1", "m1", "mixed400") for c in _ROWS_SETS] + [("alu200", "rv32im")]
+_rows_runs = {}
+
+
+@pytest.fixture(scope="module")
+def rows_lib(tmp_path_factory):
+    import ctypes
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    so = str(tmp_path_factory.mktemp("emul_rv32_rows") / "libemul_rv32_rows.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(root, "raiko_amd", "csrc"), "-o", so,
+                    os.path.join(root, "tests", "emul", "emul_rv32_rows.cpp")], check=True, capture_output=True)
+    return ctypes.CDLL(so)
+
+
+@pytest.mark.parametrize("program,chips", _ROWS_CASES)
+def test_row_bodies_write_the_numpy_tables(rows_lib, program, chips):
+    """tests/emul/emul_rv32_rows.cpp walks each segment's trace in order through rv32_rows.hpp's bodies, the last access
+    per register kept in an array: its cpu and program tables, and the muldiv table under rv32im, are the chip set's
+    shard_tables word for word in Montgomery form.  Segments of 2^13: alu200 and mixed400 end in a partial segment and
+    start their later ones from non-zero registers"""
+    import ctypes as C
+    if program not in _rows_runs:                         # one execution per program, shared by the chip sets
+        _rows_runs[program] = X.execute(_ROWS_PROGRAMS[program](), INPUT, segment_limit_po2=13, record_trace=True)
+    ex = _rows_runs[program]
+    module = X._rv32_set(chips)[0]
+    u32p = C.POINTER(C.c_uint32)
+    ptr = lambda a: a.ctypes.data_as(u32p)
+    assert len(ex.segments) >= (2 if program in ("alu200", "mixed400") else 1)
+    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
+        compared = (0, 1, 6) if chips == "rv32im" else (0, 1)           # cpu, program, muldiv
+        canon = module.shard_tables(s, data, start, end, ecalls)[0]
+        want = {k: p3.to_mont(canon[k]) for k in compared}
+        tr, n, pc_lo, pc_hi = rv32.trace_of(s, data)
+        rows = np.ascontiguousarray(np.stack([tr[k] for k in ("pc", "ins", "a", "b", "res", "next", "wr")], axis=1), dtype=np.uint32)
+        ec = np.ascontiguousarray(ecalls, dtype=np.uint32).reshape(-1, 2)
+        init = np.ascontiguousarray(start, dtype=np.uint32)
+        got = {k: np.full(w.shape, 0xDEADBEEF, dtype=np.uint32) for k, w in want.items()}
+        md = got.get(6, np.zeros((1, 1), dtype=np.uint32))
+        rc = rows_lib.emul_rv32_shard(_ROWS_SETS[chips], ptr(rows), C.c_size_t(rows.shape[0]), C.c_size_t(n), C.c_uint32(s.end_pc),
+                                      ptr(init), ptr(ec), C.c_size_t(ec.shape[0]), C.c_uint32(pc_lo),
+                                      C.c_size_t((pc_hi - pc_lo) // 4 + 1 if rows.shape[0] else 0), C.c_size_t(want[1].shape[0]),
+                                      ptr(got[0]), ptr(got[1]), ptr(md), C.c_size_t(md.shape[0]))
+        assert rc == 0, (s.index, rc)
+        for k in compared:
+            assert want[k].dtype == np.uint32 and np.array_equal(got[k], want[k]), (s.index, k)
+        if s.index and program == "alu200":
+            assert start.any()
+    assert int(ex.segments[-1].cycles) < 1 << 13
