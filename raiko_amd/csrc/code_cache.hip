@@ -214,6 +214,24 @@ int code_fingerprint(rk_ctx* ctx, const uint32_t* d_src, size_t words, uint32_t 
     return RK_OK;
 }
 
+CodeKey code_key(const rk_ctx* ctx, uint32_t po2, uint32_t cols, uint32_t queries, const uint32_t fp[4]) {
+    CodeKey key{};
+    std::memcpy(key.fp, fp, sizeof key.fp);
+    key.po2 = po2;
+    key.cols = cols;
+    key.blowup_log2 = ctx->sys.blowup_log2;
+    key.queries = queries;  // the layer sent as the tree's cap depends on it
+    key.root27m = ctx->sys.root27m;
+    key.shiftm = ctx->sys.shiftm;
+    const p2::Any& kc = ctx->h_p2;
+    std::vector<uint32_t> inst{bb::encode((uint32_t)kc.kind), bb::encode(kc.pad_free ? 1u : 0u)};
+    inst.insert(inst.end(), kc.rc_ext(), kc.rc_ext() + 8 * kc.cells());
+    inst.insert(inst.end(), kc.rc_int(), kc.rc_int() + kc.rounds_partial());
+    inst.insert(inst.end(), kc.diag(), kc.diag() + kc.cells());
+    kc.hash_elems(inst.data(), inst.size(), key.p2);
+    return key;
+}
+
 std::shared_ptr<CodeEntry> code_cache_lookup(int device, const CodeKey& key) {
     DevCache* c = cache_of(device);
     std::lock_guard<std::mutex> l(c->mu);

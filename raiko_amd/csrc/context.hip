@@ -100,6 +100,12 @@ int dev_free(rk_ctx* ctx, void* p) {
     }
     return RK_OK;
 }
+int d2h_sync(rk_ctx* ctx, void* h_dst, const void* d_src, size_t bytes) {
+    RK_HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RK_OK;
+}
+
 int upload(rk_ctx* ctx, void* d_dst, const void* h_src, size_t bytes) {
     constexpr size_t RING = (size_t)4 << 20;
     if (bytes == 0) return RK_OK;

@@ -115,6 +115,45 @@ int scratch(rk_ctx* ctx, size_t bytes, void** out);  // valid until the next scr
 // caller's buffer is free on return (large uploads fall back to copy + wait)
 int upload(rk_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 int post_launch(rk_ctx* ctx, const char* what);
+// device -> host on the ctx stream, then wait for the stream: the one way transcript-sized data reaches the host
+int d2h_sync(rk_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
+
+// dev_alloc'd block released with the scope, or caller-owned memory used in place (`adopt`: never freed here)
+struct DevBuf {
+    rk_ctx* ctx = nullptr;
+    void* p = nullptr;
+    bool borrowed = false;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : ctx(o.ctx), p(o.p), borrowed(o.borrowed) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        release();
+        ctx = o.ctx;
+        p = o.p;
+        borrowed = o.borrowed;
+        o.p = nullptr;
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    int alloc(rk_ctx* c, size_t bytes) {
+        release();
+        ctx = c;
+        return dev_alloc(c, bytes, &p);
+    }
+    void adopt(rk_ctx* c, void* ptr) {
+        release();
+        ctx = c;
+        p = ptr;
+        borrowed = true;
+    }
+    void release() {
+        if (p && !borrowed) (void)dev_free(ctx, p);
+        p = nullptr;
+        borrowed = false;
+    }
+    uint32_t* u32() const { return (uint32_t*)p; }
+};
 
 // NTT (kernels_ntt.hip)
 int ntt_reverse(rk_ctx* ctx, uint32_t* d_io, size_t size, size_t count, bool fuse_zk_shift);
@@ -236,6 +275,9 @@ struct CodeEntry {                     // what commit_group leaves behind for th
 bool code_cache_usable(int device, size_t words, size_t entry_bytes);
 // fp = the fingerprint of d_src[0 .. words) (waits for the stream); *canonical: every word was < p
 int code_fingerprint(rk_ctx* ctx, const uint32_t* d_src, size_t words, uint32_t fp[4], bool* canonical);
+// the key of the code group committed from an input of fingerprint `fp` under the context's parameter set: the shape
+// of the group and of its tree's cap, the field parameters of the transforms, the digest of the Poseidon2 instance
+CodeKey code_key(const rk_ctx* ctx, uint32_t po2, uint32_t cols, uint32_t queries, const uint32_t fp[4]);
 // the entry of `key` (a hit) or null (a miss)
 std::shared_ptr<CodeEntry> code_cache_lookup(int device, const CodeKey& key);
 // an entry with buffers of the given sizes, not yet in the cache; null when the device has no room for it

@@ -209,12 +209,6 @@ size_t proof_bound(const rk_params& p, const rk_p3_table* t, uint32_t n, const u
     return p3h::Layout(p.blowup_log2, t, n, lqd, log_n).words(p.queries);
 }
 
-int d2h(rk_ctx* ctx, void* h, const void* d, size_t bytes) {
-    RK_HIP_TRY(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RK_OK;
-}
-
 // One rk_p3_prove: the state the stages share and the stages in the order the transcript imposes
 struct ProofRun {
     rk_ctx* ctx;
@@ -288,7 +282,7 @@ int ProofRun::commit_traces() {
         RK_TRY(s.lde.alloc(ctx, s.H * s.w * 4));
         RK_TRY(rk::pcs_coset_lde_cols(ctx, s.lde.u32(), s.d_trace, s.n, s.w));
         if (!tb.on_device) RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the caller's host buffer is free again
-        if (!s.pw) s.staged.reset();   // only the lookups read the rows again
+        if (!s.pw) s.staged.release();   // only the lookups read the rows again
         tmats[t] = rk_matrix{s.lde.u32(), (uint32_t)s.H, (uint32_t)s.w, 2};
         Ht = std::max(Ht, s.H);
         log_max = std::max(log_max, s.k + blow);
@@ -338,7 +332,7 @@ int ProofRun::permutation_traces() {
                 RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)perm_entries_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(perm_entries_kernel, dim3((unsigned)((s.n + PERM_ROWS - 1) / PERM_ROWS)), dim3(PERM_ROWS), lds, ctx->stream, a);
             RK_TRY(rk::post_launch(ctx, "perm_entries_kernel"));
-            s.staged.reset();
+            s.staged.release();
             // the running sum: four base prefix sums over the row totals, in place
             const size_t nblk = (s.n + PS_BLOCK - 1) / PS_BLOCK;
             uint32_t* phi = cols.u32() + (s.pw - 4) * s.n;
@@ -433,7 +427,7 @@ int ProofRun::quotients(const Ext& alpha) {
             dom.n_globals = (uint32_t)globals.size();
         }
         RK_TRY(rk::program_eval_domain(pg, dom, alpha.c, q.u32()));
-        sel.reset();
+        sel.release();
         // the chunks' own LDE: interpolate over H_n, move to the chunk's coset, evaluate on the LDE coset
         RK_TRY(rk::ntt_reverse(ctx, q.u32(), s.n, n_qcols, /*fuse_zk_shift=*/false));
         if (qd > 1) {
@@ -496,7 +490,7 @@ int ProofRun::open() {
     }
     {
         std::vector<uint32_t> h_ys(y_words);
-        RK_TRY(d2h(ctx, h_ys.data(), d_ys.p, y_words * 4));
+        RK_TRY(rk::d2h_sync(ctx, h_ys.data(), d_ys.p, y_words * 4));
         for (const Opening& o : openings) std::memcpy(o.s->y.data() + o.y_at, &h_ys[o.d_at], 4 * o.w * o.n_points * 4);
     }
     for (const Opening& o : openings) {
@@ -546,7 +540,7 @@ int ProofRun::fri() {
         }
     }
     std::vector<uint32_t> fin(len * 4);
-    RK_TRY(d2h(ctx, fin.data(), folded.p, len * 16));
+    RK_TRY(rk::d2h_sync(ctx, fin.data(), folded.p, len * 16));
     for (size_t i = 1; i < len; i++)
         if (std::memcmp(&fin[4 * i], &fin[0], 16) != 0) return RK_ERR_INTERNAL;   // `blowup` values of a constant
     push(fin.data(), 4);
@@ -598,7 +592,7 @@ int ProofRun::queries(uint32_t* h_proof, size_t capacity, size_t* proof_words) {
                            (const GatherJob*)d_jobs.p, jobs.size());
         RK_TRY(rk::post_launch(ctx, "gather_jobs_kernel"));
         std::memcpy(h_proof, pf.data(), pf.size() * 4);
-        RK_TRY(d2h(ctx, h_proof + pf.size(), d_out.p, (size_t)at * 4));
+        RK_TRY(rk::d2h_sync(ctx, h_proof + pf.size(), d_out.p, (size_t)at * 4));
     }
     *proof_words = pf.size() + at;
     return RK_OK;

@@ -1,6 +1,6 @@
 // Shared by p3_air.hip (the AIR front end: rk_air_*, the lookup constraints, the Poseidon2 chip), fri_tables.hip (the rows
-// of the FRI lookup tables) and p3.hip / p3_verify.hip (prover, verifier): what an rk_air holds, the scoped device buffer all
-// three use, and the Poseidon2 chip as the FRI tables feed it.
+// of the FRI lookup tables) and p3.hip / p3_verify.hip (prover, verifier): what an rk_air holds and the Poseidon2 chip as
+// the FRI tables feed it.  (The scoped device buffer all of them use is rk::DevBuf of internal.hpp.)
 #pragma once
 #include "internal.hpp"
 #include "circuit_program.hpp"
@@ -24,33 +24,6 @@ struct rk_air {
 namespace rk {
 
 constexpr uint32_t NEXT_BACK = 0xffffffffu;  // a tap "one row ahead": back = -1 modulo any power-of-two domain
-
-struct DevBuf {  // dev_alloc'd block released with the scope
-    rk_ctx* ctx = nullptr;
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : ctx(o.ctx), p(o.p) { o.p = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        reset();
-        ctx = o.ctx;
-        p = o.p;
-        o.p = nullptr;
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    int alloc(rk_ctx* c, size_t bytes) {
-        reset();
-        ctx = c;
-        return rk::dev_alloc(c, bytes, &p);
-    }
-    void reset() {
-        if (p) (void)rk::dev_free(ctx, p);
-        p = nullptr;
-    }
-    uint32_t* u32() const { return (uint32_t*)p; }
-};
 
 // the Poseidon2 chip of an instance: where its columns are, and the constants its lanes read
 inline p3k::P2ChipLayout p2_chip_layout(const p2::Any& k) {

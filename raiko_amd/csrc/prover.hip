@@ -13,7 +13,7 @@
 // drawn, eval_check after poly_mix is drawn) are rk_circuit_hooks called back from the proof
 // (CircuitHal::accumulate / eval_check).  Without hooks their outputs are taken as given
 // (the synthetic S20 stand-in of SURVEY.md section 8d).
-#include "internal.hpp"
+#include "segment_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -22,6 +22,8 @@
 namespace {
 
 using bb::Ext;
+using rk::d2h_sync;
+using rk::DevBuf;
 
 // ---------------------------------------------------------------- transcript
 // WriteIOP + Poseidon2Rng (risc0-zkp prove/write_iop.rs, core/hash/poseidon2/rng.rs) over the
@@ -37,45 +39,6 @@ struct Transcript {
     uint32_t random_bits(unsigned bits) { return rng.random_bits(bits); }
 };
 
-// ---------------------------------------------------------------- device helpers
-struct DevBuf {
-    rk_ctx* ctx = nullptr;
-    void* p = nullptr;
-    bool borrowed = false;  // caller-owned memory used in place (rk_segment.on_device == 2)
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    int alloc(rk_ctx* c, size_t bytes) {
-        release();
-        ctx = c;
-        return rk::dev_alloc(c, bytes, &p);
-    }
-    void adopt(rk_ctx* c, void* ptr) {
-        release();
-        ctx = c;
-        p = ptr;
-        borrowed = true;
-    }
-    void release() {
-        if (p && !borrowed) rk::dev_free(ctx, p);
-        p = nullptr;
-        borrowed = false;
-    }
-    uint32_t* u32() const { return (uint32_t*)p; }
-};
-
-int d2h_sync(rk_ctx* ctx, void* h, const void* d, size_t bytes) {
-    RK_HIP_TRY(ctx, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RK_OK;
-}
-int h2d_sync(rk_ctx* ctx, void* d, const void* h, size_t bytes) {
-    RK_HIP_TRY(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RK_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RK_OK;
-}
-
 // ---------------------------------------------------------------- Merkle prover
 struct MerkleDev {
     size_t rows = 0, cols = 0, layers = 0, top_layer = 0, top_size = 1;
@@ -88,11 +51,7 @@ struct MerkleDev {
         cols = c;
         matrix = d_matrix;
         layers = log2u(r);
-        top_layer = 0;
-        for (size_t i = 1; i < layers; i++) {
-            if (((size_t)1 << i) > queries) break;
-            top_layer = i;
-        }
+        top_layer = rk::merkle_top_layer(r, queries);
         top_size = (size_t)1 << top_layer;
     }
     int build(rk_ctx* ctx, const uint32_t* d_matrix, size_t r, size_t c, size_t queries) {
@@ -285,65 +244,92 @@ void poly_interpolate(Ext* out, const Ext* x, const Ext* fx, size_t n, uint32_t 
     }
 }
 
-int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& seal) {
-    const rk_taps& taps = seg->taps;
-    RK_TRY(rk::check_taps(taps));
-    const rk::Shape shape = ctx->sys.shape();
-    if (!rk::shape_ok(shape) || seg->po2 < 1 || seg->po2 + shape.blowup_log2 > ntt::LAMBDA) return RK_ERR_INVALID;
-    const rk_circuit_hooks* hooks = seg->hooks;
-    const bool hook_accum = hooks && hooks->accumulate, hook_check = hooks && (hooks->eval_check || hooks->program);
-    for (int g = 0; g < 3; g++) {
-        if (taps.group_size[g] == 0) return RK_ERR_INVALID;
-        if (!seg->group[g] && !(g == 0 && hook_accum)) return RK_ERR_INVALID;
+// One rk_prove_segment: the state the stages share and the stages in the order the transcript imposes.  The flow is
+// risc0's; its shape (blow-up, fold arity, final degree, queries, proof of work) follows rk_params.
+struct SegmentRun {
+    rk_ctx* ctx;
+    const rk_segment* seg;
+    const rk_taps& taps;
+    const rk_circuit_hooks* hooks;
+    const bool hook_accum, hook_check;
+    const rk::Shape shape;
+    const unsigned BLOW;
+    const size_t N, D, QUERIES, FRI_FOLD, CHECK_SIZE;
+    const uint32_t wm;
+    const p2::Any& kc;
+    Transcript iop;
+    StageClock sw;
+    size_t total_bracket;  // the outermost bracket: opened first, closed last, charged to rk_timing.total
+    bool outer_ranged;
+
+    PolyGroup groups[3], check;
+    // With an `accumulate` hook the witness of code and data must outlive their commitment (risc0's commit_group works
+    // on a copy for the same reason): device inputs are then copied, not consumed, and host inputs are uploaded once
+    // into `raw` and copied from there.
+    DevBuf raw[3];
+    const uint32_t* d_raw[3] = {nullptr, nullptr, nullptr};
+    std::shared_ptr<rk::CodeEntry> code_ref;  // the code-cache entry this proof reads or builds
+    std::vector<uint32_t> accum_mix;
+    rk_circuit_view view{};
+    std::vector<Ext> pts;      // rk::tap_points: slot b = z * back_one^b, last slot = z^(D/N)
+    std::vector<Ext> coeff_u;  // one interpolating polynomial per register, then the check openings
+    DevBuf final_poly;         // the DEEP quotient FRI starts from: 4 planes of N, bit-reversed
+    DevBuf d_rems;
+    std::vector<Ext> rems;     // the DEEP divisions' remainders: a download queued in `deep`, waited for in `fri`
+    struct Round {
+        size_t domain;
+        DevBuf coeffs, evaluated;
+        size_t coeffs_words;
+        MerkleDev merkle;
+    };
+    std::vector<std::unique_ptr<Round>> rounds;
+
+    SegmentRun(rk_ctx* c, const rk_segment* s, const rk::Shape& sh)
+        : ctx(c), seg(s), taps(s->taps), hooks(s->hooks), hook_accum(hooks && hooks->accumulate),
+          hook_check(hooks && (hooks->eval_check || hooks->program)), shape(sh), BLOW(sh.blowup_log2), N((size_t)1 << s->po2),
+          D(N << BLOW), QUERIES(sh.queries), FRI_FOLD((size_t)1 << sh.fold_log2), CHECK_SIZE((size_t)4 << BLOW), wm(c->sys.wm),
+          kc(c->h_p2), iop(&c->h_p2), sw(c) {
+        ctx->timing = rk_timing{};
+        sw.start("segment");
+        total_bracket = sw.used.size() - 1;
+        outer_ranged = sw.ranged;
+        sw.ranged = false;
     }
-    if ((!seg->check && !hook_check) || (seg->n_globals && !seg->globals)) return RK_ERR_INVALID;
-    if (seg->n_accum_mix > (1u << 16)) return RK_ERR_INVALID;
+    // Also on the error returns.  A destructor's body runs before any member is destroyed: nothing of this proof is in
+    // flight while its buffers, `rems` (the target of a download) or the cache entry (an evicted entry frees its buffers
+    // when the last reference goes) are released.
+    ~SegmentRun() {
+        (void)hipStreamSynchronize(ctx->stream);
+        sw.resolve();
+        if (outer_ranged) rk::trace_pop();
+    }
 
-    // the flow is risc0's; its shape (blow-up, fold arity, final degree, queries, proof of work) follows rk_params
-    const unsigned BLOW = shape.blowup_log2;
-    const size_t N = (size_t)1 << seg->po2, D = N << BLOW;
-    const size_t QUERIES = shape.queries, FRI_FOLD = (size_t)1 << shape.fold_log2, FRI_MIN_DEGREE = shape.min_degree;
-    const size_t CHECK_SIZE = (size_t)4 << BLOW;
-    const uint32_t wm = ctx->sys.wm;
-    const p2::Any& kc = ctx->h_p2;
-    Transcript iop(&kc);
-    uint32_t digest[8];
-    ctx->timing = rk_timing{};
-    StageClock sw(ctx);
-    std::vector<Ext> rems;  // filled by a download that is only waited for later: must outlive `finish_on_exit`
-    // the code-cache entry this proof reads or builds: held until the stream has drained, so like `rems` it is declared
-    // before `finish_on_exit` (an evicted entry frees its buffers when the last reference goes)
-    std::shared_ptr<rk::CodeEntry> code_ref;
-    sw.start("segment");
-    const size_t total_bracket = sw.used.size() - 1;
-    struct Finish {  // also on the error returns
-        StageClock& c;
-        bool ranged;
-        ~Finish() {
-            (void)hipStreamSynchronize(c.ctx->stream);  // nothing of this proof is in flight once it returns
-            c.resolve();
-            if (ranged) rk::trace_pop();
+    int prove(std::vector<uint32_t>& seal) {
+        bind_header();
+        RK_TRY(commit_code());                                                 // code
+        RK_TRY(commit_group(2, groups[2], seg->group[2], taps.group_size[2]));  // data
+        RK_TRY(accumulate());                                                  // accum
+        RK_TRY(check_poly());  // Prover::finalize from here
+        RK_TRY(open_taps());
+        RK_TRY(deep());
+        RK_TRY(fri());
+        RK_TRY(queries());
+        if (total_bracket < sw.used.size()) {
+            sw.used[total_bracket].acc = &ctx->timing.total;
+            (void)hipEventRecord(sw.used[total_bracket].b, ctx->stream);
         }
-    } finish_on_exit{sw, sw.ranged};
-    sw.ranged = false;
+        seal.swap(iop.proof);
+        return RK_OK;
+    }
 
-    {
-        uint32_t e[16];
-        for (int i = 0; i < 16; i++) e[i] = bb::encode(seg->proof_system_info[i]);
-        kc.hash_elems(e, 16, digest);
-        iop.commit(digest);
-        for (int i = 0; i < 16; i++) e[i] = bb::encode(seg->circuit_info[i]);
-        kc.hash_elems(e, 16, digest);
-        iop.commit(digest);
-        std::vector<uint32_t> vec(seg->globals, seg->globals + seg->n_globals);
-        vec.push_back(bb::encode(seg->po2));
-        kc.hash_elems(vec.data(), vec.size(), digest);
-        iop.commit(digest);
+    void bind_header() {
+        rk::bind_header(kc, iop.rng, seg);
         iop.write(seg->globals, seg->n_globals);
         iop.write(&seg->po2, 1);
     }
 
-    auto load_trace = [&](DevBuf& dst, const uint32_t* src, size_t words) -> int {
+    // ---- loading and committing a group
+    int load_trace(DevBuf& dst, const uint32_t* src, size_t words) {
         if (seg->on_device == 2) {  // the caller gave the buffer up: transform it in place
             dst.adopt(ctx, (void*)src);
             return RK_OK;
@@ -355,15 +341,10 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         // returning), so the upload needs no synchronisation here: with page-locked buffers it is a
         // true DMA that overlaps the kernels already queued
         return RK_OK;
-    };
-    // With an `accumulate` hook the witness of code and data must outlive their commitment (risc0's
-    // commit_group works on a copy for the same reason): device inputs are then copied, not consumed,
-    // and host inputs are uploaded once into `raw` and copied from there.
-    DevBuf raw[3];
-    const uint32_t* d_raw[3] = {nullptr, nullptr, nullptr};
+    }
     // `from`: where the interpolation's first pass reads the trace when that is not `dst` itself -- a device input that
     // must stay untouched is never copied, the transform's first pass reads it and writes the prover's own buffer
-    auto load_group = [&](int g, DevBuf& dst, const uint32_t* src, size_t words, const uint32_t*& from) -> int {
+    int load_group(int g, DevBuf& dst, const uint32_t* src, size_t words, const uint32_t*& from) {
         from = nullptr;
         if (!hook_accum || g == 0) {
             if (seg->on_device != 1) return load_trace(dst, src, words);   // given up (in place) or a host buffer (upload)
@@ -379,9 +360,9 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         }
         from = d_raw[g];
         return dst.alloc(ctx, words * 4);
-    };
+    }
     // the part of commit_group that follows the loading: `from` as in load_group
-    auto commit_loaded = [&](PolyGroup& pg, const uint32_t* from, size_t count) -> int {
+    int commit_loaded(PolyGroup& pg, const uint32_t* from, size_t count) {
         sw.start("ntt");
         RK_TRY(rk::ntt_reverse_from(ctx, pg.coeffs.u32(), from ? from : pg.coeffs.u32(), N, count, /*fuse_zk_shift=*/true));
         RK_TRY(pg.build(ctx, count, N));
@@ -390,19 +371,20 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         RK_TRY(pg.merkle.build(ctx, pg.evaluated.u32(), D, count, QUERIES));
         sw.stop(&ctx->timing.hash);
         return pg.merkle.commit(ctx, iop);
-    };
+    }
     // Prover::commit_group; `preloaded`: pg.coeffs already holds the trace (written by a hook)
-    auto commit_group = [&](int g, PolyGroup& pg, const uint32_t* trace, size_t count, bool preloaded = false) -> int {
+    int commit_group(int g, PolyGroup& pg, const uint32_t* trace, size_t count, bool preloaded = false) {
         const uint32_t* from = nullptr;
         if (!preloaded) RK_TRY(load_group(g, pg.coeffs, trace, count * N, from));
         return commit_loaded(pg, from, count);
-    };
+    }
     // The code group through the device's cache (code_cache.hip): its input is fingerprinted where it lies in device
     // memory -- every word, on every call; the address is no part of the key -- and when the group committed from the
     // same words under the same parameters is there, coefficients, LDE, tree and top layer are borrowed from the
     // entry.  Everything later only reads them (tap evaluation, DEEP mix, openings, a hook's d_lde[1]).  On a miss the
     // group is committed as ever, into buffers of a new entry; the caller's buffer stays untouched in either case.
-    auto commit_code = [&](PolyGroup& pg) -> int {
+    int commit_code() {
+        PolyGroup& pg = groups[1];
         const size_t count = taps.group_size[1], words = count * N;
         const size_t coeff_bytes = words * 4, eval_bytes = count * D * 4, node_bytes = 2 * D * p2::OUT * 4;
         if (!rk::code_cache_usable(ctx->device, words, coeff_bytes + eval_bytes + node_bytes))
@@ -414,24 +396,12 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
             src = raw[1].u32();
         }
         if (hook_accum) d_raw[1] = src;  // the raw code witness reaches `accumulate` as before
-        rk::CodeKey key{};
+        uint32_t fp[4];
         bool canonical = false;
-        RK_TRY(rk::code_fingerprint(ctx, src, words, key.fp, &canonical));
-        std::shared_ptr<rk::CodeEntry> hit;
-        if (canonical) {
-            key.po2 = seg->po2;
-            key.cols = (uint32_t)count;
-            key.blowup_log2 = BLOW;
-            key.queries = (uint32_t)QUERIES;  // MerkleDev::top_layer depends on it
-            key.root27m = ctx->sys.root27m;
-            key.shiftm = ctx->sys.shiftm;
-            std::vector<uint32_t> inst{bb::encode((uint32_t)kc.kind), bb::encode(kc.pad_free ? 1u : 0u)};
-            inst.insert(inst.end(), kc.rc_ext(), kc.rc_ext() + 8 * kc.cells());
-            inst.insert(inst.end(), kc.rc_int(), kc.rc_int() + kc.rounds_partial());
-            inst.insert(inst.end(), kc.diag(), kc.diag() + kc.cells());
-            kc.hash_elems(inst.data(), inst.size(), key.p2);
-            hit = rk::code_cache_lookup(ctx->device, key);
-        }
+        RK_TRY(rk::code_fingerprint(ctx, src, words, fp, &canonical));
+        // a word >= p has no collision bound: such an input goes the ordinary way, in the context's own buffers
+        const rk::CodeKey key = canonical ? rk::code_key(ctx, seg->po2, (uint32_t)count, (uint32_t)QUERIES, fp) : rk::CodeKey{};
+        std::shared_ptr<rk::CodeEntry> hit = canonical ? rk::code_cache_lookup(ctx->device, key) : nullptr;
         pg.count = count;
         pg.size = N;
         if (hit) {
@@ -444,8 +414,7 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
             pg.merkle.top = hit->top;
             pg.merkle.commit_top(iop);
         } else {
-            // a word >= p (no collision bound for it) or no room for an entry: the context's own buffers
-            std::shared_ptr<rk::CodeEntry> fresh;
+            std::shared_ptr<rk::CodeEntry> fresh;  // null: no room for an entry either
             if (canonical) fresh = rk::code_cache_new_entry(ctx->device, key, coeff_bytes, eval_bytes, node_bytes);
             if (fresh) {
                 code_ref = fresh;
@@ -464,24 +433,21 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         }
         if (!hook_accum) raw[1].release();
         return RK_OK;
-    };
+    }
 
-    PolyGroup groups[3], check;
-    RK_TRY(commit_code(groups[1]));  // code
-    RK_TRY(commit_group(2, groups[2], seg->group[2], taps.group_size[2]));  // data
-    // the accum mix: drawn once code and data are bound (rv32im prove_segment)
-    std::vector<uint32_t> accum_mix(seg->n_accum_mix);
-    for (uint32_t i = 0; i < seg->n_accum_mix; i++) accum_mix[i] = iop.random_elem();
-    rk_circuit_view view{};
-    view.ctx = ctx;
-    view.stream = (void*)ctx->stream;
-    view.po2 = seg->po2;
-    for (int g = 0; g < 3; g++) view.group_size[g] = taps.group_size[g];
-    view.globals = seg->globals;
-    view.n_globals = seg->n_globals;
-    view.mix = accum_mix.data();
-    view.n_mix = seg->n_accum_mix;
-    if (hook_accum) {
+    // the accum mix, drawn once code and data are bound (rv32im prove_segment); then the accum group
+    int accumulate() {
+        accum_mix.resize(seg->n_accum_mix);
+        for (uint32_t i = 0; i < seg->n_accum_mix; i++) accum_mix[i] = iop.random_elem();
+        view.ctx = ctx;
+        view.stream = (void*)ctx->stream;
+        view.po2 = seg->po2;
+        for (int g = 0; g < 3; g++) view.group_size[g] = taps.group_size[g];
+        view.globals = seg->globals;
+        view.n_globals = seg->n_globals;
+        view.mix = accum_mix.data();
+        view.n_mix = seg->n_accum_mix;
+        if (!hook_accum) return commit_group(0, groups[0], seg->group[0], taps.group_size[0]);
         // CircuitHal::accumulate: the hook writes the accum witness straight into the buffer the
         // interpolation then transforms in place
         RK_TRY(groups[0].coeffs.alloc(ctx, (size_t)taps.group_size[0] * N * 4));
@@ -499,174 +465,138 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         raw[1].release();
         raw[2].release();
         view.d_trace[1] = view.d_trace[2] = nullptr;
-    } else {
-        RK_TRY(commit_group(0, groups[0], seg->group[0], taps.group_size[0]));  // accum
+        return RK_OK;
     }
 
-    // Prover::finalize
-    const Ext poly_mix = iop.random_ext();
-    const uint32_t* check_from = nullptr;
-    if (hook_check) {
-        // CircuitHal::eval_check over the LDE domain, into the buffer that becomes the check group
-        RK_TRY(check.coeffs.alloc(ctx, 4 * D * 4));
-        for (int g = 0; g < 3; g++) view.d_lde[g] = groups[g].evaluated.u32();
-        sw.start("circuit");
-        if (hooks->eval_check) {
-            if (hooks->eval_check(hooks->user, &view, poly_mix.c, check.coeffs.u32()) != 0) {
-                ctx->last_error = "circuit hook `eval_check` failed";
-                return RK_ERR_CALLBACK;
+    // the check polynomial: evaluated by the circuit (hook or step program) under poly_mix, or the caller's stand-in
+    int check_poly() {
+        const Ext poly_mix = iop.random_ext();
+        const uint32_t* check_from = nullptr;
+        if (hook_check) {
+            // CircuitHal::eval_check over the LDE domain, into the buffer that becomes the check group
+            RK_TRY(check.coeffs.alloc(ctx, 4 * D * 4));
+            for (int g = 0; g < 3; g++) view.d_lde[g] = groups[g].evaluated.u32();
+            sw.start("circuit");
+            if (hooks->eval_check) {
+                if (hooks->eval_check(hooks->user, &view, poly_mix.c, check.coeffs.u32()) != 0) {
+                    ctx->last_error = "circuit hook `eval_check` failed";
+                    return RK_ERR_CALLBACK;
+                }
+            } else {
+                // the circuit's step program, evaluated by the library (circuit_program.hip)
+                RK_TRY(rk::program_eval_check(hooks->program, &view, poly_mix.c, check.coeffs.u32()));
             }
+            sw.stop(&ctx->timing.circuit);
+        } else if (seg->on_device == 1) {
+            RK_TRY(check.coeffs.alloc(ctx, 4 * D * 4));   // pre-computed stand-in, left untouched: read by the transform's first pass
+            check_from = seg->check;
         } else {
-            // the circuit's step program, evaluated by the library (circuit_program.hip)
-            RK_TRY(rk::program_eval_check(hooks->program, &view, poly_mix.c, check.coeffs.u32()));
+            RK_TRY(load_trace(check.coeffs, seg->check, 4 * D));  // pre-computed stand-in
         }
-        sw.stop(&ctx->timing.circuit);
-    } else if (seg->on_device == 1) {
-        RK_TRY(check.coeffs.alloc(ctx, 4 * D * 4));   // pre-computed stand-in, left untouched: read by the transform's first pass
-        check_from = seg->check;
-    } else {
-        RK_TRY(load_trace(check.coeffs, seg->check, 4 * D));  // pre-computed stand-in
+        sw.start("ntt");
+        // 4 x D evaluations -> 4 x D bit-reversed coefficients = 4 * D/N columns of N (16 for blow-up 4):
+        // part c of plane e holds the coefficients n with n mod D/N = bitrev(c) of component e, i.e.
+        // check(x) = sum_j x^j g_j(x^(D/N)) with g_j in column (D/N) e + bitrev(j) (for blow-up 4 the
+        // verifier's remap [0,2,1,3]).
+        // No zk_shift here: the hook evaluates at x_i = 3*w^i, so these already are the coefficients
+        // of y -> check(3y), the form every PolyGroup is kept in (recalled items).
+        RK_TRY(rk::ntt_reverse_from(ctx, check.coeffs.u32(), check_from ? check_from : check.coeffs.u32(), D, 4, false));
+        RK_TRY(check.build(ctx, CHECK_SIZE, N));
+        sw.stop(&ctx->timing.ntt);
+        sw.start("hash");
+        RK_TRY(check.merkle.build(ctx, check.evaluated.u32(), D, CHECK_SIZE, QUERIES));
+        sw.stop(&ctx->timing.hash);
+        return check.merkle.commit(ctx, iop);
     }
-    sw.start("ntt");
-    // 4 x D evaluations -> 4 x D bit-reversed coefficients = 4 * D/N columns of N (16 for blow-up 4):
-    // part c of plane e holds the coefficients n with n mod D/N = bitrev(c) of component e, i.e.
-    // check(x) = sum_j x^j g_j(x^(D/N)) with g_j in column (D/N) e + bitrev(j) (for blow-up 4 the
-    // verifier's remap [0,2,1,3]).
-    // No zk_shift here: the hook evaluates at x_i = 3*w^i, so these already are the coefficients
-    // of y -> check(3y), the form every PolyGroup is kept in (recalled items).
-    RK_TRY(rk::ntt_reverse_from(ctx, check.coeffs.u32(), check_from ? check_from : check.coeffs.u32(), D, 4, false));
-    RK_TRY(check.build(ctx, CHECK_SIZE, N));
-    sw.stop(&ctx->timing.ntt);
-    sw.start("hash");
-    RK_TRY(check.merkle.build(ctx, check.evaluated.u32(), D, CHECK_SIZE, QUERIES));
-    sw.stop(&ctx->timing.hash);
-    RK_TRY(check.merkle.commit(ctx, iop));
 
-    sw.start("deep");
-    Ext z = iop.random_ext();
-    uint32_t w27 = ctx->sys.root27m;
-    uint32_t back_one = bb::inv(bb::pow(w27, (uint64_t)1 << (27 - seg->po2)));
-    Ext z_pow = bb::pow(z, (uint64_t)1 << BLOW, wm);
+    const DevBuf& coeffs_of(uint32_t gid) const { return (gid < 3 ? groups[gid] : check).coeffs; }
 
-    // tap openings: every register at z * back_one^back for each of its backs
-    size_t tot_taps = 0;
-    for (uint32_t r = 0; r < taps.n_regs; r++)
-        tot_taps += taps.combo_off[taps.reg_combo[r] + 1] - taps.combo_off[taps.reg_combo[r]];
-    uint32_t max_back = 0;
-    for (uint32_t b = 0; b < taps.combo_off[taps.n_combos]; b++)
-        if (taps.combo_backs[b] > max_back) max_back = taps.combo_backs[b];
-    if (max_back > 64) return RK_ERR_INVALID;
-    // device power tables: slot b = (z*back_one^b)^k, slot max_back+1 = (z^(D/N))^k
-    size_t n_pts = (size_t)max_back + 2;
-    std::vector<Ext> pts(n_pts);
-    for (uint32_t b = 0; b <= max_back; b++) pts[b] = bb::scale(z, bb::pow(back_one, b));
-    pts[max_back + 1] = z_pow;
-    std::vector<Ext> all_xs(tot_taps), coeff_u(tot_taps + CHECK_SIZE);
-    {
+    // tap openings: every register at z * back_one^back for each of its backs, the check columns at z^(D/N); sent as the
+    // coefficients of each register's interpolating polynomial.  Opens the `deep` bracket that deep() closes.
+    int open_taps() {
+        sw.start("deep");
+        pts = rk::tap_points(ctx->sys, seg->po2, taps, iop.random_ext());
+        const size_t n_pts = pts.size(), tot_taps = rk::total_taps(taps), n_ev = tot_taps + CHECK_SIZE;
         DevBuf d_pw, d_small;
         RK_TRY(d_pw.alloc(ctx, n_pts * N * 16));
-        RK_TRY(rk::ext_powers_many(ctx, d_pw.u32(), pts.data(), n_pts, N, true));
+        RK_TRY(rk::ext_powers_many(ctx, d_pw.u32(), pts.data(), n_pts, N, true));  // table j = pts[j]^k, bit-reversed
         // every evaluation of the four groups is queued before the one download: which polynomial / which power
         // table per evaluation depend on the tap set only
-        std::vector<Ext> eval_u(tot_taps + CHECK_SIZE);
+        std::vector<Ext> all_xs, eval_u(n_ev);
         std::vector<uint32_t> which, sel;
-        std::vector<size_t> first(5, 0);
-        size_t pos = 0;
+        rk::EvalSrc srcs[4];
         uint32_t reg = 0;
         for (uint32_t gid = 0; gid < 3; gid++) {
+            const size_t first = which.size();
             for (; reg < taps.n_regs && taps.reg_group[reg] == gid; reg++) {
-                uint32_t cb = taps.reg_combo[reg];
+                const uint32_t cb = taps.reg_combo[reg];
                 for (uint32_t b = taps.combo_off[cb]; b < taps.combo_off[cb + 1]; b++) {
                     which.push_back(taps.reg_offset[reg]);
                     sel.push_back(taps.combo_backs[b]);
-                    all_xs[pos++] = pts[taps.combo_backs[b]];
+                    all_xs.push_back(pts[taps.combo_backs[b]]);
                 }
             }
-            first[gid + 1] = pos;
+            srcs[gid] = rk::EvalSrc{coeffs_of(gid).u32(), which.size() - first};
         }
         for (uint32_t i = 0; i < CHECK_SIZE; i++) {
             which.push_back(i);
-            sel.push_back(max_back + 1);
+            sel.push_back((uint32_t)n_pts - 1);
         }
-        first[4] = pos + CHECK_SIZE;
-        const size_t n_ev = first[4];
+        srcs[3] = rk::EvalSrc{check.coeffs.u32(), CHECK_SIZE};
         RK_TRY(d_small.alloc(ctx, n_ev * 16));
-        uint32_t* d_out = d_small.u32();
-        rk::EvalSrc srcs[4];
-        for (uint32_t gid = 0; gid < 4; gid++)
-            srcs[gid] = rk::EvalSrc{(gid < 3 ? groups[gid] : check).coeffs.u32(), first[gid + 1] - first[gid]};
-        RK_TRY(rk::eval_dot(ctx, d_out, N, srcs, 4, which.data(), sel.data(), d_pw.u32()));
-        RK_TRY(d2h_sync(ctx, eval_u.data(), d_out, n_ev * 16));
+        RK_TRY(rk::eval_dot(ctx, d_small.u32(), N, srcs, 4, which.data(), sel.data(), d_pw.u32()));
+        RK_TRY(d2h_sync(ctx, eval_u.data(), d_small.u32(), n_ev * 16));
         // registers -> coefficients of their interpolating polynomials
+        coeff_u.resize(n_ev);
         size_t p = 0;
         for (uint32_t r = 0; r < taps.n_regs; r++) {
-            uint32_t cb = taps.reg_combo[r];
-            size_t sz = taps.combo_off[cb + 1] - taps.combo_off[cb];
+            const size_t sz = rk::reg_taps(taps, r);
             poly_interpolate(&coeff_u[p], &all_xs[p], &eval_u[p], sz, wm);
             p += sz;
         }
         for (uint32_t i = 0; i < CHECK_SIZE; i++) coeff_u[tot_taps + i] = eval_u[tot_taps + i];
+        uint32_t digest[8];
+        iop.write((const uint32_t*)coeff_u.data(), coeff_u.size() * 4);
+        kc.hash_elems((const uint32_t*)coeff_u.data(), coeff_u.size() * 4, digest);
+        iop.commit(digest);
+        return RK_OK;
     }
-    iop.write((const uint32_t*)coeff_u.data(), coeff_u.size() * 4);
-    kc.hash_elems((const uint32_t*)coeff_u.data(), coeff_u.size() * 4, digest);
-    iop.commit(digest);
 
-    // DEEP: mix all columns into one polynomial per combo, remove the openings, divide
-    Ext mix = iop.random_ext();
-    const size_t combo_count = taps.n_combos;
-    DevBuf combos;
-    RK_TRY(combos.alloc(ctx, (combo_count + 1) * N * 16));
-    {
-        // one pass over the four coefficient buffers writes every (combo, coefficient) once; the check columns mix
-        // into a combo of their own behind the tap set's
-        std::vector<uint32_t> which(taps.n_regs + CHECK_SIZE, (uint32_t)combo_count);
-        for (uint32_t r = 0; r < taps.n_regs; r++) which[r] = taps.reg_combo[r];
-        rk::MixSrc srcs[4];
-        size_t at = 0;
-        for (uint32_t gid = 0; gid < 4; gid++) {
-            const size_t n = gid < 3 ? taps.group_size[gid] : CHECK_SIZE;
-            srcs[gid] = rk::MixSrc{(gid < 3 ? groups[gid] : check).coeffs.u32(), which.data() + at, n};
-            at += n;
-        }
-        if (at != which.size()) return RK_ERR_INVALID;
-        RK_TRY(rk::mix_poly_coeffs(ctx, combos.u32(), bb::ext_one(), mix, srcs, 4, N, combo_count + 1));
-        // inputs were bit-reversed, so are the mixed polynomials: natural order for the division
-        RK_TRY(rk::bit_reverse_ext(ctx, combos.u32(), N, combo_count + 1));
-    }
-    DevBuf d_rems;
-    {
-        // combos[size*combo + i] -= cur * coeff_u[...]: accumulate per touched coefficient on the host
-        std::vector<Ext> delta((combo_count + 1) * (max_back + 2), bb::ext_zero());
-        std::vector<uint32_t> delta_idx;
-        size_t stride = (size_t)max_back + 2;
-        Ext cur = bb::ext_one();
-        size_t cur_pos = 0;
-        for (uint32_t r = 0; r < taps.n_regs; r++) {
-            uint32_t cb = taps.reg_combo[r];
-            size_t sz = taps.combo_off[cb + 1] - taps.combo_off[cb];
-            if (sz > stride || sz > N) return RK_ERR_INVALID;
-            for (size_t i = 0; i < sz; i++)
-                delta[cb * stride + i] = bb::add(delta[cb * stride + i], bb::mul(cur, coeff_u[cur_pos + i], wm));
-            cur = bb::mul(cur, mix, wm);
-            cur_pos += sz;
-        }
-        for (uint32_t i = 0; i < CHECK_SIZE; i++) {
-            delta[combo_count * stride] = bb::add(delta[combo_count * stride], bb::mul(cur, coeff_u[cur_pos++], wm));
-            cur = bb::mul(cur, mix, wm);
-        }
-        std::vector<Ext> dl;
-        for (size_t c = 0; c <= combo_count; c++) {
-            size_t sz = c < combo_count ? taps.combo_off[c + 1] - taps.combo_off[c] : 1;
-            for (size_t i = 0; i < sz; i++) {
-                delta_idx.push_back((uint32_t)(c * N + i));
-                dl.push_back(delta[c * stride + i]);
+    // DEEP: mix all columns into one polynomial per combo, remove the openings, divide, sum into final_poly
+    int deep() {
+        const Ext mix = iop.random_ext();
+        const size_t combo_count = taps.n_combos;
+        DevBuf combos;
+        RK_TRY(combos.alloc(ctx, (combo_count + 1) * N * 16));
+        {
+            // one pass over the four coefficient buffers writes every (combo, coefficient) once; the check columns mix
+            // into a combo of their own behind the tap set's
+            std::vector<uint32_t> which(taps.n_regs + CHECK_SIZE, (uint32_t)combo_count);
+            for (uint32_t r = 0; r < taps.n_regs; r++) which[r] = taps.reg_combo[r];
+            rk::MixSrc srcs[4];
+            size_t at = 0;  // ends at which.size(): check_taps made the group sizes add up to n_regs
+            for (uint32_t gid = 0; gid < 4; gid++) {
+                const size_t n = gid < 3 ? taps.group_size[gid] : CHECK_SIZE;
+                srcs[gid] = rk::MixSrc{coeffs_of(gid).u32(), which.data() + at, n};
+                at += n;
             }
+            RK_TRY(rk::mix_poly_coeffs(ctx, combos.u32(), bb::ext_one(), mix, srcs, 4, N, combo_count + 1));
+            // inputs were bit-reversed, so are the mixed polynomials: natural order for the division
+            RK_TRY(rk::bit_reverse_ext(ctx, combos.u32(), N, combo_count + 1));
         }
-        RK_TRY(rk::ext_sub_at(ctx, combos.u32(), delta_idx.data(), dl.data(), dl.size()));
+        {
+            // combos[c * N + i] -= coefficient i of combo c's folded openings (prove_segment checked that they fit in N)
+            const std::vector<Ext> cu = rk::combo_u(taps, coeff_u, mix, CHECK_SIZE, wm);
+            std::vector<uint32_t> at;
+            for (size_t c = 0; c < combo_count; c++)
+                for (size_t i = 0; i < rk::combo_taps(taps, c); i++) at.push_back((uint32_t)(c * N + i));
+            at.push_back((uint32_t)(combo_count * N));
+            RK_TRY(rk::ext_sub_at(ctx, combos.u32(), at.data(), cu.data(), cu.size()));
+        }
         // divide every combo by (x - z*w^-back) for each of its backs and the check combo by
-        // (x - z^4): round j handles the j-th back of every combo that has one, in one batch
+        // (x - z^(D/N)): round j handles the j-th back of every combo that has one, in one batch
         size_t max_sz = 1;
-        for (size_t c = 0; c < combo_count; c++) max_sz = std::max<size_t>(max_sz, taps.combo_off[c + 1] - taps.combo_off[c]);
+        for (size_t c = 0; c < combo_count; c++) max_sz = std::max(max_sz, rk::combo_taps(taps, c));
         // every round's remainders, read with the next download the transcript needs anyway (FRI's last polynomial)
         RK_TRY(d_rems.alloc(ctx, max_sz * (combo_count + 1) * 16));
         size_t n_rems = 0;
@@ -674,15 +604,14 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
             std::vector<size_t> offs;
             std::vector<Ext> zs;
             for (size_t c = 0; c < combo_count; c++) {
-                size_t sz = taps.combo_off[c + 1] - taps.combo_off[c];
-                if (j < sz) {
+                if (j < rk::combo_taps(taps, c)) {
                     offs.push_back(c * N);
                     zs.push_back(pts[taps.combo_backs[taps.combo_off[c] + j]]);
                 }
             }
             if (j == 0) {
                 offs.push_back(combo_count * N);
-                zs.push_back(z_pow);
+                zs.push_back(pts.back());
             }
             RK_TRY(rk::poly_divide_many(ctx, combos.u32(), N, offs.data(), zs.data(), offs.size(), nullptr,
                                         d_rems.u32() + n_rems * 4));
@@ -690,96 +619,113 @@ int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& sea
         }
         rems.resize(n_rems);
         RK_HIP_TRY(ctx, hipMemcpyAsync(rems.data(), d_rems.p, n_rems * 16, hipMemcpyDeviceToHost, ctx->stream));
+        RK_TRY(final_poly.alloc(ctx, N * 16));
+        RK_TRY(rk::eltwise_sum_ext(ctx, final_poly.u32(), combos.u32(), N, combo_count + 1));
+        RK_TRY(rk::bit_reverse(ctx, final_poly.u32(), N, 4));
+        combos.release();
+        sw.stop(&ctx->timing.deep);
+        return RK_OK;
     }
-    DevBuf final_poly;
-    RK_TRY(final_poly.alloc(ctx, N * 16));
-    RK_TRY(rk::eltwise_sum_ext(ctx, final_poly.u32(), combos.u32(), N, combo_count + 1));
-    RK_TRY(rk::bit_reverse(ctx, final_poly.u32(), N, 4));
-    combos.release();
-    sw.stop(&ctx->timing.deep);
 
-    // ---- fri_prove ----
-    sw.start("fri");
-    struct Round {
-        size_t domain;
-        DevBuf coeffs, evaluated;
-        size_t coeffs_words;
-        MerkleDev merkle;
-    };
-    std::vector<std::unique_ptr<Round>> rounds;
-    const uint32_t* cur_coeffs = final_poly.u32();
-    size_t cur_words = N * 4;
-    const size_t orig_domain = D;
-    while (cur_words / 4 > FRI_MIN_DEGREE && cur_words / 4 >= FRI_FOLD) {
-        std::unique_ptr<Round> r(new Round());
-        size_t size = cur_words / 4, domain = size << BLOW;
-        r->domain = domain;
-        RK_TRY(r->evaluated.alloc(ctx, domain * 16));
-        RK_TRY(rk::ntt_forward(ctx, r->evaluated.u32(), cur_coeffs, size, 4, BLOW));
-        RK_TRY(r->merkle.build(ctx, r->evaluated.u32(), domain / FRI_FOLD, FRI_FOLD * 4, QUERIES));
-        RK_TRY(r->merkle.commit(ctx, iop));
-        Ext fold_mix = iop.random_ext();
-        r->coeffs_words = size / FRI_FOLD * 4;
-        RK_TRY(r->coeffs.alloc(ctx, r->coeffs_words * 4));
-        RK_TRY(rk::fri_fold(ctx, r->coeffs.u32(), cur_coeffs, size / FRI_FOLD, fold_mix));
-        cur_coeffs = r->coeffs.u32();
-        cur_words = r->coeffs_words;
-        rounds.push_back(std::move(r));
-    }
-    {
-        DevBuf fin;
-        RK_TRY(fin.alloc(ctx, cur_words * 4));
-        RK_HIP_TRY(ctx, hipMemcpyAsync(fin.p, cur_coeffs, cur_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        RK_TRY(rk::bit_reverse(ctx, fin.u32(), cur_words / 4, 4));
-        std::vector<uint32_t> h(cur_words);
-        RK_TRY(d2h_sync(ctx, h.data(), fin.p, cur_words * 4));
-        for (const Ext& rem : rems)  // queued after the DEEP divisions: every division was exact
-            if (!bb::eq(rem, bb::ext_zero())) return RK_ERR_INTERNAL;
-        iop.write(h.data(), h.size());
-        kc.hash_elems(h.data(), h.size(), digest);
-        iop.commit(digest);
-    }
-    if (shape.pow_bits) {
-        // proof of work before the query positions exist (Plonky3 `grind`; risc0's parameter set has none):
-        // the nonce goes into the seal and, hashed, into the transcript
-        uint32_t nonce = 0;
-        RK_TRY(rk::pow_grind(ctx, iop.rng.cells, shape.pow_bits, &nonce));
-        iop.write(&nonce, 1);
-        kc.hash_elems(&nonce, 1, digest);
-        iop.commit(digest);
-        if (iop.random_bits(shape.pow_bits) != 0) return RK_ERR_INTERNAL;
-    }
-    sw.stop(&ctx->timing.fri);
-
-    // ---- queries: positions depend only on the sponge, so all openings are gathered in bulk ----
-    sw.start("query");
-    std::vector<uint32_t> pos0(QUERIES);
-    for (size_t q = 0; q < QUERIES; q++) pos0[q] = iop.random_bits(log2u(orig_domain)) % (uint32_t)orig_domain;
-    Openings og[3], ocheck;
-    std::vector<Openings> oround(rounds.size());
-    {
-        std::vector<OpenJob> jobs;
-        for (int g = 0; g < 3; g++) jobs.push_back(OpenJob{&groups[g].merkle, pos0, &og[g]});
-        jobs.push_back(OpenJob{&check.merkle, pos0, &ocheck});
-        std::vector<uint32_t> pos = pos0;
-        for (size_t k = 0; k < rounds.size(); k++) {
-            for (size_t q = 0; q < QUERIES; q++) pos[q] %= (uint32_t)(rounds[k]->domain / FRI_FOLD);
-            jobs.push_back(OpenJob{&rounds[k]->merkle, pos, &oround[k]});
+    // fri_prove: the commit rounds, the final polynomial, proof of work
+    int fri() {
+        sw.start("fri");
+        uint32_t digest[8];
+        std::vector<size_t> sizes;
+        const size_t final_degree = rk::fri_walk(N, shape, [&](size_t size, size_t) { sizes.push_back(size); });
+        const uint32_t* cur_coeffs = final_poly.u32();
+        for (size_t size : sizes) {
+            std::unique_ptr<Round> r(new Round());
+            const size_t domain = size << BLOW;
+            r->domain = domain;
+            RK_TRY(r->evaluated.alloc(ctx, domain * 16));
+            RK_TRY(rk::ntt_forward(ctx, r->evaluated.u32(), cur_coeffs, size, 4, BLOW));
+            RK_TRY(r->merkle.build(ctx, r->evaluated.u32(), domain / FRI_FOLD, FRI_FOLD * 4, QUERIES));
+            RK_TRY(r->merkle.commit(ctx, iop));
+            Ext fold_mix = iop.random_ext();
+            r->coeffs_words = size / FRI_FOLD * 4;
+            RK_TRY(r->coeffs.alloc(ctx, r->coeffs_words * 4));
+            RK_TRY(rk::fri_fold(ctx, r->coeffs.u32(), cur_coeffs, size / FRI_FOLD, fold_mix));
+            cur_coeffs = r->coeffs.u32();
+            rounds.push_back(std::move(r));
         }
-        RK_TRY(open_many(ctx, jobs));
+        {
+            const size_t cur_words = final_degree * 4;
+            DevBuf fin;
+            RK_TRY(fin.alloc(ctx, cur_words * 4));
+            RK_HIP_TRY(ctx, hipMemcpyAsync(fin.p, cur_coeffs, cur_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            RK_TRY(rk::bit_reverse(ctx, fin.u32(), final_degree, 4));
+            std::vector<uint32_t> h(cur_words);
+            RK_TRY(d2h_sync(ctx, h.data(), fin.p, cur_words * 4));
+            for (const Ext& rem : rems)  // queued after the DEEP divisions: every division was exact
+                if (!bb::eq(rem, bb::ext_zero())) return RK_ERR_INTERNAL;
+            iop.write(h.data(), h.size());
+            kc.hash_elems(h.data(), h.size(), digest);
+            iop.commit(digest);
+        }
+        if (shape.pow_bits) {
+            // proof of work before the query positions exist (Plonky3 `grind`; risc0's parameter set has none):
+            // the nonce goes into the seal and, hashed, into the transcript
+            uint32_t nonce = 0;
+            RK_TRY(rk::pow_grind(ctx, iop.rng.cells, shape.pow_bits, &nonce));
+            iop.write(&nonce, 1);
+            kc.hash_elems(&nonce, 1, digest);
+            iop.commit(digest);
+            if (iop.random_bits(shape.pow_bits) != 0) return RK_ERR_INTERNAL;
+        }
+        sw.stop(&ctx->timing.fri);
+        return RK_OK;
     }
-    for (size_t q = 0; q < QUERIES; q++) {
-        for (int g = 0; g < 3; g++) write_opening(iop, groups[g].merkle, og[g], q);
-        write_opening(iop, check.merkle, ocheck, q);
-        for (size_t k = 0; k < rounds.size(); k++) write_opening(iop, rounds[k]->merkle, oround[k], q);
+
+    // positions depend only on the sponge, so all openings are gathered in bulk
+    int queries() {
+        sw.start("query");
+        std::vector<uint32_t> pos0(QUERIES);
+        for (size_t q = 0; q < QUERIES; q++) pos0[q] = iop.random_bits(log2u(D)) % (uint32_t)D;
+        Openings og[3], ocheck;
+        std::vector<Openings> oround(rounds.size());
+        {
+            std::vector<OpenJob> jobs;
+            for (int g = 0; g < 3; g++) jobs.push_back(OpenJob{&groups[g].merkle, pos0, &og[g]});
+            jobs.push_back(OpenJob{&check.merkle, pos0, &ocheck});
+            std::vector<uint32_t> pos = pos0;
+            for (size_t k = 0; k < rounds.size(); k++) {
+                for (size_t q = 0; q < QUERIES; q++) pos[q] %= (uint32_t)(rounds[k]->domain / FRI_FOLD);
+                jobs.push_back(OpenJob{&rounds[k]->merkle, pos, &oround[k]});
+            }
+            RK_TRY(open_many(ctx, jobs));
+        }
+        for (size_t q = 0; q < QUERIES; q++) {
+            for (int g = 0; g < 3; g++) write_opening(iop, groups[g].merkle, og[g], q);
+            write_opening(iop, check.merkle, ocheck, q);
+            for (size_t k = 0; k < rounds.size(); k++) write_opening(iop, rounds[k]->merkle, oround[k], q);
+        }
+        sw.stop(&ctx->timing.query);
+        return RK_OK;
     }
-    sw.stop(&ctx->timing.query);
-    if (total_bracket < sw.used.size()) {  // the outermost bracket was opened first and closes last
-        sw.used[total_bracket].acc = &ctx->timing.total;
-        (void)hipEventRecord(sw.used[total_bracket].b, ctx->stream);
+};
+
+int prove_segment(rk_ctx* ctx, const rk_segment* seg, std::vector<uint32_t>& seal) {
+    const rk_taps& taps = seg->taps;
+    RK_TRY(rk::check_taps(taps));
+    const rk::Shape shape = ctx->sys.shape();
+    if (!rk::shape_ok(shape) || seg->po2 < 1 || seg->po2 + shape.blowup_log2 > ntt::LAMBDA) return RK_ERR_INVALID;
+    const rk_circuit_hooks* hooks = seg->hooks;
+    const bool hook_accum = hooks && hooks->accumulate, hook_check = hooks && (hooks->eval_check || hooks->program);
+    for (int g = 0; g < 3; g++) {
+        if (taps.group_size[g] == 0) return RK_ERR_INVALID;
+        if (!seg->group[g] && !(g == 0 && hook_accum)) return RK_ERR_INVALID;
     }
-    seal.swap(iop.proof);
-    return RK_OK;
+    if ((!seg->check && !hook_check) || (seg->n_globals && !seg->globals)) return RK_ERR_INVALID;
+    if (seg->n_accum_mix > (1u << 16)) return RK_ERR_INVALID;
+    // a combo's folded openings are subtracted from a mixed polynomial of 2^po2 coefficients: they must fit (asked of
+    // every combo, named by a register or not: `deep` indexes all of them).  check_taps already gives the rest of what
+    // the stages rely on: every back <= 64; a combo's backs distinct, so at most max_back + 1 of them; group sizes
+    // adding up to n_regs.
+    for (uint32_t c = 0; c < taps.n_combos; c++)
+        if (rk::combo_taps(taps, c) > ((size_t)1 << seg->po2)) return RK_ERR_INVALID;
+    SegmentRun run(ctx, seg, shape);
+    return run.prove(seal);
 }
 
 }  // namespace

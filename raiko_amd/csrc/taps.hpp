@@ -1,5 +1,6 @@
-// Host-only shape checks of the C ABI: TapSet validation and the seal-size bound.  No HIP
-// dependency, so tests/asan/ can build exactly this code with -fsanitize=address on the CPU.
+// Host-only shape checks of the C ABI: TapSet validation, the integer facts of a seal's shape that prover,
+// verifier and bound share, and the seal-size bound.  No HIP dependency, so tests/asan/ can build exactly
+// this code with -fsanitize=address on the CPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,7 +35,6 @@ inline int check_taps(const rk_taps& t) {
     return RK_OK;
 }
 
-
 // the protocol shape of a segment proof (rk_params): risc0's by default
 struct Shape {
     uint32_t queries = 50, blowup_log2 = 2, fold_log2 = 4, min_degree = 256, pow_bits = 0;
@@ -44,36 +44,69 @@ inline bool shape_ok(const Shape& s) {
            s.fold_log2 <= 4 && s.min_degree >= 1 && !(s.min_degree & (s.min_degree - 1)) && s.pow_bits <= 24;
 }
 
+// ---- the integer facts of a seal's shape, stated once for MerkleDev / TreeVerifier, the prover's and the verifier's
+// FRI loops and the bound below.  Tap sets are assumed to have passed check_taps.
+inline size_t ceil_log2(size_t n) {
+    size_t k = 0;
+    while (((size_t)1 << k) < n) k++;
+    return k;
+}
+inline size_t combo_taps(const rk_taps& t, size_t c) { return t.combo_off[c + 1] - t.combo_off[c]; }
+inline size_t reg_taps(const rk_taps& t, uint32_t r) { return combo_taps(t, t.reg_combo[r]); }
+inline size_t total_taps(const rk_taps& t) {
+    size_t n = 0;
+    for (uint32_t r = 0; r < t.n_regs; r++) n += reg_taps(t, r);
+    return n;
+}
+inline uint32_t max_back(const rk_taps& t) {
+    uint32_t m = 0;
+    for (uint32_t b = 0; b < t.combo_off[t.n_combos]; b++)
+        if (t.combo_backs[b] > m) m = t.combo_backs[b];
+    return m;
+}
+// MerkleTreeParams: the layer sent as a tree's cap is the largest i < layers with 2^i <= queries (0: the root alone)
+inline size_t merkle_top_layer(size_t rows, size_t queries) {
+    const size_t layers = ceil_log2(rows);
+    size_t top_layer = 0;
+    for (size_t i = 1; i < layers; i++) {
+        if (((size_t)1 << i) > queries) break;
+        top_layer = i;
+    }
+    return top_layer;
+}
+// fri_prove's loop: per_round(size, domain) for every round that commits a polynomial of `size` coefficients on its
+// `domain` = size << blow-up points and folds it; returns the degree of the final polynomial
+template <class F>
+inline size_t fri_walk(size_t n, const Shape& sh, F&& per_round) {
+    const size_t fold = (size_t)1 << sh.fold_log2;
+    size_t size = n;
+    while (size > sh.min_degree && size >= fold) {
+        per_round(size, size << sh.blowup_log2);
+        size /= fold;
+    }
+    return size;
+}
+
 // upper bound on the seal words of a segment under a protocol shape; 0 for one rk_prove_segment would reject
 inline size_t seal_bound_words(const rk_segment* seg, const Shape& sh = Shape()) {
     if (!seg || !shape_ok(sh) || seg->po2 < 1 || seg->po2 + sh.blowup_log2 > MAX_PO2_PLUS_2) return 0;
     const rk_taps& t = seg->taps;
     if (check_taps(t) != RK_OK) return 0;
-    auto lg = [](size_t n) {
-        size_t k = 0;
-        while (((size_t)1 << k) < n) k++;
-        return k;
-    };
-    const size_t queries = sh.queries, blow = (size_t)1 << sh.blowup_log2, fold = (size_t)1 << sh.fold_log2;
-    const size_t check_size = 4 * blow;
-    size_t N = (size_t)1 << seg->po2, D = blow * N;
-    size_t layers = lg(D);
+    const size_t queries = sh.queries, fold = (size_t)1 << sh.fold_log2;
+    const size_t check_size = (size_t)4 << sh.blowup_log2;
+    const size_t N = (size_t)1 << seg->po2, D = N << sh.blowup_log2;
+    const size_t layers = ceil_log2(D);
+    const size_t w_all = (size_t)t.group_size[0] + t.group_size[1] + t.group_size[2] + check_size;
+    // no tree's cap is wider than that of a tree too tall to limit it, and no path longer than the whole height
+    const size_t top = (size_t)1 << merkle_top_layer((size_t)1 << (8 * sizeof(size_t) - 1), queries);
     size_t words = (size_t)seg->n_globals + 1;
-    size_t tot_taps = 0;
-    for (uint32_t r = 0; r < t.n_regs; r++) tot_taps += t.combo_off[t.reg_combo[r] + 1] - t.combo_off[t.reg_combo[r]];
-    size_t w_all = (size_t)t.group_size[0] + t.group_size[1] + t.group_size[2] + check_size;
-    size_t top = 1;                           // Merkle cap: the largest power of two <= queries
-    while (top * 2 <= queries) top *= 2;
     words += 4 * top * 8;                     // top layers of the four trace trees
-    words += (tot_taps + check_size) * 4;     // coeff_u
+    words += (total_taps(t) + check_size) * 4;     // coeff_u
     words += queries * (w_all + 4 * layers * 8);   // trace openings
-    size_t size = N;
-    while (size > sh.min_degree && size >= fold) {   // fri_prove's loop
-        size_t domain = size * blow;
-        words += top * 8 + queries * (fold * 4 + lg(domain / fold) * 8);
-        size /= fold;
-    }
-    words += size * 4;
+    const size_t final_degree = fri_walk(N, sh, [&](size_t, size_t domain) {
+        words += top * 8 + queries * (fold * 4 + ceil_log2(domain / fold) * 8);
+    });
+    words += final_degree * 4;
     return words + 64;                        // + the proof-of-work nonce and slack
 }
 inline size_t seal_bound_words(const rk_segment* seg, size_t queries) {
