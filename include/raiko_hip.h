@@ -667,6 +667,49 @@ int rk_exec_rv32im_sizes(const rk_exec* ex, uint32_t index, size_t* muldiv_rows)
 int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32_t* d_cpu, uint32_t* d_program,
                                 size_t program_rows, uint32_t* d_register, uint32_t* d_byte, uint32_t* d_range,
                                 uint32_t* d_shift, uint32_t* d_muldiv, size_t muldiv_rows);
+/* THE RV32IM-ELF CHIP SET: rv32im's statement with the program bound to the ELF (raiko_amd/rv32elf.py builds the same
+ * tables in numpy and writes the AIRs).  What a shard cannot change is PREPROCESSED -- committed once per ELF by
+ * rk_p3_setup into a key, whose root names the program to the verifier -- and a shard's trace keeps what it decides:
+ *   cpu, register, muldiv   rv32im's tables, word for word
+ *   program   preprocessed RK_RV32ELF_PROGRAM_PREP_COLS columns per word of the program image: the 41 fields an rv32im
+ *             cpu row looks up, in that order, and VALID (1 where a cpu row may look the word up); trace: 1 column, how
+ *             often the shard ran the word.  The one constraint: count * (1 - VALID) = 0
+ *   byte      preprocessed (op, x, y, x op y), 2^RK_RV32_BYTE_LOG_ROWS rows; trace: the count
+ *   range     preprocessed v = 0 .. 65535; trace: the count
+ *   shift     preprocessed (k, x, lo, hi), 2^RK_RV32CF_SHIFT_LOG_ROWS rows; trace: the count
+ * THE PROGRAM IMAGE: the words of every PT_LOAD segment with PF_X set and file bytes, in program-header order, each
+ * segment's file bytes zero-padded to whole words; its rows are padded to a power of two >= 2 with the row of word 0 at
+ * pc 0.  rk_exec_program_image lists it with the loader's own walk of the program headers (host only): *n_segs /
+ * *n_words are set whenever the file is well formed, RK_ERR_CAPACITY when either buffer is too small (call again) or
+ * the file has more than RK_RV32ELF_MAX_SEGMENTS executable segments, RK_ERR_INVALID for a file rk_exec_open refuses, a
+ * misaligned executable segment or executable segments that overlap.
+ * WHAT SETUP IS TRUSTED FOR: rv32im proves every decoded field from the word's bits inside each proof; here the decode
+ * is done once, by rk_rv32elf_prep_device, outside any proof.  A verifier trusts a root exactly as far as it trusts
+ * whoever derived it from the ELF.  In exchange every executed (pc, word) is a row of that image -- a pc outside it or a
+ * word a store changed cannot be proven -- and all shards of a run answer to one root.
+ * CONSTRAINED / FREE: as rv32im (free: loads, stores and memory; the a0 an ecall leaves).
+ * rk_rv32elf_prep_device: the four preprocessed matrices, row-major Montgomery words, written on the ctx stream into
+ * device buffers of program_rows x 42, 2^18 x 4, 2^16 x 1 and 2^12 x 4 words (seg_vaddr / seg_words / words: host
+ * memory, as rk_exec_program_image gives them); returns when they are complete: hand them to rk_p3_setup as on_device
+ * matrices.  program_rows must be the power of two >= max(2, n_words): RK_ERR_CAPACITY otherwise; more than
+ * RK_RV32ELF_MAX_SEGMENTS segments or seg_words that do not sum to n_words: RK_ERR_INVALID; both before any launch.
+ * rk_exec_rv32elf_shard_device: segment `index` as the seven traces -- rv32im's cpu, register and muldiv tables and the
+ * four count columns (program_rows, 2^18, 2^16, 2^12 words) -- by rv32im's pipeline: a cycle is counted at the image row
+ * of its pc and its word compared with d_image_words (the image's words in device memory, n_words of them in segment
+ * order).  RK_ERR_INVALID when a cycle ran a pc outside the image or a word that is not the image's; sizes, capacities
+ * (program_rows as above, muldiv_rows as rk_exec_rv32im_shard_device) and stream behaviour as for
+ * rk_exec_rv32im_shard_device: everything is refused before the first launch when a size is wrong. */
+#define RK_RV32ELF_MAX_SEGMENTS 16
+#define RK_RV32ELF_PROGRAM_PREP_COLS 42
+int rk_exec_program_image(const uint8_t* elf, size_t elf_bytes, uint32_t* seg_vaddr, uint32_t* seg_words, size_t seg_capacity,
+                          size_t* n_segs, uint32_t* words, size_t word_capacity, size_t* n_words);
+int rk_rv32elf_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                           const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                           uint32_t* d_range, uint32_t* d_shift);
+int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                 const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                 uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                 uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 
@@ -1052,6 +1095,17 @@ typedef struct {
     const rk_params* params;       /* NULL = the SP1 preset */
 } rk_p3_session_opts;
 int rk_p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t n, size_t* failed_index);
+/* rk_p3_prove_shards under a key (rk_p3_setup): the way shards whose tables have preprocessed columns go through the pool.
+ * keys[d] = the key for the d-th device AS THE CALLER LISTED THEM in opts->devices (one entry, for opts->device, when
+ * n_devices == 0); keys == NULL is rk_p3_prove_shards.  Workers prove with rk_p3_prove_key, verifiers check with
+ * rk_p3_verify_key against the keys' root.  A key is read-only after rk_p3_setup, which drains its stream before it
+ * returns: any number of contexts of its GPU may read one key concurrently, which is what the pool's slots do.
+ * RK_ERR_INVALID before any context is created or configured: a NULL entry, a key of another GPU than its slot's, keys
+ * whose roots differ from each other (or some with a root and some without), a key made under another parameter set
+ * than opts->params, a shard whose table count, prep_width or -- where prep_width > 0 -- log_height is not the key's
+ * (*failed_index = that shard).  A key over tables without preprocessed columns gives rk_p3_prove_shards' exact proofs. */
+int rk_p3_prove_shards_key(const rk_p3_session_opts* opts, const rk_p3_key* const* keys, rk_p3_shard* shards, size_t n,
+                           size_t* failed_index);
 /* wall-clock per stage of the last rk_p3_prove on this ctx, milliseconds (the stream is drained at every boundary) */
 typedef struct { float lde, commit, quotient, open, fri, query, total, perm /* permutation traces + their LDE */; } rk_p3_timing;
 int rk_p3_last_timing(rk_ctx* ctx, rk_p3_timing* out);

@@ -87,6 +87,8 @@ pub const RK_RV32IM_CPU_COLS: u32 = 132;
 pub const RK_RV32IM_PROGRAM_COLS: u32 = 101;
 pub const RK_RV32IM_MULDIV_COLS: u32 = 78;
 pub const RK_RV32IM_MULDIV_MIN_LOG_ROWS: u32 = 1;
+pub const RK_RV32ELF_MAX_SEGMENTS: u32 = 16;
+pub const RK_RV32ELF_PROGRAM_PREP_COLS: u32 = 42;
 
 #[repr(C)]
 pub struct rk_air {
@@ -599,6 +601,9 @@ extern "C" {
     pub fn rk_exec_rv32cf_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
     pub fn rk_exec_rv32im_sizes(ex: *const rk_exec, index: u32, muldiv_rows: *mut usize) -> c_int;
     pub fn rk_exec_rv32im_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, d_cpu: *mut u32, d_program: *mut u32, program_rows: usize, d_register: *mut u32, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize) -> c_int;
+    pub fn rk_exec_program_image(elf: *const u8, elf_bytes: usize, seg_vaddr: *mut u32, seg_words: *mut u32, seg_capacity: usize, n_segs: *mut usize, words: *mut u32, word_capacity: usize, n_words: *mut usize) -> c_int;
+    pub fn rk_rv32elf_prep_device(ctx: *mut rk_ctx, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, words: *const u32, n_words: usize, d_program: *mut u32, program_rows: usize, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
+    pub fn rk_exec_rv32elf_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;
@@ -637,6 +642,7 @@ extern "C" {
     pub fn rk_fri_transcript_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, layout: *const u32, n_matrices: u32, ops: *const u32, n_ops: u32, d_fold_publics: *const u32, d_fold_records: *const u32, d_reduce_publics: *const u32, d_inputs: *const u32, d_roots: *const u32, d_paths: *const u32, d_observed: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_reduce: *mut u32, reduce_capacity: usize, d_ipath: *mut u32, ipath_capacity: usize, d_transcript: *mut u32, transcript_capacity: usize, d_bits: *mut u32, bits_capacity: usize, d_chip: *mut u32, chip_capacity: usize, d_state: *mut u32, state_capacity: usize) -> c_int;
     pub fn rk_p3_proof_bound_words(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
     pub fn rk_p3_prove_shards(opts: *const rk_p3_session_opts, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
+    pub fn rk_p3_prove_shards_key(opts: *const rk_p3_session_opts, keys: *const *const rk_p3_key, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
     pub fn rk_p3_last_timing(ctx: *mut rk_ctx, out: *mut rk_p3_timing) -> c_int;
     pub fn rk_last_timing(ctx: *mut rk_ctx, out: *mut rk_timing) -> c_int;
     pub fn rk_set_kernel_timing(ctx: *mut rk_ctx, enabled: c_int) -> c_int;

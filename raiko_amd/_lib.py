@@ -287,6 +287,13 @@ SYMBOLS = {
     "rk_exec_rv32im_sizes": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]),
     "rk_exec_rv32im_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rk_exec_program_image": (C.c_int, [C.c_char_p, C.c_size_t, u32p, u32p, C.c_size_t, C.POINTER(C.c_size_t), u32p, C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
+    "rk_rv32elf_prep_device": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, u32p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "rk_exec_rv32elf_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t]),
     "rk_exec_error": (C.c_char_p, [C.c_void_p]),
     "rk_exec_free": (C.c_int, [C.c_void_p]),
     "rk_program_create": (C.c_int, [_vp, _sz, _u32, C.POINTER(RkTaps), C.POINTER(_vp)]),
@@ -339,6 +346,7 @@ SYMBOLS = {
                                                 _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "rk_p3_last_timing": (C.c_int, [_vp, C.POINTER(RkP3Timing)]),
     "rk_p3_prove_shards": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
+    "rk_p3_prove_shards_key": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(_vp), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
     "rk_comm_unique_id": (C.c_int, [C.c_char_p]),
     "rk_comm_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "rk_comm_destroy": (C.c_int, [_vp]),

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/raiko_hip.h"
+#include "elf_image.hpp"
 #include "executor.hpp"
 #include "internal.hpp"
 #include "rv32_rows.hpp"
@@ -131,24 +132,10 @@ struct rk_exec {
 namespace {
 
 int load_elf(Machine& m, const uint8_t* elf, size_t n, std::string& err) {
-    auto rd16 = [&](size_t o) { return (uint32_t)elf[o] | (uint32_t)elf[o + 1] << 8; };
-    auto rd32 = [&](size_t o) { return rd16(o) | rd16(o + 2) << 16; };
-    if (n < 52 || std::memcmp(elf, "\x7f" "ELF", 4) != 0) { err = "not an ELF file"; return RK_ERR_INVALID; }
-    if (elf[4] != 1 || elf[5] != 1) { err = "not a 32-bit little-endian ELF"; return RK_ERR_INVALID; }
-    if (rd16(18) != 243) { err = "not a RISC-V ELF (e_machine != 243)"; return RK_ERR_INVALID; }
-    m.pc = rd32(24);
-    uint32_t phoff = rd32(28), phentsize = rd16(42), phnum = rd16(44);
-    if (phentsize < 32 || (uint64_t)phoff + (uint64_t)phentsize * phnum > n) { err = "program headers out of range"; return RK_ERR_INVALID; }
-    for (uint32_t i = 0; i < phnum; i++) {
-        size_t ph = phoff + (size_t)i * phentsize;
-        if (rd32(ph) != 1) continue;  // PT_LOAD
-        uint32_t off = rd32(ph + 4), vaddr = rd32(ph + 8), filesz = rd32(ph + 16), memsz = rd32(ph + 20);
-        if ((uint64_t)off + filesz > n || filesz > memsz || (uint64_t)vaddr + memsz > 0x100000000ull) {
-            err = "PT_LOAD segment out of range";
-            return RK_ERR_INVALID;
-        }
+    RK_TRY(rk_elf::walk_load_segments(elf, n, &m.pc, err, [&](uint32_t off, uint32_t vaddr, uint32_t filesz, uint32_t) {
         for (uint32_t b = 0; b < filesz; b++) m.store_byte(vaddr + b, elf[off + b]);
-    }
+        return (int)RK_OK;
+    }));
     if (m.pc & 3) { err = "misaligned entry point"; return RK_ERR_INVALID; }
     return RK_OK;
 }

@@ -598,15 +598,9 @@ int ProofRun::queries(uint32_t* h_proof, size_t capacity, size_t* proof_words) {
     return RK_OK;
 }
 
-// the parameters a key's LDEs and tree depend on (queries and pow_bits may differ between setup and proof)
-bool same_commitment_params(rk_ctx* ctx, const rk_params& a, const rk_p3_key& key) {
-    const rk_params& b = key.par;
-    return a.ext_w == b.ext_w && a.root_2_27 == b.root_2_27 && a.coset_shift == b.coset_shift && a.p2_width == b.p2_width && a.p2_m4 == b.p2_m4 &&
-           a.p2_pad_free == b.p2_pad_free && a.blowup_log2 == b.blowup_log2 && rk::p2_chip_tab(ctx->h_p2) == key.p2_tab;
-}
 // the key against the context and the tables: all of it before anything is launched
 int check_key(rk_ctx* ctx, const rk_params& par, const rk_p3_key& key, const rk_p3_table* tables, uint32_t n_tables) {
-    if (key.device != ctx->device || !same_commitment_params(ctx, par, key) || key.tables.size() != n_tables) return RK_ERR_INVALID;
+    if (key.device != ctx->device || !key.same_commitment_params(par, rk::p2_chip_tab(ctx->h_p2)) || key.tables.size() != n_tables) return RK_ERR_INVALID;
     for (uint32_t t = 0; t < n_tables; t++) {
         const rk_p3_key::Table& kt = key.tables[t];
         if (kt.prep_width != tables[t].air->prep_width) return RK_ERR_INVALID;

@@ -151,4 +151,10 @@ struct rk_p3_key {
     uint32_t root[8] = {0};
     size_t bytes = 0;
     bool has_root() const { return !mats.empty(); }
+    // whether a parameter set with Poseidon2 constants p2 (rk::p2_chip_tab) is the one the LDEs and the tree were made
+    // under: everything they depend on (queries and pow_bits may differ between setup and proof)
+    bool same_commitment_params(const rk_params& a, const std::vector<uint32_t>& p2) const {
+        return a.ext_w == par.ext_w && a.root_2_27 == par.root_2_27 && a.coset_shift == par.coset_shift && a.p2_width == par.p2_width &&
+               a.p2_m4 == par.p2_m4 && a.p2_pad_free == par.p2_pad_free && a.blowup_log2 == par.blowup_log2 && p2 == p2_tab;
+    }
 };

@@ -1,8 +1,11 @@
-// rk_p3_prove_shards (include/raiko_hip.h): uni-stark proofs of many shards in flight on one or several devices.  Per
-// device a pool of prover contexts and an uploader, kept between calls; one feeder thread per device stages the traces
-// ahead of the provers, host threads verify what is proven.  The proofs themselves are rk_p3_prove's (p3.hip), the checks
-// rk_p3_verify's (p3_verify.hip): nothing else of those files is reached from here.
+// rk_p3_prove_shards / rk_p3_prove_shards_key (include/raiko_hip.h): uni-stark proofs of many shards in flight on one or
+// several devices.  Per device a pool of prover contexts and an uploader, kept between calls; one feeder thread per
+// device stages the traces ahead of the provers, host threads verify what is proven.  The proofs themselves are
+// rk_p3_prove's / rk_p3_prove_key's (p3.hip), the checks rk_p3_verify's / rk_p3_verify_key's (p3_verify.hip): nothing else
+// of those files is reached from here.  A key (p3_host.hpp) is only read: its device, parameter set, shapes and root.
 #include "internal.hpp"
+#include "p3_air.hpp"
+#include "p3_host.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -48,12 +51,46 @@ std::vector<uint32_t> params_key(const rk_params& p) {
     return k;
 }
 
-int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t n, size_t* failed_index) {
+// the keys of a keyed run against their slots' devices, each other, the parameter set and every shard's shapes: all of it
+// from host data, before a context exists.  keys[d] belongs to devices[d].
+int check_keys(const std::vector<int>& devices, const std::vector<const rk_p3_key*>& keys, const rk_params& par,
+               const rk_p3_shard* shards, size_t n, size_t* failed_index) {
+    rk::Sys sys;
+    auto any = std::make_unique<p2::Any>();
+    if (rk::resolve_params(&par, &sys, any.get()) != RK_OK) return RK_ERR_INVALID;
+    const std::vector<uint32_t> tab = rk::p2_chip_tab(*any);
+    const rk_p3_key* first = keys.empty() ? nullptr : keys[0];
+    for (size_t d = 0; d < keys.size(); d++) {
+        const rk_p3_key* k = keys[d];
+        if (!k || k->device != devices[d]) return RK_ERR_INVALID;
+        if (!k->same_commitment_params(par, tab)) return RK_ERR_INVALID;
+        if (k->has_root() != first->has_root() || !std::equal(k->root, k->root + 8, first->root)) return RK_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n; i++)
+        for (const rk_p3_key* k : keys) {
+            const rk_p3_shard& sh = shards[i];
+            bool ok = sh.tables && sh.n_tables == k->tables.size();
+            for (uint32_t t = 0; ok && t < sh.n_tables; t++) {
+                const rk_p3_key::Table& kt = k->tables[t];
+                ok = sh.tables[t].air && rk_air_prep_width(sh.tables[t].air) == kt.prep_width &&
+                     (!kt.prep_width || sh.tables[t].log_height == kt.log_height);
+            }
+            if (!ok) {
+                if (failed_index) *failed_index = i;
+                return RK_ERR_INVALID;
+            }
+        }
+    return RK_OK;
+}
+
+// caller_keys NULL: rk_p3_prove_shards; otherwise one key per device in the caller's order (rk_p3_prove_shards_key)
+int p3_prove_shards(const rk_p3_session_opts* opts, const rk_p3_key* const* caller_keys, rk_p3_shard* shards, size_t n,
+                    size_t* failed_index) {
     if (failed_index) *failed_index = (size_t)-1;
     if (!opts || (n && !shards) || opts->batch < 1 || opts->batch > 16) return RK_ERR_INVALID;
     if (opts->n_devices < 0 || opts->n_devices > 64 || (opts->n_devices > 0 && !opts->devices)) return RK_ERR_INVALID;
     if (n == 0) return RK_OK;
-    for (size_t i = 0; i < n; i++)   // a shard carries no key: tables with preprocessed columns are rk_p3_prove_key's
+    for (size_t i = 0; !caller_keys && i < n; i++)   // no key: tables with preprocessed columns are rk_p3_prove_shards_key's
         for (uint32_t t = 0; shards[i].tables && t < shards[i].n_tables; t++)
             if (rk_air_prep_width(shards[i].tables[t].air)) {
                 if (failed_index) *failed_index = i;
@@ -62,6 +99,13 @@ int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t 
     std::vector<int> devices;
     if (opts->n_devices > 0) devices.assign(opts->devices, opts->devices + opts->n_devices);
     else devices.push_back(opts->device);
+    std::vector<const rk_p3_key*> dev_keys;   // the pools are sorted by device: each key travels with its device
+    if (caller_keys) {
+        std::vector<size_t> order(devices.size());
+        for (size_t d = 0; d < order.size(); d++) order[d] = d;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return devices[a] < devices[b]; });
+        for (size_t d : order) dev_keys.push_back(caller_keys[d]);
+    }
     std::sort(devices.begin(), devices.end());   // pools are locked in ascending order
     if (std::adjacent_find(devices.begin(), devices.end()) != devices.end()) return RK_ERR_INVALID;
     int n_gpus = 0;
@@ -75,6 +119,8 @@ int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t 
     if (key.empty()) return RK_ERR_INVALID;
     for (size_t i = 0; i < n; i++)
         if (!shards[i].h_proof || (shards[i].n_init && !shards[i].init_words)) return RK_ERR_INVALID;
+    if (caller_keys) RK_TRY(check_keys(devices, dev_keys, par, shards, n, failed_index));
+    const uint32_t* prep_root = caller_keys && dev_keys[0]->has_root() ? dev_keys[0]->root : nullptr;
 
     std::vector<std::shared_ptr<ShardPool>> pools;
     {
@@ -197,7 +243,10 @@ int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t 
             rk_p3_shard& sh = shards[i];
             int rc = RK_ERR_INTERNAL;
             try {
-                rc = rk_p3_prove(ctx, st->tables.data(), sh.n_tables, sh.init_words, sh.n_init, sh.h_proof, sh.capacity_words, &sh.proof_words);
+                rc = caller_keys ? rk_p3_prove_key(ctx, dev_keys[d], st->tables.data(), sh.n_tables, sh.init_words, sh.n_init, sh.h_proof,
+                                                   sh.capacity_words, &sh.proof_words)
+                                 : rk_p3_prove(ctx, st->tables.data(), sh.n_tables, sh.init_words, sh.n_init, sh.h_proof, sh.capacity_words,
+                                               &sh.proof_words);
             } catch (...) {
             }
             release(pool, *st);
@@ -233,7 +282,8 @@ int p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t 
             int v = RK_ERR_INTERNAL;
             try {
                 const rk_p3_shard& sh = shards[i];
-                v = rk_p3_verify(&par, sh.tables, sh.n_tables, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words);
+                v = caller_keys ? rk_p3_verify_key(&par, sh.tables, sh.n_tables, prep_root, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words)
+                                : rk_p3_verify(&par, sh.tables, sh.n_tables, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words);
             } catch (...) {
             }
             if (v != 0) {
@@ -281,7 +331,13 @@ extern "C" {
 
 int rk_p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size_t n, size_t* failed_index) {
     RK_GUARD_BEGIN
-    return p3_prove_shards(opts, shards, n, failed_index);
+    return p3_prove_shards(opts, nullptr, shards, n, failed_index);
+    RK_GUARD_END
+}
+int rk_p3_prove_shards_key(const rk_p3_session_opts* opts, const rk_p3_key* const* keys, rk_p3_shard* shards, size_t n,
+                           size_t* failed_index) {
+    RK_GUARD_BEGIN
+    return p3_prove_shards(opts, keys, shards, n, failed_index);
     RK_GUARD_END
 }
 

@@ -1,7 +1,9 @@
-// The rows of the rv32 chip sets' tables (rv32i, rv32i-cf, rv32im) as lane bodies: one call fills one row with canonical
+// The rows of the rv32 chip sets' tables (rv32i, rv32i-cf, rv32im, rv32im-elf) as lane bodies: one call fills one row with canonical
 // values, on the GPU (rv32_shards.hip: one lane per row, staged in LDS) and under plain g++ (tests/emul/emul_rv32_rows.cpp
 // walks a trace through them against numpy).  raiko_amd/rv32.py, rv32cf.py and rv32im.py are the same in numpy and name
-// every column; each chip set's rows are the previous one's with columns appended, so each row comes in pieces.
+// every column; each chip set's rows are the previous one's with columns appended, so each row comes in pieces.  rv32im-elf
+// (raiko_amd/rv32elf.py) is rv32im with the lookup tables' tuples preprocessed: its bodies (at the end) select those
+// tuples from the full rows and find a pc's row in the program image.
 #pragma once
 #include <type_traits>
 
@@ -15,10 +17,11 @@ constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_
                    SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256, IM_CPU_W = RK_RV32IM_CPU_COLS,
                    IM_PROG_W = RK_RV32IM_PROGRAM_COLS, MD_W = RK_RV32IM_MULDIV_COLS;
 // the chip set a kernel writes, and what its rows are made of
-enum ChipSet : int { CS_I, CS_CF, CS_IM };
+enum ChipSet : int { CS_I, CS_CF, CS_IM, CS_ELF };
 template <int CS>
 struct Chips {
-    static constexpr bool cf = CS != CS_I, im = CS == CS_IM;
+    // elf: rv32im's cpu, register and muldiv rows; the program, byte, range and shift traces are count columns
+    static constexpr bool cf = CS != CS_I, im = CS == CS_IM || CS == CS_ELF, elf = CS == CS_ELF;
     static constexpr unsigned cpu_w = im ? IM_CPU_W : cf ? CF_CPU_W : CPU_W, prog_w = im ? IM_PROG_W : cf ? CF_PROG_W : PROG_W;
 };
 
@@ -456,6 +459,56 @@ RK_HD bool muldiv_row(uint32_t* row, const TraceRow& r, uint32_t res) {
         row[D_K0] = ((zm & 0xffffu) + 1 + (dl & 0xffffu)) >> 16;
     }
     return want == res;
+}
+
+// ---- rv32im-elf (rv32elf.py): the preprocessed rows are the tuple columns of the full rows above
+constexpr unsigned ELF_PROG_W = RK_RV32ELF_PROGRAM_PREP_COLS, ELF_TUPLE_W = 4, ELF_VALID = ELF_PROG_W - 1;
+static_assert(P_MULT + 12 + 9 + 1 == ELF_PROG_W, "rv32im-elf program columns: the 41 looked-up fields, then VALID");
+
+// the program image: up to RK_RV32ELF_MAX_SEGMENTS runs of words; row = the words before the segment + the word's index
+struct Image {
+    uint32_t n_segs;
+    uint32_t vaddr[RK_RV32ELF_MAX_SEGMENTS], words[RK_RV32ELF_MAX_SEGMENTS];
+};
+constexpr uint32_t NO_ROW = 0xffffffffu;
+// the image row of pc, NO_ROW for a pc outside every segment or not word-aligned
+RK_HD uint32_t image_row(const Image& im, uint32_t pc) {
+    uint32_t row = NO_ROW, before = 0;
+    for (uint32_t k = 0; k < RK_RV32ELF_MAX_SEGMENTS; k++) {
+        if (k < im.n_segs) {
+            const uint32_t off = pc - im.vaddr[k];
+            if (pc >= im.vaddr[k] && (off & 3u) == 0 && (off >> 2) < im.words[k]) row = before + (off >> 2);
+            before += im.words[k];
+        }
+    }
+    return row;
+}
+// the pc of image row s < the image's words
+RK_HD uint32_t image_pc(const Image& im, uint32_t s) {
+    uint32_t pc = 0, before = 0;
+    for (uint32_t k = 0; k < RK_RV32ELF_MAX_SEGMENTS; k++) {
+        if (k < im.n_segs) {
+            if (s >= before && s - before < im.words[k]) pc = im.vaddr[k] + 4 * (s - before);
+            before += im.words[k];
+        }
+    }
+    return pc;
+}
+// full: an rv32im program row (program_row_i / _cf / _im) -> its 41 looked-up fields and VALID: one opcode class, and
+// not an OP word with bit 25 set that is no M word (rv32im.program_air's test on a looked-up row)
+RK_HD void program_prep_row(uint32_t* out, const uint32_t* full) {
+    for (unsigned c = 0; c < P_MULT; c++) out[c] = full[c];
+    for (unsigned c = 0; c < 12; c++) out[P_MULT + c] = full[P_EXT + c];
+    for (unsigned c = 0; c < 9; c++) out[P_MULT + 12 + c] = full[P_M + c];
+    uint32_t s = 0;
+    for (unsigned k = 0; k < 11; k++) s += full[P_OPC + k];
+    out[ELF_VALID] = s * (1u - (full[P_OPC + O_OP] * full[P_BITS + 25] - full[P_M + 8]));
+}
+RK_HD void byte_prep_row(uint32_t* out, const uint32_t* full) {
+    out[0] = full[Y_OP], out[1] = full[Y_X], out[2] = full[Y_Y], out[3] = full[Y_Z];
+}
+RK_HD void shift_prep_row(uint32_t* out, const uint32_t* full) {
+    out[0] = full[H_K], out[1] = full[H_X], out[2] = full[H_LO], out[3] = full[H_HI];
 }
 
 }  // namespace rv32

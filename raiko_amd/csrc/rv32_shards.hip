@@ -1,8 +1,9 @@
 // The witness of an executed segment written on the GPU (include/raiko_hip.h): the stand-in trace circuit's columns
-// (rk_exec_witness_device*) and the tables of the three rv32 chip sets (rk_exec_rv32_shard_device,
-// rk_exec_rv32cf_shard_device, rk_exec_rv32im_shard_device).  The segment is read through executor.hpp's view; what a
-// row holds is rv32_rows.hpp's lane bodies (raiko_amd/rv32.py, rv32cf.py, rv32im.py are the same in numpy and name every
-// column).  What is here: the kernels around those bodies -- the wave-level code, the atomics, the LDS staging -- and
+// (rk_exec_witness_device*) and the tables of the rv32 chip sets (rk_exec_rv32_shard_device,
+// rk_exec_rv32cf_shard_device, rk_exec_rv32im_shard_device, rk_exec_rv32elf_shard_device and the preprocessed matrices of
+// the last, rk_rv32elf_prep_device).  The segment is read through executor.hpp's view; what a
+// row holds is rv32_rows.hpp's lane bodies (raiko_amd/rv32.py, rv32cf.py, rv32im.py, rv32elf.py are the same in numpy and
+// name every column).  What is here: the kernels around those bodies -- the wave-level code, the atomics, the LDS staging -- and
 // the host driver.
 #include "internal.hpp"
 
@@ -65,7 +66,9 @@ static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32
 // The rv32 chip sets.  Per segment on the GPU: prep (decode, recompute the written value, pack the three accesses, count
 // program hits) -> block_last (last access per register per 128 rows) -> scan (exclusive max-scan of those 32-vectors)
 // -> rows (in-block resolve of each access's predecessor, the cpu row staged through LDS, RANGE16 / BYTE / SHIFT counts)
-// -> rv32im: the muldiv rows -> the program, byte, range, register and shift tables.
+// -> rv32im: the muldiv rows -> the program, byte, range, register and shift tables.  rv32im-elf: the same pipeline; a
+// cycle is counted at the image row of its pc (its word compared with the image's) and the program, byte, range and
+// shift tables leave as count columns.
 namespace rv32 {
 
 constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 for rv32i-cf / rv32im)
@@ -96,10 +99,39 @@ __device__ __forceinline__ void row_tile(uint32_t* s_rows, uint32_t* out, size_t
     for (size_t k = threadIdx.x; k < rows * W; k += blockDim.x) out[r0 * W + k] = s_rows[(k / W) * SW + k % W];
 }
 
+// One tile of a preprocessed matrix (rv32im-elf): the lane's FULL row of FW words is built in LDS as in row_tile, select
+// picks its OW tuple cells, and only those leave for HBM, in Montgomery form, as whole lines.  Every lane of the block
+// calls it.
+template <unsigned FW, unsigned OW, class F, class S>
+__device__ __forceinline__ void prep_tile(uint32_t* s_rows, uint32_t* out, size_t r0, size_t n_rows, F&& fill, S&& select) {
+    constexpr unsigned SW = FW | 1;
+    static_assert(OW <= FW, "the selected cells are staged in the full row's place");
+    uint32_t* row = s_rows + threadIdx.x * SW;
+    for (unsigned c = 0; c < FW; c++) row[c] = 0;
+    fill(row);
+    uint32_t o[OW];
+    select(o, row);
+#pragma unroll
+    for (unsigned c = 0; c < OW; c++) row[c] = enc(o[c]);
+    __syncthreads();
+    const size_t rows = n_rows - r0 < blockDim.x ? n_rows - r0 : blockDim.x;
+    for (size_t k = threadIdx.x; k < rows * OW; k += blockDim.x) out[r0 * OW + k] = s_rows[(k / OW) * SW + k % OW];
+}
+
+// ELF (rv32im-elf): the slot of a cycle is the image row of its pc -- the segment table arrives by value, in scalar
+// registers -- and its word is compared with the image's; nothing is recorded (prog_ins unused)
+template <bool ELF>
+struct ImageArgs {};   // the other chip sets: no argument bytes
+template <>
+struct ImageArgs<true> {
+    Image img;
+    const uint32_t* words;   // the image's words, device memory
+};
+template <bool ELF>
 __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
                             uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
                             uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
-                            uint32_t* __restrict__ err, uint32_t* __restrict__ mflag) {
+                            uint32_t* __restrict__ err, uint32_t* __restrict__ mflag, const ImageArgs<ELF> image) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i >= cycles) {
@@ -124,14 +156,24 @@ __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size
     }
     wval[i] = written(d, r, a0);
     acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16;
-    const uint32_t slot = (r.pc - pc_base) >> 2;
-    if (slot >= n_slots) {
-        atomicOr(err, 4u);
-        return;
+    if constexpr (ELF) {
+        const uint32_t slot = image_row(image.img, r.pc);
+        if (slot >= n_slots) {   // NO_ROW: a pc outside the image
+            atomicOr(err, 4u);
+            return;
+        }
+        atomicAdd(&prog_mult[slot], 1u);
+        if (image.words[slot] != r.ins) atomicOr(err, 1u);   // the word is not the image's: a store changed it
+    } else {
+        const uint32_t slot = (r.pc - pc_base) >> 2;
+        if (slot >= n_slots) {
+            atomicOr(err, 4u);
+            return;
+        }
+        atomicAdd(&prog_mult[slot], 1u);
+        const uint32_t old = atomicCAS(&prog_ins[slot], 0u, r.ins);
+        if (old != 0 && old != r.ins) atomicOr(err, 1u);    // one pc, two instruction words in one shard
     }
-    atomicAdd(&prog_mult[slot], 1u);
-    const uint32_t old = atomicCAS(&prog_ins[slot], 0u, r.ins);
-    if (old != 0 && old != r.ins) atomicOr(err, 1u);    // one pc, two instruction words in one shard
 }
 
 __device__ inline void unpack(uint32_t v, uint32_t& rs1, uint32_t& rs2, uint32_t& wreg, bool& wr, bool& active) {
@@ -287,6 +329,54 @@ __global__ void program_kernel(const uint32_t* __restrict__ prog_ins, const uint
     });
 }
 
+// ---- rv32im-elf: a count column of n_rows words (counts past n_counts are 0), and the four preprocessed matrices
+__global__ void count_kernel(const uint32_t* __restrict__ counts, size_t n_counts, size_t n_rows, uint32_t* __restrict__ out) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_rows) out[r] = enc(r < n_counts ? counts[r] : 0u);
+}
+
+__global__ void program_prep_kernel(const uint32_t* __restrict__ words, uint32_t n_words, const Image img, size_t n_rows,
+                                    uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    prep_tile<IM_PROG_W, ELF_PROG_W>(
+        s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows,
+        [&](uint32_t* row) {
+            if (s >= n_rows) return;
+            const bool in = s < n_words;
+            const uint32_t pc = in ? image_pc(img, (uint32_t)s) : 0u, ins = in ? words[s] : 0u;
+            const Dec d = decode(ins);
+            program_row_i(row, pc, ins, d, 0u);
+            program_row_cf(row, d);
+            program_row_im(row, ins, d);
+        },
+        [](uint32_t* o, const uint32_t* row) { program_prep_row(o, row); });
+}
+
+__global__ void byte_prep_kernel(uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    prep_tile<BYTE_W, ELF_TUPLE_W>(
+        s_rows, out, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32_BYTE_LOG_ROWS,
+        [&](uint32_t* row) {
+            if (r < (3u << 16)) byte_row(row, r, 0u);
+        },
+        [](uint32_t* o, const uint32_t* row) { byte_prep_row(o, row); });
+}
+
+__global__ void shift_prep_kernel(uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    prep_tile<SHIFT_W, ELF_TUPLE_W>(
+        s_rows, out, (size_t)blockIdx.x * blockDim.x, (size_t)1 << RK_RV32CF_SHIFT_LOG_ROWS,
+        [&](uint32_t* row) { shift_row(row, r, 0u); }, [](uint32_t* o, const uint32_t* row) { shift_prep_row(o, row); });
+}
+
+__global__ void range_prep_kernel(uint32_t* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < (1u << 16)) out[v] = enc(v);
+}
+
 __global__ void shift_kernel(const uint32_t* __restrict__ shift_mult, uint32_t* __restrict__ out) {
     extern __shared__ uint32_t s_rows[];
     const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -408,6 +498,28 @@ static size_t m_count_of(const ExecSegmentView& v) {
     return c;
 }
 
+// the program table's rows over an image of n_words words
+static size_t image_rows_for(size_t n_words) {
+    size_t rows = 2;
+    while (rows < n_words) rows <<= 1;
+    return rows;
+}
+
+// the caller's segment table as the kernels take it -> the image's words; RK_ERR_INVALID for more than
+// RK_RV32ELF_MAX_SEGMENTS segments
+static int image_of(const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs, Image* img, size_t* n_words) {
+    if (n_segs > RK_RV32ELF_MAX_SEGMENTS || (n_segs && (!seg_vaddr || !seg_words))) return RK_ERR_INVALID;
+    *img = Image{};
+    img->n_segs = n_segs;
+    *n_words = 0;
+    for (uint32_t k = 0; k < n_segs; k++) {
+        img->vaddr[k] = seg_vaddr[k];
+        img->words[k] = seg_words[k];
+        *n_words += seg_words[k];
+    }
+    return RK_OK;
+}
+
 static size_t muldiv_rows_for(size_t count) {
     size_t rows = (size_t)1 << RK_RV32IM_MULDIV_MIN_LOG_ROWS;
     while (rows < count) rows <<= 1;
@@ -417,12 +529,16 @@ static size_t muldiv_rows_for(size_t count) {
 namespace {
 
 // the tables a shard's driver writes: rv32i's five, d_shift the sixth of rv32i-cf, d_muldiv (muldiv_rows rows) the
-// seventh of rv32im
+// seventh of rv32im.  rv32im-elf: program / byte / range / shift are the count columns, img / image_words (device, n_words
+// of them) the program image the cycles are counted against
 struct ShardOut {
     uint32_t *cpu, *program;
     size_t program_rows;
     uint32_t *reg, *byte, *range, *shift, *muldiv;
     size_t muldiv_rows;
+    Image img;
+    const uint32_t* image_words;
+    size_t n_words;
 };
 
 // the driver's scratch: one allocation, each part's offset in words from one take(), rounded to 64 words
@@ -436,7 +552,7 @@ struct Scratch {
     size_t tr, ec, wval, acc, blk, final_ts, fin, init;
     size_t err, hist, bmult, pmult, pins, smult, clear_end;   // [err, clear_end): zero before the first kernel
     size_t mflag, mblk, mtotal, midx;                          // rv32im
-    Scratch(bool cf, bool im, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count) {
+    Scratch(bool cf, bool im, bool elf, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count) {
         const size_t nb = n / TB, slots = std::max<uint32_t>(n_slots, 1), sw = cf ? SHIFT_USED : 1u;
         tr = take((std::max<size_t>(cycles, 1) * sizeof(TraceRow) + 3) / 4);
         ec = take(2 * std::max<size_t>(n_ecalls, 1));
@@ -450,7 +566,7 @@ struct Scratch {
         hist = take((size_t)1 << 16);
         bmult = take((size_t)3 << 16);
         pmult = take(slots);
-        pins = take(slots);
+        pins = take(elf ? 1 : slots);   // rv32im-elf compares with the image: no word is recorded
         smult = take(sw);
         clear_end = smult + sw;
         mflag = take(im ? n : 1);
@@ -477,8 +593,10 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     if (!ec_flat.empty()) RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.ec, ec_flat.data(), ec_flat.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     RK_HIP_TRY(ctx, hipMemcpyAsync(init, v.regs, 32 * 4, hipMemcpyHostToDevice, ctx->stream));
     RK_HIP_TRY(ctx, hipMemsetAsync(err, 0, (L.clear_end - L.err) * 4, ctx->stream));
-    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
-                       (uint32_t)ec_flat.size() / 2, v.pc_lo, n_slots, wval, acc, pmult, pins, err, CH::im ? mflag : nullptr);
+    ImageArgs<CH::elf> image;
+    if constexpr (CH::elf) image = {o.img, o.image_words};
+    hipLaunchKernelGGL(prep_kernel<CH::elf>, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
+                       (uint32_t)ec_flat.size() / 2, v.pc_lo, n_slots, wval, acc, pmult, pins, err, CH::im ? mflag : nullptr, image);
     RK_TRY(rk::post_launch(ctx, "rv32 prep_kernel"));
     hipLaunchKernelGGL(block_last_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, acc, blk);
     RK_TRY(rk::post_launch(ctx, "rv32 block_last_kernel"));
@@ -503,19 +621,30 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
                            tr.size(), wval, midx, m_count, o.muldiv_rows, o.muldiv, hist, bmult, smult, err);
         RK_TRY(rk::post_launch(ctx, "rv32 muldiv_kernel"));
     }
-    const unsigned pb = (unsigned)std::min<size_t>(o.program_rows, TB);
-    hipLaunchKernelGGL(program_kernel<CS>, dim3((unsigned)((o.program_rows + pb - 1) / pb)), dim3(pb), pb * (CH::prog_w | 1) * 4,
-                       ctx->stream, pins, pmult, n_slots, v.pc_lo, o.program_rows, o.program);
-    RK_TRY(rk::post_launch(ctx, "rv32 program_kernel"));
-    hipLaunchKernelGGL(byte_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4, ctx->stream,
-                       bmult, o.byte);
-    RK_TRY(rk::post_launch(ctx, "rv32 byte_kernel"));
-    hipLaunchKernelGGL(range_kernel, dim3((1u << 16) / TB), dim3(TB), 0, ctx->stream, hist, o.range);
-    RK_TRY(rk::post_launch(ctx, "rv32 range_kernel"));
+    if constexpr (CH::elf) {   // the tuples are in the key: each lookup table's trace is its count column
+        const struct { const uint32_t* counts; size_t n_counts, n_rows; uint32_t* out; } cols[4] = {
+            {pmult, n_slots, o.program_rows, o.program}, {bmult, (size_t)3 << 16, (size_t)1 << RK_RV32_BYTE_LOG_ROWS, o.byte},
+            {hist, (size_t)1 << 16, (size_t)1 << 16, o.range}, {smult, SHIFT_USED, (size_t)1 << RK_RV32CF_SHIFT_LOG_ROWS, o.shift}};
+        for (const auto& c : cols) {
+            hipLaunchKernelGGL(count_kernel, dim3((unsigned)((c.n_rows + 255) / 256)), dim3(256), 0, ctx->stream, c.counts, c.n_counts,
+                               c.n_rows, c.out);
+            RK_TRY(rk::post_launch(ctx, "rv32 count_kernel"));
+        }
+    } else {
+        const unsigned pb = (unsigned)std::min<size_t>(o.program_rows, TB);
+        hipLaunchKernelGGL(program_kernel<CS>, dim3((unsigned)((o.program_rows + pb - 1) / pb)), dim3(pb), pb * (CH::prog_w | 1) * 4,
+                           ctx->stream, pins, pmult, n_slots, v.pc_lo, o.program_rows, o.program);
+        RK_TRY(rk::post_launch(ctx, "rv32 program_kernel"));
+        hipLaunchKernelGGL(byte_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4, ctx->stream,
+                           bmult, o.byte);
+        RK_TRY(rk::post_launch(ctx, "rv32 byte_kernel"));
+        hipLaunchKernelGGL(range_kernel, dim3((1u << 16) / TB), dim3(TB), 0, ctx->stream, hist, o.range);
+        RK_TRY(rk::post_launch(ctx, "rv32 range_kernel"));
+    }
     hipLaunchKernelGGL(register_kernel, dim3(1), dim3(32), 32 * (REG_W | 1) * 4, ctx->stream, final_ts, init, d_tr, wval,
                        w + L.fin, o.reg);
     RK_TRY(rk::post_launch(ctx, "rv32 register_kernel"));
-    if (CH::cf) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
+    if (CH::cf && !CH::elf) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
         hipLaunchKernelGGL(shift_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4,
                            ctx->stream, smult, o.shift);
         RK_TRY(rk::post_launch(ctx, "rv32 shift_kernel"));
@@ -536,7 +665,13 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
     const size_t cycles = v.trace->size(), n = (size_t)1 << v.seg->po2;
     if (cycles > n || n % TB) return RK_ERR_INTERNAL;
     uint32_t n_slots = 0;
-    if (program_rows_of(v, &n_slots) != o.program_rows) return RK_ERR_CAPACITY;
+    if (CH::elf) {   // one slot per word of the image
+        if (!o.image_words && o.n_words) return RK_ERR_INVALID;
+        if (o.n_words > (1u << 22) || image_rows_for(o.n_words) != o.program_rows) return RK_ERR_CAPACITY;
+        n_slots = (uint32_t)o.n_words;
+    } else if (program_rows_of(v, &n_slots) != o.program_rows) {
+        return RK_ERR_CAPACITY;
+    }
     if (n_slots > (1u << 22)) {
         ctx->last_error = "rk_exec_rv32_shard_device: executed pc range wider than 2^22 words";
         return RK_ERR_CAPACITY;
@@ -550,7 +685,7 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
         if (o.muldiv_rows & (o.muldiv_rows - 1) || o.muldiv_rows > std::max<size_t>(n, muldiv_rows_for(0))) return RK_ERR_INVALID;
     }
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const Scratch L(CH::cf, CH::im, cycles, v.ecalls->size(), n, n_slots, m_count);
+    const Scratch L(CH::cf, CH::im, CH::elf, cycles, v.ecalls->size(), n, n_slots, m_count);
     void* base = nullptr;
     RK_TRY(rk::dev_alloc(ctx, L.words * 4, &base));
     uint32_t* w = (uint32_t*)base;
@@ -572,8 +707,12 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
     rk::dev_free(ctx, base);
     if (st != RK_OK) return st;
     if (host_fin[32] & 7) {
-        ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
-                                           : "rk_exec_rv32_shard_device: trace and side list disagree";
+        if (CH::elf && (host_fin[32] & 5))
+            ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32elf_shard_device: an executed word is not the program image's word at its pc"
+                                               : "rk_exec_rv32elf_shard_device: a pc executed outside the program image";
+        else
+            ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
+                                               : "rk_exec_rv32_shard_device: trace and side list disagree";
         return RK_ERR_INVALID;
     }
     if (CH::im && (host_fin[32] || host_fin[33] != m_count)) {
@@ -585,6 +724,38 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
         return RK_ERR_INTERNAL;
     }
     return RK_OK;
+}
+
+// the four preprocessed matrices of an image (rk_rv32elf_prep_device): everything is checked before the first launch
+static int prep_device(rk_ctx* ctx, const Image& img, const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows,
+                       uint32_t* d_byte, uint32_t* d_range, uint32_t* d_shift) {
+    if (!ctx || !d_program || !d_byte || !d_range || !d_shift || (n_words && !words)) return RK_ERR_INVALID;
+    if (n_words > (1u << 22) || image_rows_for(n_words) != program_rows) return RK_ERR_CAPACITY;
+    RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* d_words = nullptr;
+    RK_TRY(rk::dev_alloc(ctx, std::max<size_t>(n_words, 1) * 4, &d_words));
+    auto enqueue = [&]() -> int {
+        if (n_words) RK_HIP_TRY(ctx, hipMemcpyAsync(d_words, words, n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+        const unsigned pb = (unsigned)std::min<size_t>(program_rows, TB);
+        hipLaunchKernelGGL(program_prep_kernel, dim3((unsigned)(program_rows / pb)), dim3(pb), pb * (IM_PROG_W | 1) * 4, ctx->stream,
+                           (const uint32_t*)d_words, (uint32_t)n_words, img, program_rows, d_program);
+        RK_TRY(rk::post_launch(ctx, "rv32 program_prep_kernel"));
+        hipLaunchKernelGGL(byte_prep_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4, ctx->stream, d_byte);
+        RK_TRY(rk::post_launch(ctx, "rv32 byte_prep_kernel"));
+        hipLaunchKernelGGL(range_prep_kernel, dim3((1u << 16) / 256), dim3(256), 0, ctx->stream, d_range);
+        RK_TRY(rk::post_launch(ctx, "rv32 range_prep_kernel"));
+        hipLaunchKernelGGL(shift_prep_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4, ctx->stream,
+                           d_shift);
+        return rk::post_launch(ctx, "rv32 shift_prep_kernel");
+    };
+    int st = enqueue();
+    const hipError_t e = hipStreamSynchronize(ctx->stream);   // the caller's `words` and the scratch are free to go
+    if (e != hipSuccess && st == RK_OK) {
+        ctx->last_error = std::string("rk_rv32elf_prep_device sync: ") + hipGetErrorString(e);
+        st = RK_ERR_HIP;
+    }
+    rk::dev_free(ctx, d_words);
+    return st;
 }
 
 }  // namespace rv32
@@ -641,6 +812,28 @@ int rk_exec_rv32im_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, 
     RK_GUARD_BEGIN
     return rv32::shard_device<rv32::CS_IM>(ctx, ex, index, {d_cpu, d_program, program_rows, d_register, d_byte, d_range, d_shift,
                                                             d_muldiv, muldiv_rows});
+    RK_GUARD_END
+}
+int rk_rv32elf_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                           const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                           uint32_t* d_range, uint32_t* d_shift) {
+    RK_GUARD_BEGIN
+    rv32::Image img;
+    size_t total = 0;
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
+    if (total != n_words) return RK_ERR_INVALID;
+    return rv32::prep_device(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    RK_GUARD_END
+}
+int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                 const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                 uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                 uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows) {
+    RK_GUARD_BEGIN
+    rv32::ShardOut o{d_cpu, d_program_mult, program_rows, d_register, d_byte_mult, d_range_mult, d_shift_mult, d_muldiv, muldiv_rows,
+                     {}, d_image_words, 0};
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
+    return rv32::shard_device<rv32::CS_ELF>(ctx, ex, index, o);
     RK_GUARD_END
 }
 

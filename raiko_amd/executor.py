@@ -51,6 +51,10 @@ class Execution:
     # with record_trace: per segment (registers at its start (32,), at its end (32,), ecall rows (k, 2): cycle, a0 after)
     # (rk_exec_registers / rk_exec_ecalls): the side data of the rv32i chip set (p3_rv32_shards)
     rv32: Optional[list] = None
+    # chips="rv32im-elf": the verifying key of the run -- the root of the preprocessed commitment of the ELF (8 Montgomery
+    # words) and the program table's log height, what verify_rv32_execution(prep_root=, program_log_height=) takes
+    prep_root: Optional[np.ndarray] = None
+    program_log_height: Optional[int] = None
 
 
 class ExecutorError(RuntimeError):
@@ -210,10 +214,10 @@ class Stepper:
         self.n += 1
         return seg, rows, prog, rng
 
-    def next_rv32_shard(self, hal, airs, chips="rv32i"):
-        """the next executed segment as the tables of an rv32i (five), rv32i-cf (six) or rv32im (seven) shard written on hal's GPU
-        (rv32_shard_device) -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init
-        words), or None after the last"""
+    def next_rv32_shard(self, hal, airs, chips="rv32i", key=None):
+        """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) shard
+        written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf") -> (ExecSegment, tables without
+        host traces, [(device buffer, log_height)] per table, init words), or None after the last"""
         if not self.more:
             return None
         more = C.c_int(0)
@@ -224,7 +228,7 @@ class Stepper:
         s = RkExecSegment()
         self._lib.rk_exec_segment_get(self._h, self.n, C.byref(s))
         seg = ExecSegment(s.index, s.po2, int(s.cycles), s.start_pc, s.end_pc, s.exit, tuple(s.pre_state), tuple(s.post_state))
-        tables, bufs, init = rv32_shard_device(hal, self._h, self.n, seg, airs, chips)
+        tables, bufs, init = rv32_shard_device(hal, self._h, self.n, seg, airs, chips, key)
         self.n += 1
         return seg, tables, bufs, init
 
@@ -441,7 +445,8 @@ class P3Pipeline:
     the proofs (rk_p3_verify is host code).  The contexts and the (compiled) AIRs live as long as the object: run() any
     number of programs, then close().  chips="rv32i" / "rv32i-cf" / "rv32im": every shard's tables of that chip set are written on
     the GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run
-    by check_rv32_chain."""
+    by check_rv32_chain.  chips="rv32im-elf": run() sets the program's key up first (setup_rv32_elf on the proving context),
+    proves every shard under it, checks every proof against its root, and closes it when the run ends."""
 
     def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace"):
         from . import p3
@@ -478,8 +483,16 @@ class P3Pipeline:
         todo = queue.Queue(maxsize=3)           # back-pressure: at most three shards' tables wait for the prover
         done = queue.Queue()                    # cpu tables the prover is through with: freed by the thread that owns their context
         proofs, checks, kept, errors, stmts = [], [], [], [], []
-        pool = ThreadPoolExecutor(max_workers=4)
         lookups, params, rv32i = self.lookups, self.params, self.chips in RV32_CHIPS
+        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs) if self.chips == "rv32im-elf" else None
+        vk = dict(prep_root=key.root, program_log_height=key.program_log_height) if key else {}
+        try:
+            stepper = Stepper(elf, input_words, shard_po2)
+        except Exception:
+            if key:
+                key.close()
+            raise
+        pool = ThreadPoolExecutor(max_workers=4)
 
         def prover():
             try:
@@ -489,14 +502,16 @@ class P3Pipeline:
                         return
                     if rv32i:
                         seg, tables, bufs, init = item
-                        pf = p3.prove(self.prove_hal, tables, init, device_traces=[(_ptr(b), lg) for b, lg in bufs])
+                        pf = p3.prove(self.prove_hal, tables, init, device_traces=[(_ptr(b), lg) for b, lg in bufs],
+                                      key=key.key if key else None)
                         proofs.append(pf)
                         stmts.append((tables, init))
                         if verify:
-                            checks.append(pool.submit(verify_rv32_shard, tables, pf, init, params))
+                            checks.append(pool.submit(verify_rv32_shard, tables, pf, init, params, **vk))
                         if keep_tables:
-                            kept.append(([p3.Table(t.air, b.to_host().reshape(1 << lg, t.air.width), t.public_values)
-                                          for t, (b, lg) in zip(tables, bufs)], init))
+                            preps = key.host_preps() if key else [None] * len(tables)
+                            kept.append(([p3.Table(t.air, b.to_host().reshape(1 << lg, t.air.width), t.public_values, prep=pm)
+                                          for t, (b, lg), pm in zip(tables, bufs, preps)], init))
                         done.put(bufs)
                         continue
                     seg, rows, prog, rng = item
@@ -520,13 +535,12 @@ class P3Pipeline:
 
         th = threading.Thread(target=prover)
         th.start()
-        stepper = Stepper(elf, input_words, shard_po2)
         metas, bad = [], []
         try:
             while True:
                 while not done.empty():
                     _free(done.get())
-                item = (stepper.next_rv32_shard(self.wit_hal, self.rv32_airs, self.chips) if rv32i
+                item = (stepper.next_rv32_shard(self.wit_hal, self.rv32_airs, self.chips, key) if rv32i
                         else stepper.next_shard(self.wit_hal, lookups))
                 if item is None or errors:
                     break
@@ -534,6 +548,8 @@ class P3Pipeline:
                 todo.put(item)
             ex = stepper.finish()
             ex.segments = metas
+            if key:
+                ex.prep_root, ex.program_log_height = key.root.copy(), key.program_log_height
         finally:
             todo.put(None)
             th.join()
@@ -542,6 +558,8 @@ class P3Pipeline:
             stepper.close()
             bad = [i for i, c in enumerate(checks) if c.result() != 0]
             pool.shutdown()
+            if key:
+                key.close()
         if errors:
             raise errors[0]
         if bad:
@@ -576,7 +594,11 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     written on the GPU (rk_exec_rv32_shard_device), every proof verified inside and the run checked by
     verify_rv32_execution.  chips="rv32i-cf": the same with the rv32i-cf chip set's six tables (raiko_amd/rv32cf.py,
     rk_exec_rv32cf_shard_device); chips="rv32im" with the rv32im chip set's seven (raiko_amd/rv32im.py,
-    rk_exec_rv32im_shard_device)."""
+    rk_exec_rv32im_shard_device).  chips="rv32im-elf": rv32im with the program bound to the ELF (raiko_amd/rv32elf.py):
+    setup_rv32_elf commits the program image and the fixed tables once, every shard's seven traces are written on the
+    GPU (rk_exec_rv32elf_shard_device) and proven under that key (rk_p3_prove_shards_key), and the run is checked against
+    the key's root, which the returned Execution carries as ex.prep_root (with ex.program_log_height: together the
+    verifying key)."""
     from . import p3
     from .hal import make_params
     params = params if params is not None else make_params(1)
@@ -585,19 +607,28 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     if chips in RV32_CHIPS:
         from .hal import HipHal
         hal = HipHal(device)
+        key, vk = None, {}
         try:
+            if chips == "rv32im-elf":
+                key = setup_rv32_elf(hal, elf, params)
+                vk = dict(prep_root=key.root.copy(), program_log_height=key.program_log_height)
             ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
-                                                               chips=chips)
+                                                               chips=chips, key=key)
             hal.sync()
             try:
-                proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces)
+                proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces,
+                                         key=key.key if key else None)
             finally:
                 for d in bufs:
                     for b, _lg in d:
                         b.free()
         finally:
+            if key:
+                key.close()
             hal.close()
-        verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None)
+        verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None, **vk)
+        if vk:
+            ex.prep_root, ex.program_log_height = vk["prep_root"], vk["program_log_height"]
         return ex, shards, proofs
     ex = execute(elf, input_words, segment_limit_po2=shard_po2, record_trace=True)
     shards = p3_shards(ex, lookups=lookups, ext_w=int(params.ext_w))
@@ -606,8 +637,8 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
 
 
 # ---- the rv32i chip set (raiko_amd/rv32.py): the register file and the integer ALU constrained ------------------------
-CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im")
-RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im")
+CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im", "rv32im-elf")
+RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im", "rv32im-elf")
 
 
 # per chip set: the module with its AIRs and numpy tables, the entry point that writes a shard's tables on the GPU, the
@@ -615,7 +646,8 @@ RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im")
 # segment needs) comes last
 _RV32_SETS = {"rv32i": ("rv32", "rk_exec_rv32_shard_device", (), False),
               "rv32i-cf": ("rv32cf", "rk_exec_rv32cf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), False),
-              "rv32im": ("rv32im", "rk_exec_rv32im_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True)}
+              "rv32im": ("rv32im", "rk_exec_rv32im_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True),
+              "rv32im-elf": ("rv32elf", "rk_exec_rv32elf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True)}
 
 
 def _rv32_set(chips):
@@ -707,16 +739,22 @@ def p3_rv32im_shards(ex: Execution, ext_w=None, airs=None):
     return _rv32_shards("rv32im", ex, ext_w, airs)
 
 
-def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
+def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
-    rk_exec_rv32im_shard_device ("rv32im"): segment `index` of an open executor as the tables of a shard of that chip
-    set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per table, init words)"""
+    rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key):
+    segment `index` of an open executor as the tables of a shard of that chip set, written on hal's GPU -> (tables
+    without host traces, [(device buffer, log_height)] per table, init words)"""
     from . import p3
     _module, entry, pinned, muldiv = _rv32_set(chips)
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
-    _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
+    if chips == "rv32im-elf":
+        if key is None:
+            raise ValueError("chips=\"rv32im-elf\" needs the Rv32Key of setup_rv32_elf")
+        rows.value = 1 << key.program_log_height
+    else:
+        _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
     logs = [seg.po2, rows.value.bit_length() - 1, *pinned]
     md_rows = C.c_size_t(0)
     if muldiv:
@@ -727,7 +765,15 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
     bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
     ptrs = [C.c_void_p(b.ptr) for b in bufs]
     args = ptrs[:2] + [rows.value] + ptrs[2:] + ([md_rows.value] if muldiv else [])
-    _lib.check(hal._ctx, getattr(lib, entry)(hal._ctx, handle, index, *args))
+    if chips == "rv32im-elf":
+        args = [key.seg_vaddr.ctypes.data_as(_lib.u32p), key.seg_words.ctypes.data_as(_lib.u32p), key.seg_vaddr.size,
+                C.c_void_p(key.d_words.ptr)] + args
+    try:
+        _lib.check(hal._ctx, getattr(lib, entry)(hal._ctx, handle, index, *args))
+    except Exception:
+        for b in bufs:
+            b.free()
+        raise
     pub_cpu, pub_reg = _rv32_publics(seg, start, end)
     tables = []
     for a, lg, pv in zip(airs, logs, [pub_cpu, (), pub_reg] + [()] * (len(logs) - 3)):
@@ -739,17 +785,18 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i"):
 
 
 def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
-                        chips="rv32i"):
-    """ELF -> rv32i (rv32i-cf, rv32im) shards whose tables are written on hal's GPU, one segment at a time (the executor's
-    trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables, init)], [device
-    traces], [[(device buffer, log_height)]] to free)"""
+                        chips="rv32i", key=None):
+    """ELF -> rv32i (rv32i-cf, rv32im, rv32im-elf) shards whose tables are written on hal's GPU, one segment at a time
+    (the executor's trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables,
+    init)], [device traces], [[(device buffer, log_height)]] to free).  key: the Rv32Key of chips="rv32im-elf" (its AIRs
+    are the shards')"""
     from .hal import _ptr
-    airs = airs or _rv32_airs_of(chips, ext_w)
+    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w))
     st = Stepper(elf, input_words, shard_po2)
     shards, dev, metas = [], [], []
     try:
         while True:
-            item = st.next_rv32_shard(hal, airs, chips)
+            item = st.next_rv32_shard(hal, airs, chips, key)
             if item is None:
                 break
             seg, tables, bufs, init = item
@@ -758,6 +805,10 @@ def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_
             metas.append(seg)
         ex = st.finish()
         ex.segments = metas
+    except Exception:
+        for d in dev:
+            _free(d)
+        raise
     finally:
         st.close()
     return ex, shards, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev
@@ -791,31 +842,37 @@ def rv32_publics(shards):
     return [(p3.from_mont(t[0].public_values), p3.from_mont(t[2].public_values)) for t, _init in shards]
 
 
-def verify_rv32_execution(shards, proofs, params=None, entry_pc=None):
-    """Checks a run proven with the rv32i, rv32i-cf or rv32im chip set: every shard's proof (verify_rv32_shard), then
-    check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards / p3_rv32cf_shards /
-    p3_rv32im_shards / execute_rv32_device give them.  Raises ValueError naming the shard; returns True."""
+def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None):
+    """Checks a run proven with the rv32i, rv32i-cf, rv32im or rv32im-elf chip set: every shard's proof
+    (verify_rv32_shard), then check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards /
+    p3_rv32cf_shards / p3_rv32im_shards / execute_rv32_device give them.  prep_root, program_log_height: the verifying
+    key of an rv32im-elf run (Execution.prep_root / .program_log_height): every shard must answer to that one root.
+    Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
     for k, ((tables, init), pf) in enumerate(zip(shards, proofs)):
-        rc = verify_rv32_shard(tables, pf, init, params)
+        rc = verify_rv32_shard(tables, pf, init, params, prep_root, program_log_height)
         if rc != 0:
             raise ValueError("shard %d: the proof does not verify (reason %d)" % (k, rc))
     return check_rv32_chain(rv32_publics(shards), entry_pc)
 
 
-def verify_rv32_shard(tables, proof, init, params=None) -> int:
+def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None) -> int:
     """rk_p3_verify of one rv32i (five tables), rv32i-cf (six) or rv32im (seven) shard with the register / byte / range
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
-    verifier's reason"""
+    verifier's reason.  prep_root (8 Montgomery words) with program_log_height: the statement is the rv32im-elf set's
+    seven tables under that verifying key (rk_p3_verify_key) -- the program table's height is then pinned by the
+    verifier, no longer the proof's"""
     from . import p3
     # the chip set is the one with this many tables; the program table's height (0) is the proof's, as the muldiv table's
-    sets = [_rv32_set(c)[2:] for c in RV32_CHIPS]
+    sets = [_rv32_set(c)[2:] for c in RV32_CHIPS if (c == "rv32im-elf") == (prep_root is not None)]
     pinned = next((p for p, muldiv in sets if 2 + len(p) + muldiv == len(tables)), None)
     if pinned is None:
         raise ValueError("%d tables are no rv32 chip set's shard" % len(tables))
-    pinned = (tables[0].log_height, 0, *pinned)
+    if prep_root is not None and not program_log_height:
+        raise ValueError("a verifying key is the root and the program table's log height")
+    pinned = (tables[0].log_height, int(program_log_height) if prep_root is not None else 0, *pinned)
     vt = []
     for i, t in enumerate(tables):
         v = p3.Table(t.air, None, t.public_values)
@@ -827,4 +884,111 @@ def verify_rv32_shard(tables, proof, init, params=None) -> int:
                 return 2
             v.log_height = lg
         vt.append(v)
-    return p3.verify(vt, proof, init, params)
+    return p3.verify(vt, proof, init, params, prep_root=prep_root)
+
+
+# ---- the rv32im-elf chip set (raiko_amd/rv32elf.py): the program and the fixed tables proven from a key ---------------
+def program_image_c(elf: bytes):
+    """rk_exec_program_image -> (segment vaddrs, segment word counts, the image's words): uint32 arrays"""
+    lib = _lib.load()
+    n_segs, n_words = C.c_size_t(0), C.c_size_t(0)
+    st = lib.rk_exec_program_image(bytes(elf), len(elf), None, None, 0, C.byref(n_segs), None, 0, C.byref(n_words))
+    if st != _lib.RK_ERR_CAPACITY or n_segs.value > 16:
+        _lib.check(None, st)
+    vaddr, count = np.zeros(max(n_segs.value, 1), dtype=np.uint32), np.zeros(max(n_segs.value, 1), dtype=np.uint32)
+    words = np.zeros(max(n_words.value, 1), dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_program_image(bytes(elf), len(elf), vaddr.ctypes.data_as(_lib.u32p), count.ctypes.data_as(_lib.u32p),
+                                               vaddr.size, C.byref(n_segs), words.ctypes.data_as(_lib.u32p), words.size, C.byref(n_words)))
+    return vaddr[: n_segs.value], count[: n_segs.value], words[: n_words.value]
+
+
+def p3_rv32elf_shards(ex: Execution, image, ext_w=None, airs=None):
+    """rv32im-elf shards in numpy: tables = cpu, program, register, byte, range, shift, muldiv (rv32elf.airs), the four
+    lookup tables with their preprocessed matrix in Table.prep (p3.setup commits them; rv32elf.prep_tables(image)).
+    image: rv32elf.program_image(elf).  The yardstick for rk_rv32elf_prep_device / rk_exec_rv32elf_shard_device."""
+    from . import p3, rv32elf
+    if ex.witness is None or ex.rv32 is None:
+        raise ValueError("execute(..., record_trace=True) first")
+    airs = airs or rv32elf.airs(ext_w)
+    preps = [None if m is None else p3.to_mont(m) for m in rv32elf.preps_of(image)]
+    out = []
+    for s, (_code, data), (start, end, ecalls) in zip(ex.segments, ex.witness, ex.rv32):
+        canon, _pc, _regs = rv32elf.shard_tables(s, data, start, end, ecalls, image)
+        pub_cpu, pub_reg = _rv32_publics(s, start, end)
+        pubs = [pub_cpu, (), pub_reg] + [()] * (len(canon) - 3)
+        tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
+        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
+    return out
+
+
+class Rv32Key:
+    """setup_rv32_elf's result, the proving key of one ELF under the rv32im-elf chip set: .image [(vaddr, words)], .key
+    the p3.Key over the program image and the byte / range / shift tuples, .root its 8 Montgomery words and
+    .program_log_height (together the verifying key), .d_words the image's words in device memory (what
+    rk_exec_rv32elf_shard_device compares the executed words with), .airs the seven AIRs.  close() frees the device
+    memory."""
+
+    def __init__(self, image, seg_vaddr, seg_words, key, d_words, program_log_height, airs):
+        self.image, self.seg_vaddr, self.seg_words, self.key, self.d_words = image, seg_vaddr, seg_words, key, d_words
+        self.root, self.program_log_height, self.airs = key.root, program_log_height, airs
+        self._preps = None
+
+    @property
+    def bytes(self):
+        return self.key.bytes + 4 * self.d_words.size()
+
+    def host_preps(self):
+        """the preprocessed matrices as rv32elf.prep_tables gives them (Montgomery words), in table order"""
+        from . import p3, rv32elf
+        if self._preps is None:
+            self._preps = [None if m is None else p3.to_mont(m) for m in rv32elf.preps_of(self.image)]
+        return self._preps
+
+    def close(self):
+        if self.key is not None:
+            self.key.close()
+            self.d_words.free()
+        self.key = self.d_words = None
+
+
+def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None) -> Rv32Key:
+    """The setup of `client.setup(ELF)` for the rv32im-elf chip set: the ELF's program image (rk_exec_program_image), the
+    four preprocessed matrices written on hal's GPU (rk_rv32elf_prep_device) and committed (rk_p3_setup) -> Rv32Key.
+    params: the parameter set to put hal's context under first (None: the context's current one); ext_w: the AIRs'
+    extension (default params' / the context's)."""
+    from . import p3, rv32, rv32cf, rv32elf
+    lib = _lib.load()
+    if params is not None:
+        _lib.check(hal._ctx, lib.rk_set_params(hal._ctx, C.byref(params)))
+    if airs is None:
+        airs = rv32elf.airs(int(hal.get_params().ext_w) if ext_w is None else ext_w)
+    vaddr, count, words = program_image_c(elf)
+    rows = 2
+    while rows < words.size:
+        rows <<= 1
+    logs = {1: rows.bit_length() - 1, 3: rv32.BYTE_LOG_ROWS, 4: rv32elf.RANGE_LOG_ROWS, 5: rv32cf.SHIFT_LOG_ROWS}
+    bufs = {i: hal.alloc_elem(airs[i].prep_width << lg) for i, lg in logs.items()}
+    d_words = None
+    try:
+        _lib.check(hal._ctx, lib.rk_rv32elf_prep_device(
+            hal._ctx, vaddr.ctypes.data_as(_lib.u32p), count.ctypes.data_as(_lib.u32p), vaddr.size, words.ctypes.data_as(_lib.u32p),
+            words.size, C.c_void_p(bufs[1].ptr), rows, C.c_void_p(bufs[3].ptr), C.c_void_p(bufs[4].ptr), C.c_void_p(bufs[5].ptr)))
+        tables = []
+        for i, a in enumerate(airs):
+            t = p3.Table(a, None, np.zeros(a.n_public, dtype=np.uint32))
+            t.log_height = logs.get(i, 1)
+            tables.append(t)
+        key = p3.setup(hal, tables, device_preps=[bufs[i].ptr if i in bufs else None for i in range(len(airs))])
+        try:
+            d_words = hal.copy_from_elem(words if words.size else np.zeros(1, dtype=np.uint32))
+            hal.sync()
+        except Exception:
+            key.close()
+            if d_words is not None:
+                d_words.free()
+            raise
+    finally:
+        for b in bufs.values():
+            b.free()
+    image = [(int(v), words[at - int(c):at].astype(np.int64)) for v, c, at in zip(vaddr, count, np.cumsum(count))]
+    return Rv32Key(image, vaddr, count, key, d_words, logs[1], airs)

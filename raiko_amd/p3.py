@@ -504,17 +504,22 @@ class Key:
     __del__ = close
 
 
-def setup(hal, tables):
+def setup(hal, tables, device_preps=None):
     """rk_p3_setup on hal's context under its current parameter set: commits the .prep matrices of the tables whose AIR
-    has preprocessed columns -> Key (the traces are not read)"""
+    has preprocessed columns -> Key (the traces are not read).  device_preps: optional list with, per table, the device
+    pointer of its preprocessed matrix already in the memory of hal's GPU (2^log_height x prep_width Montgomery words,
+    row-major) or None for a host matrix in .prep"""
     lib = _lib.load()
     arr, keep = _c_tables(tables)
     preps = (C.c_void_p * len(tables))()
     for i, t in enumerate(tables):
         if t.air.prep_width:
+            arr[i].log_height = t.log_height
+            if device_preps is not None and device_preps[i] is not None:
+                preps[i], arr[i].on_device = int(device_preps[i]), 1
+                continue
             assert t.prep is not None, "table %d: the AIR has preprocessed columns, the table no matrix" % i
             preps[i] = t.prep.ctypes.data
-            arr[i].log_height = t.log_height
     h = C.c_void_p()
     _lib.check(hal._ctx, lib.rk_p3_setup(hal._ctx, arr, len(tables), preps, C.byref(h)))
     del keep
@@ -542,17 +547,20 @@ def prove(hal, tables, init=(), device_traces=None, key=None):
     return out[: n.value].copy()
 
 
-def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, device_traces=None):
+def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, device_traces=None, key=None):
     """rk_p3_prove_shards: `shards` = list of (tables, init words); `batch` proofs in flight per GPU (SP1's SHARD_BATCH_SIZE).
-    -> list of proof word arrays, in order.  device_traces: optional per shard list as in prove()."""
+    -> list of proof word arrays, in order.  device_traces: optional per shard list as in prove().  key: a Key from
+    setup() on `device` (or one Key per entry of `devices`, in that order) -- rk_p3_prove_shards_key, the way shards
+    whose tables have preprocessed columns go through the pool; every proof is then checked against the key's root."""
     lib = _lib.load()
     n = len(shards)
+    bound = lib.rk_p3_proof_bound_words if key is None else lib.rk_p3_proof_bound_words_key
     arr = (_lib.RkP3Shard * n)()
     keep, bufs = [], []
     for i, (tables, init) in enumerate(shards):
         ctab, k = _c_tables(tables, device_traces[i] if device_traces else None)
         iw = np.ascontiguousarray(init, dtype=np.uint32)
-        cap = lib.rk_p3_proof_bound_words(C.byref(params), ctab, len(tables))
+        cap = bound(C.byref(params), ctab, len(tables))
         if cap == 0:
             raise _lib.RkError(_lib.RK_ERR_INVALID, "shard %d: shapes the prover rejects" % i)
         buf = np.zeros(cap, dtype=np.uint32)
@@ -566,7 +574,14 @@ def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, d
         dev_arr = (C.c_int * len(devices))(*[int(d) for d in devices])
         opts.devices, opts.n_devices = dev_arr, len(devices)
     failed = C.c_size_t(0)
-    st = lib.rk_p3_prove_shards(C.byref(opts), arr, n, C.byref(failed))
+    if key is None:
+        st = lib.rk_p3_prove_shards(C.byref(opts), arr, n, C.byref(failed))
+    else:
+        keys = list(key) if isinstance(key, (list, tuple)) else [key]
+        if len(keys) != (len(devices) if devices is not None else 1):
+            raise ValueError("one key per device")
+        karr = (C.c_void_p * len(keys))(*[k._handle.value for k in keys])
+        st = lib.rk_p3_prove_shards_key(C.byref(opts), karr, arr, n, C.byref(failed))
     if st != 0:
         e = _lib.RkError(st, lib.rk_strerror(st).decode() + (" (shard %d)" % failed.value if failed.value != C.c_size_t(-1).value else ""))
         e.segment = int(failed.value) if failed.value != C.c_size_t(-1).value else -1
