@@ -884,7 +884,9 @@ size_t rk_p3_proof_bound_words_key(const rk_params* params, const rk_p3_table* t
  * without such a table, such a table without a root or without its height: RK_ERR_INVALID.  A proof carrying another
  * height: reason 2; a preprocessed opening that does not lead to the caller's root: reason 5.
  * rk_p3_verify, rk_p3_verify_hashes, the four rk_p3_fri_* captures, rk_p3_prove and rk_p3_prove_shards refuse tables with
- * prep_width > 0 with RK_ERR_INVALID: their statements do not know the fourth batch yet. */
+ * prep_width > 0 with RK_ERR_INVALID: they have no root to check the fourth batch against.  Keyed proofs go to the _key
+ * twins instead: rk_p3_prove_key, rk_p3_verify_key, rk_p3_verify_hashes_key and the four rk_p3_fri_*_key captures below,
+ * whose formats carry the preprocessed batch and which the rk_fri_* tables are written from in the same way. */
 int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
                      const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words);
 /* p3-uni-stark `verify` on the host (no GPU): params NULL = the SP1 preset; trace / on_device of the tables are ignored;
@@ -916,6 +918,42 @@ int rk_p3_verify_hashes(const rk_params* params, const rk_p3_table* tables, uint
 int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
                        const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* publics, size_t publics_capacity,
                        uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words);
+/* The same calls over a proof under a verifying key: each _key function is its twin with prep_root as rk_p3_verify_key
+ * takes it (the 8 words of rk_p3_key_root if and only if a table has prep_width > 0, whose log_height is then pinned;
+ * otherwise RK_ERR_INVALID), returns rk_p3_verify_key's verdict, and with a NULL root and tables without preprocessed
+ * columns hands back word for word what its twin does.  With a preprocessed batch:
+ *   rk_p3_verify_hashes_key   the permutations of the keyed check: the observe of the root first in the transcript, the
+ *                             fourth batch's leaf sponges and compressions per query behind the trace batch's
+ *   rk_p3_fri_openings_key    the same format; the reduced openings include the preprocessed columns
+ *   rk_p3_fri_inputs_key      layout: a preprocessed matrix carries batch 3 and points 2; the matrices stay in the
+ *                             verifier's order, trace, preprocessed, permutation, quotient (the order of the alpha powers),
+ *                             so the batch numbers run 0.., 3.., 1.., 2...  records: per query the index, then the opened
+ *                             rows in that same order (a matrix's offset in a record is a running sum over the layout)
+ *   rk_p3_fri_input_paths_key publics: the 25 words of rk_p3_fri_input_paths | the preprocessed root 8 (the caller's
+ *                             prep_root) | log_kmax (the log LDE height of the preprocessed batch's tallest matrix): 34
+ *                             words.  records: per query the paths in batch-number order: trace 8 L | permutation
+ *                             8 log_pmax | quotient 8 L | preprocessed 8 log_kmax
+ *   rk_p3_fri_transcript_key  the same format; `observed` holds the root between init and the trace root, where the
+ *                             challenger observes it */
+int rk_p3_verify_hashes_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                            const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* states,
+                            size_t capacity_permutations, size_t* n_permutations);
+int rk_p3_fri_openings_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                           const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* shape,
+                           uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* publics_words,
+                           size_t* records_words);
+int rk_p3_fri_inputs_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                         const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* layout,
+                         size_t layout_capacity, uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity,
+                         size_t* layout_words, size_t* publics_words, size_t* records_words);
+int rk_p3_fri_input_paths_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                              const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* shape,
+                              uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* publics_words,
+                              size_t* records_words);
+int rk_p3_fri_transcript_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                             const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* ops,
+                             size_t ops_capacity, uint32_t* observed, size_t observed_capacity, uint32_t* sampled, size_t sampled_capacity,
+                             size_t* ops_words, size_t* observed_words, size_t* sampled_words);
 /* The four tables of that statement for a shape: fold (one row per query and round), path (one row per Merkle step),
  * claims (query, round, index, reduced opening: free cells here; rk_fri_reduce_* below replaces them) and the Poseidon2 chip (one row per
  * leaf sponge and compression).  *_rows = rows in use, *_log_height = the power of two they are padded to (>= 1). */
@@ -961,7 +999,9 @@ int rk_p3_fri_inputs(const rk_params* params, const rk_p3_table* tables, uint32_
                      size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* layout_words, size_t* publics_words,
                      size_t* records_words);
 /* The four tables of that statement for a shape and a layout (n_matrices entries of 5 words, as rk_p3_fri_inputs wrote
- * them).  The reduce table has one row per (query, slot, column): the slots are the matrices ordered by round (the
+ * them, or rk_p3_fri_inputs_key: batch 3 = preprocessed, points 2; the batches in the order 0, 3, 1, 2, a trace matrix
+ * first; anything else is RK_ERR_INVALID).  The reduce table has one row per (query, slot, column): the slots are the
+ * matrices ordered by round (the
  * layout's order within a round) and one single-row slot for every round without a matrix; rows_per_query = the sum of
  * their widths.  reduce_publics_words = 8 + 16 n_slots: alpha | zeta | per slot A, S of the first point, A, S of the
  * second (zero where the slot has no such point). */
@@ -1000,10 +1040,14 @@ int rk_p3_fri_input_paths(const rk_params* params, const rk_p3_table* tables, ui
                           const uint32_t* proof, size_t proof_words, uint32_t* shape, uint32_t* publics, size_t publics_capacity,
                           uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words);
 /* The six tables for a shape and a layout.  n_groups = the (round, batch) groups of a query, n_batches = the input trees
- * (2 or 3); state_rows = queries x the sponge permutations of a query, chip_rows = those of the reduce statement plus one
- * per ipath row and injection.  roots_words / paths_words: what rk_p3_fri_input_paths hands back. */
+ * (2 to 4, in batch-number order: the preprocessed tree's ipath rows, chip inputs and paths come last); state_rows =
+ * queries x the sponge permutations of a query, chip_rows = those of the reduce statement plus one per ipath row and
+ * injection.  roots_words / paths_words: what rk_p3_fri_input_paths(_key) hands back -- roots_words is 34 exactly when the
+ * layout has a batch-3 matrix, and d_roots must then be the 34-word form: the device cannot tell, the caller checks.
+ * log_kmax: the log LDE height of the preprocessed batch's tallest matrix, 0 without one; a batch-3 matrix cannot be
+ * taller than log_max, trace and quotient must reach it. */
 typedef struct {
-    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, reserved;
+    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, log_kmax;
     uint32_t fold_width, path_width, reduce_width, ipath_width, chip_width, state_width;
     uint32_t fold_log_height, path_log_height, reduce_log_height, ipath_log_height, chip_log_height, state_log_height;
     uint64_t fold_rows, path_rows, reduce_rows, ipath_rows, chip_rows, state_rows, rows_per_query;
@@ -1044,7 +1088,7 @@ int rk_p3_fri_transcript(const rk_params* params, const rk_p3_table* tables, uin
  * state_rows = those of the open statement + n_steps; transcript_publics_words = observed_words + the field elements
  * sampled by kind 1. */
 typedef struct {
-    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, n_steps, pow_bits, reserved;
+    uint32_t n_rounds, n_slots, n_groups, n_batches, log_pmax, n_steps, pow_bits, log_kmax;
     uint32_t fold_width, path_width, reduce_width, ipath_width, transcript_width, bits_width, chip_width, state_width;
     uint32_t fold_log_height, path_log_height, reduce_log_height, ipath_log_height, transcript_log_height, bits_log_height, chip_log_height,
         state_log_height;

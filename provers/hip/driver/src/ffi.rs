@@ -375,7 +375,7 @@ pub struct rk_fri_open_size_info {
     pub n_groups: u32,
     pub n_batches: u32,
     pub log_pmax: u32,
-    pub reserved: u32,
+    pub log_kmax: u32,
     pub fold_width: u32,
     pub path_width: u32,
     pub reduce_width: u32,
@@ -413,7 +413,7 @@ pub struct rk_fri_transcript_size_info {
     pub log_pmax: u32,
     pub n_steps: u32,
     pub pow_bits: u32,
-    pub reserved: u32,
+    pub log_kmax: u32,
     pub fold_width: u32,
     pub path_width: u32,
     pub reduce_width: u32,
@@ -629,6 +629,11 @@ extern "C" {
     pub fn rk_p3_verify(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize) -> c_int;
     pub fn rk_p3_verify_hashes(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, states: *mut u32, capacity_permutations: usize, n_permutations: *mut usize) -> c_int;
     pub fn rk_p3_fri_openings(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
+    pub fn rk_p3_verify_hashes_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, states: *mut u32, capacity_permutations: usize, n_permutations: *mut usize) -> c_int;
+    pub fn rk_p3_fri_openings_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
+    pub fn rk_p3_fri_inputs_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, layout: *mut u32, layout_capacity: usize, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, layout_words: *mut usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
+    pub fn rk_p3_fri_input_paths_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
+    pub fn rk_p3_fri_transcript_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, ops: *mut u32, ops_capacity: usize, observed: *mut u32, observed_capacity: usize, sampled: *mut u32, sampled_capacity: usize, ops_words: *mut usize, observed_words: *mut usize, sampled_words: *mut usize) -> c_int;
     pub fn rk_fri_chip_sizes(log_max: u32, blowup_log2: u32, queries: u32, out: *mut rk_fri_chip_size_info) -> c_int;
     pub fn rk_fri_chip_rows_device(ctx: *mut rk_ctx, log_max: u32, blowup_log2: u32, queries: u32, d_publics: *const u32, d_records: *const u32, d_fold: *mut u32, fold_capacity: usize, d_path: *mut u32, path_capacity: usize, d_claims: *mut u32, claims_capacity: usize, d_chip: *mut u32, chip_capacity: usize) -> c_int;
     pub fn rk_p3_fri_inputs(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, layout: *mut u32, layout_capacity: usize, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, layout_words: *mut usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;

@@ -131,7 +131,7 @@ class RkFriReduceSizeInfo(C.Structure):
 
 
 class RkFriOpenSizeInfo(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "reserved", "fold_width", "path_width",
+    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "log_kmax", "fold_width", "path_width",
                                           "reduce_width", "ipath_width", "chip_width", "state_width", "fold_log_height", "path_log_height",
                                           "reduce_log_height", "ipath_log_height", "chip_log_height", "state_log_height")] + \
                [(n, C.c_uint64) for n in ("fold_rows", "path_rows", "reduce_rows", "ipath_rows", "chip_rows", "state_rows", "rows_per_query",
@@ -150,7 +150,7 @@ class RkP3Table(C.Structure):
 
 
 class RkFriTranscriptSizeInfo(C.Structure):
-    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "n_steps", "pow_bits", "reserved",
+    _fields_ = [(n, C.c_uint32) for n in ("n_rounds", "n_slots", "n_groups", "n_batches", "log_pmax", "n_steps", "pow_bits", "log_kmax",
                                           "fold_width", "path_width", "reduce_width", "ipath_width", "transcript_width", "bits_width",
                                           "chip_width", "state_width", "fold_log_height", "path_log_height", "reduce_log_height",
                                           "ipath_log_height", "transcript_log_height", "bits_log_height", "chip_log_height",
@@ -326,20 +326,29 @@ SYMBOLS = {
     "rk_p3_verify": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz]),
     "rk_p3_proof_bound_words": (_sz, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32]),
     "rk_p3_verify_hashes": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, _sz, C.POINTER(_sz)]),
+    "rk_p3_verify_hashes_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, u32p, _sz, C.POINTER(_sz)]),
     "rk_p3_fri_openings": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
+                                     C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_p3_fri_openings_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
                                      C.POINTER(_sz), C.POINTER(_sz)]),
     "rk_fri_chip_sizes": (C.c_int, [_u32, _u32, _u32, C.POINTER(RkFriChipSizeInfo)]),
     "rk_fri_chip_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "rk_p3_fri_inputs": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz, u32p, _sz,
                                    C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_p3_fri_inputs_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz, u32p, _sz,
+                                   C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "rk_fri_reduce_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, C.POINTER(RkFriReduceSizeInfo)]),
     "rk_fri_reduce_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     "rk_p3_fri_input_paths": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
+                                        C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_p3_fri_input_paths_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz,
                                         C.POINTER(_sz), C.POINTER(_sz)]),
     "rk_fri_open_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, C.POINTER(RkFriOpenSizeInfo)]),
     "rk_fri_open_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
                                           _vp, _sz, _vp, _sz]),
     "rk_p3_fri_transcript": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz, u32p,
+                                       _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "rk_p3_fri_transcript_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, u32p, u32p, _sz, u32p, _sz, u32p,
                                        _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "rk_fri_transcript_sizes": (C.c_int, [_u32, _u32, _u32, u32p, _u32, u32p, _u32, C.POINTER(RkFriTranscriptSizeInfo)]),
     "rk_fri_transcript_rows_device": (C.c_int, [_vp, _u32, _u32, _u32, u32p, _u32, u32p, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,

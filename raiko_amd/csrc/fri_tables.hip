@@ -112,10 +112,11 @@ struct FriReducePlan {
     rk_fri_reduce_size_info sz;
     std::vector<uint32_t> slots;      // FRI_REDUCE_SLOT_WORDS per slot, gen(log_n) left 0 (the context's root fills it)
     std::vector<uint32_t> log_n;
-    std::vector<uint32_t> batch;      // per slot; 3 = the single row of a round without a matrix
+    std::vector<uint32_t> batch;      // per slot; FRI_OPEN_NONE = the single row of a round without a matrix
 };
 // the schedule of the reduce table from the layout of rk_p3_fri_inputs (Montgomery words; 5 per matrix): the matrices by
-// round, in the layout's order within a round, and one single-row slot for every round without a matrix
+// round, in the layout's order within a round, and one single-row slot for every round without a matrix.  Batches: 0
+// trace, 1 permutation, 2 quotient, 3 preprocessed (keyed proofs), in the verifier's order 0, 3, 1, 2
 int fri_reduce_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint32_t* layout, uint32_t n_matrices, FriReducePlan* plan) {
     rk_fri_chip_size_info chip;
     RK_TRY(fri_sizes(log_max, blow, queries, &chip));
@@ -130,7 +131,9 @@ int fri_reduce_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uin
         M& m = ms[i];
         m.batch = bb::decode(layout[5 * i]), m.rd = bb::decode(layout[5 * i + 1]), m.width = bb::decode(layout[5 * i + 2]);
         m.points = bb::decode(layout[5 * i + 3]), m.log_n = bb::decode(layout[5 * i + 4]);
-        if (m.batch > 2 || (i && m.batch < ms[i - 1].batch) || m.rd >= R || m.width == 0 || m.width > (1u << 16)) return RK_ERR_INVALID;
+        static const uint32_t place[4] = {0, 2, 3, 1};   // of a batch in the verifier's order
+        if (m.batch > 3 || (i ? place[m.batch] < place[ms[i - 1].batch] : m.batch != 0)) return RK_ERR_INVALID;
+        if (m.rd >= R || m.width == 0 || m.width > (1u << 16)) return RK_ERR_INVALID;   // rd < R: no matrix is taller than log_max
         if (m.points != (m.batch == 2 ? 1u : 2u) || m.log_n + blow + m.rd != log_max) return RK_ERR_INVALID;
         m.off = (uint32_t)off;
         off += m.width;
@@ -149,7 +152,7 @@ int fri_reduce_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uin
         if (plan->slots.size() == first) {
             plan->slots.insert(plan->slots.end(), {rd, 1u, 0u, 0u, 0u, 0u, (uint32_t)rows, 0u});
             plan->log_n.push_back(0);
-            plan->batch.push_back(3);
+            plan->batch.push_back(p3k::FRI_OPEN_NONE);
             rows += 1;
         }
         plan->slots[plan->slots.size() - p3k::FRI_REDUCE_SLOT_WORDS + 5] = 1;
@@ -200,10 +203,10 @@ int fri_open_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint3
     plan->groups.clear(), plan->levels.clear();
     plan->rowinfo.assign(2 * (size_t)r.rows_per_query, 0);
     uint64_t perms = 0;
-    uint32_t height[3] = {0, 0, 0};                  // log LDE height of a batch's tallest matrix; 0 = batch absent
+    uint32_t height[4] = {0, 0, 0, 0};               // log LDE height of a batch's tallest matrix; 0 = batch absent
     for (uint32_t m = 0; m < M;) {
         const uint32_t b = plan->red.batch[m], rd = slots[W * m];
-        if (b == 3) {
+        if (b == p3k::FRI_OPEN_NONE) {
             m++;
             continue;
         }
@@ -222,7 +225,7 @@ int fri_open_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint3
     const uint32_t G = (uint32_t)(plan->groups.size() / p3k::FRI_OPEN_GROUP_WORDS);
     uint64_t rows = 0, chips = 0, path_off = 0;
     uint32_t nb = 0;
-    for (uint32_t b = 0; b < 3; b++) {
+    for (uint32_t b = 0; b < 4; b++) {   // in batch-number order: the preprocessed tree comes last, nothing of a three-batch plan moves
         const uint32_t B = height[b];
         if (B) {
             std::vector<uint32_t> lv(p3k::FRI_OPEN_LEVEL_WORDS, p3k::FRI_OPEN_NONE);
@@ -253,8 +256,8 @@ int fri_open_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const uint3
     o.ipath_log_height = log_height(rows), o.chip_log_height = log_height(o.chip_rows), o.state_log_height = log_height(o.state_rows);
     o.fold_publics_words = r.fold_publics_words, o.fold_records_words = r.fold_records_words;
     o.reduce_publics_words = r.reduce_publics_words, o.inputs_words = r.inputs_words;
-    o.roots_words = 25, o.paths_words = (uint64_t)queries * path_off;
-    o.log_pmax = height[1];
+    o.roots_words = height[3] ? 34 : 25, o.paths_words = (uint64_t)queries * path_off;
+    o.log_pmax = height[1], o.log_kmax = height[3];
     plan->chip_base = r.chip_rows;
     return RK_OK;
 }
@@ -337,7 +340,7 @@ int fri_transcript_plan(uint32_t log_max, uint32_t blow, uint32_t queries, const
     const uint32_t N = (uint32_t)(steps.size() / p3k::FRI_TRANSCRIPT_STEP_WORDS);
     rk_fri_transcript_size_info& o = plan->sz;
     o = rk_fri_transcript_size_info{};
-    o.n_rounds = p.n_rounds, o.n_slots = p.n_slots, o.n_groups = p.n_groups, o.n_batches = p.n_batches, o.log_pmax = p.log_pmax;
+    o.n_rounds = p.n_rounds, o.n_slots = p.n_slots, o.n_groups = p.n_groups, o.n_batches = p.n_batches, o.log_pmax = p.log_pmax, o.log_kmax = p.log_kmax;
     o.n_steps = N, o.pow_bits = pow_bits;
     o.fold_width = p.fold_width + 1, o.path_width = p.path_width, o.reduce_width = p.reduce_width, o.ipath_width = p.ipath_width;
     o.transcript_width = p3k::FRI_TRANSCRIPT_FIXED + N, o.bits_width = p3k::FRI_BITS_WIDTH, o.chip_width = p.chip_width, o.state_width = p.state_width;

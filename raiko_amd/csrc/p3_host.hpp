@@ -70,7 +70,7 @@ struct Challenger {
     }
 };
 
-// keyed: the caller knows the fourth batch (rk_p3_setup / rk_p3_prove_key / rk_p3_verify_key); every other entry point
+// keyed: the caller knows the fourth batch (rk_p3_setup / rk_p3_prove_key / rk_p3_verify_key and the _key captures); every other entry point
 // refuses AIRs with preprocessed columns here, before anything else happens
 inline int check_tables(const rk_params& par, const rk_p3_table* tables, uint32_t n_tables, bool prover, uint32_t* lqd, bool keyed = false) {
     if (!tables || n_tables == 0 || n_tables > MAX_TABLES) return RK_ERR_INVALID;

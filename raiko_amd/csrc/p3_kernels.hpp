@@ -379,7 +379,8 @@ RK_HD bb::Ext fri_reduce_row(const FriReduceArgs& a, uint32_t q, uint32_t m, uin
 // matrices of one (round, batch): consecutive slots, hence consecutive reduce rows, one absorbed cell per row.
 // groups = 8 plain words each: first slot | slots | cells | first row within a query | permutations of the groups before
 // it (per query) | batch | round | 0.  rowinfo = 2 words per row of a query: the cell's number within its group | flags
-// (1 absorbs, 2 ends its group, batch << 2).  levels = 40 words per batch present: batch | B (tree height) | rows of the
+// (1 absorbs, 2 ends its group, batch << 2; batch 0 trace, 1 permutation, 2 quotient, 3 preprocessed).  levels = 40 words per
+// batch present, in batch-number order (the preprocessed tree last): batch | B (tree height) | rows of the
 // batches before it | chip inputs of the batches before it | injections | offset of the batch's path in a path record |
 // the group its leaf is | L - B | then per step the group injected there (FRI_OPEN_NONE: none).
 // digests = 8 words per (query, group), written by the sponge lanes and read by the ipath lanes.

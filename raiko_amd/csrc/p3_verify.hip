@@ -2,7 +2,7 @@
 // Plonky3's p3-uni-stark verifier.rs on p3-fri's TwoAdicFriPcs with a DuplexChallenger, several tables under shared
 // challenges, sp1-core's permutation argument between them -- and the calls that hand out what one run of it read:
 // rk_p3_verify_hashes (every Poseidon2 permutation) and the four rk_p3_fri_* captures the FRI lookup tables are written
-// from (fri_tables.hip).  Host code only.
+// from (fri_tables.hip), each with a _key twin for proofs under a verifying key.  Host code only.
 //
 // The check runs in stages over one parsed view of the proof (Opened), each doing its own reads, in the order that fixes
 // which defect a proof with several is refused for:
@@ -111,12 +111,15 @@ struct Captures {
     // group is (sum_k alpha^k p_k(x) - S) / (x - z) with S = sum_k alpha^k y_k over the same powers
     //   layout, per opened matrix in the verifier's order (Opened::mats): batch, round L - lh, width, points, log_n
     //   publics: alpha 4 | zeta 4 | per matrix and point: first power A 4, S 4
-    //   records, per query: index | trace rows | permutation rows | quotient rows
+    //   records, per query: index | trace rows | preprocessed rows (keyed) | permutation rows | quotient rows: the
+    //   layout's order, a slot's offset in a record is a running sum over the layout
     Record inputs;
     std::vector<uint32_t> layout;
-    // rk_p3_fri_input_paths: the commitments of the three input batches and the Merkle paths of their openings
-    //   publics: trace root 8 | permutation root 8 (zeros without one) | quotient root 8 | log_pmax
-    //   records, per query: trace path 8 L | permutation path 8 log_pmax | quotient path 8 L
+    // rk_p3_fri_input_paths: the commitments of the input batches and the Merkle paths of their openings
+    //   publics: trace root 8 | permutation root 8 (zeros without one) | quotient root 8 | log_pmax, and with a
+    //   preprocessed batch | the caller's preprocessed root 8 | log_kmax
+    //   records, per query, in batch-number order: trace path 8 L | permutation path 8 log_pmax | quotient path 8 L |
+    //   preprocessed path 8 log_kmax
     Record paths;
     p3h::Transcript transcript;   // rk_p3_fri_transcript
 };
@@ -436,14 +439,19 @@ void begin_captures(const Opened& o, Captures& c) {
                 put(c.inputs.publics, s.c, 4);
             }
         }
-        c.inputs.per_record = 1 + lay.trow + lay.prow + lay.qrow;
+        c.inputs.per_record = 1 + lay.trow + lay.krow + lay.prow + lay.qrow;
     }
     if (c.want & CAP_PATHS) {
-        c.paths.publics.assign(25, 0);
+        c.paths.publics.assign(lay.krow ? 34 : 25, 0);
         for (int b = 0; b < 3; b++)
             if (o.root[b]) std::copy(o.root[b], o.root[b] + 8, c.paths.publics.begin() + 8 * b);
         c.paths.publics[24] = bb::encode(lay.log_pmax);
         c.paths.per_record = 8 * (size_t)(2 * lay.log_max + lay.log_pmax);
+        if (lay.krow) {   // the fourth batch is appended: nothing of the three-batch form moves
+            std::copy(o.root[PREP], o.root[PREP] + 8, c.paths.publics.begin() + 25);
+            c.paths.publics[33] = bb::encode(lay.log_kmax);
+            c.paths.per_record += 8 * (size_t)lay.log_kmax;
+        }
     }
     for (Record* rec : {&c.openings, &c.inputs, &c.paths}) rec->records.assign(rec->per_record * o.sys.queries, 0);
 }
@@ -457,14 +465,14 @@ void record_openings(const Opened& o, const QueryView& q, uint32_t* rec) {
     }
 }
 void record_inputs(const Opened& o, const QueryView& q, uint32_t* rec) {
-    const size_t row_words[3] = {o.lay.trow, o.lay.prow, o.lay.qrow};
+    const size_t row_words[N_BATCHES] = {o.lay.trow, o.lay.prow, o.lay.qrow, o.lay.krow};
     *rec++ = bb::encode(q.index);
-    for (int b = 0; b < 3; b++)
+    for (int b : BATCH_ORDER)
         if (q.rows[b]) rec = std::copy(q.rows[b], q.rows[b] + row_words[b], rec);
 }
 void record_paths(const Opened& o, const QueryView& q, uint32_t* rec) {
-    const size_t tree[3] = {o.lay.log_max, o.lay.log_pmax, o.lay.log_max};
-    for (int b = 0; b < 3; b++)
+    const size_t tree[N_BATCHES] = {o.lay.log_max, o.lay.log_pmax, o.lay.log_max, o.lay.log_kmax};
+    for (int b = 0; b < N_BATCHES; b++)
         if (q.paths[b]) rec = std::copy(q.paths[b], q.paths[b] + 8 * tree[b], rec);
 }
 
@@ -552,6 +560,63 @@ int capture(unsigned want, bool (*scope)(const rk_params&), Statement st, uint32
     return 0;
 }
 
+// the statement of a _key entry point: the caller knows the preprocessed batch (open_statement's rule on prep_root)
+Statement keyed_statement(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root, const uint32_t* init,
+                          size_t n_init, const uint32_t* proof, size_t words) {
+    Statement st{params, tables, n_tables, init, n_init, proof, words};
+    st.keyed = true;
+    st.prep_root = prep_root;
+    return st;
+}
+
+int verify_hashes(const Statement& st, uint32_t* states, size_t capacity, size_t* n_permutations) {
+    if (!n_permutations || (capacity && !states)) return RK_ERR_INVALID;
+    const size_t w = p3h::params_or_sp1(st.params).p2_width;
+    std::vector<uint32_t> log;
+    struct Scope {   // the log is this thread's for the duration of the check, also when the verifier throws
+        explicit Scope(std::vector<uint32_t>* l) { p2::g_permute_log = l; }
+        ~Scope() { p2::g_permute_log = nullptr; }
+    };
+    int verdict;
+    {
+        Scope scope(&log);
+        verdict = p3_verify(st, /*one_thread=*/true);
+    }
+    if (verdict < 0 || (w != 16 && w != 24)) return verdict < 0 ? verdict : RK_ERR_INVALID;
+    *n_permutations = log.size() / w;
+    if (*n_permutations > capacity) return RK_ERR_CAPACITY;
+    std::memcpy(states, log.data(), log.size() * 4);
+    return verdict;
+}
+int fri_openings(const Statement& st, uint32_t shape[4], uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity,
+                 size_t* publics_words, size_t* records_words) {
+    Captures c{};
+    return capture(CAP_OPENINGS, scope_fold, st, shape, c,
+                   {{&c.openings.publics, publics, publics_capacity, publics_words}, {&c.openings.records, records, records_capacity, records_words}});
+}
+int fri_inputs(const Statement& st, uint32_t shape[4], uint32_t* layout, size_t layout_capacity, uint32_t* publics, size_t publics_capacity,
+               uint32_t* records, size_t records_capacity, size_t* layout_words, size_t* publics_words, size_t* records_words) {
+    Captures c{};
+    return capture(CAP_INPUTS, scope_fold, st, shape, c,
+                   {{&c.layout, layout, layout_capacity, layout_words},
+                    {&c.inputs.publics, publics, publics_capacity, publics_words},
+                    {&c.inputs.records, records, records_capacity, records_words}});
+}
+int fri_input_paths(const Statement& st, uint32_t shape[4], uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity,
+                    size_t* publics_words, size_t* records_words) {
+    Captures c{};
+    return capture(CAP_PATHS, scope_sponge, st, shape, c,
+                   {{&c.paths.publics, publics, publics_capacity, publics_words}, {&c.paths.records, records, records_capacity, records_words}});
+}
+int fri_transcript(const Statement& st, uint32_t shape[4], uint32_t* ops, size_t ops_capacity, uint32_t* observed, size_t observed_capacity,
+                   uint32_t* sampled, size_t sampled_capacity, size_t* ops_words, size_t* observed_words, size_t* sampled_words) {
+    Captures c{};
+    return capture(CAP_TRANSCRIPT, scope_transcript, st, shape, c,
+                   {{&c.transcript.ops, ops, ops_capacity, ops_words, /*encode=*/true},
+                    {&c.transcript.observed, observed, observed_capacity, observed_words},
+                    {&c.transcript.sampled, sampled, sampled_capacity, sampled_words}});
+}
+
 }  // namespace
 
 extern "C" {
@@ -566,33 +631,21 @@ int rk_p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_
 int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root, const uint32_t* init_words,
                      size_t n_init, const uint32_t* proof, size_t proof_words) {
     RK_GUARD_BEGIN
-    Statement st{params, tables, n_tables, init_words, n_init, proof, proof_words};
-    st.keyed = true;
-    st.prep_root = prep_root;
-    return p3_verify(st);
+    return p3_verify(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words));
     RK_GUARD_END
 }
 
 int rk_p3_verify_hashes(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
                         const uint32_t* proof, size_t proof_words, uint32_t* states, size_t capacity, size_t* n_permutations) {
     RK_GUARD_BEGIN
-    if (!n_permutations || (capacity && !states)) return RK_ERR_INVALID;
-    const size_t w = p3h::params_or_sp1(params).p2_width;
-    std::vector<uint32_t> log;
-    struct Scope {   // the log is this thread's for the duration of the check, also when the verifier throws
-        explicit Scope(std::vector<uint32_t>* l) { p2::g_permute_log = l; }
-        ~Scope() { p2::g_permute_log = nullptr; }
-    };
-    int verdict;
-    {
-        Scope scope(&log);
-        verdict = p3_verify({params, tables, n_tables, init_words, n_init, proof, proof_words}, /*one_thread=*/true);
-    }
-    if (verdict < 0 || (w != 16 && w != 24)) return verdict < 0 ? verdict : RK_ERR_INVALID;
-    *n_permutations = log.size() / w;
-    if (*n_permutations > capacity) return RK_ERR_CAPACITY;
-    std::memcpy(states, log.data(), log.size() * 4);
-    return verdict;
+    return verify_hashes({params, tables, n_tables, init_words, n_init, proof, proof_words}, states, capacity, n_permutations);
+    RK_GUARD_END
+}
+int rk_p3_verify_hashes_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                            const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t* states, size_t capacity,
+                            size_t* n_permutations) {
+    RK_GUARD_BEGIN
+    return verify_hashes(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words), states, capacity, n_permutations);
     RK_GUARD_END
 }
 
@@ -600,9 +653,17 @@ int rk_p3_fri_openings(const rk_params* params, const rk_p3_table* tables, uint3
                        const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* publics, size_t publics_capacity,
                        uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words) {
     RK_GUARD_BEGIN
-    Captures c{};
-    return capture(CAP_OPENINGS, scope_fold, {params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, c,
-                   {{&c.openings.publics, publics, publics_capacity, publics_words}, {&c.openings.records, records, records_capacity, records_words}});
+    return fri_openings({params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, publics, publics_capacity, records,
+                        records_capacity, publics_words, records_words);
+    RK_GUARD_END
+}
+int rk_p3_fri_openings_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                           const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t shape[4],
+                           uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* publics_words,
+                           size_t* records_words) {
+    RK_GUARD_BEGIN
+    return fri_openings(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words), shape, publics,
+                        publics_capacity, records, records_capacity, publics_words, records_words);
     RK_GUARD_END
 }
 
@@ -611,11 +672,17 @@ int rk_p3_fri_inputs(const rk_params* params, const rk_p3_table* tables, uint32_
                      size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* layout_words, size_t* publics_words,
                      size_t* records_words) {
     RK_GUARD_BEGIN
-    Captures c{};
-    return capture(CAP_INPUTS, scope_fold, {params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, c,
-                   {{&c.layout, layout, layout_capacity, layout_words},
-                    {&c.inputs.publics, publics, publics_capacity, publics_words},
-                    {&c.inputs.records, records, records_capacity, records_words}});
+    return fri_inputs({params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, layout, layout_capacity, publics,
+                      publics_capacity, records, records_capacity, layout_words, publics_words, records_words);
+    RK_GUARD_END
+}
+int rk_p3_fri_inputs_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                         const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* layout,
+                         size_t layout_capacity, uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity,
+                         size_t* layout_words, size_t* publics_words, size_t* records_words) {
+    RK_GUARD_BEGIN
+    return fri_inputs(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words), shape, layout, layout_capacity,
+                      publics, publics_capacity, records, records_capacity, layout_words, publics_words, records_words);
     RK_GUARD_END
 }
 
@@ -623,9 +690,17 @@ int rk_p3_fri_input_paths(const rk_params* params, const rk_p3_table* tables, ui
                           const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* publics, size_t publics_capacity,
                           uint32_t* records, size_t records_capacity, size_t* publics_words, size_t* records_words) {
     RK_GUARD_BEGIN
-    Captures c{};
-    return capture(CAP_PATHS, scope_sponge, {params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, c,
-                   {{&c.paths.publics, publics, publics_capacity, publics_words}, {&c.paths.records, records, records_capacity, records_words}});
+    return fri_input_paths({params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, publics, publics_capacity, records,
+                           records_capacity, publics_words, records_words);
+    RK_GUARD_END
+}
+int rk_p3_fri_input_paths_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                              const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t shape[4],
+                              uint32_t* publics, size_t publics_capacity, uint32_t* records, size_t records_capacity, size_t* publics_words,
+                              size_t* records_words) {
+    RK_GUARD_BEGIN
+    return fri_input_paths(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words), shape, publics,
+                           publics_capacity, records, records_capacity, publics_words, records_words);
     RK_GUARD_END
 }
 
@@ -634,11 +709,17 @@ int rk_p3_fri_transcript(const rk_params* params, const rk_p3_table* tables, uin
                          size_t observed_capacity, uint32_t* sampled, size_t sampled_capacity, size_t* ops_words, size_t* observed_words,
                          size_t* sampled_words) {
     RK_GUARD_BEGIN
-    Captures c{};
-    return capture(CAP_TRANSCRIPT, scope_transcript, {params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, c,
-                   {{&c.transcript.ops, ops, ops_capacity, ops_words, /*encode=*/true},
-                    {&c.transcript.observed, observed, observed_capacity, observed_words},
-                    {&c.transcript.sampled, sampled, sampled_capacity, sampled_words}});
+    return fri_transcript({params, tables, n_tables, init_words, n_init, proof, proof_words}, shape, ops, ops_capacity, observed,
+                          observed_capacity, sampled, sampled_capacity, ops_words, observed_words, sampled_words);
+    RK_GUARD_END
+}
+int rk_p3_fri_transcript_key(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                             const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words, uint32_t shape[4], uint32_t* ops,
+                             size_t ops_capacity, uint32_t* observed, size_t observed_capacity, uint32_t* sampled, size_t sampled_capacity,
+                             size_t* ops_words, size_t* observed_words, size_t* sampled_words) {
+    RK_GUARD_BEGIN
+    return fri_transcript(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words), shape, ops, ops_capacity,
+                          observed, observed_capacity, sampled, sampled_capacity, ops_words, observed_words, sampled_words);
     RK_GUARD_END
 }
 

@@ -865,6 +865,15 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
     seven tables under that verifying key (rk_p3_verify_key) -- the program table's height is then pinned by the
     verifier, no longer the proof's"""
     from . import p3
+    vt = rv32_verifier_tables(tables, proof, prep_root, program_log_height)
+    return 2 if vt is None else p3.verify(vt, proof, init, params, prep_root=prep_root)
+
+
+def rv32_verifier_tables(tables, proof, prep_root=None, program_log_height=None):
+    """the tables verify_rv32_shard hands the verifier -- no traces, the heights pinned as described there; None where the
+    proof's muldiv height is out of range (reason 2).  Also what the FRI statements about a shard proof take
+    (raiko_amd.fri_transcript.statement(..., prep_root=...))"""
+    from . import p3
     # the chip set is the one with this many tables; the program table's height (0) is the proof's, as the muldiv table's
     sets = [_rv32_set(c)[2:] for c in RV32_CHIPS if (c == "rv32im-elf") == (prep_root is not None)]
     pinned = next((p for p, muldiv in sets if 2 + len(p) + muldiv == len(tables)), None)
@@ -881,10 +890,10 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
         else:
             lg = int(proof[1 + i]) if len(proof) > 1 + i else 0
             if not 0 < lg <= tables[0].log_height:
-                return 2
+                return None
             v.log_height = lg
         vt.append(v)
-    return p3.verify(vt, proof, init, params, prep_root=prep_root)
+    return vt
 
 
 # ---- the rv32im-elf chip set (raiko_amd/rv32elf.py): the program and the fixed tables proven from a key ---------------

@@ -250,10 +250,10 @@ def _check_scope(params):
         raise _lib.RkError(_lib.RK_ERR_INVALID, "the FRI tables need the width-16 Poseidon2 and a fold by two")
 
 
-def fri_openings(tables, proof, init=(), params=None):
-    """rk_p3_fri_openings -> (verdict, Shape or None, publics, records): Montgomery words; nothing but the verdict
-    unless it is 0"""
-    return T.capture("rk_p3_fri_openings", 2, tables, proof, init, params)
+def fri_openings(tables, proof, init=(), params=None, prep_root=None):
+    """rk_p3_fri_openings (with prep_root, the verifying key's root: rk_p3_fri_openings_key) -> (verdict, Shape or None,
+    publics, records): Montgomery words; nothing but the verdict unless it is 0"""
+    return T.capture("rk_p3_fri_openings", 2, tables, proof, init, params, prep_root)
 
 
 _CONSTS_INC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "poseidon2_consts.inc")
@@ -300,10 +300,11 @@ class Statement:
         return p3.to_mont(list(self.shape[:4]))
 
 
-def statement(tables, proof, init=(), params=None):
-    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it)"""
+def statement(tables, proof, init=(), params=None, prep_root=None):
+    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it; prep_root: the
+    verifying key's root of a proof with preprocessed columns, rk_p3_verify_key)"""
     _check_scope(params)
-    rc, shape, pub, rec = fri_openings(tables, proof, init, params)
+    rc, shape, pub, rec = fri_openings(tables, proof, init, params, prep_root)
     if rc != 0:
         raise _lib.RkError(_lib.RK_ERR_VERIFY, "the shard proof is refused with reason %d" % rc)
     return Statement(shape, pub, rec, params)
@@ -532,13 +533,13 @@ def prove(hal, st, device=None):
     return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
-def verify_fri_statement(tables, shard_proof, init, fri_proof, params=None) -> int:
+def verify_fri_statement(tables, shard_proof, init, fri_proof, params=None, prep_root=None) -> int:
     """0 iff fri_proof proves the commit-phase checks of shard_proof: the public values (beta, roots, final polynomial)
     are recomputed from the shard proof's own transcript, all four heights are pinned to what the shape gives, and
     fri_proof is verified against them.  Otherwise the reason (rk_p3_verify's numbering; a shard proof that is itself
-    refused gives its own reason)."""
+    refused gives its own reason).  prep_root: the verifying key's root of a shard proof with preprocessed columns."""
     _check_scope(params)
-    rc, shape, pub, rec = fri_openings(tables, shard_proof, init, params)
+    rc, shape, pub, rec = fri_openings(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
     st = Statement(shape, pub, rec, params)

@@ -1,6 +1,7 @@
 """The input-batch Merkle openings of the FRI query check as lookup tables: the statement of raiko_amd.fri_reduce made larger
-by the part of rk_p3_verify that returns reason 5 -- the three rk_mmcs_verify calls that tie the rows a shard proof opened
-at a query to its trace, permutation and quotient commitments.  In fri_reduce the opened values sit in free cells P; here
+by the part of rk_p3_verify that returns reason 5 -- the rk_mmcs_verify calls that tie the rows a shard proof opened
+at a query to its trace, permutation and quotient commitments and, under a verifying key, to the key's preprocessed
+root.  In fri_reduce the opened values sit in free cells P; here
 every one of them is absorbed by a sponge whose digest walks up the batch's tree to the root.  Six tables of one proof:
 
   fold'    as in fri_reduce, unchanged.
@@ -8,7 +9,8 @@ every one of them is absorbed by a sponge whose digest walks up the batch's tree
   reduce'' fri_reduce.fri_reduce_air(..., sponge=batches): the reduce row with 43 columns behind the slot one-hot,
              PTR 8 | BUF 8 | CAP 8 | OUT 16 | FLUSH | GEND | BATCH.
            fri_reduce.schedule orders a query's slots by round and, within a round, in layout order (trace matrices, then
-           permutation, then quotient chunks): the matrices of one (round, batch) GROUP -- what rk_mmcs_verify hashes
+           preprocessed (batch 3, keyed proofs), then permutation, then quotient chunks): the matrices of one
+           (round, batch) GROUP -- what rk_mmcs_verify hashes
            together -- are consecutive slots in commit order, so the group's sponge absorbs a contiguous run of rows, the
            one cell P of each, in place.  PTR is the rate position P goes to (one-hot), BUF the rate cells after writing P,
            CAP the capacity, OUT the permutation's output on flush rows.  hash_elems with pad_free: a group starts from
@@ -22,7 +24,8 @@ every one of them is absorbed by a sponge whose digest walks up the batch's tree
   ipath    fri_ipath_air: one row per (query, batch, Merkle level).  fri_chip.fri_path_air's row without the round
            (cur 8 | sib 8 | bit | left 8 | right 8 | parent 8 | real | last | first | pos | cnt | q) | BATCH | NPOS |
            INJ | EX 8 | NODE 8 | RDF | RDI | BSEL one-hot over the batches present.  A batch whose tallest LDE has log
-           height B (L for trace and quotient, log_pmax for the permutation batch) has B steps, CNT from B down to 1.
+           height B (L for trace and quotient, log_pmax for the permutation batch, log_kmax for the preprocessed batch)
+           has B steps, CNT from B down to 1.  The trees are in batch-number order: the preprocessed tree (3) is last.
            parent = compress(left, right) (chip lookup, multiplicity REAL); NODE = compress(parent, EX) where INJ (chip
            lookup, multiplicity INJ; the argument order of rk_mmcs_verify) and NODE = parent elsewhere -- NODE is the
            helper that keeps "the next row's cur" and "the root on LAST" at degree 3; POS = 2 NPOS + BIT, the next row's
@@ -31,6 +34,10 @@ every one of them is absorbed by a sponge whose digest walks up the batch's tree
            (Q, BATCH, RDI, NPOS, EX).  Public values: the roots of the batches present.
   chip     p3.poseidon2_chip_air: now also ipath's compressions.
   state    p3.poseidon2_chip_air(n_out=16) on BUS_POSEIDON2_STATE: the sponge's permutations, all 16 cells out.
+
+Under a verifying key (statement(..., prep_root=key.root)) the opened preprocessed rows are absorbed as every other opened
+row and walked up to a root that is a public value of ipath; verify_open_statement binds that value to the root the caller
+trusts: the _key captures check the proof against it and hand it back as roots[25:33] (rk_p3_fri_input_paths_key).
 
 Nothing forces INJ by a level one-hot; BUS_IN_LEAF does.  Still free: the query indices and the
 transcript-derived public values (alpha, zeta, A, S, beta, the commit-phase and input roots, the final polynomial), which
@@ -85,7 +92,7 @@ def groups_of(layout, slots):
 
 def trees_of(shape, groups):
     out, rows, chips, path_off = [], 0, 0, 0
-    for b in range(3):
+    for b in range(4):                                             # batch-number order: the preprocessed tree last
         mine = [(i, g) for i, g in enumerate(groups) if g.batch == b]
         B = max([shape.log_max - g.rd for _, g in mine], default=0)
         if B:
@@ -159,15 +166,22 @@ def fri_ipath_air(shape, trees, ext_w=p3.EXT_W):
 
 
 # ---------------------------------------------------------------------------------------------- the statement
-def fri_input_paths(tables, proof, init=(), params=None):
-    """rk_p3_fri_input_paths -> (verdict, Shape or None, publics, records): Montgomery words; nothing but the verdict
-    unless it is 0"""
-    return T.capture("rk_p3_fri_input_paths", 2, tables, proof, init, params)
+def fri_input_paths(tables, proof, init=(), params=None, prep_root=None):
+    """rk_p3_fri_input_paths (with prep_root, the verifying key's root: rk_p3_fri_input_paths_key) -> (verdict, Shape or
+    None, publics, records): Montgomery words; nothing but the verdict unless it is 0"""
+    return T.capture("rk_p3_fri_input_paths", 2, tables, proof, init, params, prep_root)
+
+
+def root_at(batch):
+    """where a batch's root lies in the publics of rk_p3_fri_input_paths(_key): three roots | log_pmax | preprocessed root |
+    log_kmax"""
+    return 25 if batch == 3 else 8 * batch
 
 
 class Statement:
     """what the six tables state about one shard proof: fri_reduce's statement (`red`) and, from rk_p3_fri_input_paths,
-    the roots of the three input batches | log_pmax and per query the Merkle paths (Montgomery words)"""
+    the roots of the three input batches | log_pmax (| the preprocessed root | log_kmax under a verifying key) and per
+    query the Merkle paths (Montgomery words)"""
 
     def __init__(self, red, in_roots, in_paths):
         self.red, self.fold, self.shape, self.params = red, red.fold, red.shape, red.params
@@ -177,11 +191,15 @@ class Statement:
         self.batches = slot_batches(self.layout, self.slots)
         self.groups = groups_of(self.layout, self.slots)
         self.trees = trees_of(self.shape, self.groups)
-        self.log_pmax = int(p3.from_mont(self.in_roots[24:25])[0]) if self.in_roots.size == 25 else -1
-        self.per_path = 8 * (2 * self.shape.log_max + max(self.log_pmax, 0))
-        assert self.in_roots.size == 25 and self.in_paths.size == self.shape.queries * self.per_path
-        assert self.log_pmax == max([t.B for t in self.trees if t.batch == 1], default=0)
-        assert [t.B for t in self.trees if t.batch != 1] == [self.shape.log_max] * 2 and all(t.top is not None for t in self.trees)
+        height = {t.batch: t.B for t in self.trees}
+        self.roots_words = 34 if 3 in height else 25
+        assert self.in_roots.size == self.roots_words, "the roots are not in the form the layout asks for"
+        self.log_pmax = int(p3.from_mont(self.in_roots[24:25])[0])
+        self.log_kmax = int(p3.from_mont(self.in_roots[33:34])[0]) if 3 in height else 0
+        self.per_path = 8 * (2 * self.shape.log_max + self.log_pmax + self.log_kmax)
+        assert self.in_paths.size == self.shape.queries * self.per_path
+        assert self.log_pmax == height.get(1, 0) and self.log_kmax == height.get(3, 0)
+        assert height.get(0) == self.shape.log_max and height.get(2) == self.shape.log_max and all(t.top is not None for t in self.trees)
 
     layout_words = property(lambda self: self.red.layout_words)
     init = property(lambda self: self.red.init)
@@ -189,7 +207,7 @@ class Statement:
     @property
     def ipath_publics(self):
         """the roots of the batches present"""
-        return np.concatenate([self.in_roots[8 * t.batch: 8 * t.batch + 8] for t in self.trees])
+        return np.concatenate([self.in_roots[root_at(t.batch): root_at(t.batch) + 8] for t in self.trees])
 
     @property
     def perms_per_query(self):
@@ -200,11 +218,12 @@ class Statement:
         return sum(t.B + sum(v is not None for v in t.group_at) for t in self.trees)
 
 
-def statement(tables, proof, init=(), params=None):
-    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it)"""
+def statement(tables, proof, init=(), params=None, prep_root=None):
+    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it; prep_root: the
+    verifying key's root of a proof with preprocessed columns, rk_p3_verify_key)"""
     _check_scope(params)
-    red = G.statement(tables, proof, init, params)
-    rc, shape, roots, paths = fri_input_paths(tables, proof, init, params)
+    red = G.statement(tables, proof, init, params, prep_root)
+    rc, shape, roots, paths = fri_input_paths(tables, proof, init, params, prep_root)
     if rc != 0 or shape != red.shape:
         raise _lib.RkError(_lib.RK_ERR_VERIFY, "the shard proof is refused with reason %d" % rc)
     return Statement(red, roots, paths)
@@ -217,6 +236,13 @@ def heights(st):
     chip = sh.queries * (sh.n_rounds + F.steps_before(sh, sh.n_rounds) + st.ipath_chips_per_query)
     return (h_fold, h_path, h_reduce, F._log_height(sh.queries * sum(t.B for t in st.trees)), F._log_height(chip),
             F._log_height(sh.queries * st.perms_per_query))
+
+
+def _roots_bound(roots, prep_root):
+    """the preprocessed root among the captured roots is the caller's, word for word (and there is none without one)"""
+    if prep_root is None:
+        return roots.size == 25
+    return roots.size == 34 and np.array_equal(roots[25:33], np.ascontiguousarray(prep_root, dtype=np.uint32).reshape(-1))
 
 
 _AIRS = {}
@@ -373,8 +399,11 @@ def _pinned_tables(st):
 
 # ---------------------------------------------------------------------------------------------- GPU rows and proof
 def sizes(st):
-    """rk_fri_open_sizes -> dict"""
-    return T.sizes(_lib.RkFriOpenSizeInfo, "rk_fri_open_sizes", G._lead(st))
+    """rk_fri_open_sizes -> dict.  The row writer cannot tell a 25-word d_roots from the 34-word form a layout with a
+    preprocessed batch needs: the statement's roots must be what the plan reports."""
+    sz = T.sizes(_lib.RkFriOpenSizeInfo, "rk_fri_open_sizes", G._lead(st))
+    assert sz["roots_words"] == st.in_roots.size and sz["log_kmax"] == st.log_kmax
+    return sz
 
 
 def device_tables(hal, st):
@@ -389,23 +418,27 @@ def prove(hal, st, device=None):
     return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
-def verify_open_statement(tables, shard_proof, init, fri_proof, params=None) -> int:
+def verify_open_statement(tables, shard_proof, init, fri_proof, params=None, prep_root=None) -> int:
     """0 iff fri_proof proves, for shard_proof, what verify_reduce_statement states and that every opened value the reduced
     openings are computed from lies in the tree of its batch's commitment.  Shape, layout, every public value, the roots
     and the records are recomputed from the shard proof (rk_p3_fri_openings, rk_p3_fri_inputs, rk_p3_fri_input_paths), all
     six heights are pinned to what shape and layout give, and fri_proof is verified against them.  Otherwise the reason
-    (rk_p3_verify's numbering, as verify_reduce_statement)."""
+    (rk_p3_verify's numbering, as verify_reduce_statement).  prep_root: the verifying key's root of a shard proof with
+    preprocessed columns: the root the caller trusts.  The captures check the shard proof against it (refused under
+    another root) and the ipath table's public value for the preprocessed tree is that root."""
     _check_scope(params)
-    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params)
+    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape2, layout, in_pub, in_rec = G.fri_inputs(tables, shard_proof, init, params)
+    rc, shape2, layout, in_pub, in_rec = G.fri_inputs(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape3, roots, paths = fri_input_paths(tables, shard_proof, init, params)
+    rc, shape3, roots, paths = fri_input_paths(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
     if shape2 != shape or shape3 != shape or not G._check_zeta(in_pub):
+        return 1
+    if not _roots_bound(roots, prep_root):
         return 1
     st = Statement(G.Statement(F.Statement(shape, pub, rec, params), layout, in_pub, in_rec, params), roots, paths)
     return p3.verify(_pinned_tables(st), fri_proof, st.init, params=params)

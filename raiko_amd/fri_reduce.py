@@ -4,7 +4,8 @@ fri_chip those values sit in a claims table of free cells; here a reduce table c
 
 For one query and one LDE height lh the verifier computes rop[lh] = sum_k alpha^k (p_k(x) - y_k) / (x - z_k), k over every
 opened column of that height in a fixed order: the trace batch table by table (all columns at zeta, then all at
-zeta gen(log_n)), then the permutation batch the same way, then the quotient chunks at zeta.  Grouped by (matrix, point)
+zeta gen(log_n)), then -- in a proof under a verifying key -- the preprocessed batch the same way (batch 3), then the
+permutation batch the same way, then the quotient chunks at zeta.  Grouped by (matrix, point)
 every group is (sum_k alpha^k p_k(x) - S) / (x - z) with S = sum_k alpha^k y_k over the same absolute powers.  S, z and the
 group's first power A do not depend on the query: they are public values, recomputed from the shard proof on the host
 (rk_p3_fri_inputs) as beta, the roots and the final polynomial are.  Four tables of one proof:
@@ -44,11 +45,15 @@ Matrix = collections.namedtuple("Matrix", "batch rd width points log_n")
 Slot = collections.namedtuple("Slot", "rd width points rec_off log_n last_of_round row0 matrix")
 
 
-def layout_of(shape, widths, perm_widths, log_heights, lqds):
-    """the layout rk_p3_fri_inputs reports, from the tables' widths and the proof header's log heights"""
+def layout_of(shape, widths, perm_widths, log_heights, lqds, prep_widths=None):
+    """the layout rk_p3_fri_inputs (rk_p3_fri_inputs_key with prep_widths) reports, from the tables' widths and the proof
+    header's log heights: trace, preprocessed (batch 3), permutation, quotient"""
     out = []
     for w, k in zip(widths, log_heights):
         out.append(Matrix(0, shape.log_max - k - shape.blowup_log2, w, 2, k))
+    for w, k in zip(prep_widths or (), log_heights):
+        if w:
+            out.append(Matrix(3, shape.log_max - k - shape.blowup_log2, w, 2, k))
     for w, k in zip(perm_widths, log_heights):
         if w:
             out.append(Matrix(1, shape.log_max - k - shape.blowup_log2, w, 2, k))
@@ -215,10 +220,10 @@ def fri_reduce_air(shape, slots, ext_w=p3.EXT_W, sponge=False):
 
 
 # ---------------------------------------------------------------------------------------------- the statement
-def fri_inputs(tables, proof, init=(), params=None):
-    """rk_p3_fri_inputs -> (verdict, Shape or None, layout [Matrix], publics, records): Montgomery words; nothing but the
-    verdict unless it is 0"""
-    rc, shape, layout, pub, rec = T.capture("rk_p3_fri_inputs", 3, tables, proof, init, params)
+def fri_inputs(tables, proof, init=(), params=None, prep_root=None):
+    """rk_p3_fri_inputs (with prep_root, the verifying key's root: rk_p3_fri_inputs_key) -> (verdict, Shape or None,
+    layout [Matrix], publics, records): Montgomery words; nothing but the verdict unless it is 0"""
+    rc, shape, layout, pub, rec = T.capture("rk_p3_fri_inputs", 3, tables, proof, init, params, prep_root)
     if rc != 0:
         return rc, None, None, None, None
     return 0, shape, [Matrix(*[int(v) for v in row]) for row in p3.from_mont(layout).reshape(-1, 5)], pub, rec
@@ -268,11 +273,12 @@ def _check_zeta(in_publics):
     return bool(np.any(np.asarray(in_publics[5:8]) != 0))
 
 
-def statement(tables, proof, init=(), params=None):
-    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it)"""
+def statement(tables, proof, init=(), params=None, prep_root=None):
+    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it; prep_root: the
+    verifying key's root of a proof with preprocessed columns, rk_p3_verify_key)"""
     F._check_scope(params)
-    fold = F.statement(tables, proof, init, params)
-    rc, shape, layout, pub, rec = fri_inputs(tables, proof, init, params)
+    fold = F.statement(tables, proof, init, params, prep_root)
+    rc, shape, layout, pub, rec = fri_inputs(tables, proof, init, params, prep_root)
     if rc != 0 or shape != fold.shape:
         raise _lib.RkError(_lib.RK_ERR_VERIFY, "the shard proof is refused with reason %d" % rc)
     if not _check_zeta(pub):
@@ -428,18 +434,20 @@ def prove(hal, st, device=None):
     return T.prove(hal, _pinned_tables(st), st.init, device if device is not None else device_tables(hal, st))
 
 
-def verify_reduce_statement(tables, shard_proof, init, fri_proof, params=None) -> int:
+def verify_reduce_statement(tables, shard_proof, init, fri_proof, params=None, prep_root=None) -> int:
     """0 iff fri_proof proves, for shard_proof, that the reduced openings joining every query's fold chain are the ones
     rk_p3_verify computes from the rows the shard proof opened, and that the chain folds to the final polynomial.  Shape,
     layout and every public value are recomputed from the shard proof (rk_p3_fri_openings, rk_p3_fri_inputs), all four
     heights are pinned to what shape and layout give, and fri_proof is verified against them.  Otherwise the reason
     (rk_p3_verify's numbering; a shard proof that is itself refused gives its own reason; a zeta in the base field, where
-    x - z could vanish, is 1)."""
+    x - z could vanish, is 1).  prep_root: the verifying key's root of a shard proof with preprocessed columns (the
+    captures then are the _key ones and give rk_p3_verify_key's verdict: 3 under another root, which moves every
+    challenge; 5 for a preprocessed opening that does not lead to it)."""
     F._check_scope(params)
-    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params)
+    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape2, layout, in_pub, in_rec = fri_inputs(tables, shard_proof, init, params)
+    rc, shape2, layout, in_pub, in_rec = fri_inputs(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
     if shape2 != shape or not _check_zeta(in_pub):

@@ -1,6 +1,7 @@
 """What the FRI statement modules (fri_chip, fri_reduce, fri_open, fri_transcript) do alike.  Before a statement exists:
 the capture of what one verifier run over the shard proof read (`capture`: one ctypes call for all four rk_p3_fri_*
-functions).  Once a statement's AIRs and witness are written: p3 tables over rows, tables pinned to the statement's heights, the sizes the library gives, the rows written on
+functions and their _key twins for proofs under a verifying key).  Once a statement's AIRs and witness are written: p3
+tables over rows, tables pinned to the statement's heights, the sizes the library gives, the rows written on
 the GPU, the proof over them.  The modules pass what is theirs: AIRs, public values and heights per table, the table
 names as the size struct prefixes them, the struct, the names of the two library functions and the arguments both start
 with (behind the context), the host arrays the row writer reads."""
@@ -16,10 +17,18 @@ SP1_ROOT_2_27 = 0x1A427A41
 Shape = collections.namedtuple("Shape", "log_max n_rounds blowup_log2 queries root_2_27", defaults=(SP1_ROOT_2_27,))
 
 
-def capture(name, n_arrays, tables, proof, init, params):
+def capture(name, n_arrays, tables, proof, init, params, prep_root=None):
     """one of the library's rk_p3_fri_* captures of a verifier run over `proof`: `name` is the function, n_arrays the
     arrays it hands back -> (verdict, Shape or None, arrays...): Montgomery words; nothing but the verdict unless it is 0.
-    The library says how large the arrays are (RK_ERR_CAPACITY) and the call is made again with room for them."""
+    The library says how large the arrays are (RK_ERR_CAPACITY) and the call is made again with room for them.
+    prep_root: the verifying key's root (p3.Key.root) of a proof with preprocessed columns: the call goes to the _key
+    twin of `name` (a `name` that ends in _key goes there with whatever root is given, None = NULL)."""
+    keyed = ()
+    if prep_root is not None or name.endswith("_key"):
+        name = name if name.endswith("_key") else name + "_key"
+        kr = None if prep_root is None else np.ascontiguousarray(prep_root, dtype=np.uint32)
+        assert kr is None or kr.size == 8
+        keyed = (kr.ctypes.data_as(_lib.u32p) if kr is not None else None,)
     arr, keep = p3._c_tables(tables)
     iw = np.ascontiguousarray(init, dtype=np.uint32)
     pf = np.ascontiguousarray(proof, dtype=np.uint32)
@@ -29,7 +38,7 @@ def capture(name, n_arrays, tables, proof, init, params):
     out = [np.zeros(0, dtype=np.uint32)] * n_arrays
     while True:
         bufs = [x for a in out for x in (u(a) if a.size else None, a.size)]
-        rc = getattr(_lib.load(), name)(C.byref(params) if params is not None else None, arr, len(tables), u(iw), iw.size, u(pf), pf.size,
+        rc = getattr(_lib.load(), name)(C.byref(params) if params is not None else None, arr, len(tables), *keyed, u(iw), iw.size, u(pf), pf.size,
                                         u(shape), *bufs, *[C.byref(v) for v in n])
         if rc != _lib.RK_ERR_CAPACITY:
             break

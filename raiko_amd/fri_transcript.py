@@ -29,10 +29,16 @@ polynomial and the proof-of-work witness are the words that chain absorbs and gi
   state       p3.poseidon2_chip_air(n_out=16): the sponge's permutations, then the transcript's N.
 
 Still bound on the host (verify_transcript_statement): that the statement's public values are the shard proof's words --
-`observed` starts with init, the trace root and the tables' public values, and holds the roots, the final polynomial and
-the witness where the verifier reads them --, and A and S of the reduce table, which follow from alpha2, zeta and the opened
-values at zeta.  Outside: the constraint identity at zeta (reason 3).  The opened values are not observed; this restates
+`observed` starts with init, (under a verifying key: the preprocessed root,) the trace root and the tables' public values,
+and holds the roots, the final polynomial and the witness where the verifier reads them --, and A and S of the reduce
+table, which follow from alpha2, zeta and the opened values at zeta.  Outside: the constraint identity at zeta (reason 3).  The opened values are not observed; this restates
 the protocol, it does not change it.
+
+Under a verifying key (statement(..., prep_root=key.root)): the opened preprocessed rows are absorbed and walked up to a
+root that is a public value (fri_open); that root is the first thing the challenger's chain observes behind init, so
+every challenge depends on it; and the host binds it to the key the caller trusts -- verify_transcript_statement checks
+the observed segment against the caller's prep_root and against the root ipath takes.  Still outside: A and S, equality of
+the public values with the proof's words, and the constraint identity.
 
 Scope: fri_open's and pow_bits <= 27 (0 included: the witness is still observed and a sample is still popped).
 
@@ -179,10 +185,10 @@ def bits_air(log_max, pow_bits, ext_w=p3.EXT_W):
 
 
 # ---------------------------------------------------------------------------------------------- the statement
-def fri_transcript(tables, proof, init=(), params=None):
-    """rk_p3_fri_transcript -> (verdict, Shape or None, ops, observed, sampled): Montgomery words; nothing but the verdict
-    unless it is 0"""
-    return T.capture("rk_p3_fri_transcript", 3, tables, proof, init, params)
+def fri_transcript(tables, proof, init=(), params=None, prep_root=None):
+    """rk_p3_fri_transcript (with prep_root, the verifying key's root: rk_p3_fri_transcript_key) -> (verdict, Shape or None,
+    ops, observed, sampled): Montgomery words; nothing but the verdict unless it is 0"""
+    return T.capture("rk_p3_fri_transcript", 3, tables, proof, init, params, prep_root)
 
 
 def _check_scope(params):
@@ -214,11 +220,12 @@ class Statement:
         return np.concatenate([self.observed, self.sampled[: self.plan.n_pub]])
 
 
-def statement(tables, proof, init=(), params=None):
-    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it)"""
+def statement(tables, proof, init=(), params=None, prep_root=None):
+    """the statement about the shard proof `proof` of `tables` (raises unless rk_p3_verify accepts it; prep_root: the
+    verifying key's root of a proof with preprocessed columns, rk_p3_verify_key)"""
     _check_scope(params)
-    opn = H.statement(tables, proof, init, params)
-    rc, shape, ops, obs, smp = fri_transcript(tables, proof, init, params)
+    opn = H.statement(tables, proof, init, params, prep_root)
+    rc, shape, ops, obs, smp = fri_transcript(tables, proof, init, params, prep_root)
     if rc != 0 or shape != opn.shape:
         raise _lib.RkError(_lib.RK_ERR_VERIFY, "the shard proof is refused with reason %d" % rc)
     return Statement(opn, ops, obs, smp)
@@ -349,8 +356,10 @@ def _pinned_tables(st):
 
 # ---------------------------------------------------------------------------------------------- GPU rows and proof
 def sizes(st):
-    """rk_fri_transcript_sizes -> dict"""
-    return T.sizes(_lib.RkFriTranscriptSizeInfo, "rk_fri_transcript_sizes", _lead(st))
+    """rk_fri_transcript_sizes -> dict (the roots must be in the form the plan reports: fri_open.sizes)"""
+    sz = T.sizes(_lib.RkFriTranscriptSizeInfo, "rk_fri_transcript_sizes", _lead(st))
+    assert sz["roots_words"] == st.opn.in_roots.size and sz["log_kmax"] == st.opn.log_kmax
+    return sz
 
 
 def device_tables(hal, st):
@@ -367,11 +376,13 @@ def prove(hal, st, device=None):
 
 def observed_segments(st, n_init, n_public):
     """where the verifier's observes lie in `observed`, from the shape, the layout and the tables' public-value counts
-    (n_public, per table) -> dict name: (offset, words); None unless the calls are the sequence of rk_p3_verify"""
+    (n_public, per table) -> dict name: (offset, words); None unless the calls are the sequence of rk_p3_verify.  Where a
+    table has preprocessed columns the verifying key's root is observed between init and the trace root."""
     sh = st.shape
     R = sh.n_rounds
     n_perm = sum(m.batch == 1 for m in st.opn.layout)
-    ops = [(OBSERVE, n_init), (OBSERVE, 8)] + [(OBSERVE, n) for n in n_public]
+    prep = (("prep_root", 8),) if any(m.batch == 3 for m in st.opn.layout) else ()
+    ops = [(OBSERVE, n_init)] + [(OBSERVE, 8)] * len(prep) + [(OBSERVE, 8)] + [(OBSERVE, n) for n in n_public]
     if n_perm:
         ops += [(SAMPLE, 4), (SAMPLE, 4), (OBSERVE, 8)] + [(OBSERVE, 4)] * n_perm
     ops += [(SAMPLE, 4), (OBSERVE, 8), (SAMPLE, 4), (SAMPLE, 4)] + [(OBSERVE, 8), (SAMPLE, 4)] * R + [(OBSERVE, 4), (OBSERVE, 1)]
@@ -379,7 +390,7 @@ def observed_segments(st, n_init, n_public):
     if st.ops != [o for o in ops if o[0] != OBSERVE or o[1]]:
         return None
     seg, at = {}, 0
-    for name, n in (("init", n_init), ("trace_root", 8), ("public_values", sum(n_public))) + \
+    for name, n in (("init", n_init),) + prep + (("trace_root", 8), ("public_values", sum(n_public))) + \
                    ((("perm_root", 8), ("cumsums", 4 * n_perm)) if n_perm else ()) + \
                    (("quotient_root", 8), ("commit_roots", 8 * R), ("final_poly", 4), ("witness", 1)):
         seg[name] = (at, n)
@@ -388,28 +399,40 @@ def observed_segments(st, n_init, n_public):
     return seg
 
 
-def verify_transcript_statement(tables, shard_proof, init, fri_proof, params=None) -> int:
+def verify_transcript_statement(tables, shard_proof, init, fri_proof, params=None, prep_root=None) -> int:
     """0 iff fri_proof proves, for shard_proof, what verify_open_statement states and that the query indices, the proof of
     work, beta, zeta, both alpha, the roots and the final polynomial are what rk_p3_verify's challenger gives over the words
     it observes.  Everything is recomputed from the shard proof through the four capture calls; the segments of `observed`
     and `sampled` are checked word for word against the public values the other tables take (the same Montgomery arrays
     go to both sides: that is the in-STARK link), `observed` must start with init, the trace root and the tables' public
     values, all eight heights are pinned, and fri_proof is verified against them.  Otherwise the reason (rk_p3_verify's
-    numbering, as verify_open_statement; 1 where the captures do not fit each other)."""
+    numbering, as verify_open_statement; 1 where the captures do not fit each other).  prep_root: the verifying key's root
+    of a shard proof with preprocessed columns, the root the caller trusts: the observed segment behind init must be
+    that root, and so must the public value the preprocessed tree of ipath ends in."""
     _check_scope(params)
-    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params)
+    rc, shape, pub, rec = F.fri_openings(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape2, layout, in_pub, in_rec = G.fri_inputs(tables, shard_proof, init, params)
+    rc, shape2, layout, in_pub, in_rec = G.fri_inputs(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape3, roots, paths = H.fri_input_paths(tables, shard_proof, init, params)
+    rc, shape3, roots, paths = H.fri_input_paths(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
-    rc, shape4, ops, obs, smp = fri_transcript(tables, shard_proof, init, params)
+    rc, shape4, ops, obs, smp = fri_transcript(tables, shard_proof, init, params, prep_root)
     if rc != 0:
         return rc
+    return _check_bound(tables, init, fri_proof, params, prep_root, (shape, pub, rec), (shape2, layout, in_pub, in_rec), (shape3, roots, paths),
+                        (shape4, ops, obs, smp))
+
+
+def _check_bound(tables, init, fri_proof, params, prep_root, openings, inputs, in_paths, transcript) -> int:
+    """verify_transcript_statement behind its four captures (shape and arrays of each): the host-side binding, then the
+    proof.  On its own so that a test can hand it captures that were tampered with."""
+    (shape, pub, rec), (shape2, layout, in_pub, in_rec), (shape3, roots, paths), (shape4, ops, obs, smp) = openings, inputs, in_paths, transcript
     if shape2 != shape or shape3 != shape or shape4 != shape or not G._check_zeta(in_pub):
+        return 1
+    if not H._roots_bound(roots, prep_root):
         return 1
     opn = H.Statement(G.Statement(F.Statement(shape, pub, rec, params), layout, in_pub, in_rec, params), roots, paths)
     st = Statement(opn, ops, obs, smp)
@@ -425,6 +448,11 @@ def verify_transcript_statement(tables, shard_proof, init, fri_proof, params=Non
     if st.plan.n_pub != s0 + 12 + 4 * R:
         return 1
     ok = np.array_equal(at("init"), iw) and np.array_equal(at("trace_root"), roots[:8]) and np.array_equal(at("public_values"), pvs)
+    if prep_root is not None:                                # the key the caller trusts, where the chain observes it and where ipath ends
+        kr = np.ascontiguousarray(prep_root, dtype=np.uint32).reshape(-1)
+        ok = ok and "prep_root" in seg and np.array_equal(at("prep_root"), kr) and np.array_equal(at("prep_root"), roots[25:33])
+    else:
+        ok = ok and "prep_root" not in seg
     ok = ok and np.array_equal(at("quotient_root"), roots[16:24]) and (not n_perm or np.array_equal(at("perm_root"), roots[8:16]))
     ok = ok and np.array_equal(at("commit_roots"), st.fold.roots) and np.array_equal(at("final_poly"), st.fold.publics[12 * R:])
     zeta, alpha2 = st.sampled[s0 + 4: s0 + 8], st.sampled[s0 + 8: s0 + 12]

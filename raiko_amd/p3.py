@@ -610,9 +610,9 @@ def verify(tables, proof, init=(), params=None, prep_root=None) -> int:
     return rc
 
 
-def verify_hashes(tables, proof, init=(), params=None):
+def verify_hashes(tables, proof, init=(), params=None, prep_root=None):
     """rk_p3_verify_hashes -> (verdict, (n, p2_width) uint32 array: the input state of every Poseidon2 permutation the
-    check performed, in order)"""
+    check performed, in order).  prep_root: the verifying key's root -- rk_p3_verify_hashes_key, as `verify`"""
     lib = _lib.load()
     arr, keep = _c_tables(tables)
     iw = np.ascontiguousarray(init, dtype=np.uint32)
@@ -621,10 +621,15 @@ def verify_hashes(tables, proof, init=(), params=None):
     n = C.c_size_t(0)
     par = C.byref(params) if params is not None else None
     cap = 1 << 16                  # enough for a 100-query proof of a few tables: one pass; otherwise the call says how many
+    fn, keyed = lib.rk_p3_verify_hashes, ()
+    if prep_root is not None:
+        kr = np.ascontiguousarray(prep_root, dtype=np.uint32)
+        assert kr.size == 8
+        fn, keyed = lib.rk_p3_verify_hashes_key, (kr.ctypes.data_as(_lib.u32p),)
     while True:
         states = np.zeros((cap, w), dtype=np.uint32)
-        rc = lib.rk_p3_verify_hashes(par, arr, len(tables), iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
-                                     states.ctypes.data_as(_lib.u32p), cap, C.byref(n))
+        rc = fn(par, arr, len(tables), *keyed, iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size,
+                states.ctypes.data_as(_lib.u32p), cap, C.byref(n))
         if rc != _lib.RK_ERR_CAPACITY:
             break
         cap = n.value
