@@ -710,6 +710,54 @@ int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
                                  const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
                                  uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
                                  uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows);
+/* THE RV32IM-MEM CHIP SET: rv32im-elf's statement with loads, stores and memory constrained WITHIN A SHARD
+ * (raiko_amd/rv32mem.py builds the same tables in numpy, names every column and writes the AIRs).  Keyed like rv32im-elf
+ * and proven through rk_p3_prove_shards_key; nine tables, rv32im-elf's seven in their order, then memop and memory:
+ *   cpu       2^po2 x RK_RV32MEM_CPU_COLS: columns 0..131 the rv32im row, word for word; then IS_LOAD, IS_STORE, MEM_OP
+ *             (funct3 + 8 IS_STORE), MIMM_LO / MIMM_HI (imm_I of a load, imm_S of a store) and IS_SYS (looked up), the
+ *             multiplicities M_MEM = IS_LOAD WR + IS_STORE ACTIVE and N_ECW (the words the row's ecall wrote) and
+ *             EC_OP = 16 IS_SYS.  A row sends (MEM_OP, TSA, A, MIMM, B, RES) M_MEM times and (EC_OP, TSA) N_ECW times
+ *   program   preprocessed RK_RV32MEM_PROGRAM_PREP_COLS columns: rv32im-elf's 41 fields, the six above, VALID (rv32im-elf's,
+ *             and 0 on a LOAD / STORE word whose funct3 the executor traps); trace: the count
+ *   register, byte, range, shift, muldiv   as for rv32im-elf (the counts include the lookups of memop and memory)
+ *   memop     memop_rows x RK_RV32MEM_MEMOP_COLS: one row per recorded access (rk_exec_mem_accesses) in list order, then
+ *             padding rows (ONE = 1, the rest 0): the op one-hot, the cpu row's tuple, the address sum with its carries and
+ *             split into word address and byte offset, the bytes of the word before and after and of rs2, the selected
+ *             byte / half, its sign bit, the previous access's timestamp and the difference's limbs
+ *   memory    memory_rows x RK_RV32MEM_MEMORY_COLS: one row per distinct touched word in ascending address order: (WL, WH,
+ *             INIT lo / hi, FINAL lo / hi, FTS, REAL, GL, GH, WL4, SAME, FINV), the word address as WL + 2^14 WH (WL, 4 WL and
+ *             WH range-checked), the distance to the next row's address limb by limb (SAME and GL when the high limbs
+ *             agree, GH otherwise) and the inverse of FTS (a real row was touched); then rows of zeros.  THE BOUNDARY
+ *             TABLE: what a link between shards would bind
+ * CONSTRAINED: everything rv32im-elf constrains; the value LB / LH / LW / LBU / LHU write and the word SB / SH / SW leave,
+ * against one history per word inside the shard.  FREE: INIT of every touched word (the boundary to the previous shard
+ * and to the ELF's data image), what an ecall writes, the a0 it leaves.
+ * rk_exec_mem_accesses: the access list of segment `index` (needs record_trace): *n entries of four words (cycle within
+ * the segment, word address addr >> 2, word before, word after) in cycle order -- one per store, one per load whose rd is
+ * not x0 (after = before) and one per word an ecall READ wrote, at the ecall's cycle in ascending address order.
+ * Instruction fetch and the reads of an ecall COMMIT are not recorded.  RK_ERR_CAPACITY with *n set when more than
+ * `capacity` entries.
+ * rk_exec_rv32mem_sizes: the rows of the memop and the memory table (2^max(RK_RV32MEM_MIN_LOG_ROWS, ceil(log2 count)));
+ * RK_ERR_CAPACITY for a segment with more accesses than 2^(po2 + 1).  rk_rv32mem_prep_device: rk_rv32elf_prep_device
+ * with the 48-column program matrix.  rk_exec_rv32mem_shard_device: rk_exec_rv32elf_shard_device with the two tables
+ * more; memop_rows / memory_rows: a power of two from what rk_exec_rv32mem_sizes gives up to 2^(po2 + 1).
+ * RK_ERR_INVALID, before any launch and with nothing written, for a buffer with fewer rows than that, more than
+ * 2^(po2 + 1) or not a power of two, and for an access list that is not in cycle order. */
+#define RK_RV32MEM_CPU_COLS 141
+#define RK_RV32MEM_PROGRAM_PREP_COLS 48
+#define RK_RV32MEM_MEMOP_COLS 64
+#define RK_RV32MEM_MEMORY_COLS 13
+#define RK_RV32MEM_MIN_LOG_ROWS 1
+int rk_exec_mem_accesses(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n);
+int rk_exec_rv32mem_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows);
+int rk_rv32mem_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                           const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                           uint32_t* d_range, uint32_t* d_shift);
+int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                 const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                 uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                 uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                 uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 

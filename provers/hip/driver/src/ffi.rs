@@ -89,6 +89,11 @@ pub const RK_RV32IM_MULDIV_COLS: u32 = 78;
 pub const RK_RV32IM_MULDIV_MIN_LOG_ROWS: u32 = 1;
 pub const RK_RV32ELF_MAX_SEGMENTS: u32 = 16;
 pub const RK_RV32ELF_PROGRAM_PREP_COLS: u32 = 42;
+pub const RK_RV32MEM_CPU_COLS: u32 = 141;
+pub const RK_RV32MEM_PROGRAM_PREP_COLS: u32 = 48;
+pub const RK_RV32MEM_MEMOP_COLS: u32 = 64;
+pub const RK_RV32MEM_MEMORY_COLS: u32 = 13;
+pub const RK_RV32MEM_MIN_LOG_ROWS: u32 = 1;
 
 #[repr(C)]
 pub struct rk_air {
@@ -604,6 +609,10 @@ extern "C" {
     pub fn rk_exec_program_image(elf: *const u8, elf_bytes: usize, seg_vaddr: *mut u32, seg_words: *mut u32, seg_capacity: usize, n_segs: *mut usize, words: *mut u32, word_capacity: usize, n_words: *mut usize) -> c_int;
     pub fn rk_rv32elf_prep_device(ctx: *mut rk_ctx, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, words: *const u32, n_words: usize, d_program: *mut u32, program_rows: usize, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
     pub fn rk_exec_rv32elf_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize) -> c_int;
+    pub fn rk_exec_mem_accesses(ex: *const rk_exec, index: u32, out: *mut u32, capacity: usize, n: *mut usize) -> c_int;
+    pub fn rk_exec_rv32mem_sizes(ex: *const rk_exec, index: u32, memop_rows: *mut usize, memory_rows: *mut usize) -> c_int;
+    pub fn rk_rv32mem_prep_device(ctx: *mut rk_ctx, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, words: *const u32, n_words: usize, d_program: *mut u32, program_rows: usize, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
+    pub fn rk_exec_rv32mem_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize, d_memop: *mut u32, memop_rows: usize, d_memory: *mut u32, memory_rows: usize) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;

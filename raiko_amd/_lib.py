@@ -294,6 +294,13 @@ SYMBOLS = {
     "rk_exec_rv32elf_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_size_t]),
+    "rk_exec_mem_accesses": (C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rk_exec_rv32mem_sizes": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rk_rv32mem_prep_device": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, u32p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "rk_exec_rv32mem_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rk_exec_error": (C.c_char_p, [C.c_void_p]),
     "rk_exec_free": (C.c_int, [C.c_void_p]),
     "rk_program_create": (C.c_int, [_vp, _sz, _u32, C.POINTER(RkTaps), C.POINTER(_vp)]),

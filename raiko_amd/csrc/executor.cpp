@@ -114,6 +114,12 @@ struct rk_exec {
     // TraceRow -- and the lowest / highest pc executed (the rv32i chip set's program table, rk_exec_rv32_*)
     std::vector<std::vector<std::array<uint32_t, 2>>> ecalls;
     std::vector<std::array<uint32_t, 2>> pc_range;
+    // per segment, with record_trace: (cycle, word address, old word, new word) of every data access the rv32im-mem chip
+    // set proves (ExecSegmentView.mem); `mem_now` collects the running segment's, `cycle_now` is its cycle counter
+    std::vector<std::vector<std::array<uint32_t, 4>>> mem;
+    std::vector<std::array<uint32_t, 4>> mem_now;
+    uint32_t cycle_now = 0;
+    mutable std::vector<size_t> mem_words;       // per segment: exec_mem_words's answer, SIZE_MAX until asked
     // the machine between segments (rk_exec_open / rk_exec_next_segment run it one segment at a time)
     Machine m;
     std::unique_ptr<p2::Any> k;                  // the default Poseidon2 instance: state digests at the boundaries
@@ -185,6 +191,7 @@ int step(Machine& m, rk_exec& ex, const rk_exec_opts& o, size_t& in_pos, std::st
         }
         case 0x03: {                                                                 // loads
             uint32_t addr = a + (uint32_t)sext(ins >> 20, 12);
+            const uint32_t seen = row && rd != 0 ? m.load_word(addr & ~3u) : 0u;   // the word as the access finds it
             switch (f3) {
                 case 0: res = (uint32_t)(int32_t)(int8_t)m.load_byte(addr); break;
                 case 4: res = m.load_byte(addr); break;
@@ -200,11 +207,13 @@ int step(Machine& m, rk_exec& ex, const rk_exec_opts& o, size_t& in_pos, std::st
                     break;
                 default: return trap("illegal instruction");
             }
+            if (row && rd != 0) ex.mem_now.push_back({ex.cycle_now, addr >> 2, seen, seen});
             wr = true;
             break;
         }
         case 0x23: {                                                                 // stores
             uint32_t addr = a + (uint32_t)sext(((ins >> 25) << 5) | ((ins >> 7) & 31), 12);
+            const uint32_t seen = row ? m.load_word(addr & ~3u) : 0u;
             switch (f3) {
                 case 0: m.store_byte(addr, (uint8_t)b); break;
                 case 1:
@@ -217,6 +226,7 @@ int step(Machine& m, rk_exec& ex, const rk_exec_opts& o, size_t& in_pos, std::st
                     break;
                 default: return trap("illegal instruction");
             }
+            if (row) ex.mem_now.push_back({ex.cycle_now, addr >> 2, seen, m.load_word(addr & ~3u)});
             break;
         }
         case 0x13: {                                                                 // OP-IMM
@@ -287,7 +297,9 @@ int step(Machine& m, rk_exec& ex, const rk_exec_opts& o, size_t& in_pos, std::st
                     uint32_t dst = m.x[10], cap = m.x[11], got = 0;
                     if (dst & 3) return trap("misaligned read destination");
                     while (got < cap && in_pos < o.n_input_words) {
-                        *m.word_ptr(dst + 4 * got) = o.input_words[in_pos++];
+                        uint32_t* w = m.word_ptr(dst + 4 * got);
+                        if (row) ex.mem_now.push_back({ex.cycle_now, (dst + 4 * got) >> 2, *w, o.input_words[in_pos]});
+                        *w = o.input_words[in_pos++];
                         got++;
                     }
                     m.x[10] = got;
@@ -359,6 +371,7 @@ int exec_next(rk_exec* ex, int* more) {
     std::copy(m.x, m.x + 32, regs.begin());
     std::vector<std::array<uint32_t, 2>> ecalls;
     uint32_t pc_lo = 0xffffffffu, pc_hi = 0;
+    ex->mem_now.clear();
     if (o.record_trace) trace.reserve((size_t)std::min<uint64_t>(limit, (uint64_t)1 << 22));  // 28 bytes per cycle, no regrowth copies
     while (cycles < limit) {
         if (o.session_limit && ex->total >= o.session_limit) {
@@ -367,6 +380,7 @@ int exec_next(rk_exec* ex, int* more) {
             break;
         }
         TraceRow row{};
+        ex->cycle_now = (uint32_t)cycles;
         if (o.profile) ex->pc_cycles[m.pc]++;
         int r = step(m, *ex, o, ex->in_pos, ex->error, o.record_trace ? &row : nullptr);
         if (r < 0) { ex->st = r; break; }
@@ -395,6 +409,8 @@ int exec_next(rk_exec* ex, int* more) {
             ex->traces.push_back(std::move(trace));
             ex->ecalls.push_back(std::move(ecalls));
             ex->pc_range.push_back({pc_lo, pc_hi});
+            ex->mem.push_back(std::move(ex->mem_now));
+            ex->mem_now.clear();
         }
         if (ex->segments.size() > (1u << 20)) { ex->error = "more than 2^20 segments"; ex->st = RK_ERR_CAPACITY; }
     }
@@ -413,11 +429,26 @@ int exec_elf(const uint8_t* elf, size_t elf_bytes, const rk_exec_opts* o, rk_exe
 
 }  // namespace
 
+// Not safe for two threads on one executor: the answer is kept in a mutable vector.  Its callers (rk_exec_rv32mem_sizes,
+// rk_exec_rv32mem_shard_device) run on the thread that steps the executor, as every rk_exec_* call on one handle must.
+size_t exec_mem_words(const rk_exec* ex, uint32_t index) {
+    if (!ex || index >= ex->mem.size()) return 0;
+    if (ex->mem_words.size() < ex->mem.size()) ex->mem_words.resize(ex->mem.size(), SIZE_MAX);
+    if (ex->mem_words[index] == SIZE_MAX) {
+        std::vector<uint32_t> a;
+        a.reserve(ex->mem[index].size());
+        for (const auto& m : ex->mem[index]) a.push_back(m[1]);
+        std::sort(a.begin(), a.end());
+        ex->mem_words[index] = (size_t)(std::unique(a.begin(), a.end()) - a.begin());
+    }
+    return ex->mem_words[index];
+}
+
 int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out) {
     if (!ex || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
     if (ex->traces[index].size() != ex->segments[index].cycles) return RK_ERR_INTERNAL;
     *out = ExecSegmentView{&ex->segments[index], &ex->traces[index], ex->regs[index].data(), &ex->ecalls[index],
-                           ex->pc_range[index][0], ex->pc_range[index][1]};
+                           ex->pc_range[index][0], ex->pc_range[index][1], &ex->mem[index]};
     return RK_OK;
 }
 
@@ -585,6 +616,14 @@ int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capa
     *n = ec.size();
     if (ec.size() > capacity || (!out && !ec.empty())) return RK_ERR_CAPACITY;
     for (size_t k = 0; k < ec.size(); k++) out[2 * k] = ec[k][0], out[2 * k + 1] = ec[k][1];
+    return RK_OK;
+}
+int rk_exec_mem_accesses(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n) {
+    if (!ex || !n || index >= ex->mem.size()) return RK_ERR_INVALID;
+    const auto& mem = ex->mem[index];
+    *n = mem.size();
+    if (mem.size() > capacity || (!out && !mem.empty())) return RK_ERR_CAPACITY;
+    for (size_t k = 0; k < mem.size(); k++) std::copy(mem[k].begin(), mem[k].end(), out + 4 * k);
     return RK_OK;
 }
 

@@ -19,8 +19,14 @@ struct ExecSegmentView {
     const uint32_t* regs;                                 // x0..x31 at the segment's start, then at its end
     const std::vector<std::array<uint32_t, 2>>* ecalls;   // (cycle, a0 after the call) of every ecall row, in cycle order
     uint32_t pc_lo, pc_hi;                                // the lowest / highest pc executed
+    // (cycle, word address addr >> 2, old word, new word) of every store, every load whose rd is not x0 (new = old) and
+    // every word an ecall READ writes, in cycle order (the words of one ecall in ascending address order)
+    const std::vector<std::array<uint32_t, 4>>* mem;
 };
 
 // RK_ERR_INVALID: no executor, or no recorded segment `index`; RK_ERR_INTERNAL: the trace is not seg->cycles rows long.
 // Not part of the library's ABI.
 __attribute__((visibility("hidden"))) int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out);
+// the distinct word addresses in the access list of recorded segment `index` (the rows of the rv32im-mem memory table):
+// counted by a sort on the first call, remembered for the next
+__attribute__((visibility("hidden"))) size_t exec_mem_words(const rk_exec* ex, uint32_t index);

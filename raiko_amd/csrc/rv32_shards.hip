@@ -1,7 +1,7 @@
 // The witness of an executed segment written on the GPU (include/raiko_hip.h): the stand-in trace circuit's columns
 // (rk_exec_witness_device*) and the tables of the rv32 chip sets (rk_exec_rv32_shard_device,
-// rk_exec_rv32cf_shard_device, rk_exec_rv32im_shard_device, rk_exec_rv32elf_shard_device and the preprocessed matrices of
-// the last, rk_rv32elf_prep_device).  The segment is read through executor.hpp's view; what a
+// rk_exec_rv32cf_shard_device, rk_exec_rv32im_shard_device, rk_exec_rv32elf_shard_device, rk_exec_rv32mem_shard_device and
+// the preprocessed matrices of the last two, rk_rv32elf_prep_device / rk_rv32mem_prep_device).  The segment is read through executor.hpp's view; what a
 // row holds is rv32_rows.hpp's lane bodies (raiko_amd/rv32.py, rv32cf.py, rv32im.py, rv32elf.py are the same in numpy and
 // name every column).  What is here: the kernels around those bodies -- the wave-level code, the atomics, the LDS staging -- and
 // the host driver.
@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include "rv32_rows.hpp"
 
@@ -68,10 +70,12 @@ static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32
 // -> rows (in-block resolve of each access's predecessor, the cpu row staged through LDS, RANGE16 / BYTE / SHIFT counts)
 // -> rv32im: the muldiv rows -> the program, byte, range, register and shift tables.  rv32im-elf: the same pipeline; a
 // cycle is counted at the image row of its pc (its word compared with the image's) and the program, byte, range and
-// shift tables leave as count columns.
+// shift tables leave as count columns.  rv32im-mem: rv32im-elf's pipeline and, from the access list: keys (word address,
+// list index; the ecall rows' per-cycle counts) -> rocPRIM's stable radix sort by the 30 address bits -> heads per block,
+// scan -> link (each access's predecessor, the boundary rows) -> the memop rows.
 namespace rv32 {
 
-constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 for rv32i-cf / rv32im)
+constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 / 141 for rv32i-cf / rv32im / rv32im-mem)
 
 // a histogram bin += 1 for every lane with `on`; the lanes of a wave that agree with its first active lane add once
 __device__ inline void hist_add(uint32_t* h, uint32_t v, bool on) {
@@ -234,7 +238,7 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
                                                    const uint32_t* __restrict__ pre, const uint32_t* __restrict__ init,
                                                    uint32_t* __restrict__ out, uint32_t* __restrict__ hist,
                                                    uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
-                                                   size_t n) {
+                                                   const uint32_t* __restrict__ necw, size_t n) {
     using CH = Chips<CS>;
     extern __shared__ uint32_t s_rows[];            // TB x (cpu_w | 1)
     __shared__ uint32_t s_wave[32][TB / 64];
@@ -283,6 +287,7 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
             cpu_row_i(row, r, d, wval[i], tsa, e1, pb, pw, wr ? value_at(pw, wreg, tr, wval, init) : 0, m);
             if constexpr (CH::cf) cpu_row_cf(row, r, d, m);
             if constexpr (CH::im) cpu_row_im(row, d);
+            if constexpr (CH::mem) cpu_row_mem(row, d, necw[i]);   // necw: the access list's entries per cycle at ecall rows
         } else {
             trace_cells(padding_row(end_pc), false, row);
         }
@@ -335,11 +340,12 @@ __global__ void count_kernel(const uint32_t* __restrict__ counts, size_t n_count
     if (r < n_rows) out[r] = enc(r < n_counts ? counts[r] : 0u);
 }
 
+template <bool MEM>   // MEM: rv32im-mem's 48 columns
 __global__ void program_prep_kernel(const uint32_t* __restrict__ words, uint32_t n_words, const Image img, size_t n_rows,
                                     uint32_t* __restrict__ out) {
     extern __shared__ uint32_t s_rows[];
     const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    prep_tile<IM_PROG_W, ELF_PROG_W>(
+    prep_tile<IM_PROG_W, MEM ? MEM_PROG_W : ELF_PROG_W>(
         s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows,
         [&](uint32_t* row) {
             if (s >= n_rows) return;
@@ -350,7 +356,10 @@ __global__ void program_prep_kernel(const uint32_t* __restrict__ words, uint32_t
             program_row_cf(row, d);
             program_row_im(row, ins, d);
         },
-        [](uint32_t* o, const uint32_t* row) { program_prep_row(o, row); });
+        [](uint32_t* o, const uint32_t* row) {
+            if constexpr (MEM) program_prep_row_mem(o, row, decode(row[2] | row[3] << 16));
+            else program_prep_row(o, row);
+        });
 }
 
 __global__ void byte_prep_kernel(uint32_t* __restrict__ out) {
@@ -483,6 +492,97 @@ __global__ void muldiv_kernel(const TraceRow* __restrict__ tr, size_t cycles, co
     });
 }
 
+// ---- rv32im-mem: the memop and memory tables from the access list (acc: count entries in cycle order)
+// one lane per access: its sort key (the word address, 30 bits) and payload (its list index); an access at an ecall row
+// is counted at its cycle (necw: what rows_kernel writes as N_ECW)
+__global__ void mem_keys_kernel(const MemAccess* __restrict__ acc, size_t count, const TraceRow* __restrict__ tr,
+                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ necw) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const MemAccess m = acc[k];
+    keys[k] = m.waddr;
+    vals[k] = (uint32_t)k;
+    if ((tr[m.cycle].ins & 0x7fu) == OPCODES[O_SYSTEM]) atomicAdd(&necw[m.cycle], 1u);   // m.cycle < cycles: checked on the host
+}
+
+__device__ inline bool mem_head(const uint32_t* keys, size_t i, size_t count) {
+    return i < count && (i == 0 || keys[i] != keys[i - 1]);
+}
+
+// per block of TB sorted positions: how many start a run of one address
+__global__ void mhead_count_kernel(const uint32_t* __restrict__ keys, size_t count, uint32_t* __restrict__ hblk) {
+    const int c = __syncthreads_count(mem_head(keys, (size_t)blockIdx.x * TB + threadIdx.x, count));
+    if (threadIdx.x == 0) hblk[blockIdx.x] = (uint32_t)c;
+}
+
+// one lane per sorted position i: the access before it at its word is its left neighbour unless it heads its run (pts, in
+// list order).  A head writes the boundary row of its word: its index is the heads before it (hblk: the exclusive scan
+// over blocks, then the ballot compaction of mcompact_kernel), INIT its own old word, FINAL / FTS its run's tail, found
+// by binary search for the next address, and the limb-wise distance to that address.  The block's rows leave LDS as whole lines.
+__global__ void __launch_bounds__(TB) mem_link_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                       const MemAccess* __restrict__ acc, size_t count,
+                                                       const uint32_t* __restrict__ hblk, uint32_t* __restrict__ pts,
+                                                       uint32_t* __restrict__ out, size_t n_rows, uint32_t* __restrict__ hist,
+                                                       uint32_t* __restrict__ err) {
+    __shared__ uint32_t s_rows[TB * BD_W];
+    __shared__ uint32_t s_wave[TB / 64];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool on = i < count, head = mem_head(keys, i, count);
+    const uint32_t key = on ? keys[i] : 0u;
+    if (on) pts[vals[i]] = head ? 0u : 3 * acc[vals[i - 1]].cycle + 1;
+    const uint64_t bal = __ballot(head);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t li = (uint32_t)__popcll(bal & ((1ull << lane) - 1)), total = 0;
+    for (unsigned w = 0; w < TB / 64; w++) {
+        if (w < wave) li += s_wave[w];
+        total += s_wave[w];
+    }
+    uint32_t row[BD_W] = {0};
+    if (head) {
+        size_t lo = i + 1, hi = count;   // the first position past the run
+        while (lo < hi) {
+            const size_t mid = (lo + hi) / 2;
+            if (keys[mid] == key) lo = mid + 1;
+            else hi = mid;
+        }
+        const MemAccess first = acc[vals[i]], last = acc[vals[lo - 1]];
+        memory_row(row, key, first.before, last.after, 3 * last.cycle + 1, lo < count, lo < count ? keys[lo] : 0u);
+        for (unsigned c = 0; c < BD_W; c++) s_rows[li * BD_W + c] = enc(row[c]);
+    }
+    for (unsigned c : BD_RANGE) hist_add(hist, row[c], head);
+    __syncthreads();
+    const size_t r0 = hblk[blockIdx.x];
+    if (r0 + total > n_rows) {   // the device's count of distinct words is not the host's (reported after the run)
+        if (threadIdx.x == 0) atomicOr(err, 64u);
+        return;
+    }
+    for (size_t k = threadIdx.x; k < (size_t)total * BD_W; k += TB) out[r0 * BD_W + k] = s_rows[k];
+}
+
+// one lane per memop row: row k < count is the witness of access k, rows past count padding (ONE = 1, the rest 0); the
+// RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms
+__global__ void memop_kernel(const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval, const MemAccess* __restrict__ acc,
+                             const uint32_t* __restrict__ pts, size_t count, size_t n_rows, uint32_t* __restrict__ out,
+                             uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
+                             uint32_t* __restrict__ err) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<MO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+        row[G_ONE] = 1;
+        const bool on = k < count;
+        if (on) {
+            const MemAccess m = acc[k];
+            const TraceRow r = tr[m.cycle];
+            if (!memop_row(row, m, r, decode(r.ins), wval[m.cycle], pts[k])) atomicOr(err, 32u);   // not what the instruction names
+        }
+        for (unsigned c : MO_RANGE) hist_add(hist, row[c], on);
+        hist_add(shift_mult, 256u + row[G_TOP], on);   // (1, top byte) -> row 256 + x
+        for (unsigned j = 0; j < 6; j++) hist_add(byte_mult, row[G_W + 2 * j] << 8 | row[G_W + 2 * j + 1], on);   // AND (op 1)
+    });
+}
+
 static size_t program_rows_of(const ExecSegmentView& v, uint32_t* n_slots) {
     const uint32_t slots = v.trace->empty() ? 0 : (v.pc_hi - v.pc_lo) / 4 + 1;
     size_t rows = 2;
@@ -526,6 +626,13 @@ static size_t muldiv_rows_for(size_t count) {
     return rows;
 }
 
+// rv32im-mem: the memop / memory table's rows for `count` accesses / distinct words
+static size_t mem_rows_for(size_t count) {
+    size_t rows = (size_t)1 << RK_RV32MEM_MIN_LOG_ROWS;
+    while (rows < count) rows <<= 1;
+    return rows;
+}
+
 namespace {
 
 // the tables a shard's driver writes: rv32i's five, d_shift the sixth of rv32i-cf, d_muldiv (muldiv_rows rows) the
@@ -539,6 +646,10 @@ struct ShardOut {
     Image img;
     const uint32_t* image_words;
     size_t n_words;
+    uint32_t* memop = nullptr;   // rv32im-mem
+    size_t memop_rows = 0;
+    uint32_t* memory = nullptr;
+    size_t memory_rows = 0;
 };
 
 // the driver's scratch: one allocation, each part's offset in words from one take(), rounded to 64 words
@@ -552,7 +663,9 @@ struct Scratch {
     size_t tr, ec, wval, acc, blk, final_ts, fin, init;
     size_t err, hist, bmult, pmult, pins, smult, clear_end;   // [err, clear_end): zero before the first kernel
     size_t mflag, mblk, mtotal, midx;                          // rv32im
-    Scratch(bool cf, bool im, bool elf, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count) {
+    size_t macc, mkeys, mvals, mkeys2, mvals2, mpts, necw, hblk, htotal;   // rv32im-mem
+    Scratch(bool cf, bool im, bool elf, bool mem, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count,
+            size_t mem_count) {
         const size_t nb = n / TB, slots = std::max<uint32_t>(n_slots, 1), sw = cf ? SHIFT_USED : 1u;
         tr = take((std::max<size_t>(cycles, 1) * sizeof(TraceRow) + 3) / 4);
         ec = take(2 * std::max<size_t>(n_ecalls, 1));
@@ -573,6 +686,19 @@ struct Scratch {
         mblk = take(im ? nb : 1);
         mtotal = take(1);
         midx = take(std::max<size_t>(m_count, 1));
+        macc = mkeys = mvals = mkeys2 = mvals2 = mpts = necw = hblk = htotal = 0;
+        if (mem) {
+            const size_t mc = std::max<size_t>(mem_count, 1);
+            macc = take(4 * mc);
+            mkeys = take(mc);
+            mvals = take(mc);
+            mkeys2 = take(mc);
+            mvals2 = take(mc);
+            mpts = take(mc);
+            necw = take(n);
+            hblk = take((mc + TB - 1) / TB);
+            htotal = take(1);
+        }
     }
 };
 
@@ -581,7 +707,7 @@ struct Scratch {
 // the copies and the launches of one shard, in stream order; returns at the first error
 template <int CS>
 static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& o, const Scratch& L, uint32_t* w,
-                         const std::vector<uint32_t>& ec_flat, uint32_t n_slots, size_t m_count) {
+                         const std::vector<uint32_t>& ec_flat, uint32_t n_slots, size_t m_count, void* sort_tmp, size_t sort_bytes) {
     using CH = Chips<CS>;
     const std::vector<TraceRow>& tr = *v.trace;
     const size_t n = (size_t)1 << v.seg->po2, nb = n / TB;
@@ -598,6 +724,30 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     hipLaunchKernelGGL(prep_kernel<CH::elf>, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
                        (uint32_t)ec_flat.size() / 2, v.pc_lo, n_slots, wval, acc, pmult, pins, err, CH::im ? mflag : nullptr, image);
     RK_TRY(rk::post_launch(ctx, "rv32 prep_kernel"));
+    const size_t mem_count = CH::mem ? v.mem->size() : 0;
+    const MemAccess* macc = (const MemAccess*)(w + L.macc);
+    if constexpr (CH::mem) {   // the sorted access list, each access's predecessor and the boundary rows (before rows_kernel: necw)
+        static_assert(sizeof(MemAccess) == 16, "an access is four words, as the executor records it");
+        RK_HIP_TRY(ctx, hipMemsetAsync(w + L.necw, 0, ((size_t)1 << v.seg->po2) * 4, ctx->stream));
+        RK_HIP_TRY(ctx, hipMemsetAsync(w + L.htotal, 0, 4, ctx->stream));
+        RK_HIP_TRY(ctx, hipMemsetAsync(o.memory, 0, o.memory_rows * BD_W * 4, ctx->stream));   // the rows past the touched words
+        if (mem_count) {
+            RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.macc, v.mem->data(), mem_count * sizeof(MemAccess), hipMemcpyHostToDevice, ctx->stream));
+            const unsigned kb = (unsigned)((mem_count + TB - 1) / TB);
+            hipLaunchKernelGGL(mem_keys_kernel, dim3(kb), dim3(TB), 0, ctx->stream, macc, mem_count, d_tr, w + L.mkeys, w + L.mvals, w + L.necw);
+            RK_TRY(rk::post_launch(ctx, "rv32 mem_keys_kernel"));
+            size_t bytes = sort_bytes;
+            RK_HIP_TRY(ctx, rocprim::radix_sort_pairs(sort_tmp, bytes, w + L.mkeys, w + L.mkeys2, w + L.mvals, w + L.mvals2, mem_count, 0, 30,
+                                                      ctx->stream));
+            hipLaunchKernelGGL(mhead_count_kernel, dim3(kb), dim3(TB), 0, ctx->stream, w + L.mkeys2, mem_count, w + L.hblk);
+            RK_TRY(rk::post_launch(ctx, "rv32 mhead_count_kernel"));
+            hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w + L.hblk, (size_t)kb, w + L.htotal);
+            RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+            hipLaunchKernelGGL(mem_link_kernel, dim3(kb), dim3(TB), 0, ctx->stream, w + L.mkeys2, w + L.mvals2, macc, mem_count, w + L.hblk,
+                               w + L.mpts, o.memory, o.memory_rows, hist, err);
+            RK_TRY(rk::post_launch(ctx, "rv32 mem_link_kernel"));
+        }
+    }
     hipLaunchKernelGGL(block_last_kernel, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, acc, blk);
     RK_TRY(rk::post_launch(ctx, "rv32 block_last_kernel"));
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, blk, nb, final_ts);
@@ -606,7 +756,7 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     if (lds > 64 * 1024)   // rv32im's 133-word rows: past the default dynamic LDS limit (160 KiB per CU)
         RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)rows_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(rows_kernel<CS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), v.seg->end_pc, acc, wval,
-                       blk, init, o.cpu, hist, bmult, smult, n);
+                       blk, init, o.cpu, hist, bmult, smult, w + L.necw, n);
     RK_TRY(rk::post_launch(ctx, "rv32 rows_kernel"));
     if (CH::im) {   // the muldiv rows: count per block, scan, compact, then one lane per row (before the byte / range /
                     // shift tables: its counts go into theirs)
@@ -620,6 +770,12 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
         hipLaunchKernelGGL(muldiv_kernel, dim3((unsigned)(o.muldiv_rows / b)), dim3(b), b * (MD_W | 1) * 4, ctx->stream, d_tr,
                            tr.size(), wval, midx, m_count, o.muldiv_rows, o.muldiv, hist, bmult, smult, err);
         RK_TRY(rk::post_launch(ctx, "rv32 muldiv_kernel"));
+    }
+    if constexpr (CH::mem) {   // one lane per memop row (before the count columns: its counts go into theirs)
+        const unsigned b = (unsigned)std::min<size_t>(o.memop_rows, TB);
+        hipLaunchKernelGGL(memop_kernel, dim3((unsigned)(o.memop_rows / b)), dim3(b), b * (MO_W | 1) * 4, ctx->stream, d_tr, wval, macc,
+                           w + L.mpts, mem_count, o.memop_rows, o.memop, hist, bmult, smult, err);
+        RK_TRY(rk::post_launch(ctx, "rv32 memop_kernel"));
     }
     if constexpr (CH::elf) {   // the tuples are in the key: each lookup table's trace is its count column
         const struct { const uint32_t* counts; size_t n_counts, n_rows; uint32_t* out; } cols[4] = {
@@ -658,7 +814,8 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
 template <int CS>
 static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const ShardOut& o) {
     using CH = Chips<CS>;
-    if (!ctx || !o.cpu || !o.program || !o.reg || !o.byte || !o.range || (CH::cf && !o.shift) || (CH::im && !o.muldiv))
+    if (!ctx || !o.cpu || !o.program || !o.reg || !o.byte || !o.range || (CH::cf && !o.shift) || (CH::im && !o.muldiv) ||
+        (CH::mem && (!o.memop || !o.memory)))
         return RK_ERR_INVALID;
     ExecSegmentView v;
     RK_TRY(exec_segment_view(ex, index, &v));
@@ -684,16 +841,38 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
         }
         if (o.muldiv_rows & (o.muldiv_rows - 1) || o.muldiv_rows > std::max<size_t>(n, muldiv_rows_for(0))) return RK_ERR_INVALID;
     }
+    const size_t mem_count = CH::mem ? v.mem->size() : 0, mem_words = CH::mem ? exec_mem_words(ex, index) : 0;
+    if (CH::mem) {   // powers of two that hold every row, at most twice the cpu table; nothing is written otherwise
+        const struct { size_t rows, need; const char* what; } t[2] = {{o.memop_rows, mem_rows_for(mem_count), "memop"},
+                                                                      {o.memory_rows, mem_rows_for(mem_words), "memory"}};
+        for (const auto& c : t)
+            if (c.rows < c.need || c.rows & (c.rows - 1) || c.rows > 2 * n) {
+                ctx->last_error = std::string("rk_exec_rv32mem_shard_device: the ") + c.what + " table's rows are not a power of two from what the segment needs up to twice the cpu table's";
+                return RK_ERR_INVALID;
+            }
+        static_assert(sizeof(MemAccess) == sizeof((*v.mem)[0]), "an access is four words, as the executor records it");
+        if (!mem_list_ok(v.trace->data(), cycles, (const MemAccess*)v.mem->data(), mem_count)) {
+            ctx->last_error = "rk_exec_rv32mem_shard_device: the access list is not in cycle order or is not the trace's loads, stores and ecalls";
+            return RK_ERR_INVALID;
+        }
+    }
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const Scratch L(CH::cf, CH::im, CH::elf, cycles, v.ecalls->size(), n, n_slots, m_count);
+    const Scratch L(CH::cf, CH::im, CH::elf, CH::mem, cycles, v.ecalls->size(), n, n_slots, m_count, mem_count);
+    rk::DevBuf sort_tmp;   // rocPRIM's temporary storage for the sort of mem_count pairs
+    size_t sort_bytes = 0;
+    if (mem_count) {
+        RK_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                  (uint32_t*)nullptr, mem_count, 0, 30, ctx->stream));
+        RK_TRY(sort_tmp.alloc(ctx, std::max<size_t>(sort_bytes, 4)));
+    }
     void* base = nullptr;
     RK_TRY(rk::dev_alloc(ctx, L.words * 4, &base));
     uint32_t* w = (uint32_t*)base;
     std::vector<uint32_t> ec_flat(2 * v.ecalls->size());
     for (size_t k = 0; k < v.ecalls->size(); k++) ec_flat[2 * k] = (*v.ecalls)[k][0], ec_flat[2 * k + 1] = (*v.ecalls)[k][1];
-    int st = shard_enqueue<CS>(ctx, v, o, L, w, ec_flat, n_slots, m_count);
+    int st = shard_enqueue<CS>(ctx, v, o, L, w, ec_flat, n_slots, m_count, sort_tmp.p, sort_bytes);
     // the tables are complete and the scratch can go: read back the final registers and the error flags
-    uint32_t host_fin[34] = {0};
+    uint32_t host_fin[35] = {0};
     auto hip = [&](hipError_t e, const char* what) {
         if (e != hipSuccess && st == RK_OK) {
             ctx->last_error = std::string("rk_exec_rv32_shard_device ") + what + ": " + hipGetErrorString(e);
@@ -703,9 +882,18 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
     hip(hipMemcpyAsync(host_fin, w + L.fin, 32 * 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     hip(hipMemcpyAsync(host_fin + 32, w + L.err, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     if (CH::im) hip(hipMemcpyAsync(host_fin + 33, w + L.mtotal, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
+    if (CH::mem && mem_count) hip(hipMemcpyAsync(host_fin + 34, w + L.htotal, 4, hipMemcpyDeviceToHost, ctx->stream), "d2h");
     hip(hipStreamSynchronize(ctx->stream), "sync");
     rk::dev_free(ctx, base);
     if (st != RK_OK) return st;
+    if (CH::mem && (host_fin[32] & 32)) {
+        ctx->last_error = "rk_exec_rv32mem_shard_device: an access is not the one its instruction names";
+        return RK_ERR_INTERNAL;
+    }
+    if (CH::mem && ((host_fin[32] & 64) || host_fin[34] != mem_words)) {
+        ctx->last_error = "rk_exec_rv32mem_shard_device: the distinct words on the device are not the host's";
+        return RK_ERR_INTERNAL;
+    }
     if (host_fin[32] & 7) {
         if (CH::elf && (host_fin[32] & 5))
             ctx->last_error = host_fin[32] & 1 ? "rk_exec_rv32elf_shard_device: an executed word is not the program image's word at its pc"
@@ -727,6 +915,7 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
 }
 
 // the four preprocessed matrices of an image (rk_rv32elf_prep_device): everything is checked before the first launch
+template <bool MEM>
 static int prep_device(rk_ctx* ctx, const Image& img, const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows,
                        uint32_t* d_byte, uint32_t* d_range, uint32_t* d_shift) {
     if (!ctx || !d_program || !d_byte || !d_range || !d_shift || (n_words && !words)) return RK_ERR_INVALID;
@@ -737,7 +926,7 @@ static int prep_device(rk_ctx* ctx, const Image& img, const uint32_t* words, siz
     auto enqueue = [&]() -> int {
         if (n_words) RK_HIP_TRY(ctx, hipMemcpyAsync(d_words, words, n_words * 4, hipMemcpyHostToDevice, ctx->stream));
         const unsigned pb = (unsigned)std::min<size_t>(program_rows, TB);
-        hipLaunchKernelGGL(program_prep_kernel, dim3((unsigned)(program_rows / pb)), dim3(pb), pb * (IM_PROG_W | 1) * 4, ctx->stream,
+        hipLaunchKernelGGL(program_prep_kernel<MEM>, dim3((unsigned)(program_rows / pb)), dim3(pb), pb * (IM_PROG_W | 1) * 4, ctx->stream,
                            (const uint32_t*)d_words, (uint32_t)n_words, img, program_rows, d_program);
         RK_TRY(rk::post_launch(ctx, "rv32 program_prep_kernel"));
         hipLaunchKernelGGL(byte_prep_kernel, dim3((1u << RK_RV32_BYTE_LOG_ROWS) / TB), dim3(TB), TB * (BYTE_W | 1) * 4, ctx->stream, d_byte);
@@ -822,7 +1011,29 @@ int rk_rv32elf_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_
     size_t total = 0;
     RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
     if (total != n_words) return RK_ERR_INVALID;
-    return rv32::prep_device(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    return rv32::prep_device<false>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    RK_GUARD_END
+}
+int rk_rv32mem_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                           const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                           uint32_t* d_range, uint32_t* d_shift) {
+    RK_GUARD_BEGIN
+    rv32::Image img;
+    size_t total = 0;
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
+    if (total != n_words) return RK_ERR_INVALID;
+    return rv32::prep_device<true>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    RK_GUARD_END
+}
+int rk_exec_rv32mem_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows) {
+    RK_GUARD_BEGIN
+    if (!memop_rows || !memory_rows) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    if (v.mem->size() > ((size_t)2 << v.seg->po2)) return RK_ERR_CAPACITY;
+    *memop_rows = rv32::mem_rows_for(v.mem->size());
+    *memory_rows = rv32::mem_rows_for(exec_mem_words(ex, index));
+    return RK_OK;
     RK_GUARD_END
 }
 int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
@@ -834,6 +1045,18 @@ int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
                      {}, d_image_words, 0};
     RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
     return rv32::shard_device<rv32::CS_ELF>(ctx, ex, index, o);
+    RK_GUARD_END
+}
+int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                 const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                 uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                 uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                 uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows) {
+    RK_GUARD_BEGIN
+    rv32::ShardOut o{d_cpu, d_program_mult, program_rows, d_register, d_byte_mult, d_range_mult, d_shift_mult, d_muldiv, muldiv_rows,
+                     {}, d_image_words, 0, d_memop, memop_rows, d_memory, memory_rows};
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
+    return rv32::shard_device<rv32::CS_MEM>(ctx, ex, index, o);
     RK_GUARD_END
 }
 

@@ -55,6 +55,9 @@ class Execution:
     # words) and the program table's log height, what verify_rv32_execution(prep_root=, program_log_height=) takes
     prep_root: Optional[np.ndarray] = None
     program_log_height: Optional[int] = None
+    # with record_trace: per segment the access list (k, 4): cycle, word address, word before, word after
+    # (rk_exec_mem_accesses): the side data of the rv32im-mem chip set (p3_rv32mem_shards)
+    mem: Optional[list] = None
 
 
 class ExecutorError(RuntimeError):
@@ -114,6 +117,7 @@ def execute(elf: bytes, input_words: Sequence[int] = (), segment_limit_po2: int 
                 _lib.check(None, lib.rk_exec_lookup_tables(handle, sg.index, rng.ctypes.data_as(_lib.u32p), prog.ctypes.data_as(_lib.u32p), C.byref(rows)))
                 ex.lookup_tables.append((prog, rng))
             ex.rv32 = [_rv32_side(lib, handle, sg.index) for sg in segs]
+            ex.mem = [mem_accesses(lib, handle, sg.index) for sg in segs]
         if profile:
             cnt = C.c_size_t(0)
             lib.rk_exec_profile(handle, None, None, 0, C.byref(cnt))
@@ -215,9 +219,10 @@ class Stepper:
         return seg, rows, prog, rng
 
     def next_rv32_shard(self, hal, airs, chips="rv32i", key=None):
-        """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) shard
-        written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf") -> (ExecSegment, tables without
-        host traces, [(device buffer, log_height)] per table, init words), or None after the last"""
+        """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) or
+        rv32im-mem (nine) shard written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf" /
+        "rv32im-mem") -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words),
+        or None after the last"""
         if not self.more:
             return None
         more = C.c_int(0)
@@ -445,8 +450,8 @@ class P3Pipeline:
     the proofs (rk_p3_verify is host code).  The contexts and the (compiled) AIRs live as long as the object: run() any
     number of programs, then close().  chips="rv32i" / "rv32i-cf" / "rv32im": every shard's tables of that chip set are written on
     the GPU (Stepper.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run
-    by check_rv32_chain.  chips="rv32im-elf": run() sets the program's key up first (setup_rv32_elf on the proving context),
-    proves every shard under it, checks every proof against its root, and closes it when the run ends."""
+    by check_rv32_chain.  chips="rv32im-elf" / "rv32im-mem": run() sets the program's key up first (setup_rv32_elf on the
+    proving context), proves every shard under it, checks every proof against its root, and closes it when the run ends."""
 
     def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace"):
         from . import p3
@@ -484,7 +489,7 @@ class P3Pipeline:
         done = queue.Queue()                    # cpu tables the prover is through with: freed by the thread that owns their context
         proofs, checks, kept, errors, stmts = [], [], [], [], []
         lookups, params, rv32i = self.lookups, self.params, self.chips in RV32_CHIPS
-        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs) if self.chips == "rv32im-elf" else None
+        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips) if self.chips in KEYED_CHIPS else None
         vk = dict(prep_root=key.root, program_log_height=key.program_log_height) if key else {}
         try:
             stepper = Stepper(elf, input_words, shard_po2)
@@ -598,7 +603,8 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     setup_rv32_elf commits the program image and the fixed tables once, every shard's seven traces are written on the
     GPU (rk_exec_rv32elf_shard_device) and proven under that key (rk_p3_prove_shards_key), and the run is checked against
     the key's root, which the returned Execution carries as ex.prep_root (with ex.program_log_height: together the
-    verifying key)."""
+    verifying key).  chips="rv32im-mem": rv32im-elf with loads, stores and memory constrained within every shard
+    (raiko_amd/rv32mem.py): nine traces per shard (rk_exec_rv32mem_shard_device), the same key protocol."""
     from . import p3
     from .hal import make_params
     params = params if params is not None else make_params(1)
@@ -609,8 +615,8 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
         hal = HipHal(device)
         key, vk = None, {}
         try:
-            if chips == "rv32im-elf":
-                key = setup_rv32_elf(hal, elf, params)
+            if chips in KEYED_CHIPS:
+                key = setup_rv32_elf(hal, elf, params, chips=chips)
                 vk = dict(prep_root=key.root.copy(), program_log_height=key.program_log_height)
             ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
                                                                chips=chips, key=key)
@@ -637,8 +643,11 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
 
 
 # ---- the rv32i chip set (raiko_amd/rv32.py): the register file and the integer ALU constrained ------------------------
-CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im", "rv32im-elf")
-RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im", "rv32im-elf")
+CHIPS = ("trace", "rv32i", "rv32i-cf", "rv32im", "rv32im-elf", "rv32im-mem")
+RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im", "rv32im-elf", "rv32im-mem")
+KEYED_CHIPS = ("rv32im-elf", "rv32im-mem")           # proven under the key of setup_rv32_elf
+# the tables past the muldiv table whose height the proof carries: rv32im-mem's memop and memory, at most twice the cpu's
+_RV32_MEM_TABLES = {"rv32im-mem": 2}
 
 
 # per chip set: the module with its AIRs and numpy tables, the entry point that writes a shard's tables on the GPU, the
@@ -647,7 +656,8 @@ RV32_CHIPS = ("rv32i", "rv32i-cf", "rv32im", "rv32im-elf")
 _RV32_SETS = {"rv32i": ("rv32", "rk_exec_rv32_shard_device", (), False),
               "rv32i-cf": ("rv32cf", "rk_exec_rv32cf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), False),
               "rv32im": ("rv32im", "rk_exec_rv32im_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True),
-              "rv32im-elf": ("rv32elf", "rk_exec_rv32elf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True)}
+              "rv32im-elf": ("rv32elf", "rk_exec_rv32elf_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True),
+              "rv32im-mem": ("rv32mem", "rk_exec_rv32mem_shard_device", (("rv32cf", "SHIFT_LOG_ROWS"),), True)}
 
 
 def _rv32_set(chips):
@@ -677,6 +687,17 @@ def _rv32_side(lib, handle, index):
     ec = np.zeros((max(n.value, 1), 2), dtype=np.uint32)
     _lib.check(None, lib.rk_exec_ecalls(handle, index, ec.ctypes.data_as(_lib.u32p), ec.shape[0], C.byref(n)))
     return start, end, ec[: n.value]
+
+
+def mem_accesses(lib, handle, index):
+    """rk_exec_mem_accesses -> (k, 4) uint32: cycle, word address, word before, word after"""
+    n = C.c_size_t(0)
+    st = lib.rk_exec_mem_accesses(handle, index, None, 0, C.byref(n))
+    if st != _lib.RK_ERR_CAPACITY:
+        _lib.check(None, st)
+    out = np.zeros((max(n.value, 1), 4), dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_mem_accesses(handle, index, out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n)))
+    return out[: n.value]
 
 
 def p3_rv32_airs(ext_w=None):
@@ -741,17 +762,18 @@ def p3_rv32im_shards(ex: Execution, ext_w=None, airs=None):
 
 def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
-    rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key):
-    segment `index` of an open executor as the tables of a shard of that chip set, written on hal's GPU -> (tables
-    without host traces, [(device buffer, log_height)] per table, init words)"""
+    rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key) /
+    rk_exec_rv32mem_shard_device ("rv32im-mem", key likewise): segment `index` of an open executor as the tables of a
+    shard of that chip set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per
+    table, init words)"""
     from . import p3
     _module, entry, pinned, muldiv = _rv32_set(chips)
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
-    if chips == "rv32im-elf":
-        if key is None:
-            raise ValueError("chips=\"rv32im-elf\" needs the Rv32Key of setup_rv32_elf")
+    if chips in KEYED_CHIPS:
+        if key is None or key.chips != chips:
+            raise ValueError("chips=\"%s\" needs the Rv32Key of setup_rv32_elf(chips=\"%s\")" % (chips, chips))
         rows.value = 1 << key.program_log_height
     else:
         _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
@@ -760,12 +782,19 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None):
     if muldiv:
         _lib.check(None, lib.rk_exec_rv32im_sizes(handle, index, C.byref(md_rows)))
         logs.append(md_rows.value.bit_length() - 1)
+    mem_rows = [C.c_size_t(0), C.c_size_t(0)]
+    if chips in _RV32_MEM_TABLES:    # a segment with more accesses than twice its cycles is refused here (RK_ERR_CAPACITY)
+        _lib.check(None, lib.rk_exec_rv32mem_sizes(handle, index, C.byref(mem_rows[0]), C.byref(mem_rows[1])))
+        logs += [r.value.bit_length() - 1 for r in mem_rows]
     if len(airs) != len(logs):
         raise ValueError("%d AIRs for the %d tables of %s" % (len(airs), len(logs), chips))
     bufs = [hal.alloc_elem(a.width << lg) for a, lg in zip(airs, logs)]
     ptrs = [C.c_void_p(b.ptr) for b in bufs]
-    args = ptrs[:2] + [rows.value] + ptrs[2:] + ([md_rows.value] if muldiv else [])
-    if chips == "rv32im-elf":
+    n_fixed = len(logs) - _RV32_MEM_TABLES.get(chips, 0)
+    args = ptrs[:2] + [rows.value] + ptrs[2:n_fixed] + ([md_rows.value] if muldiv else [])
+    for b, r in zip(ptrs[n_fixed:], mem_rows):
+        args += [b, r.value]
+    if chips in KEYED_CHIPS:
         args = [key.seg_vaddr.ctypes.data_as(_lib.u32p), key.seg_words.ctypes.data_as(_lib.u32p), key.seg_vaddr.size,
                 C.c_void_p(key.d_words.ptr)] + args
     try:
@@ -843,10 +872,11 @@ def rv32_publics(shards):
 
 
 def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None):
-    """Checks a run proven with the rv32i, rv32i-cf, rv32im or rv32im-elf chip set: every shard's proof
+    """Checks a run proven with the rv32i, rv32i-cf, rv32im, rv32im-elf or rv32im-mem chip set: every shard's proof
     (verify_rv32_shard), then check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards /
     p3_rv32cf_shards / p3_rv32im_shards / execute_rv32_device give them.  prep_root, program_log_height: the verifying
-    key of an rv32im-elf run (Execution.prep_root / .program_log_height): every shard must answer to that one root.
+    key of an rv32im-elf or rv32im-mem run (Execution.prep_root / .program_log_height): every shard must answer to that
+    one root.  Under rv32im-mem the shards' memories are NOT chained: every shard's INIT values are free.
     Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
@@ -862,8 +892,9 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
     verifier's reason.  prep_root (8 Montgomery words) with program_log_height: the statement is the rv32im-elf set's
-    seven tables under that verifying key (rk_p3_verify_key) -- the program table's height is then pinned by the
-    verifier, no longer the proof's"""
+    seven tables (or the rv32im-mem set's nine) under that verifying key (rk_p3_verify_key) -- the program table's
+    height is then pinned by the verifier, no longer the proof's.  The memop and memory tables' heights are the proof's,
+    refused (reason 2) unless 0 < log height <= the cpu table's + 1"""
     from . import p3
     vt = rv32_verifier_tables(tables, proof, prep_root, program_log_height)
     return 2 if vt is None else p3.verify(vt, proof, init, params, prep_root=prep_root)
@@ -875,8 +906,8 @@ def rv32_verifier_tables(tables, proof, prep_root=None, program_log_height=None)
     (raiko_amd.fri_transcript.statement(..., prep_root=...))"""
     from . import p3
     # the chip set is the one with this many tables; the program table's height (0) is the proof's, as the muldiv table's
-    sets = [_rv32_set(c)[2:] for c in RV32_CHIPS if (c == "rv32im-elf") == (prep_root is not None)]
-    pinned = next((p for p, muldiv in sets if 2 + len(p) + muldiv == len(tables)), None)
+    sets = [_rv32_set(c)[2:] + (_RV32_MEM_TABLES.get(c, 0),) for c in RV32_CHIPS if (c in KEYED_CHIPS) == (prep_root is not None)]
+    pinned, n_mem = next(((p, m) for p, muldiv, m in sets if 2 + len(p) + muldiv + m == len(tables)), (None, 0))
     if pinned is None:
         raise ValueError("%d tables are no rv32 chip set's shard" % len(tables))
     if prep_root is not None and not program_log_height:
@@ -889,7 +920,7 @@ def rv32_verifier_tables(tables, proof, prep_root=None, program_log_height=None)
             v.log_height = pinned[i]
         else:
             lg = int(proof[1 + i]) if len(proof) > 1 + i else 0
-            if not 0 < lg <= tables[0].log_height:
+            if not 0 < lg <= tables[0].log_height + (1 if i >= len(tables) - n_mem else 0):
                 return None
             v.log_height = lg
         vt.append(v)
@@ -937,9 +968,9 @@ class Rv32Key:
     rk_exec_rv32elf_shard_device compares the executed words with), .airs the seven AIRs.  close() frees the device
     memory."""
 
-    def __init__(self, image, seg_vaddr, seg_words, key, d_words, program_log_height, airs):
+    def __init__(self, image, seg_vaddr, seg_words, key, d_words, program_log_height, airs, chips="rv32im-elf"):
         self.image, self.seg_vaddr, self.seg_words, self.key, self.d_words = image, seg_vaddr, seg_words, key, d_words
-        self.root, self.program_log_height, self.airs = key.root, program_log_height, airs
+        self.root, self.program_log_height, self.airs, self.chips = key.root, program_log_height, airs, chips
         self._preps = None
 
     @property
@@ -947,10 +978,10 @@ class Rv32Key:
         return self.key.bytes + 4 * self.d_words.size()
 
     def host_preps(self):
-        """the preprocessed matrices as rv32elf.prep_tables gives them (Montgomery words), in table order"""
-        from . import p3, rv32elf
+        """the preprocessed matrices as the chip set's prep_tables gives them (Montgomery words), in table order"""
+        from . import p3
         if self._preps is None:
-            self._preps = [None if m is None else p3.to_mont(m) for m in rv32elf.preps_of(self.image)]
+            self._preps = [None if m is None else p3.to_mont(m) for m in _rv32_set(self.chips)[0].preps_of(self.image)]
         return self._preps
 
     def close(self):
@@ -960,17 +991,20 @@ class Rv32Key:
         self.key = self.d_words = None
 
 
-def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None) -> Rv32Key:
+def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf") -> Rv32Key:
     """The setup of `client.setup(ELF)` for the rv32im-elf chip set: the ELF's program image (rk_exec_program_image), the
     four preprocessed matrices written on hal's GPU (rk_rv32elf_prep_device) and committed (rk_p3_setup) -> Rv32Key.
     params: the parameter set to put hal's context under first (None: the context's current one); ext_w: the AIRs'
-    extension (default params' / the context's)."""
+    extension (default params' / the context's).  chips="rv32im-mem": that chip set's key (rk_rv32mem_prep_device: the
+    program matrix has 48 columns) and nine AIRs."""
     from . import p3, rv32, rv32cf, rv32elf
+    if chips not in KEYED_CHIPS:
+        raise ValueError("chips must be one of %s" % (KEYED_CHIPS,))
     lib = _lib.load()
     if params is not None:
         _lib.check(hal._ctx, lib.rk_set_params(hal._ctx, C.byref(params)))
     if airs is None:
-        airs = rv32elf.airs(int(hal.get_params().ext_w) if ext_w is None else ext_w)
+        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w)
     vaddr, count, words = program_image_c(elf)
     rows = 2
     while rows < words.size:
@@ -979,7 +1013,8 @@ def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None) -> Rv32K
     bufs = {i: hal.alloc_elem(airs[i].prep_width << lg) for i, lg in logs.items()}
     d_words = None
     try:
-        _lib.check(hal._ctx, lib.rk_rv32elf_prep_device(
+        prep_device = lib.rk_rv32mem_prep_device if chips == "rv32im-mem" else lib.rk_rv32elf_prep_device
+        _lib.check(hal._ctx, prep_device(
             hal._ctx, vaddr.ctypes.data_as(_lib.u32p), count.ctypes.data_as(_lib.u32p), vaddr.size, words.ctypes.data_as(_lib.u32p),
             words.size, C.c_void_p(bufs[1].ptr), rows, C.c_void_p(bufs[3].ptr), C.c_void_p(bufs[4].ptr), C.c_void_p(bufs[5].ptr)))
         tables = []
@@ -1000,4 +1035,23 @@ def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None) -> Rv32K
         for b in bufs.values():
             b.free()
     image = [(int(v), words[at - int(c):at].astype(np.int64)) for v, c, at in zip(vaddr, count, np.cumsum(count))]
-    return Rv32Key(image, vaddr, count, key, d_words, logs[1], airs)
+    return Rv32Key(image, vaddr, count, key, d_words, logs[1], airs, chips)
+
+
+def p3_rv32mem_shards(ex: Execution, image, ext_w=None, airs=None):
+    """rv32im-mem shards in numpy: rv32elf's seven tables, then memop and memory (rv32mem.airs), the four lookup tables
+    with their preprocessed matrix in Table.prep (rv32mem.prep_tables(image)).  The yardstick for rk_rv32mem_prep_device
+    / rk_exec_rv32mem_shard_device."""
+    from . import p3, rv32mem
+    if ex.witness is None or ex.rv32 is None or ex.mem is None:
+        raise ValueError("execute(..., record_trace=True) first")
+    airs = airs or rv32mem.airs(ext_w)
+    preps = [None if m is None else p3.to_mont(m) for m in rv32mem.preps_of(image)]
+    out = []
+    for s, (_code, data), (start, end, ecalls), mem in zip(ex.segments, ex.witness, ex.rv32, ex.mem):
+        canon, _pc, _regs = rv32mem.shard_tables(s, data, start, end, ecalls, image, mem)
+        pub_cpu, pub_reg = _rv32_publics(s, start, end)
+        pubs = [pub_cpu, (), pub_reg] + [()] * (len(canon) - 3)
+        tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
+        out.append((tables, np.array(list(s.pre_state) + list(s.post_state), dtype=np.uint32)))
+    return out

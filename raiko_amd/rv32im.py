@@ -83,7 +83,16 @@ def cpu_air(ext_w=None):
     """-> the cpu Air: rv32i-cf's body (and its named constraints) plus the M selectors' send"""
     from . import p3
     b = p3.AirBuilder(CPU_COLS, rv32.N_PUBLIC_CPU, p3.EXT_W if ext_w is None else ext_w)
-    names = rv32cf.cpu_constraints(b, PROGRAM_TUPLE)
+    names = cpu_constraints(b, PROGRAM_TUPLE)
+    air = b.build()
+    air.constraint_names = names
+    return air
+
+
+def cpu_constraints(b, program_tuple):
+    """the rv32im cpu AIR's interactions and constraints into builder b (the rv32im-mem cpu table appends its columns,
+    rv32mem.py); program_tuple: the cpu columns looked up in the program table -> {name: constraint index}"""
+    names = rv32cf.cpu_constraints(b, program_tuple)
     named = _namer(b, names)
     L = b.local
     b.send(BUS_MULDIV, [MOP, A_LO, A_HI, B_LO, B_HI, RES_LO, RES_HI], mult=M_W, mult_is_const=False)
@@ -91,9 +100,7 @@ def cpu_air(ext_w=None):
     named("mop", L(MOP) - lin([(sel[j], j) for j in range(1, 8)]))
     named("is_m", L(IS_M) - lin([(s, 1) for s in sel]))
     named("m_w", L(M_W) - L(IS_M) * L(WR))       # WR is 0 on padding rows, so M_W is too
-    air = b.build()
-    air.constraint_names = names
-    return air
+    return names
 
 
 def program_air(ext_w=None):
