@@ -23,6 +23,13 @@
 // last round: reads conflict-free, writes 2-way.
 //
 // Phase functions are RK_HD: tests/emul/emul.cpp runs them lane by lane on the CPU.
+//
+// Global addressing (all kernels but the inverse strided one, which is HBM-bound and gains nothing from it): every
+// access is "workgroup-uniform pointer + 32-bit lane byte offset" (ld_lane(), st_lane()).  The
+// uniform part -- column base (col * n stays 64-bit), tile base, fs / zk row and the per-register step (m << 10,
+// m * S) -- is the same for every lane of the workgroup and lives in scalar registers; only the lane's own offset
+// is a vector register, so an access needs no 64-bit vector address arithmetic.  The largest lane offset is
+// stated at each phase; all are below 2^26 bytes (a strided tile spans at most 2^8 rows of stride 2^14 words).
 #pragma once
 #include "ntt_core.hpp"
 
@@ -38,6 +45,29 @@ constexpr unsigned NTHR = 1024;
 // LDS skew: 4 words every 64, so the stride-4 lane pattern of the L = 2 rounds spreads over the banks
 RK_HD unsigned phys(unsigned e) { return e + ((e >> 6) << 2); }
 constexpr unsigned LDS_WORDS = (1u << TILE_LOG) + ((1u << TILE_LOG) >> 6) * 4;
+// Load / store at `uniform` advanced by a lane's own byte offset (unsigned 32-bit, zero-extended).  The empty asm
+// pins the uniform pointer to a scalar register pair: without it the compiler folds the lane offset into the base
+// first and then adds the per-register step to a 64-bit vector address, one v_add_co / v_addc_co pair per access.
+// The asm hides where the pointer came from, so its address space (global) is restated.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RK_NF_GLOBAL __attribute__((address_space(1)))
+#else
+#define RK_NF_GLOBAL
+#endif
+template <class T>
+RK_HD T ld_lane(const T* uniform, uint32_t lane_bytes) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(uniform));
+#endif
+    return *(const RK_NF_GLOBAL T*)((const RK_NF_GLOBAL char*)uniform + lane_bytes);
+}
+template <class T>
+RK_HD void st_lane(T* uniform, uint32_t lane_bytes, const T& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(uniform));
+#endif
+    *(RK_NF_GLOBAL T*)((RK_NF_GLOBAL char*)uniform + lane_bytes) = v;
+}
 
 struct Args {
     uint32_t* dst;
@@ -52,10 +82,14 @@ struct Args {
 };
 
 // ---- twiddles of one stage, compile-time stage position ----------------------------------
-template <int LS, int B>
+// UB: uniform base + lane offset (rlow < 2^10); the inverse strided kernels keep plain indexing (see inv_strided_a)
+template <int LS, int B, bool UB = true>
 RK_HD void stage_tw(uint32_t* w, const uint32_t* tw, unsigned rlow) {
 #pragma unroll
-    for (int j = 0; j < (1 << B); j++) w[j] = tw[(1u << (LS + B)) + ((unsigned)j << LS) + rlow];
+    for (int j = 0; j < (1 << B); j++) {
+        if constexpr (UB) w[j] = ld_lane(tw + (1u << (LS + B)) + ((unsigned)j << LS), 4u * rlow);
+        else w[j] = tw[(1u << (LS + B)) + ((unsigned)j << LS) + rlow];
+    }
 }
 // forward (DIT) stages LS .. LS+NST-1 on 16 registers: (x, y) -> (x + y w^j, x - y w^j).
 // Values stay "lazy" in [0, 2p) between stages, between rounds (LDS) and until the store:
@@ -85,12 +119,12 @@ RK_HD void dit(uint32_t* v, const uint32_t* tw, unsigned rlow) {
 }
 // inverse (DIF) stages LS+NST-1 .. LS on 16 registers: (x, y) -> (x + y, (x - y) w^-j), canonical values;
 // x - y in (-p, p) needs no reduction before the signed Montgomery product
-template <int LS, int NST>
+template <int LS, int NST, bool UB = true>
 RK_HD void dif(uint32_t* v, const uint32_t* tw, unsigned rlow) {
     static_for<0, NST>([&](auto bc) __attribute__((always_inline)) {
         constexpr int b = NST - 1 - decltype(bc)::value;
         uint32_t w[1 << b];
-        stage_tw<LS, b>(w, tw, rlow);
+        stage_tw<LS, b, UB>(w, tw, rlow);
 #pragma unroll
         for (int m = 0; m < 16; m++) {
             if (m & (1 << b)) continue;
@@ -166,7 +200,7 @@ RK_HD STile<G> stile_of(const Args& a, size_t block) {
 RK_HD void fwd_contig_a(const Args& a, const ntt::Tables& tb, const CTile& t, uint32_t* lds, unsigned tid) {
     // round L = 2: e = (tid >> 2) << 6 | m << 2 | (tid & 3), value = src[e >> 2] = src[16 * (tid >> 2) + m]
     uint32_t v[16];
-    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 16 * (size_t)(tid >> 2));
+    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 16 * (size_t)(tid >> 2));  // lane offset < 2^14 bytes
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         V4 u = s[q];
@@ -183,21 +217,22 @@ RK_HD void fwd_contig_b(const ntt::Tables& tb, uint32_t* lds, unsigned tid) {
 }
 RK_HD void fwd_contig_c(const Args& a, const ntt::Tables& tb, const CTile& t, const uint32_t* lds, unsigned tid) {
     uint32_t v[16], f[16];
-    const uint32_t* fs = a.fs + ((size_t)t.sp << TILE_LOG) + tid;
+    // lane offset: 4 tid < 2^12 bytes, here and in the stores
+    const uint32_t* fs = a.fs + ((size_t)t.sp << TILE_LOG);
 #pragma unroll
-    for (int m = 0; m < 16; m++) f[m] = fs[m << 10];
+    for (int m = 0; m < 16; m++) f[m] = ld_lane(fs + (m << 10), 4u * tid);
     lds_read<10>(v, lds, tid);
     dit<10, 4>(v, tb.small[0], tid);
-    uint32_t* d = a.dst + t.base + tid;
+    uint32_t* d = a.dst + t.base;
 #pragma unroll
-    for (int m = 0; m < 16; m++) d[m << 10] = bb::mul(v[m], f[m]);  // lazy in, canonical out
+    for (int m = 0; m < 16; m++) st_lane(d + (m << 10), 4u * tid, bb::mul(v[m], f[m]));  // lazy in, canonical out
 }
 
 // =========================== forward, contiguous, not expanding ============================
 // 14 stages: (0,1) | 2..5 | 6..9 | 10..13; the first round reads 16 consecutive words per lane
 RK_HD void fwd_contig0_a(const Args& a, const ntt::Tables& tb, const CTile& t, uint32_t* lds, unsigned tid) {
     uint32_t v[16];
-    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 16 * (size_t)tid);
+    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 16 * (size_t)tid);  // lane offset < 2^16 bytes
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         V4 u = s[q];
@@ -212,7 +247,7 @@ RK_HD void fwd_contig0_a(const Args& a, const ntt::Tables& tb, const CTile& t, u
 // and runs stage 1 only; the other rounds are the non-expanding ones
 RK_HD void fwd_contig1_a(const Args& a, const ntt::Tables& tb, const CTile& t, uint32_t* lds, unsigned tid) {
     uint32_t v[16];
-    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 8 * (size_t)tid);
+    const V4* s = reinterpret_cast<const V4*>(a.src + t.src_base + 8 * (size_t)tid);  // lane offset < 2^15 bytes
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         V4 u = s[q];
@@ -237,12 +272,13 @@ RK_HD void fwd_contig0_b(const ntt::Tables& tb, uint32_t* lds, unsigned tid) {
 // four-step twiddle on the way in, stages 13..0 as 4 | 4 | 4 | 2, then 1/n (and the zk shift)
 RK_HD void inv_contig_a(const Args& a, const ntt::Tables& tb, const CTile& t, uint32_t* lds, unsigned tid) {
     uint32_t v[16], f[16];
-    const uint32_t* s = a.src + t.src_base + tid;
-    const uint32_t* fs = a.fs + ((size_t)t.sp << TILE_LOG) + tid;
+    // lane offset: 4 tid < 2^12 bytes
+    const uint32_t* s = a.src + t.src_base;
+    const uint32_t* fs = a.fs + ((size_t)t.sp << TILE_LOG);
 #pragma unroll
     for (int m = 0; m < 16; m++) {
-        v[m] = s[m << 10];
-        f[m] = fs[m << 10];
+        v[m] = ld_lane(s + (m << 10), 4u * tid);
+        f[m] = ld_lane(fs + (m << 10), 4u * tid);
     }
 #pragma unroll
     for (int m = 0; m < 16; m++) v[m] = bb::mul(v[m], f[m]);
@@ -274,14 +310,15 @@ RK_HD void inv_contig_e(const Args& a, const CTile& t, const uint32_t* lds, unsi
     for (int i = 0; i < 4; i++) {
         unsigned e = 4 * (tid + i * NTHR);
         V4 u = *reinterpret_cast<const V4*>(lds + phys(e));
+        // lane offset: 16 tid < 2^14 bytes; the quarter i of the tile is part of the uniform base
         if (a.zk) {
-            size_t pos = ((size_t)t.sp << TILE_LOG) + e;  // position inside the column
-            V4 z = *reinterpret_cast<const V4*>(a.zk + pos);
+            size_t pos = ((size_t)t.sp << TILE_LOG) + 4 * i * NTHR;  // position inside the column, lane 0
+            V4 z = ld_lane(reinterpret_cast<const V4*>(a.zk + pos), 16u * tid);
             u = V4{bb::mul(u.x, z.x), bb::mul(u.y, z.y), bb::mul(u.z, z.z), bb::mul(u.w, z.w)};
         } else {
             u = V4{bb::mul(u.x, a.scale), bb::mul(u.y, a.scale), bb::mul(u.z, a.scale), bb::mul(u.w, a.scale)};
         }
-        *reinterpret_cast<V4*>(a.dst + t.base + e) = u;
+        st_lane(reinterpret_cast<V4*>(a.dst + t.base + 4 * i * NTHR), 16u * tid, u);
     }
 }
 
@@ -289,14 +326,21 @@ RK_HD void inv_contig_e(const Args& a, const CTile& t, const uint32_t* lds, unsi
 // lane: lo = tid & (T - 1) (column of the tile), r = tid >> logT (G - 4 bits)
 // round at row-stage 0 (G - 4 stages): rows 16 r + m      (tile index layout L = logT)
 // round at row-stage G - 4 (4 stages): rows m << (G-4) | r (tile index m << 10 | tid, L = 10)
+// lane offsets: 4 (row * S + lo) with row < 2^G <= 2^8, S = 2^14 words and lo < 2^10: below 2^24 bytes, 32-bit
+// arithmetic; the register's row step (m * S, (m << (G-4)) * S) is uniform
+template <int G>
+RK_HD uint32_t srow_bytes(const STile<G>& t, unsigned row, unsigned lo) {
+    return 4u * (row * (uint32_t)t.S + lo);
+}
 template <int G>
 RK_HD void fwd_strided_a(const Args& a, const ntt::Tables& tb, const STile<G>& t, uint32_t* lds, unsigned tid) {
     constexpr int LOGT = TILE_LOG - G;
     unsigned lo = tid & ((1u << LOGT) - 1), r = tid >> LOGT;
     uint32_t v[16];
-    const uint32_t* s = a.src + t.base + (size_t)(16 * r) * t.S + lo;
+    const uint32_t* s = a.src + t.base;
+    const uint32_t off = srow_bytes(t, 16 * r, lo);
 #pragma unroll
-    for (int m = 0; m < 16; m++) v[m] = s[(size_t)m * t.S];
+    for (int m = 0; m < 16; m++) v[m] = ld_lane(s + (size_t)m * t.S, off);
     dit<0, G - 4, true>(v, tb.small[0], 0);
     lds_write<LOGT>(v, lds, tid);  // e = (16 r + m) << logT | lo = round_e0<LOGT>(tid) | m << logT
 }
@@ -308,24 +352,27 @@ RK_HD void fwd_strided_b(const Args& a, const ntt::Tables& tb, const STile<G>& t
     if constexpr (G > 4) {
         lds_read<10>(v, lds, tid);
     } else {
-        const uint32_t* s = a.src + t.base + lo;
+        const uint32_t* s = a.src + t.base;
 #pragma unroll
-        for (int m = 0; m < 16; m++) v[m] = s[(size_t)m * t.S];
+        for (int m = 0; m < 16; m++) v[m] = ld_lane(s + (size_t)m * t.S, 4u * lo);
     }
     dit<G - 4, 4, G == 4>(v, tb.small[0], r);
-    uint32_t* d = a.dst + t.base + (size_t)r * t.S + lo;
+    uint32_t* d = a.dst + t.base;
+    const uint32_t off = srow_bytes(t, r, lo);
 #pragma unroll
-    for (int m = 0; m < 16; m++) d[((size_t)m << (G - 4)) * t.S] = bb::ucanon(v[m]);
+    for (int m = 0; m < 16; m++) st_lane(d + ((size_t)m << (G - 4)) * t.S, off, bb::ucanon(v[m]));
 }
 template <int G>
 RK_HD void inv_strided_a(const Args& a, const ntt::Tables& tb, const STile<G>& t, uint32_t* lds, unsigned tid) {
     constexpr int LOGT = TILE_LOG - G;
     unsigned lo = tid & ((1u << LOGT) - 1), r = tid >> LOGT;
     uint32_t v[16];
+    // plain 64-bit indexing here and in inv_strided_b: the inverse strided pass runs at its HBM rate, and with uniform
+    // bases (80 VALU instructions fewer per lane-tile at G = 6) its traced time did not drop (profiles/r07_*)
     const uint32_t* s = a.src + t.base + (size_t)r * t.S + lo;
 #pragma unroll
     for (int m = 0; m < 16; m++) v[m] = s[((size_t)m << (G - 4)) * t.S];
-    dif<G - 4, 4>(v, tb.small[1], r);
+    dif<G - 4, 4, false>(v, tb.small[1], r);
     if constexpr (G > 4) {
         lds_write<10>(v, lds, tid);
     } else {
@@ -340,7 +387,7 @@ RK_HD void inv_strided_b(const Args& a, const ntt::Tables& tb, const STile<G>& t
     unsigned lo = tid & ((1u << LOGT) - 1), r = tid >> LOGT;
     uint32_t v[16];
     lds_read<LOGT>(v, lds, tid);
-    dif<0, G - 4>(v, tb.small[1], 0);
+    dif<0, G - 4, false>(v, tb.small[1], 0);
     uint32_t* d = a.dst + t.base + (size_t)(16 * r) * t.S + lo;
 #pragma unroll
     for (int m = 0; m < 16; m++) d[(size_t)m * t.S] = v[m];

@@ -46,12 +46,14 @@ RK_HD uint64_t mul_sc(uint32_t x, uint32_t c) { return (uint64_t)x * (uint64_t)c
 RK_HD int64_t smad_sc(int64_t acc, int32_t x, int32_t c) { return acc + (int64_t)x * (int64_t)c; }
 RK_HD int64_t smul_sc(int32_t x, int32_t c) { return (int64_t)x * (int64_t)c; }
 
-// acc + x * K with a literal multiplier: one v_mad_u64_u32
+// acc + x * K with a literal multiplier: one v_mad_u64_u32.  The addend is an input of its own, not tied to
+// the result: a tied accumulator that is still live afterwards costs a v_mov_b64 first.
 template <int K>
 RK_HD uint64_t madk(uint32_t x, uint64_t acc) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "n"(K) : "vcc");
-    return acc;
+    uint64_t r;
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(x), "n"(K), "v"(acc) : "vcc");
+    return r;
 #else
     return acc + (uint64_t)x * (uint64_t)K;
 #endif
@@ -71,8 +73,9 @@ RK_HD uint64_t mulk(uint32_t x) {
 template <int K>
 RK_HD int64_t smadk(int32_t x, int64_t acc) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "n"(K) : "vcc");
-    return acc;
+    int64_t r;
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(x), "n"(K), "v"(acc) : "vcc");
+    return r;
 #else
     return acc + (int64_t)x * (int64_t)K;
 #endif
@@ -326,8 +329,8 @@ static RK_HD void m_ext_redc_s(const int32_t* y, int32_t* r) {
         if constexpr (M4K == 0) {
             int64_t t2 = smadk<2>(b, t1);           // 2b +  c +  d
             int64_t t3 = smadk<2>(d, t0);           //  a +  b + 2d
-            int64_t t4 = (t1 << 2) + t3;            //  a +  b + 4c + 6d
-            int64_t t5 = (t0 << 2) + t2;            // 4a + 6b +  c +  d
+            int64_t t4 = t1 * 4 + t3;               //  a +  b + 4c + 6d (times 4, not << 2: t1 may be negative)
+            int64_t t5 = t0 * 4 + t2;               // 4a + 6b +  c +  d
             w[i] = t3 + t5;                         // 5a + 7b +  c + 3d
             w[i + 1] = t5;
             w[i + 2] = t2 + t4;                     //  a + 3b + 5c + 7d

@@ -166,10 +166,12 @@ def algorithmic_bytes(po2: int, widths: Sequence[int], blowup_log2: int = 2, fol
 
 
 # VALU instructions of one Poseidon2 permutation as shipped (tools/census_p2.py on the gfx950 ISA of
-# poseidon2_core.hpp: 6195 dynamic v_* instructions with all 24 output cells live, the partial rounds in
-# blocks of three -- 6737 with them one at a time (RK_P2_DIRECT), 7159 with the closed form of round 1;
+# poseidon2_core.hpp: 6080 dynamic v_* instructions with all 24 output cells live, the partial rounds in
+# blocks of three -- 6195 while the literal-multiplier mads still tied their addend to the result (115 64-bit
+# register copies), 6629 with the partial rounds one at a time (RK_P2_DIRECT; 6737 with tied addends), 7159 with the
+# closed form of round 1;
 # kernels that keep only the digest / capacity cells run slightly fewer)
-P2_VALU_PER_PERMUTATION = 6195
+P2_VALU_PER_PERMUTATION = 6080
 
 
 def poseidon2_permutations(po2: int, widths: Sequence[int]) -> dict:

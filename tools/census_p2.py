@@ -50,21 +50,25 @@ def main():
     assert len(inner) == 2, loops
 
     def count(a, b):
-        n = fast = 0
+        # VALU, plain add/sub among them, 64-bit register copies among them, and s_nop (not VALU: hazard padding)
+        n = fast = mov64 = nop = 0
         for l in lines[a:b + 1]:
             t = l.strip().split(" ")[0] if l.strip() else ""
             if t.startswith("v_"):
                 n += 1
                 fast += bool(re.match(r"v_(add|sub|subrev)_u32", t))
-        return n, fast
+                mov64 += t.startswith("v_mov_b64")
+            nop += t == "s_nop"
+        return n, fast, mov64, nop
 
     total = list(count(outer[0], outer[1]))
     for a, b in inner:  # bodies run 4 times (rounds 0..3 and 4..7), counted once above
-        n, f = count(a, b)
-        total[0] += 3 * n
-        total[1] += 3 * f
+        for i, c in enumerate(count(a, b)):
+            total[i] += 3 * c
     print("VALU instructions per permutation: %d (plain add/sub: %d); loop bodies: %s" %
           (total[0], total[1], [count(a, b)[0] for a, b in inner]))
+    print("v_mov_b64 per permutation: %d; in the loop bodies: %s" % (total[2], [count(a, b)[2] for a, b in inner]))
+    print("s_nop per permutation: %d; in the loop bodies: %s" % (total[3], [count(a, b)[3] for a, b in inner]))
     return 0
 
 
