@@ -459,6 +459,14 @@ class Table:
     def from_canonical(cls, air, trace, public_values=(), prep=None):
         return cls(air, to_mont(trace), to_mont(np.array(list(public_values), dtype=np.uint64)), None if prep is None else to_mont(prep))
 
+    @classmethod
+    def pinned(cls, air, log_height, public_mont=()):
+        """a table without a trace at a stated height: a verifier's, or one whose trace is in device memory (0: the
+        height the proof carries)"""
+        t = cls(air, None, public_mont)
+        t.log_height = log_height
+        return t
+
 
 def _c_tables(tables, device_traces=None):
     arr = (_lib.RkP3Table * len(tables))()

@@ -1,5 +1,5 @@
 """The rv32i chip set: an executed segment proven as a uni-stark shard whose AIRs constrain the register file and the
-integer ALU, not only the pc chain (executor.p3_trace_air).  Five tables per shard, tied by lookups:
+integer ALU, not only the pc chain (p3_trace.p3_trace_air).  Five tables per shard, tied by lookups:
 
   cpu       one row per cycle (RV32_CPU_COLS columns): the stand-in trace's 16 columns at their old places, the decoded
             fields the row looks up in the program table, three register accesses with their previous timestamps, the
@@ -9,7 +9,7 @@ integer ALU, not only the pc chain (executor.p3_trace_air).  Five tables per sha
   register  32 rows: sends every register's initial value at timestamp 0, receives its final (value, timestamp); both are
             bound to the shard's public values through shift registers of 32 columns per limb stream
   byte      2^18 rows (3 * 2^16 used): (op, x, y, x op y) for AND / OR / XOR of two bytes, proven from their bits
-  range     executor.p3_range_air: the 16-bit values
+  range     p3_trace.p3_range_air: the 16-bit values
 
 Registers follow an offline memory argument on the REGISTER bus: access k of row r (k = 1 read rs1, 2 read rs2, 3 write
 the destination) happens at timestamp 3r + k, receives (reg, previous value, previous timestamp) and sends (reg, value,
@@ -25,9 +25,10 @@ The witness recomputes the ALU result of constrained ops (TraceRow.res is 0 when
 hold on every active row, written or not.
 
 `shard_tables` builds every table of a segment in numpy from the recorded trace and the executor's side data
-(executor.p3_rv32_shards): the yardstick for rk_exec_rv32_shard_device."""
+(rv32_sets.p3_rv32_shards): the yardstick for rk_exec_rv32_shard_device."""
 import numpy as np
 
+from .p3_trace import p3_range_air
 from .segment import P
 
 BUS_PROGRAM, BUS_RANGE16, BUS_REGISTER, BUS_BYTE = 1, 2, 5, 6
@@ -268,7 +269,6 @@ def byte_air(ext_w=None):
 
 def airs(ext_w=None):
     """-> (cpu, program, register, byte, range): the AIRs of one rv32i shard, in table order"""
-    from .executor import p3_range_air
     return cpu_air(ext_w), program_air(ext_w), register_air(ext_w), byte_air(ext_w), p3_range_air(ext_w)
 
 

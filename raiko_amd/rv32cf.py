@@ -27,13 +27,14 @@ Every new multiplicity column (IS_BR, IS_SHIFT, M_SA, M_SB, IS_LINK for NXH) is 
 constrained except the loads and stores (LB / LH / LW / LBU / LHU / SB / SH / SW: memory stays free) and the a0 an ecall
 leaves; the program table is still not bound to the ELF.
 
-`shard_tables` builds every table of a segment in numpy (executor.p3_rv32cf_shards): the yardstick for
+`shard_tables` builds every table of a segment in numpy (rv32_sets.p3_rv32cf_shards): the yardstick for
 rk_exec_rv32cf_shard_device."""
 import numpy as np
 
 from . import rv32
 from .rv32 import (ACTIVE, A_HI, A_LO, B_HI, B_LO, IMM_HI, IMM_LO, IS_IMM, IS_LINK, NX_HI, NX_LO, PC_HI, PC_LO, RES_HI,
                    RES_LO, RS2, SA, SA_CHK, SB, SB_CHK, SNE, WR, lin)
+from .p3_trace import p3_range_air
 from .segment import P
 
 BUS_SHIFT = 7
@@ -227,7 +228,6 @@ def shift_air(ext_w=None):
 
 def airs(ext_w=None):
     """-> (cpu, program, register, byte, range, shift): the AIRs of one rv32i-cf shard, in table order"""
-    from .executor import p3_range_air
     return (cpu_air(ext_w), program_air(ext_w), rv32.register_air(ext_w), rv32.byte_air(ext_w), p3_range_air(ext_w),
             shift_air(ext_w))
 

@@ -30,12 +30,13 @@ distance DEV < 2^12.  |q b + r| < 2^63 for signed operands and q b + r < 2^64 fo
 is an equation over the integers and q, r are the truncated quotient and remainder.  The multiplicity MULT is boolean,
 the sum of the one-hot op selectors, and once 0 stays 0 down the table.
 
-`shard_tables` builds every table of a segment in numpy (executor.p3_rv32im_shards): the yardstick for
+`shard_tables` builds every table of a segment in numpy (rv32_sets.p3_rv32im_shards): the yardstick for
 rk_exec_rv32im_shard_device."""
 import numpy as np
 
 from . import rv32, rv32cf
 from .rv32 import A_HI, A_LO, B_HI, B_LO, RES_HI, RES_LO, WR, lin
+from .p3_trace import p3_range_air
 from .segment import P
 
 BUS_MULDIV = 8
@@ -230,7 +231,6 @@ def muldiv_air(ext_w=None):
 
 def airs(ext_w=None):
     """-> (cpu, program, register, byte, range, shift, muldiv): the AIRs of one rv32im shard, in table order"""
-    from .executor import p3_range_air
     return (cpu_air(ext_w), program_air(ext_w), rv32.register_air(ext_w), rv32.byte_air(ext_w), p3_range_air(ext_w),
             rv32cf.shift_air(ext_w), muldiv_air(ext_w))
 

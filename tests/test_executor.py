@@ -234,6 +234,23 @@ def test_stepping_the_executor_gives_the_same_run():
         X.Stepper(b"not an elf")
 
 
+def test_step_yields_each_segment_then_none():
+    """Stepper.step runs one segment per call and returns its ExecSegment, in order; after the last it returns None, on
+    every further call too, and finish() has the journal of the whole run"""
+    image = A.elf(A.assemble(LOOP)[0])
+    whole = X.execute(image, segment_limit_po2=13)
+    assert len(whole.segments) == 2
+    st = X.Stepper(image, segment_limit_po2=13)
+    try:
+        assert [st.step() for _ in whole.segments] == whole.segments
+        assert st.step() is None and st.step() is None and st.next() is None
+        ex = st.finish()
+    finally:
+        st.close()
+    assert ex.journal == whole.journal and len(ex.journal) == 4
+    assert (ex.exit_code, ex.total_cycles) == (whole.exit_code, whole.total_cycles)
+
+
 def test_profile_counts_cycles_per_pc():
     """rk_exec_opts.profile / rk_exec_profile: what `profile: true` of the request switches on in the reference
     (env_builder.enable_profiler, bonsai.rs:252-255) -- here the cycles spent at each program counter"""
