@@ -15,37 +15,54 @@ constexpr int HASH_BLOCK = 256;
 // lane-cycles of a lane-per-parent one, so it only pays where the level is latency-bound anyway
 constexpr size_t CELLS_MAX_OUT = rk::HASH_FOLD_TOP_MAX;
 
-// C = the configured p2::Core (width 24 or 16, external 4x4 block): one kernel instance per Core.
-// pad_free: the last partial block leaves the remaining rate cells as they are (Plonky3
+// C = the configured p2::Core (width 24 or 16, external 4x4 block): one kernel instance per Core and sponge kind.
+// PAD_FREE: the last partial block leaves the remaining rate cells as they are (Plonky3
 // PaddingFreeSponge) instead of zero-padding them (risc0); an empty row then takes no permutation.
-template <class C>
+//
+// A row ends with a partial block (zero-padded: also the one block of an empty row), which takes the full
+// permutation, or with a whole block, of which only the digest is read.  The blocks before that only hand their
+// capacity on, the next block overwrites the rate -- except before a padding-free partial block, which keeps rate
+// cells of its predecessor: such a row takes the full permutation throughout.  Every path runs one loop and then
+// one permutation, so that no 24-cell state has to be merged between two inlined permutations.
+template <class C, bool PAD_FREE>
 __global__ __launch_bounds__(HASH_BLOCK, 5) void hash_rows_kernel(uint32_t* __restrict__ out,
                                                                const uint32_t* __restrict__ matrix, size_t rows,
-                                                               size_t cols, const typename C::Consts* __restrict__ kc,
-                                                               int pad_free) {
+                                                               uint32_t cols, const typename C::Consts* __restrict__ kc) {
     size_t row = (size_t)blockIdx.x * HASH_BLOCK + threadIdx.x;
     if (row >= rows) return;
     const typename C::Consts& k = *kc;
     uint32_t s[C::CELLS];
 #pragma unroll
     for (int i = 0; i < C::CELLS; i++) s[i] = 0;
-    size_t full = cols / C::RATE;
-    const uint32_t* src = matrix + row;
-    for (size_t b = 0; b < full; b++) {
+    const uint32_t full = cols / C::RATE, rem = cols - full * C::RATE;
+    // a column's address is a wave-uniform pointer plus the lane
+    const uint32_t* src = matrix + (size_t)blockIdx.x * HASH_BLOCK;
+    const unsigned lane = threadIdx.x;
+    auto load_block = [&](uint32_t b) {
 #pragma unroll
-        for (int i = 0; i < C::RATE; i++) s[i] = src[(b * C::RATE + i) * rows];
-        C::permute(s, k);
-    }
-    size_t rem = cols - full * C::RATE;
-    if (rem != 0 || (cols == 0 && !pad_free)) {
+        for (int i = 0; i < C::RATE; i++) s[i] = (src + (size_t)(b * C::RATE + i) * rows)[lane];
+    };
+    if (rem != 0 || (cols == 0 && !PAD_FREE)) {
+        for (uint32_t b = 0; b < full; b++) {
+            load_block(b);
+            if constexpr (PAD_FREE) C::permute(s, k);
+            else C::template permute<C::RATE, p2::OUT>(s, k);
+        }
 #pragma unroll
         for (int i = 0; i < C::RATE; i++) {
-            if ((size_t)i < rem) s[i] = src[(full * C::RATE + i) * rows];
-            else if (!pad_free) s[i] = 0u;
+            if ((uint32_t)i < rem) s[i] = (src + (size_t)(full * C::RATE + i) * rows)[lane];
+            else if (!PAD_FREE) s[i] = 0u;
         }
         C::permute(s, k);
+    } else if (full != 0) {
+        for (uint32_t b = 0; b + 1 < full; b++) {
+            load_block(b);
+            C::template permute<C::RATE, p2::OUT>(s, k);
+        }
+        load_block(full - 1);
+        C::template permute<0, p2::OUT>(s, k);
     }
-    uint4* o = reinterpret_cast<uint4*>(out + row * p2::OUT);
+    uint4* o = reinterpret_cast<uint4*>(out + (size_t)blockIdx.x * HASH_BLOCK * p2::OUT) + 2 * lane;
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
 }
@@ -66,7 +83,7 @@ __global__ __launch_bounds__(HASH_BLOCK) void hash_fold_kernel(uint32_t* __restr
     s[8] = c.x; s[9] = c.y; s[10] = c.z; s[11] = c.w; s[12] = d.x; s[13] = d.y; s[14] = d.z; s[15] = d.w;
 #pragma unroll
     for (int j = 16; j < C::CELLS; j++) s[j] = 0;
-    C::permute(s, k);
+    C::template permute<0, p2::OUT, 16>(s, k);
     uint4* o = reinterpret_cast<uint4*>(nodes + idx * p2::OUT);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -126,13 +143,13 @@ __global__ __launch_bounds__(HASH_BLOCK) void pow_grind_kernel(uint32_t* __restr
     s[0] = w;
 #pragma unroll
     for (int i = 1; i < C::CELLS; i++) s[i] = 0;
-    C::permute(s, k);
+    C::template permute<0, p2::OUT, 1>(s, k);
     uint32_t c[C::CELLS];
 #pragma unroll
     for (int i = 0; i < C::CELLS; i++) c[i] = cells[i];
 #pragma unroll
     for (int i = 0; i < p2::OUT; i++) c[i] = bb::add(c[i], s[i]);
-    C::permute(c, k);
+    C::template permute<0, 4>(c, k);  // the four outputs random_bits draws
     const uint32_t v = bb::decode(c[0]) ^ bb::decode(c[1]) ^ bb::decode(c[2]) ^ bb::decode(c[3]);
     if ((v & mask) == 0) atomicMin(best, w);
 }
@@ -151,7 +168,7 @@ __global__ __launch_bounds__(HASH_BLOCK) void duplex_grind_kernel(uint32_t* __re
     uint32_t s[C::CELLS];
 #pragma unroll
     for (int i = 0; i < C::CELLS; i++) s[i] = (unsigned)i == n_input ? bb::mul(w, bb::R2) : state[i];  // state already holds the buffered inputs
-    C::permute(s, *kc);
+    C::template permute<(C::RATE - 1) / 4 * 4, 4>(s, *kc);  // the block of the last rate cell
     if ((bb::decode(s[C::RATE - 1]) & mask) == 0) atomicMin(best, w);
 }
 
@@ -171,11 +188,15 @@ namespace rk {
 int hash_rows(rk_ctx* ctx, uint32_t* d_out, const uint32_t* d_matrix, size_t rows, size_t cols) {
     if (rows == 0) return RK_ERR_INVALID;
     size_t blocks = (rows + HASH_BLOCK - 1) / HASH_BLOCK;
-    if (blocks > 0x7fffffffu) return RK_ERR_INVALID;
+    if (blocks > 0x7fffffffu || cols > 0x7fffffffu) return RK_ERR_INVALID;
     KTimer kt(ctx, RK_KCLASS_HASH_ROWS, (double)rows * cols * 4 + (double)rows * 32);
-    RK_P2_DISPATCH(ctx, hipLaunchKernelGGL(hash_rows_kernel<C>, dim3((unsigned)blocks), dim3(HASH_BLOCK), 0, ctx->stream, d_out,
-                                           d_matrix, rows, cols, (const typename C::Consts*)ctx->d_p2,
-                                           ctx->h_p2.pad_free ? 1 : 0));
+    if (ctx->h_p2.pad_free) {
+        RK_P2_DISPATCH(ctx, hipLaunchKernelGGL((hash_rows_kernel<C, true>), dim3((unsigned)blocks), dim3(HASH_BLOCK), 0, ctx->stream,
+                                               d_out, d_matrix, rows, (uint32_t)cols, (const typename C::Consts*)ctx->d_p2));
+    } else {
+        RK_P2_DISPATCH(ctx, hipLaunchKernelGGL((hash_rows_kernel<C, false>), dim3((unsigned)blocks), dim3(HASH_BLOCK), 0, ctx->stream,
+                                               d_out, d_matrix, rows, (uint32_t)cols, (const typename C::Consts*)ctx->d_p2));
+    }
     return post_launch(ctx, "hash_rows_kernel");
 }
 

@@ -38,10 +38,13 @@ struct ColRef {
 
 // nat_bits != 0: lane t is the NATURAL index of a layout-2 matrix (column-major, committed row r stored at index
 // bitrev(r)): its loads are then coalesced and the digest goes to row bitrev(t); otherwise lane t is the committed row
-template <class C>
+// The blocks of a row as in hash_rows_kernel (PAD_FREE is the sponge kind): chained ones keep the capacity, a whole
+// last block the digest, a partial last block the full permutation, and so does every block of a padding-free row
+// that ends with a partial one.
+template <class C, bool PAD_FREE>
 __global__ __launch_bounds__(HASH_BLOCK, 5) void hash_rows_multi_kernel(uint32_t* __restrict__ out, uint64_t mats_addr, uint64_t cols_addr,
                                                                      uint32_t n_cols, size_t rows,
-                                                                     const typename C::Consts* __restrict__ kc, int pad_free, unsigned nat_bits,
+                                                                     const typename C::Consts* __restrict__ kc, unsigned nat_bits,
                                                                      unsigned bits) {
     const size_t t = (size_t)blockIdx.x * HASH_BLOCK + threadIdx.x;
     if (t >= rows) return;
@@ -58,20 +61,29 @@ __global__ __launch_bounds__(HASH_BLOCK, 5) void hash_rows_multi_kernel(uint32_t
         const MatDesc m = {mats[cr.mat].base, mats[cr.mat].width, mats[cr.mat].row_major};
         return m.row_major == 1 ? m.base[row * m.width + cr.col] : m.base[(size_t)cr.col * rows + (m.row_major == 2 ? nat : row)];
     };
-    const uint32_t full = n_cols / C::RATE;
-    for (uint32_t b = 0; b < full; b++) {
+    const uint32_t full = n_cols / C::RATE, rem = n_cols - full * C::RATE;
+    if (rem != 0 || (n_cols == 0 && !PAD_FREE)) {
+        for (uint32_t b = 0; b < full; b++) {
 #pragma unroll
-        for (int i = 0; i < C::RATE; i++) s[i] = load(b * C::RATE + i);
-        C::permute(s, k);
-    }
-    const uint32_t rem = n_cols - full * C::RATE;
-    if (rem != 0 || (n_cols == 0 && !pad_free)) {
+            for (int i = 0; i < C::RATE; i++) s[i] = load(b * C::RATE + i);
+            if constexpr (PAD_FREE) C::permute(s, k);
+            else C::template permute<C::RATE, p2::OUT>(s, k);
+        }
 #pragma unroll
         for (int i = 0; i < C::RATE; i++) {
             if ((uint32_t)i < rem) s[i] = load(full * C::RATE + i);
-            else if (!pad_free) s[i] = 0u;
+            else if (!PAD_FREE) s[i] = 0u;
         }
         C::permute(s, k);
+    } else if (full != 0) {
+        for (uint32_t b = 0; b + 1 < full; b++) {
+#pragma unroll
+            for (int i = 0; i < C::RATE; i++) s[i] = load(b * C::RATE + i);
+            C::template permute<C::RATE, p2::OUT>(s, k);
+        }
+#pragma unroll
+        for (int i = 0; i < C::RATE; i++) s[i] = load((full - 1) * C::RATE + i);
+        C::template permute<0, p2::OUT>(s, k);
     }
     uint4* o = reinterpret_cast<uint4*>(out + row * p2::OUT);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
@@ -93,7 +105,7 @@ __global__ __launch_bounds__(HASH_BLOCK) void compress_inject_kernel(uint32_t* _
     s[8] = b0.x; s[9] = b0.y; s[10] = b0.z; s[11] = b0.w; s[12] = b1.x; s[13] = b1.y; s[14] = b1.z; s[15] = b1.w;
 #pragma unroll
     for (int j = 16; j < C::CELLS; j++) s[j] = 0;
-    C::permute(s, k);
+    C::template permute<0, p2::OUT, 16>(s, k);
     uint4* o = reinterpret_cast<uint4*>(nodes + (n + i) * p2::OUT);
     o[0] = make_uint4(s[0], s[1], s[2], s[3]);
     o[1] = make_uint4(s[4], s[5], s[6], s[7]);
@@ -140,10 +152,17 @@ int hash_level(rk_ctx* ctx, const rk_matrix* mats, uint32_t n, uint32_t h, uint3
     RK_TRY(rk::upload(ctx, d, pack.data(), pack.size()));  // through the page-locked ring: no wait (21 FRI layers of a proof commit one after the other)
     const unsigned blocks = (unsigned)(((size_t)h + HASH_BLOCK - 1) / HASH_BLOCK);
     rk::KTimer kt(ctx, RK_KCLASS_HASH_ROWS, (double)h * cols.size() * 4 + (double)h * 32);
-    RK_P2_DISPATCH(ctx, hipLaunchKernelGGL(hash_rows_multi_kernel<C>, dim3(blocks), dim3(HASH_BLOCK), 0, ctx->stream, d_out,
-                                           (uint64_t)(uintptr_t)d, (uint64_t)(uintptr_t)((unsigned char*)d + desc_bytes),
-                                           (uint32_t)cols.size(), (size_t)h, (const typename C::Consts*)ctx->d_p2,
-                                           ctx->h_p2.pad_free ? 1 : 0, all_nat ? 1u : 0u, log2u(h)));
+    if (ctx->h_p2.pad_free) {
+        RK_P2_DISPATCH(ctx, hipLaunchKernelGGL((hash_rows_multi_kernel<C, true>), dim3(blocks), dim3(HASH_BLOCK), 0, ctx->stream, d_out,
+                                               (uint64_t)(uintptr_t)d, (uint64_t)(uintptr_t)((unsigned char*)d + desc_bytes),
+                                               (uint32_t)cols.size(), (size_t)h, (const typename C::Consts*)ctx->d_p2,
+                                               all_nat ? 1u : 0u, log2u(h)));
+    } else {
+        RK_P2_DISPATCH(ctx, hipLaunchKernelGGL((hash_rows_multi_kernel<C, false>), dim3(blocks), dim3(HASH_BLOCK), 0, ctx->stream, d_out,
+                                               (uint64_t)(uintptr_t)d, (uint64_t)(uintptr_t)((unsigned char*)d + desc_bytes),
+                                               (uint32_t)cols.size(), (size_t)h, (const typename C::Consts*)ctx->d_p2,
+                                               all_nat ? 1u : 0u, log2u(h)));
+    }
     return rk::post_launch(ctx, "hash_rows_multi_kernel");
 }
 

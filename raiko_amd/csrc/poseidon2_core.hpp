@@ -280,8 +280,43 @@ static inline void derive(Consts& k) {
     while (n < PR_STREAM_WORDS) k.pr_stream[n++] = 0;
 }
 
+// External layer circ(2*M4, M4, ..., M4), M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]] (M4K = 0) or
+// circ(2,3,1,1) (M4K = 1).  M4 is linear, so M4(y_b) + sum_b' M4(y_b') = M4(y_b + c) with the column sums
+// c_j = sum_b y[4b + j]: the layer is  c -> z_i = y_i + c_(i & 3) -> M4(z_b) -> REDC, block by block.  Per round at
+// width 24: 24 mads for c, 24 for z, 8 64-bit adds per block, against 60 + 20 + 24 for M4 per block, the sum of
+// the M4 outputs over the blocks and that sum added to every cell (RK_P2_EXT_M4_FIRST keeps that form for A/B).  Only
+// a block's four z and its M4 temporaries are alive at a time, and a caller that needs some blocks only pays c plus
+// those blocks.  w = M_E y is the same exact integer in both forms, so every REDC output is the same 32-bit word.
+//
+// M4 on exact 64-bit integers.  M4K = 0 follows the Poseidon2 paper's add / double schedule (eight v_lshl_add_u64;
+// times 2 and times 4, not shifts: the signed values may be negative); M4K = 1 is the block sum plus z_i + 2 z_(i+1).
+template <class T>
+static RK_HD void m4_wide(T a, T b, T c, T d, T* w) {
+    if constexpr (M4K == 0) {
+        T t0 = a + b, t1 = c + d;
+        T t2 = b * 2 + t1;  // 2b +  c +  d
+        T t3 = d * 2 + t0;  //  a +  b + 2d
+        T t4 = t1 * 4 + t3;  //  a +  b + 4c + 6d
+        T t5 = t0 * 4 + t2;  // 4a + 6b +  c +  d
+        w[0] = t3 + t5;      // 5a + 7b +  c + 3d
+        w[1] = t5;
+        w[2] = t2 + t4;      //  a + 3b + 5c + 7d
+        w[3] = t4;
+    } else {
+        T sum = (a + b) + (c + d);
+        w[0] = (b * 2 + a) + sum;  // 2a + 3b +  c +  d
+        w[1] = (c * 2 + b) + sum;  //  a + 2b + 3c +  d
+        w[2] = (d * 2 + c) + sum;  //  a +  b + 2c + 3d
+        w[3] = (a * 2 + d) + sum;  // 3a +  b +  c + 2d
+    }
+}
+
+#if defined(RK_P2_EXT_M4_FIRST)
+// the earlier forms: M4 per block on the 32-bit cells, then the sum over the blocks added to every cell; the
+// template parameters are accepted and ignored (every cell is read and written)
 // External layer circ(2*M4, M4, ..., M4), M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]], on
 // canonical cells, exact: w[i] < 112 p < 2^38.  Then s[i] = w[i] * 2^-32 (mod p) in [0, p + 53).
+template <int NZ = CELLS>
 static RK_HD void m_ext_redc(uint32_t* s) {
     uint64_t w[CELLS];
 #pragma unroll
@@ -319,6 +354,7 @@ static RK_HD void m_ext_redc(uint32_t* s) {
 // v_mad_i64_i32 (sums like a + b do not fit 32 bits here), the rest are 64-bit shift-adds
 // (v_lshl_add_u64) -- ten instructions per four cells, against two per CELL for a canonicalisation
 // that would let the unsigned form above be used.
+template <int B0 = 0, int BN = CELLS / 4>
 static RK_HD void m_ext_redc_s(const int32_t* y, int32_t* r) {
     int64_t w[CELLS];
 #pragma unroll
@@ -354,6 +390,69 @@ static RK_HD void m_ext_redc_s(const int32_t* y, int32_t* r) {
     for (int i = 0; i < CELLS; i++) r[i] = bb::redc64(w[i] + t[i & 3]);
 }
 
+#else
+// The layer on canonical cells, exact: c_j < (W/4) p, z_i < (W/4 + 1) p <= 7p, w_i <= 16 z < 112 p < 2^38.  Then
+// s[i] = w[i] * 2^-32 (mod p) in [0, p + 53).  Two canonical cells add in 32 bits (< 2p < 2^32) before they enter
+// the 64-bit column sum.  Cells NZ .. W-1 are known to be zero (the capacity of a fresh sponge, the padding of a
+// compression): they are neither summed nor added, z_i = c_(i & 3) there.
+template <int NZ = CELLS>
+static RK_HD void m_ext_redc(uint32_t* s) {
+    static_assert(NZ >= 1 && NZ <= CELLS, "NZ leading cells may be non-zero");
+    uint64_t c[4];
+    static_for<0, 4>([&](auto jc) __attribute__((always_inline)) {
+        constexpr int J = decltype(jc)::value;
+        constexpr int N = NZ > J ? (NZ - J + 3) / 4 : 0;  // non-zero cells of column J
+        uint64_t acc = 0;
+        static_for<0, N / 2>([&](auto pc) __attribute__((always_inline)) {
+            constexpr int I = 8 * decltype(pc)::value + J;
+            const uint32_t pr = s[I] + s[I + 4];
+            if constexpr (I == J) acc = pr;
+            else acc = madk<1>(pr, acc);
+        });
+        if constexpr (N % 2 == 1) {
+            if constexpr (N == 1) acc = s[J];
+            else acc = madk<1>(s[4 * (N - 1) + J], acc);
+        }
+        c[J] = acc;
+    });
+#pragma unroll
+    for (int i = 0; i < CELLS; i += 4) {
+        uint64_t z[4], w[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) z[j] = i + j < NZ ? madk<1>(s[i + j], c[j]) : c[j];
+        m4_wide<uint64_t>(z[0], z[1], z[2], z[3], w);
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[i + j] = bb::uredc64(w[j]);
+    }
+}
+
+// The same layer on signed-lazy cells |y| < p (S-box outputs), exact in int64: |c_j| < (W/4) p, |z_i| < 7p,
+// |w_i| < 112 p (49 p for M4K = 1), then r[i] = w[i] * 2^-32 (mod p) as a signed value, |r| <= p/2 + 53.  Sums like
+// a + b do not fit 32 bits here, so the cells enter 64 bits through v_mad_i64_i32 (times 1), two per cell; the rest
+// is 64-bit shift-adds.  Only the blocks B0 .. B0 + BN - 1 are produced (cells 4 B0 .. 4 (B0 + BN) - 1 of r); the
+// column sums still read every cell of y.
+template <int B0 = 0, int BN = CELLS / 4>
+static RK_HD void m_ext_redc_s(const int32_t* y, int32_t* r) {
+    static_assert(B0 >= 0 && BN >= 1 && 4 * (B0 + BN) <= CELLS, "blocks of four cells");
+    int64_t c[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        c[j] = smulk<1>(y[j]);
+#pragma unroll
+        for (int b = 4; b < CELLS; b += 4) c[j] = smadk<1>(y[b + j], c[j]);
+    }
+#pragma unroll
+    for (int i = 4 * B0; i < 4 * (B0 + BN); i += 4) {
+        int64_t z[4], w[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) z[j] = smadk<1>(y[i + j], c[j]);
+        m4_wide<int64_t>(z[0], z[1], z[2], z[3], w);
+#pragma unroll
+        for (int j = 0; j < 4; j++) r[i + j] = bb::redc64(w[j]);
+    }
+}
+#endif
+
 // (x + c)^7 * 2^(-6*32) as a signed-lazy value, |result| < p.  x + c must fit an int32: x unsigned in
 // [0, p + 2^22) with c = rc - p, or x a signed REDC output (|x| <= p/2 + 53) with c centred.
 static RK_HD int32_t sbox7_lazy(uint32_t x, uint32_t c_mp) {
@@ -365,13 +464,15 @@ static RK_HD int32_t sbox7_lazy(uint32_t x, uint32_t c_mp) {
 }
 // One full round on the 32-bit patterns of the cells (unsigned after the first layer / the partial
 // rounds, signed otherwise: the offset form of the round constants follows, see derive()).
+// Only the blocks B0 .. B0 + BN - 1 of the output are written; the other cells of s are left as they were.
+template <int B0 = 0, int BN = CELLS / 4>
 static RK_HD void full_round(uint32_t* s, const Consts& k, int r) {
     int32_t y[CELLS], o[CELLS];
 #pragma unroll
     for (int i = 0; i < CELLS; i++) y[i] = sbox7_lazy(s[i], k.rc_ext_in[r * CELLS + i]);
-    m_ext_redc_s(y, o);
+    m_ext_redc_s<B0, BN>(y, o);
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) s[i] = (uint32_t)o[i];
+    for (int i = 4 * B0; i < 4 * (B0 + BN); i++) s[i] = (uint32_t)o[i];
 }
 
 // Reader of Consts::pr_stream.  On the device the constants live in scalar registers: chunks of
@@ -532,17 +633,31 @@ static RK_HD void partial_rounds(uint32_t* s, const Consts& k) {
 }
 #endif
 
+// The permutation.  A caller that reads only the cells KEEP0 .. KEEP0 + KEEPN - 1 of the result (whole blocks of
+// four: the digest 0..7, the capacity W-8..W-1 of a sponge whose next block overwrites the rate) says so, and one
+// whose input cells NZ .. W-1 are zero says that: the last full round is then peeled out of its rolled loop and its
+// layer produces the kept blocks only (column sums, then z, M4 and REDC for those blocks), and the first layer skips
+// the zero cells.  The kept cells are word for word those of the full form; the other cells of s are unspecified.
+// The defaults are the full form: every cell written, no input assumed zero.
+template <int KEEP0 = 0, int KEEPN = CELLS, int NZ = CELLS>
 static RK_HD void permute(uint32_t* s, const Consts& k) {
-    m_ext_redc(s);  // canonical Montgomery input -> plain residues (scale 2^0), cells in [0, p + 53)
+    static_assert(KEEP0 % 4 == 0 && KEEPN % 4 == 0 && KEEP0 >= 0 && KEEPN >= 4 && KEEP0 + KEEPN <= CELLS, "kept cells are whole blocks");
+    m_ext_redc<NZ>(s);  // canonical Montgomery input -> plain residues (scale 2^0), cells in [0, p + 53)
 #pragma unroll 1
     for (int r = 0; r < ROUNDS_HALF_FULL; r++) full_round(s, k, r);
     // signed cells (|x| <= p/2 + 53) scaled by 2^(32 * -2800): partial_rounds() owns the scale
     partial_rounds(s, k);  // Montgomery form again, canonical
+    if constexpr (KEEPN == CELLS) {
 #pragma unroll 1
-    for (int r = ROUNDS_HALF_FULL; r < 2 * ROUNDS_HALF_FULL; r++) full_round(s, k, r);
-    // per-cell rescale to Montgomery form + canonical range: cells the caller never reads cost nothing
+        for (int r = ROUNDS_HALF_FULL; r < 2 * ROUNDS_HALF_FULL; r++) full_round(s, k, r);
+    } else {
+#pragma unroll 1
+        for (int r = ROUNDS_HALF_FULL; r < 2 * ROUNDS_HALF_FULL - 1; r++) full_round(s, k, r);
+        full_round<KEEP0 / 4, KEEPN / 4>(s, k, 2 * ROUNDS_HALF_FULL - 1);
+    }
+    // per-cell rescale to Montgomery form + canonical range, kept cells only
 #pragma unroll
-    for (int i = 0; i < CELLS; i++) s[i] = bb::canon(bb::smul_const((int32_t)s[i], (int32_t)k.fix[1], k.fix1_q));
+    for (int i = KEEP0; i < KEEP0 + KEEPN; i++) s[i] = bb::canon(bb::smul_const((int32_t)s[i], (int32_t)k.fix[1], k.fix1_q));
 }
 
 };  // struct Core
