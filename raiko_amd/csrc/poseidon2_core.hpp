@@ -93,28 +93,40 @@ RK_HD int64_t smulk(int32_t x) {
 
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef uint32_t sgpr16 __attribute__((ext_vector_type(16)));
+typedef sgpr16 __attribute__((aligned(4))) sgpr16_u;   // a scalar load needs dword alignment only
+// The chunks are plain loads from the constant address space through a wave-uniform pointer: the compiler selects
+// s_load_dwordx16 and, because the load is its own, puts the s_waitcnt before the first read, copy or spill of the
+// destination.  An earlier form issued the load from inline asm without a wait and handed the registers back as an
+// ordinary "=s" value: the compiler may copy such a value at once (a live-range split), SGPRs with an SMEM load in
+// flight have no interlock, and the copy then holds whatever was in the registers before.  That happened in
+// hash_rows_multi_kernel at width 24 and showed as digests that changed from run to run once two proofs contended for
+// memory.  Nothing in flight is ever a C++ value here.
 struct KStream {
     const uint32_t* p;
     sgpr16 cur, nxt;
-    __device__ __forceinline__ explicit KStream(const uint32_t* base) : p(base) {
-        asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cur) : "s"(p));
-        asm volatile("s_load_dwordx16 %0, %1, 0x40" : "=s"(nxt) : "s"(p));
+    static __device__ __forceinline__ sgpr16 chunk(const uint32_t* q) {
+        return *(const __attribute__((address_space(4))) sgpr16_u*)(uintptr_t)q;
     }
-    // `acc` (the running sum the constant is about to be multiplied into) is threaded through the
-    // wait so that the scheduler keeps it between the products of two chunks: without that it
-    // bunches several wait + load pairs together and nothing overlaps the load latency
+    __device__ __forceinline__ explicit KStream(const uint32_t* base) : p(base) {
+        asm volatile("" : "+s"(p));   // uniform, and opaque: the loads are not merged with the caller's own of *kc
+        cur = chunk(p);
+        nxt = chunk(p + 16);
+    }
+    // The pointer and `acc` (the running sum the constant is about to be multiplied into) go through one empty asm
+    // statement: the load of the chunk after next cannot be issued before that sum exists, so the compiler neither
+    // bunches the loads of several chunks together at the top (2400 constants do not fit the SGPRs) nor loses the
+    // overlap of a chunk's latency with the products of the chunk before it.
     template <int POS, class A>
     __device__ __forceinline__ uint32_t get(A& acc) {
         uint32_t c = cur[POS & 15];
         if constexpr ((POS & 15) == 15) {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nxt), "+v"(acc));
             cur = nxt;
-            // the chunk after next (byte offset as an immediate: no pointer arithmetic to hoist)
-            asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(nxt) : "s"(p), "n"((POS / 16 + 2) * 64));
+            asm volatile("" : "+s"(p), "+v"(acc));
+            nxt = chunk(p + (POS / 16 + 2) * 16);
         }
         return c;
     }
-    __device__ __forceinline__ void drain() { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nxt)); }
+    __device__ __forceinline__ void drain() {}
 };
 #else
 struct KStream {
@@ -476,9 +488,9 @@ static RK_HD void full_round(uint32_t* s, const Consts& k, int r) {
 }
 
 // Reader of Consts::pr_stream.  On the device the constants live in scalar registers: chunks of
-// 16 are fetched with s_load_dwordx16 one chunk ahead of their use (the compiler's own scheduling
-// of ~2400 scalar loads spills SGPRs), and the wait is attached to the chunk's registers so that
-// no use can move above it.  Positions are consumed strictly in order.
+// 16 are fetched one chunk ahead of their use (left to itself the compiler's scheduling of ~2400
+// scalar loads spills SGPRs: KStream says where each chunk's load may start, the compiler issues
+// it and waits for it).  Positions are consumed strictly in order.
 #if defined(RK_P2_DIRECT)
 // The partial rounds, one at a time, at three instructions per cell per round.  With S the sum of
 // the cells (after the S-box on cell 0) the layer is y_i = d_i x_i + S.  In Montgomery form

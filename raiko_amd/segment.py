@@ -166,14 +166,16 @@ def algorithmic_bytes(po2: int, widths: Sequence[int], blowup_log2: int = 2, fol
 
 
 # VALU instructions of one Poseidon2 permutation as shipped (tools/census_p2.py on the gfx950 ISA of
-# poseidon2_core.hpp: 5990 dynamic v_* instructions with all 24 output cells live and no input cell known to be
-# zero, the external layer summing columns before M4, the partial rounds in blocks of three -- 6080 with M4 per
+# poseidon2_core.hpp: 6038 dynamic v_* instructions with all 24 output cells live and no input cell known to be
+# zero, the external layer summing columns before M4, the partial rounds in blocks of three -- 5990 while KStream
+# issued its scalar loads from inline asm (unsound: DESIGN 5.3), 6080 with M4 per
 # block first (RK_P2_EXT_M4_FIRST), 6195 while the literal-multiplier mads still tied their addend to the result
 # (115 64-bit register copies), 6629 with the partial rounds one at a time (RK_P2_DIRECT; 6737 with tied addends),
 # 7159 with the closed form of round 1;
-# the kernels keep only the digest / capacity cells and run fewer: `census_p2.py --kernels` counts 5831 for a
-# chained block of hash_rows_kernel and 5814 for hash_fold_kernel, profiles/r08_census.txt)
-P2_VALU_PER_PERMUTATION = 5990
+# the kernels keep only the digest / capacity cells and run fewer: `census_p2.py --kernels` counts 5865 for a
+# chained block of hash_rows_kernel and 5862 for hash_fold_kernel; 5831 / 5814 in profiles/r08_census.txt, before
+# the KStream change)
+P2_VALU_PER_PERMUTATION = 6038
 
 
 def poseidon2_permutations(po2: int, widths: Sequence[int]) -> dict:

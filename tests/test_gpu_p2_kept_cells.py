@@ -2,7 +2,8 @@
 under the same parameter blob: hash_rows_kernel at every column count where a row takes another path (no block, only a
 partial block, exactly one block, chained blocks with and without a partial one), both sponge kinds; the lane-per-parent
 folds and the cell-parallel top through rk_merkle_build; compress_inject_kernel through a commitment of a tall and a
-short matrix; one proof-of-work search of each kind.  300 rows: the last workgroup is partial, and the compared rows
+short matrix; one proof-of-work search of each kind; uni-stark proofs under the width-24 set with two in flight, which
+once changed from run to run.  300 rows: the last workgroup is partial, and the compared rows
 include lanes 0, 63, 64, 255, 256.  The host side is tests/test_p2_ext_layer.py."""
 import ctypes as C
 
@@ -111,3 +112,25 @@ def test_grinds(cfg, orc, w, m4):
     assert nonce.value == want
     state, inputs = o.rand_elems(rng, (w,)), o.rand_elems(rng, (5,))
     assert h.duplex_grind(state, inputs, bits) == orc.or_duplex_grind(o.ptr(state), o.ptr(inputs), 5, bits)
+
+
+def test_two_proofs_in_flight_repeat_under_the_width_24_set():
+    """three rv32i-cf shards under risc0's set (width 24, zero-padding sponge) through p3.prove_shards: with two and
+    three proofs in flight, call after call, the words are those of one proof at a time.  While p2 KStream issued its
+    scalar loads from inline asm, hash_rows_multi_kernel copied a chunk's registers before the load had landed whenever a
+    second proof contended for memory: the second call with batch = 2 gave other words from the permutation root on, or
+    a proof that did not verify.  Whether a stale copy shows depends on timing, so this test can pass over the hazard;
+    tests/test_p2_kstream.py holds the source"""
+    import rv32_cf_programs as CP
+    from raiko_amd import p3
+    from raiko_amd import executor as X
+    from raiko_amd.hal import make_params
+    blob = make_params(0, queries=8, pow_bits=6)
+    ex = X.execute(CP.cf_program(100), [11, 22, 33, 44], segment_limit_po2=13, record_trace=True)
+    shards = X.p3_rv32cf_shards(ex, ext_w=int(blob.ext_w))
+    assert len(shards) == 3
+    want = p3.prove_shards(shards, blob, batch=1, verify=True)
+    for batch in (2, 2, 3, 2):
+        got = p3.prove_shards(shards, blob, batch=batch, verify=True)
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a, b), (batch, k)
