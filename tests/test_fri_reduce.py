@@ -16,6 +16,7 @@ import field_ref as FR
 import oracle_lib as o
 import p2_chip_ref as R
 import p3_ref
+import threshold_cases as T
 from p3_cases import P3_CASES, init_of, tables_of
 from raiko_amd import _lib, hal, p3
 from raiko_amd import fri_chip as F
@@ -490,7 +491,8 @@ def slot_words(st):
     return np.array(out, dtype=np.uint32)
 
 
-@pytest.mark.parametrize("case", CASES + ["sp1_width_301"])     # 301 columns: more than a workgroup takes at once
+# 301 columns: more than a workgroup takes at once; A, B: the shards of tests/test_gpu_fri_widths.py (64 / 65, 255 / 256 / 257, 513)
+@pytest.mark.parametrize("case", CASES + ["sp1_width_301", "A", "B"])
 def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     """the lane bodies of rk_fri_reduce_rows_device (p3_kernels.hpp), run as the kernels run them -- the reduce kernel's
     scans across emulated 64-lane waves (tests/emul/emul_fri_reduce.cpp) --, write the numpy witness word for word"""
@@ -499,7 +501,10 @@ def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(o.ROOT, "raiko_amd", "csrc"), "-o", so, src],
                    check=True, capture_output=True)
     lib = C.CDLL(so)
-    blob, tables, init, pf = setup(params, case)
+    if case in T.FRI_SHARDS:
+        blob, tables, init, pf = T.fri_setup(case, hal.make_params, o.oracle_p3_prove)
+    else:
+        blob, tables, init, pf = setup(params, case)
     st = G.statement(tables, pf, init, blob)
     want = [p3.to_mont(r) for r in G.witness(st)]
     rc_ext, rc_int, diag, m4 = R.tables_of()

@@ -40,8 +40,10 @@ def test_coset_lde_rows(cfg, preset, k, w):
 
 
 @pytest.mark.parametrize("preset", [0, 1])
-@pytest.mark.parametrize("k,w,npts", [(2, 1, 1), (5, 3, 2), (9, 70, 2), (12, 130, 3), (14, 8, 8)])
+@pytest.mark.parametrize("k,w,npts", [(2, 1, 1), (5, 3, 2), (9, 70, 2), (12, 130, 3), (14, 8, 8), (17, 3, 2)])
 def test_eval_at_and_reduce_openings(cfg, preset, k, w, npts):
+    """(17, 3, 2): h = 2^17 rows are 128 per chunk of bary_dot_kernel, two sweeps of its BARY_Y sub-rows
+    (tests/test_launch_thresholds.py holds the arithmetic)"""
     h, apply = cfg
     blow = int(apply(preset).blowup_log2)
     orc = o.oracle()
@@ -186,15 +188,19 @@ def test_coset_lde_rows_other_blowups(cfg, blow, k, w):
     assert np.array_equal(h.pcs_eval_at(out, n << blow, w, z), ys)
 
 
-@pytest.mark.parametrize("preset,k,w,npts", [(1, 9, 37, 2), (0, 7, 5, 3), (1, 14, 130, 2), (1, 3, 1, 1)])
+@pytest.mark.parametrize("preset,k,w,npts", [(1, 9, 37, 2), (0, 7, 5, 3), (1, 14, 130, 2), (1, 3, 1, 1),
+                                             (1, 15, 9, 4), (0, 15, 5, 4)])
 def test_column_major_forms_equal_the_row_major_ones(preset, k, w, npts):
     """rk_pcs_coset_lde_cols / rk_pcs_eval_at_many_cols / rk_pcs_reduce_openings_cols and rk_mmcs_commit on layout 2: the
     LDE as the NTT leaves it (columns in natural order) gives the same committed rows, the same tree, the same opened values
-    and the same reduced opening as the row-major operators (which are pinned against the oracle above)"""
+    and the same reduced opening as the row-major operators (which are pinned against the oracle above); the opened
+    values also against the oracle on the downloaded row-major LDE.  k = 15: 512 rows per chunk of bary_dot_cols_kernel,
+    two strides of its 256 lanes; four points: its <4> instance (tests/test_launch_thresholds.py)"""
     from raiko_amd import hal as H
     h = H.HipHal(0)
     try:
         par = h.set_params(preset)
+        o.oracle_set_params(preset)
         blow = int(par.blowup_log2)
         n, Hh = 1 << k, (1 << k) << blow
         rng = np.random.default_rng(100 * k + w)
@@ -215,10 +221,15 @@ def test_column_major_forms_equal_the_row_major_ones(preset, k, w, npts):
         pts = o.rand_elems(rng, (npts, 4))
         ys = h.pcs_eval_at_many(rows, Hh, w, pts)
         assert np.array_equal(h.pcs_eval_at_many_cols(cols, Hh, w, pts), ys)
+        want = np.zeros((npts, w, 4), dtype=np.uint32)
+        for j in range(npts):
+            o.oracle().or_pcs_eval_at(o.ptr(want[j]), o.ptr(R), Hh, w, o.ptr(pts[j]))
+        assert np.array_equal(ys, want)
         alpha, start = o.rand_elems(rng, (4,)), o.rand_elems(rng, (Hh, 4))
         ro_r, ro_c = h.copy_from_elem(start), h.copy_from_elem(start)
         h.pcs_reduce_openings(ro_r, rows, Hh, w, pts, ys, alpha, 11)
         h.pcs_reduce_openings_cols(ro_c, cols, Hh, w, pts, ys, alpha, 11)
         assert np.array_equal(ro_r.to_host(), ro_c.to_host())
     finally:
+        o.oracle_set_params()
         h.close()
