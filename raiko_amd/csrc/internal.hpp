@@ -5,6 +5,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -232,7 +233,6 @@ int scatter(rk_ctx* ctx, uint32_t* d_into, size_t into_words, const uint32_t* h_
 int program_eval_check(const rk_program* prog, const rk_circuit_view* view, const uint32_t poly_mix[4], uint32_t* d_check);
 int program_poly_ext(const rk_program* prog, uint32_t wm, const uint32_t poly_mix[4], const uint32_t* eval_u_ext, size_t n_taps,
                      const uint32_t* globals, uint32_t n_globals, const uint32_t* mix, uint32_t n_mix, uint32_t out_ext[4]);
-// d_ext[idx[i]] -= delta[i]
 // Plonky3 two-adic PCS steps on row-major matrices (kernels_pcs.hip)
 // keep_cols != nullptr: *keep_cols receives the column-major natural-order evaluations (w columns of h << blow-up
 // words, a dev_alloc'd block the caller frees) the rows were transposed from
@@ -245,7 +245,46 @@ int pcs_eval_at(rk_ctx* ctx, uint32_t* d_out_ext, const uint32_t* d_lde, size_t 
 int pcs_reduce_openings(rk_ctx* ctx, uint32_t* d_ro_ext, const uint32_t* d_lde, size_t H, size_t w, size_t n_points,
                         const uint32_t* h_points, const uint32_t* h_ys, const bb::Ext& alpha, uint64_t alpha_offset, bool cols = false);
 int pcs_coset_lde_cols(rk_ctx* ctx, uint32_t* d_cols, const uint32_t* d_in, size_t h, size_t w);
+// d_ext[idx[i]] -= delta[i]
 int ext_sub_at(rk_ctx* ctx, uint32_t* d_ext, const uint32_t* h_idx, const bb::Ext* h_delta, size_t n);
+
+// The contexts an entry point with several proofs in flight keeps per device between calls (session.hip and
+// p3_shards.hip, each with a map of its own: their allocator caches and parameter sets differ).
+struct CtxPool {
+    struct Slot {   // a prover context and the parameter set it was configured with: they come and go together
+        rk_ctx* ctx = nullptr;
+        std::vector<uint32_t> key;
+    };
+    std::mutex busy;                 // one run at a time per device (an entry point may be entered from many threads)
+    std::vector<Slot> slots;
+    rk_ctx* uploader = nullptr;      // stages host-resident inputs ahead of the provers (its own stream)
+    // at least n_workers contexts on `device`, the first n_workers carrying `params`: only those whose key differs are
+    // configured again, so an equal set costs nothing next time
+    int ensure(int device, size_t n_workers, const rk_params* params, const std::vector<uint32_t>& key) {
+        while (slots.size() < n_workers) {
+            slots.emplace_back();   // first the slot, then its context: a failed push_back would leak one
+            const int st = rk_ctx_create(device, nullptr, &slots.back().ctx);
+            if (st != RK_OK) {
+                slots.pop_back();
+                return st;
+            }
+        }
+        for (size_t j = 0; j < n_workers; j++) {
+            if (slots[j].key == key) continue;
+            RK_TRY(rk_set_params(slots[j].ctx, params));
+            slots[j].key = key;
+        }
+        return RK_OK;
+    }
+    int ensure_uploader(int device) { return uploader ? RK_OK : rk_ctx_create(device, nullptr, &uploader); }
+    void clear() {
+        for (Slot& s : slots) (void)rk_ctx_destroy(s.ctx);
+        slots.clear();
+        if (uploader) (void)rk_ctx_destroy(uploader);
+        uploader = nullptr;
+    }
+    ~CtxPool() { clear(); }
+};
 // p3_shards.hip: the contexts rk_p3_prove_shards keeps per device (freed by rk_session_release)
 void p3_release_pools();
 

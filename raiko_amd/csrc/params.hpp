@@ -4,6 +4,9 @@
 // (reference call sites provers/risc0/driver/src/bonsai.rs:271 and
 // provers/sp1/driver/src/lib.rs:48-57 -- both crates families are outside the reference tree).
 #pragma once
+#include <memory>
+#include <vector>
+
 #include "../../include/raiko_hip.h"
 #include "taps.hpp"
 #include "poseidon2_any.hpp"
@@ -91,6 +94,20 @@ inline int resolve_params(const rk_params* in, Sys* sys, p2::Any* p2any) {
     sys->fri_min_degree = in->fri_min_degree;
     sys->pow_bits = in->pow_bits;
     return RK_OK;
+}
+
+// every word that defines a parameter set (the tables by value), so that an equal set is recognised whoever built it;
+// empty for a set that does not resolve
+inline std::vector<uint32_t> params_key(const rk_params& p) {
+    Sys sys;
+    auto any = std::make_unique<p2::Any>();  // ~50 KiB: not on the stack
+    if (resolve_params(&p, &sys, any.get()) != RK_OK) return {};
+    std::vector<uint32_t> k = {p.ext_w, p.root_2_27, p.coset_shift, p.p2_width, p.p2_m4, p.p2_pad_free, p.queries, p.blowup_log2,
+                               p.fri_fold_log2, p.fri_min_degree, p.pow_bits};
+    k.insert(k.end(), any->rc_ext(), any->rc_ext() + 8 * any->cells());
+    k.insert(k.end(), any->rc_int(), any->rc_int() + any->rounds_partial());
+    k.insert(k.end(), any->diag(), any->diag() + any->cells());
+    return k;
 }
 
 }  // namespace rk

@@ -68,6 +68,29 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert lib.rk_session_release() == 0
 
 
+def test_shard_pool_argument_checks_come_before_the_gpu():
+    """rk_p3_prove_shards refuses bad options and device lists from host data alone, in this order: the options, an
+    empty batch (RK_OK, before the list is looked at for duplicates), duplicates, then the device count."""
+    from raiko_amd import _lib
+    lib = _lib.load()
+
+    def call(n=0, shards=None, **kw):
+        opts = _lib.RkP3SessionOpts(**dict(dict(device=0, batch=1, verify=0), **kw))
+        return lib.rk_p3_prove_shards(C.byref(opts), shards, n, None)
+
+    one = (_lib.RkP3Shard * 1)()
+    dup, ok = (C.c_int * 2)(0, 0), (C.c_int * 1)(0)
+    assert lib.rk_p3_prove_shards(None, None, 0, None) == -1           # opts == NULL
+    assert call(batch=0) == -1 and call(batch=17) == -1
+    assert call(devices=dup, n_devices=65) == -1
+    assert call(devices=None, n_devices=2) == -1                       # a count without a list
+    assert call(n=0, devices=dup, n_devices=2) == 0                    # nothing to prove: the list is not looked at
+    assert call(n=1, shards=one, devices=dup, n_devices=2) == -1       # duplicate GPU
+    n = C.c_int(-1)
+    if not (lib.rk_device_count(C.byref(n)) == 0 and n.value > 0):
+        assert call(n=1, shards=one, devices=ok, n_devices=1) == -4    # RK_ERR_NODEVICE: no proof comes out of a CPU
+
+
 def test_product_never_imports_the_oracle():
     """the product package must not reference oracle/ or the tests' oracle binding"""
     pkg = os.path.join(ROOT, "raiko_amd")
