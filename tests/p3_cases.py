@@ -188,8 +188,13 @@ def air_of(name, arg, preset=1):
     return _AIRS[key]
 
 
-def tables_of(case):
+def tables_of(case, air_preset=None):
+    """the case's tables; air_preset: the preset whose extension (EXT_W) the AIRs with interactions are written for,
+    where the case is proven under another field than its own preset's (tests/fri_param_sets.py)"""
     preset, _, specs, _ = P3_CASES[case]
+    if air_preset is not None:
+        assert not any(name == "merkle" for name, _, _ in specs)
+        preset = air_preset
     out = []
     for i, (name, k, arg) in enumerate(specs):
         if name == "merkle":

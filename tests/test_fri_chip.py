@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import field_ref as FR
+import fri_param_sets as PS
 import oracle_lib as o
 import p2_chip_ref as R
 import p3_ref
@@ -140,6 +141,16 @@ def test_honest_statement(params, case):
     assert F.verify_fri_statement(tables, pf, init, fp, blob) == 0
 
 
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_reference_holds_under_parameter_sets(params, pset, case):
+    """the oracle and the numpy witness alone under every set of tests/fri_param_sets.py; the witness's Poseidon2 against
+    the tests' restatement under the oracle's tables and matrix"""
+    st, rows = PS.check_reference(F, F.verify_fri_statement, pset, case)
+    assert R.tables_of()[3] == int(st.params.p2_m4) and st.ext_w == int(st.params.ext_w)
+    assert np.array_equal(rows[3], R.chip_trace(rows[3][:, :16], R.tables_of(), rows[3][:, -1]))
+    assert [r.shape[0] for r in rows] == [1 << h for h in F.heights(st.shape)]
+
+
 def test_mutated_shard_proofs_give_the_verifiers_verdict_and_no_records(params):
     blob, tables, init, pf = setup(params, CASES[0])
     seen = set()
@@ -160,8 +171,8 @@ class Forge:
     """the honest statement of CASES[0] and what a forger needs: canonical rows to vary, the verdict of both verifiers
     on the oracle's proof of a variation"""
 
-    def __init__(self, params):
-        self.blob, self.tables, self.init, self.pf = setup(params, CASES[0])
+    def __init__(self, params, pset=None):
+        self.blob, self.tables, self.init, self.pf = setup(params, CASES[0]) if pset is None else PS.cpu_shard(pset, CASES[0])
         self.st = F.statement(self.tables, self.pf, self.init, self.blob)
         self.rows = F.witness(self.st)
         self.sh = self.st.shape
@@ -248,6 +259,26 @@ def test_forged_public_values(forge):
         pub = f.pub.copy()
         pub[at] = (int(pub[at]) + 1) % P
         assert f.verdict(f.rows, pub) == 3
+
+
+@pytest.fixture(params=[None, "m4_0"], ids=["preset1", "m4_0"])
+def forge_sets(request, params):
+    return Forge(params, request.param)
+
+
+def test_forged_path_bit_under_parameter_sets(forge_sets):
+    """the first forgery of test_forged_paths once more under the other external matrix: still refused"""
+    f, pc = forge_sets, forge_sets.pc
+    off, lf, chip0 = f.path_at(3, 2)
+    rows = f.copy()
+    r = rows[1][off + lf - 1]
+    r[pc.BIT] ^= 1
+    left, right = r[pc.RIGHT: pc.RIGHT + 8].copy(), r[pc.LEFT: pc.LEFT + 8].copy()
+    r[pc.LEFT: pc.LEFT + 8], r[pc.RIGHT: pc.RIGHT + 8] = left, right
+    new = R.chip_trace(np.concatenate([left, right])[None, :], f.tabs)
+    rows[3][chip0 + lf] = new[0]
+    r[pc.PARENT: pc.PARENT + 8] = new[0, F.CHIP_OUT: F.CHIP_OUT + 8]
+    assert f.tabs[3] == int(f.blob.p2_m4) and f.verdict(f.rows) == 0 and f.verdict(rows) == 3
 
 
 def test_forged_paths(forge):
@@ -371,8 +402,8 @@ def test_kernel_lanes_on_the_cpu(params, tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(o.ROOT, "raiko_amd", "csrc"), "-o", so, src],
                    check=True, capture_output=True)
     lib = C.CDLL(so)
-    for case in CASES:
-        blob, tables, init, pf = setup(params, case)
+    for pset, case in [(None, c) for c in CASES] + PS.ROW_IDS:       # the sets: fri_path_lane<0>, other tables, another field
+        blob, tables, init, pf = setup(params, case) if pset is None else PS.cpu_shard(pset, case)
         st = F.statement(tables, pf, init, blob)
         want = [p3.to_mont(r) for r in F.witness(st)]
         rc_ext, rc_int, diag, m4 = R.tables_of()
@@ -383,5 +414,6 @@ def test_kernel_lanes_on_the_cpu(params, tmp_path):
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         lib.emul_fri_chip_rows(sh.log_max, sh.blowup_log2, sh.queries, gen_l, int(p3.to_mont([st.ext_w])[0]), vp(st.publics), vp(st.records),
                                vp(tab), m4, *[vp(g) for g in got], C.c_size_t(got[3].shape[0]))
+        assert m4 == int(blob.p2_m4)
         for g, w in zip(got, want):
-            assert np.array_equal(g, w)
+            assert np.array_equal(g, w), (pset, case)

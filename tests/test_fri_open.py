@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import field_ref as FR
+import fri_param_sets as PS
 import oracle_lib as o
 import p2_chip_ref as R
 from p3_cases import P3_CASES, init_of, tables_of
@@ -202,6 +203,16 @@ def test_honest_statement(params, case):
             H.statement(tables, bad, init, blob)
 
 
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_reference_holds_under_parameter_sets(params, pset, case):
+    """the oracle and the numpy witness alone under every set of tests/fri_param_sets.py"""
+    st, rows = PS.check_reference(H, H.verify_open_statement, pset, case)
+    sz = H.sizes(st)
+    assert [r.shape[0] for r in rows] == [1 << h for h in H.heights(st)]
+    assert int(rows[4][:, -1].sum()) == sz["chip_rows"] and int(rows[5][:, -1].sum()) == sz["state_rows"]
+    assert any(v is not None for t in st.trees for v in t.group_at)          # a shorter matrix is injected into an input path
+
+
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.uint32).tobytes()).hexdigest()
 
@@ -270,8 +281,8 @@ class Forge:
     """the honest statement of FORGE_CASE and what a forger needs: canonical rows to vary, the verdict of both verifiers on
     the oracle's proof of a variation"""
 
-    def __init__(self, params):
-        self.blob, self.tables, self.init, self.pf = setup(params, FORGE_CASE)
+    def __init__(self, params, pset=None):
+        self.blob, self.tables, self.init, self.pf = setup(params, FORGE_CASE) if pset is None else PS.cpu_shard(pset, FORGE_CASE)
         self.st = st = H.statement(self.tables, self.pf, self.init, self.blob)
         self.rows = H.witness(st)
         self.sh, self.slots = st.shape, st.slots
@@ -404,6 +415,23 @@ def test_forged_opened_values(forge):
     t = f.st.trees[k]
     assert [f.bad_rows(rows, i) for i in (0, 1, 2, 4, 5)] == [[]] * 5
     assert f.bad_rows(rows, 3) == [f.irow(q, k, t.B - 1)] and f.verdict(rows) == 3
+
+
+def test_forged_opened_value_and_path_bit_under_the_other_matrix(params):
+    """one forgery of test_forged_opened_values and one of test_forged_paths once more under m4_0: opened values moved
+    with every table redone, and a path bit flipped with the path redone above it, are still refused by the root"""
+    f = Forge(params, "m4_0")
+    assert int(f.blob.p2_m4) == 0 and f.consts[3] == 0 and f.verdict(f.rows) == 0
+    q, gi, rec, touched = moved_records(f)
+    rows = H.witness(f.st, records=rec)
+    k = next(i for i, t in enumerate(f.st.trees) if t.batch == f.st.groups[gi].batch)
+    assert [f.bad_rows(rows, i) for i in (0, 1, 2, 4, 5)] == [[]] * 5
+    assert f.bad_rows(rows, 3) == [f.irow(q, k, f.st.trees[k].B - 1)] and f.verdict(rows) == 3
+    q, k, s = 3, 1, 2
+    t = f.st.trees[k]
+    bit = int(f.rows[3][f.irow(q, k, s)][f.ic.BIT])
+    rows = H.witness(f.st, bits={(k, s, q): 1 - bit})
+    assert f.bad_rows(rows, 3) == [f.irow(q, k, s), f.irow(q, k, t.B - 1)] and f.verdict(rows) == 3
 
 
 def test_forged_sponge(forge):
@@ -583,21 +611,22 @@ def plan_words(st):
 
 
 # a partial last block behind full ones (13, 28 cells) and three trees; injections on the first step of both trees
-@pytest.mark.parametrize("case", ["sp1_lookup_beside_plain", "sp1_twelve_tables"])
+@pytest.mark.parametrize("case", ["sp1_lookup_beside_plain", "sp1_twelve_tables"] + PS.ROW_IDS, ids=lambda c: c if isinstance(c, str) else PS.row_id(*c))
 def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     so = str(tmp_path / "libemul_fri_open.so")
     src = os.path.join(o.EMUL_DIR, "emul_fri_open.cpp")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(o.ROOT, "raiko_amd", "csrc"), "-o", so, src],
                    check=True, capture_output=True)
     lib = C.CDLL(so)
-    blob, tables, init, pf = setup(params, case)
+    blob, tables, init, pf = PS.cpu_shard(*case) if isinstance(case, tuple) else setup(params, case)   # a set: the lane bodies <0>, other tables
     st = H.statement(tables, pf, init, blob)
     if case == "sp1_twelve_tables":
         assert all(t.group_at[0] is not None for t in st.trees)
-    else:
+    elif case == "sp1_lookup_beside_plain":
         assert any(g.cells > 8 and g.cells % 8 for g in st.groups)
     want = [p3.to_mont(r) for r in H.witness(st)]
     rc_ext, rc_int, diag, m4 = R.tables_of()
+    assert m4 == int(blob.p2_m4)
     tab = p3.to_mont(np.concatenate([rc_ext.reshape(-1), rc_int, diag]))
     sh = st.shape
     cw = G.ReduceCols(len(st.slots)).width

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import field_ref as FR
+import fri_param_sets as PS
 import oracle_lib as o
 import p2_chip_ref as R
 import p3_ref
@@ -262,12 +263,22 @@ def test_honest_statement(params, case):
     assert G.verify_reduce_statement(tables, pf, init, fp, blob) == 0
 
 
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_reference_holds_under_parameter_sets(params, pset, case):
+    """the oracle and the numpy witness alone under every set of tests/fri_param_sets.py"""
+    st, rows = PS.check_reference(G, G.verify_reduce_statement, pset, case)
+    assert (st.ext_w, st.coset_shift) == (int(st.params.ext_w), int(st.params.coset_shift))
+    assert [r.shape[0] for r in rows] == [1 << h for h in G.heights(st)]
+    c = G.ReduceCols(len(st.slots))
+    assert int(rows[2][:, c.RCV].sum()) == st.shape.queries * st.shape.n_rounds
+
+
 class Forge:
     """the honest statement of CASES[0] and what a forger needs: canonical rows to vary, the verdict of both verifiers on
     the oracle's proof of a variation"""
 
-    def __init__(self, params):
-        self.blob, self.tables, self.init, self.pf = setup(params, CASES[0])
+    def __init__(self, params, pset=None):
+        self.blob, self.tables, self.init, self.pf = setup(params, CASES[0]) if pset is None else PS.cpu_shard(pset, CASES[0])
         self.st = G.statement(self.tables, self.pf, self.init, self.blob)
         self.rows = G.witness(self.st)
         self.sh, self.slots = self.st.shape, self.st.slots
@@ -339,6 +350,22 @@ def test_forged_opened_values(forge):
         assert bad2 and bad2.isdisjoint(bad)
         rows[2][r][c.PV] = redone[r][c.PV]
         assert f.verdict(rows) == 3
+
+
+def test_forged_opened_value_under_the_other_matrix(params):
+    """the first two forgeries of test_forged_opened_values once more under m4_0: still refused, for the same reasons"""
+    f = Forge(params, "m4_0")
+    c = f.c
+    assert int(f.blob.p2_m4) == 0 and f.verdict(f.rows) == 0
+    q, m, col = 3, 1, 2
+    rows = f.copy()
+    bump(rows[2][f.at(q, m, col)], c.PV)
+    assert f.bad_rows(rows) == [f.at(q, m, col) - 1] and f.verdict(rows) == 3
+    rows = f.copy()
+    rec = f.rec.copy()
+    bump(rec[q], 1 + f.slots[m].rec_off + col)
+    rows[2] = G.reduce_rows(f.st, records=rec)
+    assert f.bad_rows(rows) == [] and f.verdict(rows) == 8
 
 
 def test_forged_running_cells(forge):
@@ -492,7 +519,7 @@ def slot_words(st):
 
 
 # 301 columns: more than a workgroup takes at once; A, B: the shards of tests/test_gpu_fri_widths.py (64 / 65, 255 / 256 / 257, 513)
-@pytest.mark.parametrize("case", CASES + ["sp1_width_301", "A", "B"])
+@pytest.mark.parametrize("case", CASES + ["sp1_width_301", "A", "B"] + PS.ROW_IDS, ids=lambda c: c if isinstance(c, str) else PS.row_id(*c))
 def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     """the lane bodies of rk_fri_reduce_rows_device (p3_kernels.hpp), run as the kernels run them -- the reduce kernel's
     scans across emulated 64-lane waves (tests/emul/emul_fri_reduce.cpp) --, write the numpy witness word for word"""
@@ -501,13 +528,16 @@ def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(o.ROOT, "raiko_amd", "csrc"), "-o", so, src],
                    check=True, capture_output=True)
     lib = C.CDLL(so)
-    if case in T.FRI_SHARDS:
+    if isinstance(case, tuple):            # a set of tests/fri_param_sets.py: fri_path_lane<0>, shiftm, wm and gen_l of another field
+        blob, tables, init, pf = PS.cpu_shard(*case)
+    elif case in T.FRI_SHARDS:
         blob, tables, init, pf = T.fri_setup(case, hal.make_params, o.oracle_p3_prove)
     else:
         blob, tables, init, pf = setup(params, case)
     st = G.statement(tables, pf, init, blob)
     want = [p3.to_mont(r) for r in G.witness(st)]
     rc_ext, rc_int, diag, m4 = R.tables_of()
+    assert m4 == int(blob.p2_m4)
     tab = p3.to_mont(np.concatenate([rc_ext.reshape(-1), rc_int, diag]))
     got = [np.zeros_like(w) for w in want]
     sh = st.shape

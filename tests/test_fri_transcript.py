@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import field_ref as FR
+import fri_param_sets as PS
 import oracle_lib as o
 import p2_chip_ref as R
 from p3_cases import P3_CASES, tables_of
@@ -179,6 +180,24 @@ def test_honest_statement(params, case):
         assert p3.verify(tables, pf, other, params=blob) != 0 != X.verify_transcript_statement(tables, pf, other, fp, blob)
 
 
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_reference_holds_under_parameter_sets(params, pset, case):
+    """the oracle and the numpy witness alone under every set of tests/fri_param_sets.py; the challenger replayed in plain
+    Python under the set's constants and matrix gives the captured samples"""
+    st, rows = PS.check_reference(X, X.verify_transcript_statement, pset, case, transcript=True)
+    blob, tables, iw, pf = PS.cpu_shard(pset, case, transcript=True)
+    sz = X.sizes(st)
+    assert [r.shape[0] for r in rows] == [1 << h for h in X.heights(st)]
+    assert int(rows[7][:, -1].sum()) == sz["state_rows"] == H.sizes(st.opn)["state_rows"] + sz["n_steps"]
+    assert st.plan.pow_bits == int(blob.pow_bits) >= 1 and st.shape.queries == PS.TRANSCRIPT_SHARDS[case][0]
+    rc, shape, ops, obs, smp = X.fri_transcript(tables, pf, iw, blob)
+    ops_c = [tuple(int(v) for v in p) for p in p3.from_mont(ops).reshape(-1, 2)]
+    consts = F.poseidon2_tables(blob)
+    assert consts[3] == int(blob.p2_m4)
+    sampled, _ = challenger_replay(ops_c, p3.from_mont(obs), consts)
+    assert rc == 0 and sampled == [int(v) for v in p3.from_mont(smp)]
+
+
 def test_fold_air_without_the_index_bus_is_unchanged(params):
     sh = F.Shape(9, 8, 1, 10)
     a, b_ = F.fri_fold_air(sh, coset_shift=31), F.fri_fold_air(sh, coset_shift=31, index_bus=False)
@@ -237,9 +256,12 @@ def test_new_entry_points_refuse_malformed_arguments(params):
 
 # ---------------------------------------------------------------------------------------------- what the statement adds; forgeries
 class Forge:
-    def __init__(self):
+    def __init__(self, pset=None):
         case, queries, init, more = FORGE
-        self.blob, self.tables, self.iw, self.pf = setup(o.oracle_set_params, case, queries, init, more)
+        if pset is None:
+            self.blob, self.tables, self.iw, self.pf = setup(o.oracle_set_params, case, queries, init, more)
+        else:
+            self.blob, self.tables, self.iw, self.pf = PS.cpu_shard(pset, case, transcript=True)
         self.st = X.statement(self.tables, self.pf, self.iw, self.blob)
         self.rows = X.witness(self.st)
         self.pubs = [FR.from_mont(v.astype(np.uint64)) for v in X.public_values(self.st)]
@@ -339,6 +361,22 @@ def test_forged_indices(forge):
     assert f.verdict(rows) == 8
 
 
+def test_forged_index_bit_under_the_other_matrix(params):
+    """the first two forgeries of test_forged_indices once more under m4_0: still refused, for the same reasons"""
+    f = Forge("m4_0")
+    bc = f.bc
+    assert int(f.blob.p2_m4) == 0 and f.verdict(f.rows) == 0
+    r = 3
+    rows = f.copy()
+    rows[5][r][bc.B + 1] ^= 1
+    assert f.bad_rows(rows, 5) == [r] and f.verdict(rows) == 3
+    rows = f.copy()
+    v = int(rows[5][r][bc.VALUE]) ^ 2
+    assert v < P
+    rows[5][r] = X.bits_row(r, v, f.st.shape.log_max, f.st.plan.pow_bits)
+    assert f.bad_rows(rows, 5) == [] and f.verdict(rows) == 8
+
+
 def test_forged_public_values(forge):
     """one word of a beta, of a commit-phase root, of the final polynomial and of the proof-of-work witness changed in the
     transcript's public values only: the row that absorbs or gives it no longer holds it"""
@@ -404,18 +442,23 @@ def step_words(plan):
     return np.array(out, dtype=np.uint32)
 
 
-@pytest.mark.parametrize("case", ["sp1_mixed_fib8_cubic4", "sp1_lookup_beside_plain", "sp1_same_height"])
+@pytest.mark.parametrize("case", ["sp1_mixed_fib8_cubic4", "sp1_lookup_beside_plain", "sp1_same_height"] + PS.ROW_IDS,
+                         ids=lambda c: c if isinstance(c, str) else PS.row_id(*c))
 def test_kernel_lanes_on_the_cpu(params, tmp_path, case):
     so = str(tmp_path / "libemul_fri_transcript.so")
     src = os.path.join(o.EMUL_DIR, "emul_fri_transcript.cpp")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(o.ROOT, "raiko_amd", "csrc"), "-o", so, src],
                    check=True, capture_output=True)
     lib = C.CDLL(so)
-    queries, init, more = FULL[case]
-    blob, tables, iw, pf = setup(params, case, queries, init, more)
+    if isinstance(case, tuple):            # a set of tests/fri_param_sets.py: fri_transcript_chain_lane<0>, other tables, another field
+        blob, tables, iw, pf = PS.cpu_shard(*case, transcript=True)
+    else:
+        queries, init, more = FULL[case]
+        blob, tables, iw, pf = setup(params, case, queries, init, more)
     st = X.statement(tables, pf, iw, blob)
     want = [p3.to_mont(r) for r in X.witness(st)]
     rc_ext, rc_int, diag, m4 = R.tables_of()
+    assert m4 == int(blob.p2_m4)
     tab = p3.to_mont(np.concatenate([rc_ext.reshape(-1), rc_int, diag]))
     sh = st.shape
     fold, trn, bits, state = (np.zeros_like(want[k]) for k in (0, 4, 5, 7))

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fri_param_sets as PS
 import oracle_lib as o
 from p3_cases import P3_CASES, init_of, tables_of
 from raiko_amd import _lib, hal, p3
@@ -15,12 +16,17 @@ from raiko_amd.hal import _ptr
 pytestmark = pytest.mark.gpu
 
 
-def shard(h, case, **more):
-    preset, over, _, _ = P3_CASES[case]
+def shard(h, case, pset=None, **more):
+    """the shard proof of `case` on the GPU, under the case's own parameters or under a set of tests/fri_param_sets.py"""
+    if pset is None:
+        preset, over, _, _ = P3_CASES[case]
+        tables, init = tables_of(case), init_of(case)
+    else:
+        preset, over = PS.shard_params(pset, case)
+        tables, init = PS.shard_tables(pset, case)
     over = dict(over, **more)
     blob = h.set_params(preset, **over)
     o.oracle_set_params(preset, **over)
-    tables, init = tables_of(case), init_of(case)
     pf = p3.prove(h, tables, init)
     return blob, tables, init, pf
 
@@ -38,6 +44,50 @@ def test_gpu_rows_equal_the_witness(case):
         for (buf, lh), w in zip(dev, want):
             got = buf.to_host().reshape(w.shape)
             assert np.array_equal(got, w), np.argwhere(got != w)[:8]
+    finally:
+        o.oracle_set_params()
+        h.close()
+
+
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_gpu_rows_under_parameter_sets(pset, case):
+    """fri_path_kernel<0> and <1>, the chip under other tables, the fold chain in another field, blow-ups 8 and 16"""
+    h = hal.HipHal(0)
+    try:
+        blob, tables, init, pf = shard(h, case, pset)
+        ctx = h.get_params()
+        assert (ctx.p2_m4, ctx.ext_w, ctx.blowup_log2) == (blob.p2_m4, blob.ext_w, blob.blowup_log2)
+        assert np.array_equal(pf, o.oracle_p3_prove(tables, init))
+        st = F.statement(tables, pf, init, blob)
+        want = [p3.to_mont(r) for r in F.witness(st)]
+        dev = F.device_tables(h, st)
+        assert [lh for _, lh in dev] == list(F.heights(st.shape))
+        for (buf, lh), w in zip(dev, want):
+            got = buf.to_host().reshape(w.shape)
+            assert np.array_equal(got, w), np.argwhere(got != w)[:8]
+    finally:
+        o.oracle_set_params()
+        h.close()
+
+
+@pytest.mark.parametrize("pset", PS.PROVE_SETS)
+def test_gpu_proves_the_statement_under_parameter_sets(pset):
+    """the statement proven from device tables at the case's own small query count, interpreted and compiled"""
+    h = hal.HipHal(0)
+    try:
+        blob, tables, init, pf = shard(h, PS.PROVE_CASE, pset)
+        st = F.statement(tables, pf, init, blob)
+        dev = F.device_tables(h, st)
+        host = F.host_tables(st)
+        got = F.prove(h, st, dev)
+        assert np.array_equal(got, o.oracle_p3_prove(host, st.init))
+        assert p3.verify(host, got, st.init, params=blob) == 0
+        assert F.verify_fri_statement(tables, pf, init, got, blob) == 0
+        for air in F.airs(st):
+            air.compile(h)
+        again = F.prove(h, st, dev)
+        assert np.array_equal(again, got)
+        assert p3.verify(host, again, st.init, params=blob) == 0 and F.verify_fri_statement(tables, pf, init, again, blob) == 0
     finally:
         o.oracle_set_params()
         h.close()

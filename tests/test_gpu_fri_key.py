@@ -6,7 +6,7 @@ goes through the same; bad arguments are refused with nothing written; and a sta
 points with a NULL root writes the unkeyed statement's words.
 
 Every GPU step runs in a child process of its own under a time limit of its own (this file run as a script: `python
-tests/test_gpu_fri_key.py STEP [CASE]`), once: a step that fails is not started again, and after a step that ended by a
+tests/test_gpu_fri_key.py STEP [CASE [SET]]`, SET a parameter set of tests/fri_param_sets.py), once: a step that fails is not started again, and after a step that ended by a
 signal or ran into its time limit no further step is started."""
 import os
 import subprocess
@@ -17,6 +17,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)          # run as a script: the package lies beside tests/
+import fri_param_sets as PS  # noqa: E402
 # gate_cubic     gate_table(6, 2, cubic=True) alone: the preprocessed tree at full height, a group of fewer than 8 cells
 # gate_two       gate_table(5, 9) beside gate_table(8, 17): two preprocessed matrices of different heights -- an injection
 #                inside the preprocessed tree --, groups of 9 and 17 cells (two and three sponge blocks)
@@ -28,16 +31,17 @@ OVER = dict(queries=7, pow_bits=2)
 _stop = []          # set by a step that faulted or hung: nothing more is started on the GPU
 
 
-def run_step(step, case="", limit=300):
+def run_step(step, case="", limit=300, pset=""):
+    """pset: a parameter set of tests/fri_param_sets.py, "" = SP1's preset under OVER"""
     if _stop:
         pytest.fail("not started: the step %s ended abnormally before" % _stop[0])
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case], cwd=ROOT, capture_output=True, text=True, timeout=limit)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case, pset], cwd=ROOT, capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired:
-        _stop.append(step + " " + case)
-        pytest.fail("%s %s ran into its time limit of %d s" % (step, case, limit))
+        _stop.append(" ".join((step, case, pset)))
+        pytest.fail("%s %s %s ran into its time limit of %d s" % (step, case, pset, limit))
     if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _stop.append(step + " " + case)
+        _stop.append(" ".join((step, case, pset)))
     assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
     return r.stdout
 
@@ -45,6 +49,11 @@ def run_step(step, case="", limit=300):
 @pytest.mark.parametrize("case", ROW_CASES)
 def test_gpu_rows_equal_the_witness(case):
     assert "rows ok" in run_step("rows", case)
+
+
+def test_gpu_keyed_rows_under_the_other_matrix():
+    """the keyed transcript statement (a fourth input batch, the key's root absorbed first) with the <0> kernels and the K2 chain"""
+    assert "rows ok" in run_step("rows", PS.KEYED_CASE, pset=PS.KEYED_SET)
 
 
 def test_gpu_proves_the_statement_bound_to_the_key():
@@ -87,6 +96,7 @@ def _keyed_shard(h, case, **more):
     over = dict(OVER, **more)
     blob = h.set_params(1, **over)
     o.oracle_set_params(1, **over)
+    assert h.get_params().p2_m4 == blob.p2_m4
     tables, init = _tables(case), p3.to_mont([167009, 10, 3])
     key = p3.setup(h, tables)
     try:
@@ -108,9 +118,10 @@ def _same(dev, want):
         assert np.array_equal(got, w), (k, np.argwhere(got != w)[:8])
 
 
-def step_rows(h, case):
+def step_rows(h, case, pset=""):
     from raiko_amd import fri_open as H, fri_reduce as G, fri_transcript as X, p3
-    blob, tables, ver, init, pf, root = _keyed_shard(h, case)
+    blob, tables, ver, init, pf, root = _keyed_shard(h, case, **(PS.PARAM_SETS[pset][1] if pset else {}))
+    assert not pset or blob.p2_m4 == PS.PARAM_SETS[pset][1]["p2_m4"]
     st = X.statement(ver, pf, init, blob, prep_root=root)
     opn, sh = st.opn, st.shape
     hts = {t.batch: t.B for t in opn.trees}
@@ -261,14 +272,14 @@ def step_unchanged(h, case):
     print("unchanged ok")
 
 
-def main(step, case):
+def main(step, case="", pset=""):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as o
     from raiko_amd import hal
     h = hal.HipHal(0)
     try:
-        {"rows": step_rows, "prove": step_prove, "elf": step_elf, "refuse": step_refuse, "unchanged": step_unchanged}[step](h, case)
+        {"rows": step_rows, "prove": step_prove, "elf": step_elf, "refuse": step_refuse, "unchanged": step_unchanged}[step](h, case, *([pset] if pset else []))
     finally:
         o.oracle_set_params()
         h.close()
@@ -276,4 +287,4 @@ def main(step, case):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:4]))

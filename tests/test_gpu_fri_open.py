@@ -4,7 +4,7 @@ oracle's over the witness; verify_open_statement accepts it; undersized or wrong
 written; the tables the chip, the reduce and the open statement share hold the same words whichever of them wrote the rows.
 
 Every GPU step runs in a child process of its own under a time limit of its own (this file run as a script: `python
-tests/test_gpu_fri_open.py STEP [CASE]`), once: a step that fails is not started again, and after a step that ended by a
+tests/test_gpu_fri_open.py STEP [CASE [SET]]`, SET a parameter set of tests/fri_param_sets.py), once: a step that fails is not started again, and after a step that ended by a
 signal or ran into its time limit no further step is started."""
 import os
 import subprocess
@@ -15,6 +15,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)          # run as a script: the package lies beside tests/
+import fri_param_sets as PS  # noqa: E402
 # the cases of tests/test_fri_open.py: groups of fewer than 8 cells, of exactly 8 and 16, of 13, 20, 28 and 301 (38 blocks
 # in one lane); two and three trees, a permutation tree shorter than the others; injections from the first step on; blow-up 2
 ROW_CASES = ["sp1_mixed_fib8_cubic4", "sp1_same_height", "sp1_lookup_beside_plain", "sp1_blow2_wide_k9", "sp1_width_301", "sp1_tiny_beside_tall",
@@ -22,16 +25,17 @@ ROW_CASES = ["sp1_mixed_fib8_cubic4", "sp1_same_height", "sp1_lookup_beside_plai
 _stop = []          # set by a step that faulted or hung: nothing more is started on the GPU
 
 
-def run_step(step, case="", limit=300):
+def run_step(step, case="", limit=300, pset=""):
+    """pset: a parameter set of tests/fri_param_sets.py, "" = the case's own parameters"""
     if _stop:
         pytest.fail("not started: the step %s ended abnormally before" % _stop[0])
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case], cwd=ROOT, capture_output=True, text=True, timeout=limit)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case, pset], cwd=ROOT, capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired:
-        _stop.append(step + " " + case)
-        pytest.fail("%s %s ran into its time limit of %d s" % (step, case, limit))
+        _stop.append(" ".join((step, case, pset)))
+        pytest.fail("%s %s %s ran into its time limit of %d s" % (step, case, pset, limit))
     if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _stop.append(step + " " + case)
+        _stop.append(" ".join((step, case, pset)))
     assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
     return r.stdout
 
@@ -39,6 +43,18 @@ def run_step(step, case="", limit=300):
 @pytest.mark.parametrize("case", ROW_CASES)
 def test_gpu_rows_equal_the_witness(case):
     assert "rows ok" in run_step("rows", case)
+
+
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_gpu_rows_under_parameter_sets(pset, case):
+    """fri_path_kernel, fri_open_sponge_kernel and fri_open_ipath_kernel <0> and <1>, the chips under other tables, another field, blow-ups 8 and 16"""
+    assert "rows ok" in run_step("rows", case, pset=pset)
+
+
+@pytest.mark.parametrize("pset", PS.PROVE_SETS)
+def test_gpu_proves_the_statement_under_parameter_sets(pset):
+    """the statement proven from device tables at the case's own small query count, interpreted and compiled"""
+    assert "proof ok" in run_step("prove", PS.PROVE_CASE, pset=pset)
 
 
 def test_gpu_proves_the_statement_from_device_tables():
@@ -55,23 +71,30 @@ def test_gpu_shared_tables_are_the_same_words_in_every_statement():
 
 
 # ---------------------------------------------------------------------------------------------- the steps (child process)
-def _shard(h, case, **more):
+def _shard(h, case, pset="", **more):
+    import fri_param_sets as PS
     import oracle_lib as o
     from p3_cases import P3_CASES, init_of, tables_of
     from raiko_amd import p3
-    preset, over, _, _ = P3_CASES[case]
+    if pset:
+        preset, over = PS.shard_params(pset, case)
+        tables, init = PS.shard_tables(pset, case)
+    else:
+        preset, over, _, _ = P3_CASES[case]
+        tables, init = tables_of(case), init_of(case)
     over = dict(over, **more)
     blob = h.set_params(preset, **over)
     o.oracle_set_params(preset, **over)
-    tables, init = tables_of(case), init_of(case)
+    got = h.get_params()
+    assert (got.p2_m4, got.ext_w, got.blowup_log2) == (blob.p2_m4, blob.ext_w, blob.blowup_log2)
     return blob, tables, init, p3.prove(h, tables, init)
 
 
-def step_rows(h, case):
+def step_rows(h, case, pset=""):
     import numpy as np
     import oracle_lib as o
     from raiko_amd import fri_open as H, p3
-    blob, tables, init, pf = _shard(h, case)
+    blob, tables, init, pf = _shard(h, case, pset=pset)
     assert np.array_equal(pf, o.oracle_p3_prove(tables, init))
     st = H.statement(tables, pf, init, blob)
     want = [p3.to_mont(r) for r in H.witness(st)]
@@ -83,14 +106,15 @@ def step_rows(h, case):
     print("rows ok")
 
 
-def step_prove(h, case):
+def step_prove(h, case, pset=""):
+    """pset: under a parameter set, at the case's own query count; else SP1's 100 queries"""
     import numpy as np
     import oracle_lib as o
     from raiko_amd import fri_open as H, p3
-    blob, tables, init, pf = _shard(h, case, queries=100)
+    blob, tables, init, pf = _shard(h, case, pset=pset) if pset else _shard(h, case, queries=100)
     st = H.statement(tables, pf, init, blob)
     sz = H.sizes(st)
-    assert sz["path_rows"] >= 1 << 12 and sz["ipath_rows"] == 100 * 24 and sz["state_rows"] == 100 * 4
+    assert pset or sz["path_rows"] >= 1 << 12 and sz["ipath_rows"] == 100 * 24 and sz["state_rows"] == 100 * 4
     dev = H.device_tables(h, st)
     host = H.host_tables(st)
     for (buf, lh), t in zip(dev, host):
@@ -101,7 +125,9 @@ def step_prove(h, case):
     assert H.verify_open_statement(tables, pf, init, got, blob) == 0
     for air in H.airs(st):
         air.compile(h)
-    assert np.array_equal(H.prove(h, st, dev), got)
+    again = H.prove(h, st, dev)
+    assert np.array_equal(again, got) and p3.verify(host, again, st.init, params=blob) == 0
+    assert H.verify_open_statement(tables, pf, init, again, blob) == 0
     assert np.array_equal(H.prove(h, st), got)                 # rows written anew
     print("proof ok")
 
@@ -180,14 +206,14 @@ def step_shared(h, case):
     print("shared ok")
 
 
-def main(step, case):
+def main(step, case="", pset=""):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as o
     from raiko_amd import hal
     h = hal.HipHal(0)
     try:
-        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse, "shared": step_shared}[step](h, case)
+        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse, "shared": step_shared}[step](h, case, *([pset] if pset else []))
     finally:
         o.oracle_set_params()
         h.close()
@@ -195,4 +221,4 @@ def main(step, case):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:4]))

@@ -5,7 +5,7 @@ witness; verify_transcript_statement accepts it; undersized, null, ill-planned o
 nothing written; the six tables shared with the open statement hold the same words whichever call wrote them.
 
 Every GPU step runs in a child process of its own under a time limit of its own (this file run as a script: `python
-tests/test_gpu_fri_transcript.py STEP [CASE]`), once: a step that fails is not started again, and after a step that ended
+tests/test_gpu_fri_transcript.py STEP [CASE [SET]]`, SET a parameter set of tests/fri_param_sets.py), once: a step that fails is not started again, and after a step that ended
 by a signal or ran into its time limit no further step is started."""
 import os
 import subprocess
@@ -16,6 +16,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)          # run as a script: the package lies beside tests/
+import fri_param_sets as PS  # noqa: E402
 # the cases of tests/test_fri_transcript.py: (queries, init, further overrides) per case of tests/test_gpu_fri_open.py --
 # 7, 8 and 100 queries (the indices end with the proof-of-work block; one duplex that absorbs nothing; twelve), with and
 # without a permutation batch, an empty init, pow_bits = 0
@@ -25,16 +28,17 @@ ROW_CASES = {"sp1_mixed_fib8_cubic4": (7, [5, 6, 7], {}), "sp1_same_height": (10
 _stop = []          # set by a step that faulted or hung: nothing more is started on the GPU
 
 
-def run_step(step, case="", limit=300):
+def run_step(step, case="", limit=300, pset=""):
+    """pset: a parameter set of tests/fri_param_sets.py, "" = the case's own parameters"""
     if _stop:
         pytest.fail("not started: the step %s ended abnormally before" % _stop[0])
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case], cwd=ROOT, capture_output=True, text=True, timeout=limit)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), step, case, pset], cwd=ROOT, capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired:
-        _stop.append(step + " " + case)
-        pytest.fail("%s %s ran into its time limit of %d s" % (step, case, limit))
+        _stop.append(" ".join((step, case, pset)))
+        pytest.fail("%s %s %s ran into its time limit of %d s" % (step, case, pset, limit))
     if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _stop.append(step + " " + case)
+        _stop.append(" ".join((step, case, pset)))
     assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
     return r.stdout
 
@@ -42,6 +46,19 @@ def run_step(step, case="", limit=300):
 @pytest.mark.parametrize("case", list(ROW_CASES))
 def test_gpu_rows_equal_the_witness(case):
     assert "rows ok" in run_step("rows", case)
+
+
+@pytest.mark.parametrize("pset,case", PS.ROW_IDS, ids=[PS.row_id(*x) for x in PS.ROW_IDS])
+def test_gpu_rows_under_parameter_sets(pset, case):
+    """every two-instantiation kernel of csrc/fri_tables.hip under both external matrices -- fri_path_kernel, fri_open_sponge_kernel,
+    fri_open_ipath_kernel <0> and <1>, fri_transcript_chain_kernel<K2> and <K3> --, other tables, another field, blow-ups 8 and 16"""
+    assert "rows ok" in run_step("rows", case, pset=pset)
+
+
+@pytest.mark.parametrize("pset", PS.PROVE_SETS)
+def test_gpu_proves_the_statement_under_parameter_sets(pset):
+    """the statement proven from device tables at the case's own small query count, interpreted and compiled"""
+    assert "proof ok" in run_step("prove", PS.PROVE_CASE, pset=pset)
 
 
 def test_gpu_proves_the_statement_from_device_tables():
@@ -57,26 +74,38 @@ def test_gpu_shared_tables_are_the_same_words_in_both_statements():
     assert "shared ok" in run_step("shared", "sp1_mixed_fib8_cubic4")
 
 
+def test_gpu_shared_tables_are_the_same_words_under_the_other_matrix():
+    assert "shared ok" in run_step("shared", PS.SHARED_CASE, pset=PS.SHARED_SET)
+
+
 # ---------------------------------------------------------------------------------------------- the steps (child process)
-def _shard(h, case, queries=None, init=None, **more):
+def _shard(h, case, queries=None, init=None, pset="", **more):
     import numpy as np
     import oracle_lib as o
     from p3_cases import P3_CASES, tables_of
     from raiko_amd import p3
-    q, i, m = ROW_CASES[case]
-    preset, over, _, _ = P3_CASES[case]
-    over = dict(over, queries=q if queries is None else queries, **dict(m, **more))
+    if pset:
+        assert queries is None and init is None
+        preset, over = PS.shard_params(pset, case, transcript=True)
+        tables, iw = PS.shard_tables(pset, case, transcript=True)
+        over = dict(over, **more)
+    else:
+        q, i, m = ROW_CASES[case]
+        preset, over, _, _ = P3_CASES[case]
+        over = dict(over, queries=q if queries is None else queries, **dict(m, **more))
+        tables, iw = tables_of(case), p3.to_mont(np.array(i if init is None else init, dtype=np.uint64))
     blob = h.set_params(preset, **over)
     o.oracle_set_params(preset, **over)
-    tables, iw = tables_of(case), p3.to_mont(np.array(i if init is None else init, dtype=np.uint64))
+    got = h.get_params()
+    assert (got.p2_m4, got.ext_w, got.blowup_log2) == (blob.p2_m4, blob.ext_w, blob.blowup_log2)
     return blob, tables, iw, p3.prove(h, tables, iw), (preset, over)
 
 
-def step_rows(h, case):
+def step_rows(h, case, pset=""):
     import numpy as np
     import oracle_lib as o
     from raiko_amd import fri_transcript as X, p3
-    blob, tables, init, pf, _ = _shard(h, case)
+    blob, tables, init, pf, _ = _shard(h, case, pset=pset)
     assert np.array_equal(pf, o.oracle_p3_prove(tables, init))
     st = X.statement(tables, pf, init, blob)
     want = [p3.to_mont(r) for r in X.witness(st)]
@@ -88,14 +117,15 @@ def step_rows(h, case):
     print("rows ok")
 
 
-def step_prove(h, case):
+def step_prove(h, case, pset=""):
+    """pset: under a parameter set, at the shard's own query count and with compiled AIRs too; else SP1's 100 queries"""
     import numpy as np
     import oracle_lib as o
     from raiko_amd import fri_transcript as X, p3
-    blob, tables, init, pf, _ = _shard(h, case, queries=100)
+    blob, tables, init, pf, _ = _shard(h, case, pset=pset) if pset else _shard(h, case, queries=100)
     st = X.statement(tables, pf, init, blob)
     sz = X.sizes(st)
-    assert sz["path_rows"] >= 1 << 12 and sz["bits_rows"] == 101 and sz["state_rows"] == 100 * 4 + sz["n_steps"] and sz["n_steps"] < 100
+    assert pset or sz["path_rows"] >= 1 << 12 and sz["bits_rows"] == 101 and sz["state_rows"] == 100 * 4 + sz["n_steps"] and sz["n_steps"] < 100
     dev = X.device_tables(h, st)
     host = X.host_tables(st)
     for (buf, lh), t in zip(dev, host):
@@ -104,6 +134,12 @@ def step_prove(h, case):
     assert np.array_equal(got, o.oracle_p3_prove(host, st.init))
     assert p3.verify(host, got, st.init, params=blob) == 0
     assert X.verify_transcript_statement(tables, pf, init, got, blob) == 0
+    if pset:
+        for air in X.airs(st):
+            air.compile(h)
+        again = X.prove(h, st, dev)
+        assert np.array_equal(again, got) and p3.verify(host, again, st.init, params=blob) == 0
+        assert X.verify_transcript_statement(tables, pf, init, again, blob) == 0
     assert np.array_equal(X.prove(h, st), got)                 # rows written anew
     print("proof ok")
 
@@ -166,13 +202,13 @@ def step_refuse(h, case):
     print("refusals ok")
 
 
-def step_shared(h, case):
+def step_shared(h, case, pset=""):
     """the rows of the open and the transcript statement written one after the other on one context: what they share is
     written by one stage of the library (csrc/fri_tables.hip), so it is the same words in both -- compared table against
     table, without the numpy witness"""
     import numpy as np
     from raiko_amd import fri_open as H, fri_transcript as X
-    blob, tables, init, pf, _ = _shard(h, case)
+    blob, tables, init, pf, _ = _shard(h, case, pset=pset)
     st = X.statement(tables, pf, init, blob)
     rows = lambda names, dev: {n: b.to_host().reshape(1 << lh, -1) for n, (b, lh) in zip(names, dev)}
     opn = rows(H.TABLE_NAMES, H.device_tables(h, st.opn))
@@ -190,14 +226,14 @@ def step_shared(h, case):
     print("shared ok")
 
 
-def main(step, case):
+def main(step, case="", pset=""):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as o
     from raiko_amd import hal
     h = hal.HipHal(0)
     try:
-        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse, "shared": step_shared}[step](h, case)
+        {"rows": step_rows, "prove": step_prove, "refuse": step_refuse, "shared": step_shared}[step](h, case, *([pset] if pset else []))
     finally:
         o.oracle_set_params()
         h.close()
@@ -205,4 +241,4 @@ def main(step, case):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:4]))
