@@ -758,6 +758,36 @@ int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
                                  uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
                                  uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
                                  uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows);
+/* THE LINK BETWEEN SHARD MEMORIES (raiko_amd/rv32link.py; the first of the designs a boundary table admits: a digest).
+ * With the link on, a real row of the memory table also SENDS (WL, WH, I_LO, I_HI, F_LO, F_HI) on bus RK_RV32LINK_BUS,
+ * which no table receives, and the table carries 8 public values no constraint reads: the digest of the shard's JOURNAL,
+ * one (word address, INIT, FINAL) per touched word, ascending.  The verifier is handed the journal, recomputes the digest
+ * (rk_rv32mem_journal_root) against the public values, adds the receiving side itself (rk_p3_verify_claims with the
+ * journal's limb tuples as receive claims) and replays the journals shard after shard from the ELF's memory image
+ * (rk_exec_memory_image): INIT of a word must be what the image holds, then the image's word becomes FINAL.  Public values
+ * are observed before the permutation challenges are sampled, so the journal is fixed (up to a collision of the digest)
+ * before the challenges exist, and the LogUp identity makes the multiset of real boundary rows the journal.  STILL FREE:
+ * what an ecall writes and the a0 it leaves.  The verifier's work is linear in the touched words.  The rk_p3_fri_*
+ * captures of a linked proof replay rk_p3_verify_key and stop at reason 8: the FRI statements do not cover it.
+ * The digest: the rk_mmcs_commit root of the memory_rows x RK_RV32LINK_TUPLE row-major Montgomery matrix of the limb
+ * tuples, rows of zeros past the real ones.
+ * rk_exec_memory_image: every PT_LOAD segment's file bytes, as the executor's loader stores them, merged into (word
+ * address, word) pairs in ascending address order: a later segment overwrites an earlier one byte by byte, bytes of a
+ * word outside every segment's file bytes are 0.  RK_ERR_CAPACITY with *n set when more than `capacity` words.  Host only.
+ * rk_rv32mem_journal_device: from a finished device memory table (memory_rows x RK_RV32MEM_MEMORY_COLS, Montgomery) the
+ * journal (canonical, 3 words per real row, in row order; capacity memory_rows rows), the link matrix (memory_rows x
+ * RK_RV32LINK_TUPLE, Montgomery), the tree over it (d_nodes: 2 * memory_rows * 8 words, as rk_mmcs_commit) with its root
+ * in h_root, and the count of real rows in *n_real.  RK_ERR_INVALID before any launch for NULL buffers or memory_rows
+ * not a power of two >= 2; RK_ERR_INVALID after the run for a table whose real rows are not a prefix or which holds a
+ * limb that is no 16-bit value (a 14-bit WL).
+ * rk_rv32mem_journal_root: the same digest on the host from a journal of n rows (canonical) at table height
+ * 2^log_rows.  RK_ERR_INVALID for n > 2^log_rows, an address >= 2^30 or addresses that do not strictly ascend. */
+#define RK_RV32LINK_BUS 11
+#define RK_RV32LINK_TUPLE 6
+int rk_exec_memory_image(const uint8_t* elf, size_t elf_bytes, uint32_t* out_addr, uint32_t* out_words, size_t capacity, size_t* n);
+int rk_rv32mem_journal_device(rk_ctx* ctx, const uint32_t* d_memory, size_t memory_rows, uint32_t* d_journal, uint32_t* d_link,
+                              uint32_t* d_nodes, size_t* n_real, uint32_t h_root[8]);
+int rk_rv32mem_journal_root(const rk_params* params, const uint32_t* journal, size_t n, uint32_t log_rows, uint32_t root[8]);
 const char* rk_exec_error(const rk_exec* ex);
 int rk_exec_free(rk_exec* ex);
 
@@ -944,6 +974,28 @@ int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_
  * 5 input opening, 6 commit-phase opening, 7 final polynomial, 8 the cumulative sums of the lookups do not cancel. */
 int rk_p3_verify(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* init_words, size_t n_init,
                  const uint32_t* proof, size_t proof_words);
+/* CLAIMS: interactions the VERIFIER adds to the lookup argument of a proof.  A claim is n tuples of tuple_len Montgomery
+ * words on one bus, each with multiplicity 1 (repeats allowed), sent (sign +1) or received (sign -1) by no table of the
+ * proof.  rk_p3_verify_claims is rk_p3_verify (prep_root NULL) / rk_p3_verify_key with
+ *     sum of the tables' cumulative sums + sum over the claims of sign / rlc(tuple) == 0
+ * in place of a sum of zero, rlc = chal[0] + chal[1] bus + sum_j chal[2 + j] x_j under the proof's own permutation
+ * challenges.  Reason 8: any other total, or a tuple whose rlc is zero.  RK_ERR_INVALID: a tuple longer than the tables'
+ * challenges cover (4 (tuple_len + 2) > the largest n_chal of the tables), a non-canonical word, a sign that is not +-1,
+ * NULL tuples with n != 0, or claims against tables without lookups.  n_claims == 0: exactly rk_p3_verify / rk_p3_verify_key.
+ * THE CALLER'S DUTY: the challenges must not have been chosen knowing the tuples.  The tuples have to be bound into
+ * init_words or into a public value of a table (both are observed before the challenges are sampled), e.g. by a digest
+ * the caller recomputes; otherwise a prover picks the tuples after the challenges and the check is UNSOUND.  The function
+ * does not do this itself. */
+typedef struct {
+    uint32_t bus;
+    uint32_t tuple_len;
+    int32_t sign;                  /* +1 the claim sends, -1 it receives */
+    const uint32_t* tuples;        /* n x tuple_len Montgomery words, host */
+    size_t n;
+} rk_p3_claim;
+int rk_p3_verify_claims(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root,
+                        const uint32_t* init_words, size_t n_init, const uint32_t* proof, size_t proof_words,
+                        const rk_p3_claim* claims, uint32_t n_claims);
 /* rk_p3_verify that also hands back EVERY Poseidon2 permutation the check performed -- the transcript's, the leaf sponges
  * over the opened rows, the Merkle compressions, the proof of work's -- as input states (p2_width Montgomery words each,
  * in the order they happened): what the Poseidon2 chip of a recursion / compress layer has to prove for this proof
@@ -1198,6 +1250,11 @@ int rk_p3_prove_shards(const rk_p3_session_opts* opts, rk_p3_shard* shards, size
  * (*failed_index = that shard).  A key over tables without preprocessed columns gives rk_p3_prove_shards' exact proofs. */
 int rk_p3_prove_shards_key(const rk_p3_session_opts* opts, const rk_p3_key* const* keys, rk_p3_shard* shards, size_t n,
                            size_t* failed_index);
+/* rk_p3_prove_shards / rk_p3_prove_shards_key (keys NULL: the former) whose verifier threads call rk_p3_verify_claims:
+ * claims[i] / n_claims[i] are shard i's claims (see rk_p3_verify_claims, and the caller's duty there).  claims == NULL
+ * behaves as rk_p3_prove_shards_key; with claims, n_claims must not be NULL.  rk_p3_shard keeps its layout. */
+int rk_p3_prove_shards_claims(const rk_p3_session_opts* opts, const rk_p3_key* const* keys, rk_p3_shard* shards,
+                              const rk_p3_claim* const* claims, const uint32_t* n_claims, size_t n, size_t* failed_index);
 /* wall-clock per stage of the last rk_p3_prove on this ctx, milliseconds (the stream is drained at every boundary) */
 typedef struct { float lde, commit, quotient, open, fri, query, total, perm /* permutation traces + their LDE */; } rk_p3_timing;
 int rk_p3_last_timing(rk_ctx* ctx, rk_p3_timing* out);

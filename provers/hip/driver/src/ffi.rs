@@ -94,6 +94,8 @@ pub const RK_RV32MEM_PROGRAM_PREP_COLS: u32 = 48;
 pub const RK_RV32MEM_MEMOP_COLS: u32 = 64;
 pub const RK_RV32MEM_MEMORY_COLS: u32 = 13;
 pub const RK_RV32MEM_MIN_LOG_ROWS: u32 = 1;
+pub const RK_RV32LINK_BUS: u32 = 11;
+pub const RK_RV32LINK_TUPLE: u32 = 6;
 
 #[repr(C)]
 pub struct rk_air {
@@ -326,6 +328,16 @@ pub struct rk_p3_table {
     pub public_values: *const u32,
     pub n_public: u32,
     pub on_device: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct rk_p3_claim {
+    pub bus: u32,
+    pub tuple_len: u32,
+    pub sign: i32,
+    pub tuples: *const u32,
+    pub n: usize,
 }
 
 #[repr(C)]
@@ -613,6 +625,9 @@ extern "C" {
     pub fn rk_exec_rv32mem_sizes(ex: *const rk_exec, index: u32, memop_rows: *mut usize, memory_rows: *mut usize) -> c_int;
     pub fn rk_rv32mem_prep_device(ctx: *mut rk_ctx, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, words: *const u32, n_words: usize, d_program: *mut u32, program_rows: usize, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
     pub fn rk_exec_rv32mem_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize, d_memop: *mut u32, memop_rows: usize, d_memory: *mut u32, memory_rows: usize) -> c_int;
+    pub fn rk_exec_memory_image(elf: *const u8, elf_bytes: usize, out_addr: *mut u32, out_words: *mut u32, capacity: usize, n: *mut usize) -> c_int;
+    pub fn rk_rv32mem_journal_device(ctx: *mut rk_ctx, d_memory: *const u32, memory_rows: usize, d_journal: *mut u32, d_link: *mut u32, d_nodes: *mut u32, n_real: *mut usize, h_root: *mut u32) -> c_int;
+    pub fn rk_rv32mem_journal_root(params: *const rk_params, journal: *const u32, n: usize, log_rows: u32, root: *mut u32) -> c_int;
     pub fn rk_exec_error(ex: *const rk_exec) -> *const c_char;
     pub fn rk_exec_free(ex: *mut rk_exec) -> c_int;
     pub fn rk_air_create(steps: *const rk_air_step, n_steps: usize, width: u32, n_public: u32, out: *mut *mut rk_air) -> c_int;
@@ -636,6 +651,7 @@ extern "C" {
     pub fn rk_p3_proof_bound_words_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
     pub fn rk_p3_verify_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize) -> c_int;
     pub fn rk_p3_verify(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize) -> c_int;
+    pub fn rk_p3_verify_claims(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, claims: *const rk_p3_claim, n_claims: u32) -> c_int;
     pub fn rk_p3_verify_hashes(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, states: *mut u32, capacity_permutations: usize, n_permutations: *mut usize) -> c_int;
     pub fn rk_p3_fri_openings(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, shape: *mut u32, publics: *mut u32, publics_capacity: usize, records: *mut u32, records_capacity: usize, publics_words: *mut usize, records_words: *mut usize) -> c_int;
     pub fn rk_p3_verify_hashes_key(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32, prep_root: *const u32, init_words: *const u32, n_init: usize, proof: *const u32, proof_words: usize, states: *mut u32, capacity_permutations: usize, n_permutations: *mut usize) -> c_int;
@@ -657,6 +673,7 @@ extern "C" {
     pub fn rk_p3_proof_bound_words(params: *const rk_params, tables: *const rk_p3_table, n_tables: u32) -> usize;
     pub fn rk_p3_prove_shards(opts: *const rk_p3_session_opts, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
     pub fn rk_p3_prove_shards_key(opts: *const rk_p3_session_opts, keys: *const *const rk_p3_key, shards: *mut rk_p3_shard, n: usize, failed_index: *mut usize) -> c_int;
+    pub fn rk_p3_prove_shards_claims(opts: *const rk_p3_session_opts, keys: *const *const rk_p3_key, shards: *mut rk_p3_shard, claims: *const *const rk_p3_claim, n_claims: *const u32, n: usize, failed_index: *mut usize) -> c_int;
     pub fn rk_p3_last_timing(ctx: *mut rk_ctx, out: *mut rk_p3_timing) -> c_int;
     pub fn rk_last_timing(ctx: *mut rk_ctx, out: *mut rk_timing) -> c_int;
     pub fn rk_set_kernel_timing(ctx: *mut rk_ctx, enabled: c_int) -> c_int;

@@ -171,6 +171,10 @@ class RkP3Shard(C.Structure):
                 ("h_proof", u32p), ("capacity_words", C.c_size_t), ("proof_words", C.c_size_t)]
 
 
+class RkP3Claim(C.Structure):
+    _fields_ = [("bus", C.c_uint32), ("tuple_len", C.c_uint32), ("sign", C.c_int32), ("tuples", u32p), ("n", C.c_size_t)]
+
+
 class RkP3SessionOpts(C.Structure):
     _fields_ = [("device", C.c_int), ("batch", C.c_int), ("verify", C.c_int), ("devices", C.POINTER(C.c_int)), ("n_devices", C.c_int),
                 ("params", C.POINTER(RkParams))]
@@ -301,6 +305,10 @@ SYMBOLS = {
     "rk_exec_rv32mem_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rk_exec_memory_image": (C.c_int, [C.c_char_p, C.c_size_t, u32p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rk_rv32mem_journal_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_size_t), u32p]),
+    "rk_rv32mem_journal_root": (C.c_int, [C.POINTER(RkParams), u32p, C.c_size_t, C.c_uint32, u32p]),
     "rk_exec_error": (C.c_char_p, [C.c_void_p]),
     "rk_exec_free": (C.c_int, [C.c_void_p]),
     "rk_program_create": (C.c_int, [_vp, _sz, _u32, C.POINTER(RkTaps), C.POINTER(_vp)]),
@@ -321,6 +329,7 @@ SYMBOLS = {
     "rk_p3_prove_key": (C.c_int, [_vp, _vp, C.POINTER(RkP3Table), _u32, u32p, _sz, u32p, _sz, C.POINTER(_sz)]),
     "rk_p3_proof_bound_words_key": (_sz, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32]),
     "rk_p3_verify_key": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz]),
+    "rk_p3_verify_claims": (C.c_int, [C.POINTER(RkParams), C.POINTER(RkP3Table), _u32, u32p, u32p, _sz, u32p, _sz, C.POINTER(RkP3Claim), _u32]),
     "rk_p2_chip_width": (_u32, [C.POINTER(RkParams)]),
     "rk_p2_chip_air": (C.c_int, [C.POINTER(RkParams), _u32, C.POINTER(_vp)]),
     "rk_p2_chip_air_ex": (C.c_int, [C.POINTER(RkParams), _u32, _u32, C.POINTER(_vp)]),
@@ -363,6 +372,8 @@ SYMBOLS = {
     "rk_p3_last_timing": (C.c_int, [_vp, C.POINTER(RkP3Timing)]),
     "rk_p3_prove_shards": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
     "rk_p3_prove_shards_key": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(_vp), C.POINTER(RkP3Shard), _sz, C.POINTER(_sz)]),
+    "rk_p3_prove_shards_claims": (C.c_int, [C.POINTER(RkP3SessionOpts), C.POINTER(_vp), C.POINTER(RkP3Shard),
+                                            C.POINTER(C.POINTER(RkP3Claim)), u32p, _sz, C.POINTER(_sz)]),
     "rk_comm_unique_id": (C.c_int, [C.c_char_p]),
     "rk_comm_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "rk_comm_destroy": (C.c_int, [_vp]),

@@ -1,6 +1,7 @@
-// rk_exec_program_image (include/raiko_hip.h): the executable image of an ELF, listed with the loader's own walk of the
-// program headers (elf_image.hpp).  Host only, plain C++.
+// rk_exec_program_image and rk_exec_memory_image (include/raiko_hip.h): the executable image of an ELF and its whole
+// memory image, listed with the loader's own walk of the program headers (elf_image.hpp).  Host only, plain C++.
 #include <algorithm>
+#include <map>
 #include <new>
 #include <vector>
 
@@ -61,6 +62,37 @@ int rk_exec_program_image(const uint8_t* elf, size_t elf_bytes, uint32_t* seg_va
             seg_words[k] = (uint32_t)image[k].words.size();
             std::copy(image[k].words.begin(), image[k].words.end(), words + at);
         }
+        return RK_OK;
+    } catch (const std::bad_alloc&) {
+        return RK_ERR_NOMEM;
+    } catch (...) {
+        return RK_ERR_INTERNAL;
+    }
+}
+
+// the memory image: every word that holds a file byte of a PT_LOAD segment, the bytes stored in program-header order as
+// the executor's loader stores them (a later segment overwrites an earlier one), the word's other bytes 0
+int rk_exec_memory_image(const uint8_t* elf, size_t elf_bytes, uint32_t* out_addr, uint32_t* out_words, size_t capacity, size_t* n) {
+    try {
+        if (!elf || !n) return RK_ERR_INVALID;
+        *n = 0;
+        std::map<uint32_t, uint32_t> image;   // word address -> word, ascending
+        std::string err;
+        uint32_t entry = 0;
+        const int st = rk_elf::walk_load_segments(elf, elf_bytes, &entry, err, [&](uint32_t off, uint32_t vaddr, uint32_t filesz, uint32_t) {
+            for (uint32_t b = 0; b < filesz; b++) {
+                const uint32_t a = vaddr + b, sh = 8 * (a & 3);
+                uint32_t& w = image[a >> 2];
+                w = (w & ~(0xffu << sh)) | (uint32_t)elf[off + b] << sh;
+            }
+            return (int)RK_OK;
+        });
+        if (st != RK_OK) return st;
+        *n = image.size();
+        if (image.size() > capacity) return RK_ERR_CAPACITY;
+        if (!image.empty() && (!out_addr || !out_words)) return RK_ERR_INVALID;
+        size_t k = 0;
+        for (const auto& kv : image) out_addr[k] = kv.first, out_words[k++] = kv.second;
         return RK_OK;
     } catch (const std::bad_alloc&) {
         return RK_ERR_NOMEM;

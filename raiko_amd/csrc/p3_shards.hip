@@ -1,4 +1,4 @@
-// rk_p3_prove_shards / rk_p3_prove_shards_key (include/raiko_hip.h): uni-stark proofs of many shards in flight on one or
+// rk_p3_prove_shards / rk_p3_prove_shards_key / rk_p3_prove_shards_claims (include/raiko_hip.h): uni-stark proofs of many shards in flight on one or
 // several devices.  Per device a pool of prover contexts and an uploader, kept between calls; one feeder thread per
 // device stages the traces ahead of the provers, host threads verify what is proven.  The proofs themselves are
 // rk_p3_prove's / rk_p3_prove_key's (p3.hip), the checks rk_p3_verify's / rk_p3_verify_key's (p3_verify.hip): nothing else
@@ -62,9 +62,11 @@ struct Staged {
 };
 
 // caller_keys NULL: rk_p3_prove_shards; otherwise one key per device in the caller's order (rk_p3_prove_shards_key)
+// claims NULL: none; otherwise claims[i] / n_claims[i] are what shard i's verifier adds (rk_p3_prove_shards_claims)
 int p3_prove_shards(const rk_p3_session_opts* opts, const rk_p3_key* const* caller_keys, rk_p3_shard* shards, size_t n,
-                    size_t* failed_index) {
+                    size_t* failed_index, const rk_p3_claim* const* claims = nullptr, const uint32_t* n_claims = nullptr) {
     if (failed_index) *failed_index = (size_t)-1;
+    if (claims && !n_claims) return RK_ERR_INVALID;
     if (!opts || (n && !shards) || !rk::inflight::opts_ok(opts->batch, 0, opts->n_devices, opts->devices)) return RK_ERR_INVALID;
     if (n == 0) return RK_OK;
     for (size_t i = 0; !caller_keys && i < n; i++)   // no key: tables with preprocessed columns are rk_p3_prove_shards_key's
@@ -157,6 +159,9 @@ int p3_prove_shards(const rk_p3_session_opts* opts, const rk_p3_key* const* call
     // host work (~40 ms for 100 queries)
     calls.verify = [&](size_t i) -> int {
         const rk_p3_shard& sh = shards[i];
+        if (claims)   // a NULL root is the unkeyed check there
+            return rk_p3_verify_claims(&par, sh.tables, sh.n_tables, prep_root, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words, claims[i],
+                                       n_claims[i]);
         return caller_keys ? rk_p3_verify_key(&par, sh.tables, sh.n_tables, prep_root, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words)
                            : rk_p3_verify(&par, sh.tables, sh.n_tables, sh.init_words, sh.n_init, sh.h_proof, sh.proof_words);
     };
@@ -195,6 +200,12 @@ int rk_p3_prove_shards_key(const rk_p3_session_opts* opts, const rk_p3_key* cons
                            size_t* failed_index) {
     RK_GUARD_BEGIN
     return p3_prove_shards(opts, keys, shards, n, failed_index);
+    RK_GUARD_END
+}
+int rk_p3_prove_shards_claims(const rk_p3_session_opts* opts, const rk_p3_key* const* keys, rk_p3_shard* shards,
+                              const rk_p3_claim* const* claims, const uint32_t* n_claims, size_t n, size_t* failed_index) {
+    RK_GUARD_BEGIN
+    return p3_prove_shards(opts, keys, shards, n, failed_index, claims, n_claims);
     RK_GUARD_END
 }
 

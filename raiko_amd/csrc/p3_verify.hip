@@ -14,7 +14,7 @@
 //                      openings, the fold rounds
 // Verdicts: 0 accept; 1 malformed / short / trailing / non-canonical word, 2 shape mismatch, 3 constraint identity
 // (OodEvaluationMismatch), 4 proof of work, 5 input opening, 6 commit-phase opening, 7 final polynomial, 8 the lookups'
-// cumulative sums do not cancel.  The total length is checked before any query: a proof with trailing words AND a
+// cumulative sums do not cancel (rk_p3_verify_claims: with the caller's claims added, see add_claims).  The total length is checked before any query: a proof with trailing words AND a
 // defect inside a query is refused with 1.
 #include "p3_host.hpp"
 
@@ -54,6 +54,37 @@ Selectors selectors_at(const Ext& x, unsigned log_n, uint32_t root27m, uint32_t 
     s.is_trans = bb::sub(x, bb::ext_from(g_inv));
     s.inv_zeroifier = bb::inv(z_h, wm);
     return s;
+}
+Ext load_ext(const uint32_t* p);
+// the claims' side of the lookup argument under the proof's challenges: total += sign / rlc(tuple) per tuple, rlc =
+// chal[0] + chal[1] bus + sum_j chal[2 + j] x_j.  false for a tuple whose rlc is zero (reason 8)
+bool add_claims(const rk_p3_claim* claims, uint32_t n_claims, const std::vector<uint32_t>& pchal, uint32_t wm, Ext& total) {
+    for (uint32_t c = 0; c < n_claims; c++) {
+        const rk_p3_claim& cl = claims[c];
+        const Ext head = bb::add(load_ext(&pchal[0]), bb::scale(load_ext(&pchal[4]), bb::encode(cl.bus)));
+        Ext sum = bb::ext_zero();
+        for (size_t i = 0; i < cl.n; i++) {
+            Ext rlc = head;
+            for (uint32_t j = 0; j < cl.tuple_len; j++)
+                rlc = bb::add(rlc, bb::scale(load_ext(&pchal[4 * (2 + (size_t)j)]), cl.tuples[i * cl.tuple_len + j]));
+            if (bb::eq(rlc, bb::ext_zero())) return false;
+            sum = bb::add(sum, bb::inv(rlc, wm));
+        }
+        total = cl.sign > 0 ? bb::add(total, sum) : bb::sub(total, sum);
+    }
+    return true;
+}
+// the arguments of the claims: what RK_ERR_INVALID names in the header
+int check_claims(const rk_p3_claim* claims, uint32_t n_claims, uint32_t n_chal) {
+    if (n_claims && !claims) return RK_ERR_INVALID;
+    for (uint32_t c = 0; c < n_claims; c++) {
+        const rk_p3_claim& cl = claims[c];
+        if ((cl.sign != 1 && cl.sign != -1) || cl.bus >= bb::P || (cl.n && cl.tuple_len && !cl.tuples)) return RK_ERR_INVALID;
+        if (4 * ((uint64_t)cl.tuple_len + 2) > n_chal) return RK_ERR_INVALID;   // also: tables without lookups (n_chal 0)
+        for (size_t i = 0; i < cl.n * cl.tuple_len; i++)
+            if (cl.tuples[i] >= bb::P) return RK_ERR_INVALID;
+    }
+    return 0;
 }
 Ext load_ext(const uint32_t* p) { return Ext{{p[0], p[1], p[2], p[3]}}; }
 void put(std::vector<uint32_t>& v, const uint32_t* w, size_t n) { v.insert(v.end(), w, w + n); }
@@ -135,6 +166,8 @@ struct Statement {   // the arguments of rk_p3_verify
     size_t words;
     bool keyed = false;                    // rk_p3_verify_key: the caller knows the preprocessed batch
     const uint32_t* prep_root = nullptr;   // the verifying key's root, null when no table has preprocessed columns
+    const rk_p3_claim* claims = nullptr;   // rk_p3_verify_claims: interactions the verifier adds to the lookup argument
+    uint32_t n_claims = 0;
 };
 // the input batches.  The numbers are what the captures index by; the ORDER of a proof and of the reduced openings is
 // trace, preprocessed, permutation, quotient (BATCH_ORDER)
@@ -190,6 +223,9 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
     const uint32_t n_tables = o.n_tables = st.n_tables;
     RK_TRY(p3h::check_tables(o.par, tables, n_tables, false, o.lqd, st.keyed));
     if (!st.proof || (st.n_init && !st.init)) return RK_ERR_INVALID;
+    uint32_t n_chal = 0;   // a table without lookups has none
+    for (uint32_t t = 0; t < n_tables; t++) n_chal = std::max(n_chal, tables[t].air->n_chal);
+    RK_TRY(check_claims(st.claims, st.n_claims, n_chal));
     {   // the verifying key: the root and the pinned height of every table with preprocessed columns, both or neither
         bool any = false;
         for (uint32_t t = 0; t < n_tables; t++) {
@@ -224,8 +260,6 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
     ch.observe(o.root[TRACE], 8);
     for (uint32_t t = 0; t < n_tables; t++) ch.observe(tables[t].public_values, tables[t].n_public);
     // lookups: the permutation challenges, the second commitment, the cumulative sums (which must cancel)
-    uint32_t n_chal = 0;
-    for (uint32_t t = 0; t < n_tables; t++) n_chal = std::max(n_chal, tables[t].air->n_chal);
     o.pchal.assign(n_chal, 0);
     if (o.lay.prow) {
         const Ext pa = ch.sample_ext(), pb = ch.sample_ext();
@@ -244,7 +278,7 @@ int open_statement(Opened& o, const Statement& st, p3h::Transcript* log) {
             ch.observe(o.cumsum[t], 4);
             total = bb::add(total, load_ext(o.cumsum[t]));
         }
-        if (!bb::eq(total, bb::ext_zero())) return 8;
+        if (!add_claims(st.claims, st.n_claims, o.pchal, o.sys.wm, total) || !bb::eq(total, bb::ext_zero())) return 8;
     }
     o.alpha = ch.sample_ext();
     if (!(o.root[QUOTIENT] = r.take(8))) return 1;
@@ -632,6 +666,17 @@ int rk_p3_verify_key(const rk_params* params, const rk_p3_table* tables, uint32_
                      size_t n_init, const uint32_t* proof, size_t proof_words) {
     RK_GUARD_BEGIN
     return p3_verify(keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words));
+    RK_GUARD_END
+}
+
+int rk_p3_verify_claims(const rk_params* params, const rk_p3_table* tables, uint32_t n_tables, const uint32_t* prep_root, const uint32_t* init_words,
+                        size_t n_init, const uint32_t* proof, size_t proof_words, const rk_p3_claim* claims, uint32_t n_claims) {
+    RK_GUARD_BEGIN
+    Statement st = prep_root ? keyed_statement(params, tables, n_tables, prep_root, init_words, n_init, proof, proof_words)
+                             : Statement{params, tables, n_tables, init_words, n_init, proof, proof_words};
+    st.claims = claims;
+    st.n_claims = n_claims;
+    return p3_verify(st);
     RK_GUARD_END
 }
 

@@ -70,6 +70,10 @@ class Execution:
     # with record_trace: per segment the access list (k, 4): cycle, word address, word before, word after
     # (rk_exec_mem_accesses): the side data of the rv32im-mem chip set (p3_rv32mem_shards)
     mem: Optional[list] = None
+    # chips="rv32im-mem" with link=True (raiko_amd/rv32link.py): per shard the journal (k, 3) uint32 -- word address, INIT,
+    # FINAL of every touched word, ascending -- and the run's final image of the touched words {word address: word}
+    journals: Optional[list] = None
+    final_memory: Optional[dict] = None
 
 
 class ExecutorError(RuntimeError):

@@ -555,13 +555,30 @@ def prove(hal, tables, init=(), device_traces=None, key=None):
     return out[: n.value].copy()
 
 
-def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, device_traces=None, key=None):
+def _c_claims(claims):
+    """claims: [(bus, sign, tuples (n, tuple_len) Montgomery words)] -> (RkP3Claim array, what keeps its pointers alive)"""
+    arr = (_lib.RkP3Claim * max(len(claims), 1))()
+    keep = []
+    for i, (bus, sign, tuples) in enumerate(claims):
+        t = np.ascontiguousarray(tuples, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("a claim's tuples are an (n, tuple_len) array")
+        arr[i].bus, arr[i].tuple_len, arr[i].sign = int(bus), t.shape[1], int(sign)
+        arr[i].tuples, arr[i].n = t.ctypes.data_as(_lib.u32p), t.shape[0]
+        keep.append(t)
+    return arr, keep
+
+
+def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, device_traces=None, key=None, claims=None):
     """rk_p3_prove_shards: `shards` = list of (tables, init words); `batch` proofs in flight per GPU (SP1's SHARD_BATCH_SIZE).
     -> list of proof word arrays, in order.  device_traces: optional per shard list as in prove().  key: a Key from
     setup() on `device` (or one Key per entry of `devices`, in that order) -- rk_p3_prove_shards_key, the way shards
-    whose tables have preprocessed columns go through the pool; every proof is then checked against the key's root."""
+    whose tables have preprocessed columns go through the pool; every proof is then checked against the key's root.
+    claims: per shard the list of claims (as verify's) its verifier adds -- rk_p3_prove_shards_claims."""
     lib = _lib.load()
     n = len(shards)
+    if claims is not None and len(claims) != n:
+        raise ValueError("one list of claims per shard")
     bound = lib.rk_p3_proof_bound_words if key is None else lib.rk_p3_proof_bound_words_key
     arr = (_lib.RkP3Shard * n)()
     keep, bufs = [], []
@@ -582,13 +599,21 @@ def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, d
         dev_arr = (C.c_int * len(devices))(*[int(d) for d in devices])
         opts.devices, opts.n_devices = dev_arr, len(devices)
     failed = C.c_size_t(0)
-    if key is None:
-        st = lib.rk_p3_prove_shards(C.byref(opts), arr, n, C.byref(failed))
-    else:
+    karr = None
+    if key is not None:
         keys = list(key) if isinstance(key, (list, tuple)) else [key]
         if len(keys) != (len(devices) if devices is not None else 1):
             raise ValueError("one key per device")
         karr = (C.c_void_p * len(keys))(*[k._handle.value for k in keys])
+    if claims is not None:
+        per = [_c_claims(c) for c in claims]
+        keep.append(per)
+        carr = (C.POINTER(_lib.RkP3Claim) * max(n, 1))(*[C.cast(a, C.POINTER(_lib.RkP3Claim)) for a, _k in per])
+        counts = np.array([len(c) for c in claims] or [0], dtype=np.uint32)
+        st = lib.rk_p3_prove_shards_claims(C.byref(opts), karr, arr, carr, counts.ctypes.data_as(_lib.u32p), n, C.byref(failed))
+    elif key is None:
+        st = lib.rk_p3_prove_shards(C.byref(opts), arr, n, C.byref(failed))
+    else:
         st = lib.rk_p3_prove_shards_key(C.byref(opts), karr, arr, n, C.byref(failed))
     if st != 0:
         e = _lib.RkError(st, lib.rk_strerror(st).decode() + (" (shard %d)" % failed.value if failed.value != C.c_size_t(-1).value else ""))
@@ -598,17 +623,25 @@ def prove_shards(shards, params, device=0, batch=3, verify=True, devices=None, d
     return [bufs[i][: arr[i].proof_words].copy() for i in range(n)]
 
 
-def verify(tables, proof, init=(), params=None, prep_root=None) -> int:
+def verify(tables, proof, init=(), params=None, prep_root=None, claims=None) -> int:
     """rk_p3_verify (host only).  params: an RkParams blob (raiko_amd.hal.make_params) or None for the SP1 preset.
     prep_root: the verifying key's root (Key.root) -- rk_p3_verify_key; the tables with preprocessed columns then need
-    their pinned log_height"""
+    their pinned log_height.  claims: [(bus, sign, tuples (n, tuple_len) Montgomery words)], interactions the verifier
+    adds to the lookup argument -- rk_p3_verify_claims.  The caller must have bound the tuples into init or a public
+    value: see include/raiko_hip.h"""
     lib = _lib.load()
     arr, keep = _c_tables(tables)
     iw = np.ascontiguousarray(init, dtype=np.uint32)
     pf = np.ascontiguousarray(proof, dtype=np.uint32)
     par = C.byref(params) if params is not None else None
     args = (iw.ctypes.data_as(_lib.u32p), iw.size, pf.ctypes.data_as(_lib.u32p), pf.size)
-    if prep_root is None:
+    if claims is not None:
+        kr = None if prep_root is None else np.ascontiguousarray(prep_root, dtype=np.uint32)
+        assert kr is None or kr.size == 8
+        carr, ckeep = _c_claims(claims)
+        rc = lib.rk_p3_verify_claims(par, arr, len(tables), None if kr is None else kr.ctypes.data_as(_lib.u32p), *args, carr, len(claims))
+        del ckeep
+    elif prep_root is None:
         rc = lib.rk_p3_verify(par, arr, len(tables), *args)
     else:
         kr = np.ascontiguousarray(prep_root, dtype=np.uint32)

@@ -4,7 +4,7 @@ circuit (raiko_amd/p3_trace.py) or one of the rv32 chip sets (raiko_amd/rv32_set
 import ctypes as C
 from typing import Sequence
 
-from . import _lib, p3
+from . import _lib, p3, rv32link
 from .executor import Stepper, execute
 from .p3_trace import next_trace_shard, p3_program_air, p3_range_air, p3_shards, p3_trace_air
 from .rv32_sets import (CHIPS, KEYED_CHIPS, RV32_CHIPS, _free, _rv32_airs_of, check_rv32_chain, execute_rv32_device,
@@ -20,20 +20,27 @@ class P3Pipeline:
     number of programs, then close().  chips="rv32i" / "rv32i-cf" / "rv32im": every shard's tables of that chip set are written on
     the GPU (rv32_sets.next_rv32_shard; `lookups` does not apply), every proof is checked by verify_rv32_shard and the run
     by check_rv32_chain.  chips="rv32im-elf" / "rv32im-mem": run() sets the program's key up first (setup_rv32_elf on the
-    proving context), proves every shard under it, checks every proof against its root, and closes it when the run ends."""
+    proving context), proves every shard under it, checks every proof against its root, and closes it when the run ends.
+    link=True (chips="rv32im-mem" only; ValueError otherwise): the shards' memories are linked (raiko_amd/rv32link.py) --
+    every proof is checked with its journal as claims, the run by rv32link.check_memory_chain from the ELF's memory
+    image, and the Execution carries ex.journals and ex.final_memory."""
 
-    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace"):
+    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace", link=False):
         from .hal import HipHal, make_params
         if chips not in CHIPS:
             raise ValueError("chips must be one of %s" % (CHIPS,))
+        if link and chips != "rv32im-mem":
+            raise ValueError("link=True needs chips=\"rv32im-mem\"")
         self.params = params if params is not None else make_params(1)
-        self.lookups, self.chips = lookups, chips
+        self.lookups, self.chips, self.link = lookups, chips, link
         ext_w = int(self.params.ext_w)
-        self.rv32_airs = _rv32_airs_of(chips, ext_w) if chips in RV32_CHIPS else None
+        self.rv32_airs = _rv32_airs_of(chips, ext_w, link) if chips in RV32_CHIPS else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
         _lib.check(self.prove_hal._ctx, self.prove_hal._lib.rk_set_params(self.prove_hal._ctx, C.byref(self.params)))
+        if link:    # the journal's digest is committed on the witness context: under the prover's parameter set
+            _lib.check(self.wit_hal._ctx, self.wit_hal._lib.rk_set_params(self.wit_hal._ctx, C.byref(self.params)))
         if compile_airs:
             for a in self.rv32_airs or (self.cpu_air, self.prog_air, self.range_air):
                 if a is not None:
@@ -53,9 +60,9 @@ class P3Pipeline:
         from .hal import _ptr
         todo = queue.Queue(maxsize=3)           # back-pressure: at most three shards' tables wait for the prover
         done = queue.Queue()                    # device tables the prover is through with: freed by the thread that owns their context
-        proofs, checks, kept, errors, stmts = [], [], [], [], []
-        params, rv32i = self.params, self.chips in RV32_CHIPS
-        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips) if self.chips in KEYED_CHIPS else None
+        proofs, checks, kept, errors, stmts, journals = [], [], [], [], [], []
+        params, rv32i, link = self.params, self.chips in RV32_CHIPS, self.link
+        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips, link=link) if self.chips in KEYED_CHIPS else None
         vk = dict(prep_root=key.root, program_log_height=key.program_log_height) if key else {}
         try:
             stepper = Stepper(elf, input_words, shard_po2)
@@ -65,7 +72,7 @@ class P3Pipeline:
             raise
         pool = ThreadPoolExecutor(max_workers=4)
         if rv32i:
-            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key)
+            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key, link)
         else:
             next_shard = lambda: next_trace_shard(stepper, self.wit_hal, (self.cpu_air, self.prog_air, self.range_air), self.lookups)
         check = verify_rv32_shard if rv32i else p3.verify
@@ -77,13 +84,15 @@ class P3Pipeline:
                     item = todo.get()
                     if item is None:
                         return
-                    _seg, tables, bufs, init = item
+                    _seg, tables, bufs, init = item[:4]
+                    jk = dict(journal=item[4]) if link else {}
+                    journals.extend(item[4:])
                     pf = p3.prove(self.prove_hal, tables, init, device_traces=[None if d is None else (_ptr(d[0]), d[1]) for d in bufs],
                                   key=key.key if key else None)
                     proofs.append(pf)
                     stmts.append((tables, init))
                     if verify:
-                        checks.append(pool.submit(check, tables, pf, init, params, **vk))
+                        checks.append(pool.submit(check, tables, pf, init, params, **vk, **jk))
                     if keep_tables:
                         kept.append(([t if d is None else p3.Table(t.air, d[0].to_host().reshape(1 << d[1], t.air.width), t.public_values, prep=pm)
                                       for t, d, pm in zip(tables, bufs, preps or [None] * len(tables))], init))
@@ -125,13 +134,16 @@ class P3Pipeline:
             raise _lib.RkError(_lib.RK_ERR_VERIFY, "shard %d does not verify" % bad[0])
         if rv32i and verify:
             check_rv32_chain(rv32_publics(stmts), entry_pc=metas[0].start_pc if metas else None)
+        if link:
+            ex.journals = journals
+            ex.final_memory = rv32link.check_memory_chain(journals, rv32link.memory_image(elf))
         return ex, proofs, kept
 
 
 def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 20, params=None, device: int = 0,
-                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace"):
+                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace", link=False):
     """one program through a P3Pipeline of its own"""
-    pipe = P3Pipeline(params, device, lookups, compile_airs, chips)
+    pipe = P3Pipeline(params, device, lookups, compile_airs, chips, link)
     try:
         return pipe.run(elf, input_words, shard_po2, verify, keep_tables)
     finally:
@@ -139,7 +151,7 @@ def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), 
 
 
 def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, params=None, device: int = 0, batch: int = 3,
-                         lookups=False, chips="trace"):
+                         lookups=False, chips="trace", link=False):
     """ELF -> executed shards -> one uni-stark proof per shard through rk_p3_prove_shards (every proof verified inside):
     the shape of `client.prove(&pk, stdin)` on the SP1 side (provers/sp1/driver/src/lib.rs:44-57; SHARD_SIZE / SHARD_BATCH_SIZE,
     docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)
@@ -152,25 +164,33 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     GPU (rk_exec_rv32elf_shard_device) and proven under that key (rk_p3_prove_shards_key), and the run is checked against
     the key's root, which the returned Execution carries as ex.prep_root (with ex.program_log_height: together the
     verifying key).  chips="rv32im-mem": rv32im-elf with loads, stores and memory constrained within every shard
-    (raiko_amd/rv32mem.py): nine traces per shard (rk_exec_rv32mem_shard_device), the same key protocol."""
+    (raiko_amd/rv32mem.py): nine traces per shard (rk_exec_rv32mem_shard_device), the same key protocol.  link=True
+    (chips="rv32im-mem" only; ValueError otherwise): the shards' memories are linked (raiko_amd/rv32link.py): every
+    shard's journal is read off its memory table on the GPU (rk_rv32mem_journal_device), its digest is the table's public
+    values, the pool's verifiers check every proof with the journal as claims (rk_p3_prove_shards_claims), and the run is
+    checked by verify_rv32_execution(journals=, image=) from the ELF's memory image.  The Execution then carries
+    ex.journals and ex.final_memory (the final words of everything the run touched)."""
     from .hal import make_params
     params = params if params is not None else make_params(1)
     if chips not in CHIPS:
         raise ValueError("chips must be one of %s" % (CHIPS,))
+    if link and chips != "rv32im-mem":
+        raise ValueError("link=True needs chips=\"rv32im-mem\"")
     if chips in RV32_CHIPS:
         from .hal import HipHal
         hal = HipHal(device)
         key, vk = None, {}
         try:
             if chips in KEYED_CHIPS:
-                key = setup_rv32_elf(hal, elf, params, chips=chips)
+                key = setup_rv32_elf(hal, elf, params, chips=chips, link=link)
                 vk = dict(prep_root=key.root.copy(), program_log_height=key.program_log_height)
-            ex, shards, dev_traces, bufs = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
-                                                               chips=chips, key=key)
+            ex, shards, dev_traces, bufs, *journals = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
+                                                                          chips=chips, key=key, link=link)
             hal.sync()
             try:
                 proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces,
-                                         key=key.key if key else None)
+                                         key=key.key if key else None,
+                                         claims=[rv32link.claims_of(j) for j in journals[0]] if link else None)
             finally:
                 for d in bufs:
                     _free(d)
@@ -178,7 +198,13 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
             if key:
                 key.close()
             hal.close()
+        if link:
+            image = rv32link.memory_image(elf)
+            vk.update(journals=journals[0], image=image)
         verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None, **vk)
+        if link:
+            ex.journals, ex.final_memory = journals[0], rv32link.check_memory_chain(journals[0], image)
+            del vk["journals"], vk["image"]
         if vk:
             ex.prep_root, ex.program_log_height = vk["prep_root"], vk["program_log_height"]
         return ex, shards, proofs

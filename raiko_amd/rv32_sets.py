@@ -9,7 +9,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, p3, rv32, rv32cf, rv32elf, rv32im, rv32mem
+from . import _lib, p3, rv32, rv32cf, rv32elf, rv32im, rv32link, rv32mem
 from .executor import Execution, Stepper, _rv32_side
 
 
@@ -64,9 +64,16 @@ def _rv32_set(chips):
     return _BY_NAME[chips].module, _BY_NAME[chips]
 
 
-def _rv32_airs_of(chips, ext_w=None):
-    """the AIRs of one shard of chip set `chips`, in table order"""
-    return _rv32_set(chips)[0].airs(ext_w)
+def _rv32_airs_of(chips, ext_w=None, link=False):
+    """the AIRs of one shard of chip set `chips`, in table order.  link: the rv32im-mem set with its shard memories
+    linked (raiko_amd/rv32link.py: the memory AIR sends the journal and carries its digest)"""
+    _link_ok(chips, link)
+    return (rv32link if link else _rv32_set(chips)[0]).airs(ext_w)
+
+
+def _link_ok(chips, link):
+    if link and chips != "rv32im-mem":
+        raise ValueError("link=True needs chips=\"rv32im-mem\"")
 
 
 def p3_rv32_airs(ext_w=None):
@@ -97,12 +104,16 @@ def _host_preps(cs, image, n_tables):
     return [None if m is None else p3.to_mont(m) for m in cs.module.preps_of(image)]
 
 
-def shards(chips, ex: Execution, image=None, ext_w=None, airs=None):
+def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, params=None):
     """one shard of chip set `chips` per executed segment, every table built in numpy (the set's shard_tables) from
     ex.witness, ex.rv32 and what else the set takes (image: rv32elf.program_image(elf); ex.mem) -> [(tables, init
     words)], init = the state digests as in p3_shards.  A keyed set's lookup tables carry their preprocessed matrix in
-    Table.prep (p3.setup commits them)."""
+    Table.prep (p3.setup commits them).  link (rv32im-mem): rv32link's AIRs, the memory table's public values the digest
+    of the shard's journal under `params` (None: the SP1 preset) -> [(tables, init words, journal)]."""
     module, cs = _rv32_set(chips)
+    _link_ok(chips, link)
+    if link:
+        module = rv32link
     if ex.witness is None or ex.rv32 is None or ("mem" in cs.extra and ex.mem is None):
         raise ValueError("execute(..., record_trace=True) first")
     airs = airs or module.airs(ext_w)
@@ -110,9 +121,13 @@ def shards(chips, ex: Execution, image=None, ext_w=None, airs=None):
     extra = {"image": lambda k: image, "mem": lambda k: ex.mem[k]}
     out = []
     for k, (s, (_code, data), (start, end, ecalls)) in enumerate(zip(ex.segments, ex.witness, ex.rv32)):
-        canon, _pc, _regs = module.shard_tables(s, data, start, end, ecalls, *(extra[name](k) for name in cs.extra))
-        tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, _publics(s, start, end, len(canon)), preps)]
-        out.append((tables, s.init_words()))
+        canon, _pc, _regs, *digest = module.shard_tables(s, data, start, end, ecalls, *(extra[name](k) for name in cs.extra),
+                                                          **(dict(params=params) if link else {}))
+        pubs = _publics(s, start, end, len(canon))
+        if link:
+            pubs[rv32link.MEMORY_TABLE] = digest[0]
+        tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
+        out.append((tables, s.init_words()) + ((rv32link.journal_of_table(canon[rv32link.MEMORY_TABLE]),) if link else ()))
     return out
 
 
@@ -148,13 +163,16 @@ def p3_rv32mem_shards(ex: Execution, image, ext_w=None, airs=None):
     return shards("rv32im-mem", ex, image, ext_w, airs)
 
 
-def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None):
+def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, link=False):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
     rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key) /
     rk_exec_rv32mem_shard_device ("rv32im-mem", key likewise): segment `index` of an open executor as the tables of a
     shard of that chip set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per
-    table, init words)"""
+    table, init words).  link (rv32im-mem, airs rv32link's): after the tables are written rk_rv32mem_journal_device reads
+    the memory table, its digest (under the parameter set of hal's context, which must be the prover's) becomes that
+    table's public values and the journal (k, 3) uint32 is handed back as a fourth element"""
     _module, cs = _rv32_set(chips)
+    _link_ok(chips, link)
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
@@ -188,17 +206,47 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None):
         for b in bufs:
             b.free()
         raise
-    tables = [p3.Table.pinned(a, lg, pv) for a, lg, pv in zip(airs, logs, _publics(seg, start, end, len(logs)))]
-    return tables, list(zip(bufs, logs)), seg.init_words()
+    pubs = _publics(seg, start, end, len(logs))
+    journal = ()
+    if link:
+        try:
+            root, j = journal_device(hal, bufs[rv32link.MEMORY_TABLE], logs[rv32link.MEMORY_TABLE])
+        except Exception:
+            for b in bufs:
+                b.free()
+            raise
+        pubs[rv32link.MEMORY_TABLE], journal = root, (j,)
+    tables = [p3.Table.pinned(a, lg, pv) for a, lg, pv in zip(airs, logs, pubs)]
+    return (tables, list(zip(bufs, logs)), seg.init_words()) + journal
 
 
-def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None):
+def journal_device(hal, d_memory, log_rows, keep=False):
+    """rk_rv32mem_journal_device over a finished device memory table of 2^log_rows rows -> (root: 8 Montgomery words,
+    journal (k, 3) uint32); keep: also the link matrix (rows, 6) and the count of real rows as the device reports it"""
+    lib = _lib.load()
+    rows = 1 << log_rows
+    work = [hal.alloc_elem(3 * rows), hal.alloc_elem(rv32link.N_DIGEST * 2 * rows), hal.alloc_elem(len(rv32link.LINK_TUPLE) * rows)]
+    try:
+        root, n_real = np.zeros(rv32link.N_DIGEST, dtype=np.uint32), C.c_size_t(0)
+        d_journal, d_nodes, d_link = (C.c_void_p(b.ptr) for b in work)
+        _lib.check(hal._ctx, lib.rk_rv32mem_journal_device(hal._ctx, C.c_void_p(d_memory.ptr), rows, d_journal, d_link, d_nodes,
+                                                           C.byref(n_real), root.ctypes.data_as(_lib.u32p)))
+        journal = work[0].to_host().reshape(rows, 3)[: n_real.value].copy()
+        if keep:
+            return root, journal, work[2].to_host().reshape(rows, len(rv32link.LINK_TUPLE)).copy(), int(n_real.value)
+        return root, journal
+    finally:
+        for b in work:
+            b.free()
+
+
+def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None, link=False):
     """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) or
     rv32im-mem (nine) shard written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf" /
     "rv32im-mem") -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words),
-    or None after the last"""
+    or None after the last.  link: as rv32_shard_device, the journal a fifth element"""
     seg = stepper.step()
-    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key))
+    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key, link))
 
 
 def _free(bufs):
@@ -209,21 +257,24 @@ def _free(bufs):
 
 
 def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
-                        chips="rv32i", key=None):
+                        chips="rv32i", key=None, link=False):
     """ELF -> rv32i (rv32i-cf, rv32im, rv32im-elf) shards whose tables are written on hal's GPU, one segment at a time
     (the executor's trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables,
     init)], [device traces], [[(device buffer, log_height)]] to free).  key: the Rv32Key of chips="rv32im-elf" (its AIRs
-    are the shards')"""
+    are the shards').  link (rv32im-mem; key from setup_rv32_elf(link=True)): the shards' memories linked, the journals
+    a fifth element of the result"""
     from .hal import _ptr
-    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w))
+    _link_ok(chips, link)
+    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w, link))
     st = Stepper(elf, input_words, shard_po2)
-    out, dev, metas = [], [], []
+    out, dev, metas, journals = [], [], [], []
     try:
         while True:
-            item = next_rv32_shard(st, hal, airs, chips, key)
+            item = next_rv32_shard(st, hal, airs, chips, key, link)
             if item is None:
                 break
-            seg, tables, bufs, init = item
+            seg, tables, bufs, init = item[:4]
+            journals += item[4:]
             out.append((tables, init))
             dev.append(bufs)
             metas.append(seg)
@@ -235,7 +286,7 @@ def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_
         raise
     finally:
         st.close()
-    return ex, out, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev
+    return (ex, out, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev) + ((journals,) if link else ())
 
 
 def check_rv32_chain(publics, entry_pc=None):
@@ -262,35 +313,61 @@ def check_rv32_chain(publics, entry_pc=None):
 
 def rv32_publics(shards):
     """[(cpu public values, register public values)] canonical, per shard of [(tables, init)]"""
-    return [(p3.from_mont(t[0].public_values), p3.from_mont(t[2].public_values)) for t, _init in shards]
+    return [(p3.from_mont(sh[0][0].public_values), p3.from_mont(sh[0][2].public_values)) for sh in shards]
 
 
-def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None):
+def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None, journals=None,
+                          image=None):
     """Checks a run proven with the rv32i, rv32i-cf, rv32im, rv32im-elf or rv32im-mem chip set: every shard's proof
     (verify_rv32_shard), then check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards /
     p3_rv32cf_shards / p3_rv32im_shards / execute_rv32_device give them.  prep_root, program_log_height: the verifying
     key of an rv32im-elf or rv32im-mem run (Execution.prep_root / .program_log_height): every shard must answer to that
-    one root.  Under rv32im-mem the shards' memories are NOT chained: every shard's INIT values are free.
+    one root.  Under rv32im-mem WITHOUT journals the shards' memories are not chained: every shard's INIT values are
+    free.  journals (one per shard) with image (rv32link.memory_image(elf)): the run was proven with link=True; every
+    proof is checked with its journal (verify_rv32_shard), and after check_rv32_chain the journals are replayed from the
+    ELF's memory image (rv32link.check_memory_chain): INIT of every touched word is what the shards before left there.
     Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
-    for k, ((tables, init), pf) in enumerate(zip(shards, proofs)):
-        rc = verify_rv32_shard(tables, pf, init, params, prep_root, program_log_height)
+    if journals is not None and (len(journals) != len(shards) or image is None):
+        raise ValueError("journals: one per shard, with the ELF's memory image")
+    for k, ((tables, init, *_j), pf) in enumerate(zip(shards, proofs)):
+        rc = verify_rv32_shard(tables, pf, init, params, prep_root, program_log_height,
+                               journal=None if journals is None else journals[k])
         if rc != 0:
             raise ValueError("shard %d: the proof does not verify (reason %d)" % (k, rc))
-    return check_rv32_chain(rv32_publics(shards), entry_pc)
+    check_rv32_chain(rv32_publics(shards), entry_pc)
+    if journals is not None:
+        rv32link.check_memory_chain(journals, image)
+    return True
 
 
-def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None) -> int:
+def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None, journal=None) -> int:
     """rk_p3_verify of one rv32i (five tables), rv32i-cf (six) or rv32im (seven) shard with the register / byte / range
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
     verifier's reason.  prep_root (8 Montgomery words) with program_log_height: the statement is the rv32im-elf set's
     seven tables (or the rv32im-mem set's nine) under that verifying key (rk_p3_verify_key) -- the program table's
     height is then pinned by the verifier, no longer the proof's.  The memop and memory tables' heights are the proof's,
-    refused (reason 2) unless 0 < log height <= the cpu table's + 1"""
+    refused (reason 2) unless 0 < log height <= the cpu table's + 1.  journal: the shard was proven with link=True
+    (rv32link's AIRs): the digest of the journal at the proof's memory-table height is recomputed and must be that
+    table's public values (reason 2 otherwise, also for a journal that is malformed or taller than the table); the proof
+    is then verified with the journal's tuples as receive claims (rk_p3_verify_claims)"""
     vt = rv32_verifier_tables(tables, proof, prep_root, program_log_height)
-    return 2 if vt is None else p3.verify(vt, proof, init, params, prep_root=prep_root)
+    if vt is None:
+        return 2
+    if journal is None:
+        return p3.verify(vt, proof, init, params, prep_root=prep_root)
+    bd = vt[rv32link.MEMORY_TABLE] if len(vt) > rv32link.MEMORY_TABLE else None
+    if bd is None or bd.public_values.size != rv32link.N_DIGEST:
+        raise ValueError("a journal goes with the nine tables of a linked rv32im-mem shard")
+    try:
+        digest = rv32link.journal_root(journal, bd.log_height, params)
+    except _lib.RkError:
+        return 2
+    if not np.array_equal(digest, bd.public_values):
+        return 2
+    return p3.verify(vt, proof, init, params, prep_root=prep_root, claims=rv32link.claims_of(journal))
 
 
 def rv32_verifier_tables(tables, proof, prep_root=None, program_log_height=None):
@@ -355,20 +432,22 @@ class Rv32Key:
         self.key = self.d_words = None
 
 
-def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf") -> Rv32Key:
+def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf", link=False) -> Rv32Key:
     """The setup of `client.setup(ELF)` for the rv32im-elf chip set: the ELF's program image (rk_exec_program_image), the
     four preprocessed matrices written on hal's GPU (rk_rv32elf_prep_device) and committed (rk_p3_setup) -> Rv32Key.
     params: the parameter set to put hal's context under first (None: the context's current one); ext_w: the AIRs'
     extension (default params' / the context's).  chips="rv32im-mem": that chip set's key (rk_rv32mem_prep_device: the
-    program matrix has 48 columns) and nine AIRs."""
+    program matrix has 48 columns) and nine AIRs.  link (rv32im-mem): the nine AIRs are rv32link's; the key itself --
+    the preprocessed matrices, their heights, the root -- is the same either way."""
     if chips not in KEYED_CHIPS:
         raise ValueError("chips must be one of %s" % (KEYED_CHIPS,))
+    _link_ok(chips, link)
     cs = _rv32_set(chips)[1]
     lib = _lib.load()
     if params is not None:
         _lib.check(hal._ctx, lib.rk_set_params(hal._ctx, C.byref(params)))
     if airs is None:
-        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w)
+        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w, link)
     vaddr, count, words = program_image_c(elf)
     rows = 2
     while rows < words.size:

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "raiko_hip.h")
 FFI_RS = os.path.join(ROOT, "provers", "hip", "driver", "src", "ffi.rs")
 
-SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "size_t": "usize", "float": "f32",
+SCALARS = {"int": "c_int", "int32_t": "i32", "uint32_t": "u32","uint64_t": "u64", "uint8_t": "u8", "size_t": "usize", "float": "f32",
            "double": "f64", "char": "c_char", "void": "c_void"}
 
 
