@@ -155,8 +155,11 @@ def test_linked_air_holds_and_leaves_the_journal_on_the_link_bus(name, airs):
         assert len(journal) == 1
 
 
-def test_forged_boundary_rows_under_the_linked_air(airs):
-    """the forgeries of test_rv32_mem_chips.py::test_forged_boundary_rows, refused by the same named constraints"""
+@pytest.mark.parametrize("ext", ["sp1", "risc0"])
+def test_forged_boundary_rows_under_the_linked_air(airs, ext):
+    """the forgeries of test_rv32_mem_chips.py::test_forged_boundary_rows, refused by the same named constraints, with
+    the AIRs built for either extension (x^4 - 3, x^4 + 11)"""
+    airs = airs if ext == "sp1" else rv32link.airs(P - 11)
     _elf, ex, image, preps = T._run("forge")
     s, (_c, data), (start, end, ecalls), mem = next(T._shards(ex))
     canon = rv32link.shard_tables(s, data, start, end, ecalls, image, mem)[0]
