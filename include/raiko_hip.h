@@ -731,7 +731,8 @@ int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
  *             TABLE: what a link between shards would bind
  * CONSTRAINED: everything rv32im-elf constrains; the value LB / LH / LW / LBU / LHU write and the word SB / SH / SW leave,
  * against one history per word inside the shard.  FREE: INIT of every touched word (the boundary to the previous shard
- * and to the ELF's data image), what an ecall writes, the a0 it leaves.
+ * and to the ELF's data image; the link below binds it), what an ecall writes, the a0 it leaves (the io form below binds
+ * both).
  * rk_exec_mem_accesses: the access list of segment `index` (needs record_trace): *n entries of four words (cycle within
  * the segment, word address addr >> 2, word before, word after) in cycle order -- one per store, one per load whose rd is
  * not x0 (after = before) and one per word an ecall READ wrote, at the ecall's cycle in ascending address order.
@@ -758,6 +759,51 @@ int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
                                  uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
                                  uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
                                  uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows);
+/* THE IO FORM OF RV32IM-MEM: ecalls bound to the run's input and exit code (raiko_amd/rv32io.py builds the same tables in
+ * numpy, names every column and writes the AIRs).  Ten tables, rv32im-mem's nine in their order, then io; a key of its
+ * own: rk_rv32io_prep_device is rk_rv32mem_prep_device with the program tuple of the word 0x00000073 reading a0 and a1
+ * (RS1 = 10, RS2 = 11, WREG = 10).  DECODE OF THE ECALL WORD IS TRUSTED TO SETUP, as all decode under rv32im-elf.
+ *   cpu     2^po2 x RK_RV32IO_CPU_COLS: rv32im-mem's 141 columns (N_ECW = EC_OP = 0: no send to memop; an ecall row's A and B
+ *           are a0 and a1), then T0_LO / T0_HI, PT_TS, DT_LO, DT_HI, R5 = 5 IS_SYS, T0Z: an ecall row reads x5 as a fourth
+ *           register access at TSA and sends (TSA, T0, A, B, RES) on bus RK_RV32IO_BUS; no row is active after a HALT row
+ *   memop   an ECW row obeys SW's constraints (A its address, MI = 0, B and BB the word it leaves); its tuple comes from an
+ *           io word row
+ *   io      io_rows x RK_RV32IO_IO_COLS: one head row per ecall in cycle order (HALT / READ / COMMIT one-hot from T0 in
+ *           {0, 1, 2}; HALT and COMMIT leave a0; READ leaves GOT = min(a1, N_INPUT - POS), proven limb by limb in RANGE16
+ *           with is-zero flags), after a READ head GOT word rows -- word k sends (16, TS, A + 4 k, 0, V, 0) to memop and the
+ *           stream tuple (POS_WL, POS_WH, V_LO, V_HI, 0, 0) on bus RK_RV32IO_INPUT_BUS, which no table receives -- then
+ *           padding; POS runs through every row
+ * The io table's RK_RV32IO_PUBLICS public values: POS_START, POS_END, N_INPUT, HALTED, EXIT_LO, EXIT_HI, then 8 words no
+ * constraint reads: the digest of input[POS_START .. POS_END) as stream tuples -- rk_rv32mem_journal_root of the journal
+ * (position, word, 0) at the io table's height.  The verifier recomputes it from ITS input, adds the stream tuples as
+ * receive claims (rk_p3_verify_claims: this is the caller's duty stated there) and chains POS over the shards.
+ * CONSTRAINED: what READ stores and where, the a0 every call leaves, the exit code.  STILL FREE: the bytes COMMIT appends
+ * to the journal are not read through the memory argument and the journal is no public output.  The rk_p3_fri_* statements
+ * do not cover an io proof, as for linked proofs.
+ * rk_exec_ecall_args: per ecall row of segment `index` (needs record_trace) five words -- cycle, t0, a0 before the call,
+ * a1, input position before it -- in cycle order; *pos_start (may be NULL): the input position at the segment's start.
+ * RK_ERR_CAPACITY with *n set when more than `capacity` entries.  TraceRow.a / .b of an ecall row stay 0.
+ * rk_exec_rv32io_sizes: rk_exec_rv32mem_sizes and the io table's rows, 2^max(1, ceil(log2(ecalls + words read))).
+ * rk_exec_rv32io_shard_device: rk_exec_rv32mem_shard_device in io form with the tenth table; h_publics receives the io
+ * table's RK_RV32IO_PUBLICS public values (Montgomery; the digest is committed under ctx's parameter set).
+ * RK_ERR_INVALID / RK_ERR_CAPACITY before any launch for NULL buffers, io_rows not a power of two >= 2, below what
+ * rk_exec_rv32io_sizes gives or above 2^(po2 + 1), and a side list that is not the trace's ecall rows in cycle order. */
+#define RK_RV32IO_CPU_COLS 148
+#define RK_RV32IO_IO_COLS 47
+#define RK_RV32IO_BUS 12
+#define RK_RV32IO_INPUT_BUS 13
+#define RK_RV32IO_PUBLICS 14
+int rk_exec_ecall_args(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n, uint32_t* pos_start);
+int rk_rv32io_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                          const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                          uint32_t* d_range, uint32_t* d_shift);
+int rk_exec_rv32io_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows, size_t* io_rows);
+int rk_exec_rv32io_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows, uint32_t* d_io,
+                                size_t io_rows, uint32_t h_publics[RK_RV32IO_PUBLICS]);
 /* THE LINK BETWEEN SHARD MEMORIES (raiko_amd/rv32link.py; the first of the designs a boundary table admits: a digest).
  * With the link on, a real row of the memory table also SENDS (WL, WH, I_LO, I_HI, F_LO, F_HI) on bus RK_RV32LINK_BUS,
  * which no table receives, and the table carries 8 public values no constraint reads: the digest of the shard's JOURNAL,
@@ -767,7 +813,7 @@ int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
  * (rk_exec_memory_image): INIT of a word must be what the image holds, then the image's word becomes FINAL.  Public values
  * are observed before the permutation challenges are sampled, so the journal is fixed (up to a collision of the digest)
  * before the challenges exist, and the LogUp identity makes the multiset of real boundary rows the journal.  STILL FREE:
- * what an ecall writes and the a0 it leaves.  The verifier's work is linear in the touched words.  The rk_p3_fri_*
+ * what an ecall writes and the a0 it leaves (bound by the io form above; then the COMMIT journal remains).  The verifier's work is linear in the touched words.  The rk_p3_fri_*
  * captures of a linked proof replay rk_p3_verify_key and stop at reason 8: the FRI statements do not cover it.
  * The digest: the rk_mmcs_commit root of the memory_rows x RK_RV32LINK_TUPLE row-major Montgomery matrix of the limb
  * tuples, rows of zeros past the real ones.

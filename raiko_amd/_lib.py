@@ -305,6 +305,13 @@ SYMBOLS = {
     "rk_exec_rv32mem_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rk_exec_ecall_args": (C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "rk_rv32io_prep_device": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, u32p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "rk_exec_rv32io_sizes": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rk_exec_rv32io_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p]),
     "rk_exec_memory_image": (C.c_int, [C.c_char_p, C.c_size_t, u32p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rk_rv32mem_journal_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t), u32p]),

@@ -114,6 +114,10 @@ struct rk_exec {
     // TraceRow -- and the lowest / highest pc executed (the rv32i chip set's program table, rk_exec_rv32_*)
     std::vector<std::vector<std::array<uint32_t, 2>>> ecalls;
     std::vector<std::array<uint32_t, 2>> pc_range;
+    // per segment, with record_trace: (cycle, t0, a0 before the call, a1, input position before it) of every ecall row --
+    // what the call read, beside what it left (rk_exec_ecall_args; the io form of the rv32im-mem chip set)
+    std::vector<std::vector<std::array<uint32_t, 5>>> ecall_args;
+    std::vector<uint32_t> in_start;              // per segment, with record_trace: the input position at its start
     // per segment, with record_trace: (cycle, word address, old word, new word) of every data access the rv32im-mem chip
     // set proves (ExecSegmentView.mem); `mem_now` collects the running segment's, `cycle_now` is its cycle counter
     std::vector<std::vector<std::array<uint32_t, 4>>> mem;
@@ -370,6 +374,8 @@ int exec_next(rk_exec* ex, int* more) {
     std::array<uint32_t, 64> regs{};
     std::copy(m.x, m.x + 32, regs.begin());
     std::vector<std::array<uint32_t, 2>> ecalls;
+    std::vector<std::array<uint32_t, 5>> ecall_args;
+    const uint32_t in_start = (uint32_t)ex->in_pos;
     uint32_t pc_lo = 0xffffffffu, pc_hi = 0;
     ex->mem_now.clear();
     if (o.record_trace) trace.reserve((size_t)std::min<uint64_t>(limit, (uint64_t)1 << 22));  // 28 bytes per cycle, no regrowth copies
@@ -382,11 +388,15 @@ int exec_next(rk_exec* ex, int* more) {
         TraceRow row{};
         ex->cycle_now = (uint32_t)cycles;
         if (o.profile) ex->pc_cycles[m.pc]++;
+        const std::array<uint32_t, 5> before{(uint32_t)cycles, m.x[5], m.x[10], m.x[11], (uint32_t)ex->in_pos};
         int r = step(m, *ex, o, ex->in_pos, ex->error, o.record_trace ? &row : nullptr);
         if (r < 0) { ex->st = r; break; }
         if (o.record_trace) {
             trace.push_back(row);
-            if (row.ins == 0x00000073u) ecalls.push_back({(uint32_t)cycles, m.x[10]});
+            if (row.ins == 0x00000073u) {
+                ecalls.push_back({(uint32_t)cycles, m.x[10]});
+                ecall_args.push_back(before);
+            }
             pc_lo = std::min(pc_lo, row.pc);
             pc_hi = std::max(pc_hi, row.pc);
         }
@@ -408,6 +418,8 @@ int exec_next(rk_exec* ex, int* more) {
         if (o.record_trace) {
             ex->traces.push_back(std::move(trace));
             ex->ecalls.push_back(std::move(ecalls));
+            ex->ecall_args.push_back(std::move(ecall_args));
+            ex->in_start.push_back(in_start);
             ex->pc_range.push_back({pc_lo, pc_hi});
             ex->mem.push_back(std::move(ex->mem_now));
             ex->mem_now.clear();
@@ -448,7 +460,8 @@ int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out) {
     if (!ex || index >= ex->segments.size() || index >= ex->traces.size()) return RK_ERR_INVALID;
     if (ex->traces[index].size() != ex->segments[index].cycles) return RK_ERR_INTERNAL;
     *out = ExecSegmentView{&ex->segments[index], &ex->traces[index], ex->regs[index].data(), &ex->ecalls[index],
-                           ex->pc_range[index][0], ex->pc_range[index][1], &ex->mem[index]};
+                           ex->pc_range[index][0], ex->pc_range[index][1], &ex->mem[index], &ex->ecall_args[index], ex->in_start[index],
+                           (size_t)ex->o.n_input_words};
     return RK_OK;
 }
 
@@ -616,6 +629,15 @@ int rk_exec_ecalls(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capa
     *n = ec.size();
     if (ec.size() > capacity || (!out && !ec.empty())) return RK_ERR_CAPACITY;
     for (size_t k = 0; k < ec.size(); k++) out[2 * k] = ec[k][0], out[2 * k + 1] = ec[k][1];
+    return RK_OK;
+}
+int rk_exec_ecall_args(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n, uint32_t* pos_start) {
+    if (!ex || !n || index >= ex->ecall_args.size()) return RK_ERR_INVALID;
+    const auto& ea = ex->ecall_args[index];
+    *n = ea.size();
+    if (pos_start) *pos_start = ex->in_start[index];
+    if (ea.size() > capacity || (!out && !ea.empty())) return RK_ERR_CAPACITY;
+    for (size_t k = 0; k < ea.size(); k++) std::copy(ea[k].begin(), ea[k].end(), out + 5 * k);
     return RK_OK;
 }
 int rk_exec_mem_accesses(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n) {

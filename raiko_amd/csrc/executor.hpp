@@ -22,6 +22,10 @@ struct ExecSegmentView {
     // (cycle, word address addr >> 2, old word, new word) of every store, every load whose rd is not x0 (new = old) and
     // every word an ecall READ writes, in cycle order (the words of one ecall in ascending address order)
     const std::vector<std::array<uint32_t, 4>>* mem;
+    // (cycle, t0, a0 before the call, a1, input position before it) of every ecall row, in cycle order
+    const std::vector<std::array<uint32_t, 5>>* ecall_args;
+    uint32_t in_start;                                    // the input position at the segment's start
+    size_t n_input;                                       // the run's input words
 };
 
 // RK_ERR_INVALID: no executor, or no recorded segment `index`; RK_ERR_INTERNAL: the trace is not seg->cycles rows long.

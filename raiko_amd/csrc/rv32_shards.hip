@@ -74,7 +74,10 @@ static int witness_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, uint32
 // cycle is counted at the image row of its pc (its word compared with the image's) and the program, byte, range and
 // shift tables leave as count columns.  rv32im-mem: rv32im-elf's pipeline and, from the access list: keys (word address,
 // list index; the ecall rows' per-cycle counts) -> rocPRIM's stable radix sort by the 30 address bits -> heads per block,
-// scan -> link (each access's predecessor, the boundary rows) -> the memop rows.
+// scan -> link (each access's predecessor, the boundary rows) -> the memop rows.  The io form of rv32im-mem
+// (rk_exec_rv32io_shard_device, raiko_amd/rv32io.py): the same pipeline over the io form of the trace (patch: an ecall
+// row's a / b / res become the call's a0 / a1 / t0), the read of x5 in the scans, and from the ecall side list: offsets
+// per ecall (1 + the words it stored), scan -> the io rows and the stream matrix -> its commitment (rk_mmcs_commit).
 namespace rv32 {
 
 constexpr unsigned TB = 128;   // rows per block (the cpu rows kernel stages TB x 69 words in LDS, 121 / 133 / 141 for rv32i-cf / rv32im / rv32im-mem)
@@ -133,7 +136,9 @@ struct ImageArgs<true> {
     Image img;
     const uint32_t* words;   // the image's words, device memory
 };
-template <bool ELF>
+// IO (the io form, raiko_amd/rv32io.py): the key reads an ecall word as `ecall a0, a1` and bit 17 of acc marks its row: the
+// fourth access, of x5
+template <bool ELF, bool IO>
 __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size_t n, const uint32_t* __restrict__ ecalls,
                             uint32_t n_ecalls, uint32_t pc_base, uint32_t n_slots, uint32_t* __restrict__ wval,
                             uint32_t* __restrict__ acc, uint32_t* __restrict__ prog_mult, uint32_t* __restrict__ prog_ins,
@@ -147,7 +152,7 @@ __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size
         return;
     }
     const TraceRow r = tr[i];
-    const Dec d = decode(r.ins);
+    const Dec d = IO ? decode_io(r.ins) : decode(r.ins);
     if (mflag) mflag[i] = d.is_m && d.wr;   // rv32im: the rows with M_W = 1, one muldiv row each
     uint32_t a0 = 0;
     if (d.opc == O_SYSTEM) {   // the side list is in cycle order: binary search
@@ -161,7 +166,7 @@ __global__ void prep_kernel(const TraceRow* __restrict__ tr, size_t cycles, size
         else atomicOr(err, 2u);
     }
     wval[i] = written(d, r, a0);
-    acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16;
+    acc[i] = d.rs1 | d.rs2 << 5 | d.wreg << 10 | d.wr << 15 | 1u << 16 | (IO ? d.is_sys << 17 : 0u);
     if constexpr (ELF) {
         const uint32_t slot = image_row(image.img, r.pc);
         if (slot >= n_slots) {   // NO_ROW: a pc outside the image
@@ -203,6 +208,7 @@ __global__ void block_last_kernel(const uint32_t* __restrict__ acc, uint32_t* __
         atomicMax(&s[rs1], tsa);
         atomicMax(&s[rs2], tsa + 1);
         if (wr) atomicMax(&s[wreg], tsa + 2);
+        if (acc[i] >> 17 & 1) atomicMax(&s[5], tsa);   // the io form: an ecall row reads x5 at tsa (its rs1 is x10)
     }
     __syncthreads();
     if (threadIdx.x < 32) blk[(size_t)blockIdx.x * 32 + threadIdx.x] = s[threadIdx.x];
@@ -227,10 +233,30 @@ __global__ void scan_kernel(uint32_t* __restrict__ blk, size_t nb, uint32_t* __r
     if (c == 31) final_ts[r] = run;
 }
 
-__device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* tr, const uint32_t* wval, const uint32_t* init) {
+// io: the trace is the io form's (io_patch_kernel): an ecall row's a / b / res hold a0 / a1 / t0, and its first timestamp
+// is also that of its read of x5
+__device__ inline uint32_t value_at(uint32_t ts, uint32_t reg, const TraceRow* tr, const uint32_t* wval, const uint32_t* init,
+                                    bool io = false) {
     if (ts == 0) return init[reg];
     const uint32_t j = (ts - 1) / 3, k = (ts - 1) % 3;
+    if (io && k == 0 && reg == 5 && tr[j].ins == ECALL_WORD) return tr[j].res;
     return k == 0 ? tr[j].a : k == 1 ? tr[j].b : wval[j];
+}
+
+// the io form: one lane per entry of the ecall side list writes a0 / a1 / t0 into its trace row's a / b / res (0 as the
+// executor records them: other chip sets read them); err |= 256 for an entry that is at no ecall row
+__global__ void io_patch_kernel(TraceRow* __restrict__ tr, size_t cycles, const EcallArg* __restrict__ args, size_t count,
+                                uint32_t* __restrict__ err) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const EcallArg e = args[k];
+    if (e.cycle >= cycles || tr[e.cycle].ins != ECALL_WORD) {
+        atomicOr(err, 256u);
+        return;
+    }
+    tr[e.cycle].a = e.a0;
+    tr[e.cycle].b = e.a1;
+    tr[e.cycle].res = e.t0;
 }
 
 // the cpu table: each access's predecessor from the scans, then the chip set's row pieces and its lookups' counts
@@ -249,6 +275,7 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
     uint32_t rs1, rs2, wreg;
     bool wr, active;
     unpack(acc[i], rs1, rs2, wreg, wr, active);
+    const bool sys = CH::io && (acc[i] >> 17 & 1);   // the io form: the row also reads x5, at tsa
     const uint32_t tsa = (uint32_t)(3 * i + 1);
     // per register: the latest access among this wave's rows up to this one (inclusive max-scan over the lanes)
     uint32_t incl[32];
@@ -259,6 +286,7 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
             if (rs1 == r) v = tsa;
             if (rs2 == r) v = tsa + 1;
             if (wr && wreg == r) v = tsa + 2;
+            if (CH::io && r == 5 && sys) v = tsa;
         }
 #pragma unroll
         for (unsigned off = 1; off < 64; off <<= 1) {
@@ -269,7 +297,7 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
         if (lane == 63) s_wave[r][wave] = v;
     }
     __syncthreads();
-    uint32_t e1 = 0, e2 = 0, e3 = 0;
+    uint32_t e1 = 0, e2 = 0, e3 = 0, e5 = 0;
 #pragma unroll
     for (unsigned r = 0; r < 32; r++) {
         uint32_t ex = __shfl_up(incl[r], 1);
@@ -279,17 +307,21 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
         if (rs1 == r) e1 = ex;
         if (rs2 == r) e2 = ex;
         if (wreg == r) e3 = ex;
+        if (CH::io && r == 5) e5 = ex;
     }
     row_tile<CH::cpu_w>(s_rows, out, (size_t)blockIdx.x * TB, n, [&](uint32_t* row) {
         Mults m;
         if (active) {
-            const TraceRow r = tr[i];
-            const Dec d = decode(r.ins);
+            TraceRow r = tr[i];
+            const Dec d = CH::io ? decode_io(r.ins) : decode(r.ins);
+            const uint32_t t0 = r.res;
+            if (CH::io && sys) r.res = 0;   // as the executor records it
             const uint32_t pb = rs2 == rs1 ? tsa : e2, pw = wr ? (wreg == rs2 ? tsa + 1 : wreg == rs1 ? tsa : e3) : 0;
-            cpu_row_i(row, r, d, wval[i], tsa, e1, pb, pw, wr ? value_at(pw, wreg, tr, wval, init) : 0, m);
+            cpu_row_i(row, r, d, wval[i], tsa, e1, pb, pw, wr ? value_at(pw, wreg, tr, wval, init, CH::io) : 0, m);
             if constexpr (CH::cf) cpu_row_cf(row, r, d, m);
             if constexpr (CH::im) cpu_row_im(row, d);
             if constexpr (CH::mem) cpu_row_mem(row, d, necw[i]);   // necw: the access list's entries per cycle at ecall rows
+            if constexpr (CH::io) cpu_row_io(row, d, t0, tsa, e5);
         } else {
             trace_cells(padding_row(end_pc), false, row);
         }
@@ -303,6 +335,10 @@ __global__ void __launch_bounds__(TB) rows_kernel(const TraceRow* __restrict__ t
         hist_add(hist, row[DW_HI], wr);
         hist_add(hist, row[SA_CHK], m.is_slt);
         hist_add(hist, row[SB_CHK], m.is_slt);
+        if constexpr (CH::io) {
+            hist_add(hist, row[DT_LO], sys);
+            hist_add(hist, row[DT_HI], sys);
+        }
         if (m.bop)
             for (unsigned k = 0; k < 4; k++)
                 atomicAdd(&byte_mult[(m.bop - 1) << 16 | ((m.ba >> (8 * k)) & 255) << 8 | ((m.bb >> (8 * k)) & 255)], 1u);
@@ -342,7 +378,7 @@ __global__ void count_kernel(const uint32_t* __restrict__ counts, size_t n_count
     if (r < n_rows) out[r] = enc(r < n_counts ? counts[r] : 0u);
 }
 
-template <bool MEM>   // MEM: rv32im-mem's 48 columns
+template <int MEM>   // 0: rv32im-elf's 42 columns; 1: rv32im-mem's 48; 2: the io form's 48 (the ecall word reads a0, a1)
 __global__ void program_prep_kernel(const uint32_t* __restrict__ words, uint32_t n_words, const Image img, size_t n_rows,
                                     uint32_t* __restrict__ out) {
     extern __shared__ uint32_t s_rows[];
@@ -359,7 +395,8 @@ __global__ void program_prep_kernel(const uint32_t* __restrict__ words, uint32_t
             program_row_im(row, ins, d);
         },
         [](uint32_t* o, const uint32_t* row) {
-            if constexpr (MEM) program_prep_row_mem(o, row, decode(row[2] | row[3] << 16));
+            if constexpr (MEM == 2) program_prep_row_io(o, row, decode(row[2] | row[3] << 16));
+            else if constexpr (MEM == 1) program_prep_row_mem(o, row, decode(row[2] | row[3] << 16));
             else program_prep_row(o, row);
         });
 }
@@ -413,11 +450,11 @@ __global__ void range_kernel(const uint32_t* __restrict__ hist, uint32_t* __rest
 // 32 lanes: the register table; fin gets the final values
 __global__ void register_kernel(const uint32_t* __restrict__ final_ts, const uint32_t* __restrict__ init,
                                 const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval,
-                                uint32_t* __restrict__ fin, uint32_t* __restrict__ out) {
+                                uint32_t* __restrict__ fin, uint32_t* __restrict__ out, uint32_t io) {
     __shared__ uint32_t s_fin[32];
     extern __shared__ uint32_t s_rows[];
     const unsigned r = threadIdx.x;
-    s_fin[r] = value_at(final_ts[r], r, tr, wval, init);
+    s_fin[r] = value_at(final_ts[r], r, tr, wval, init, io != 0);
     fin[r] = s_fin[r];
     __syncthreads();
     row_tile<REG_W>(s_rows, out, 0, 32, [&](uint32_t* row) { register_row(row, r, final_ts[r], init, s_fin); });
@@ -568,7 +605,7 @@ __global__ void __launch_bounds__(TB) mem_link_kernel(const uint32_t* __restrict
 __global__ void memop_kernel(const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval, const MemAccess* __restrict__ acc,
                              const uint32_t* __restrict__ pts, size_t count, size_t n_rows, uint32_t* __restrict__ out,
                              uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
-                             uint32_t* __restrict__ err) {
+                             uint32_t* __restrict__ err, uint32_t io) {
     extern __shared__ uint32_t s_rows[];
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     row_tile<MO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
@@ -577,11 +614,102 @@ __global__ void memop_kernel(const TraceRow* __restrict__ tr, const uint32_t* __
         if (on) {
             const MemAccess m = acc[k];
             const TraceRow r = tr[m.cycle];
-            if (!memop_row(row, m, r, decode(r.ins), wval[m.cycle], pts[k])) atomicOr(err, 32u);   // not what the instruction names
+            if (!memop_row(row, m, r, decode(r.ins), wval[m.cycle], pts[k], io != 0)) atomicOr(err, 32u);   // not what the instruction names
         }
         for (unsigned c : MO_RANGE) hist_add(hist, row[c], on);
         hist_add(shift_mult, 256u + row[G_TOP], on);   // (1, top byte) -> row 256 + x
         for (unsigned j = 0; j < 6; j++) hist_add(byte_mult, row[G_W + 2 * j] << 8 | row[G_W + 2 * j + 1], on);   // AND (op 1)
+    });
+}
+
+// ---- the io form (raiko_amd/rv32io.py): the io table from the ecall side list (args: count entries in cycle order)
+// per block of TB ecalls: ecall e takes 1 + GOT rows (GOT: necw at its cycle, what mem_keys_kernel counted); eoff[e] = the
+// rows of the block's ecalls before it (a wave scan, the waves' totals through LDS), eblk[block] = the block's rows, which
+// mscan_kernel turns into the rows before the block
+__global__ void __launch_bounds__(TB) io_offsets_kernel(const EcallArg* __restrict__ args, size_t count, const uint32_t* __restrict__ necw,
+                                                         uint32_t* __restrict__ eoff, uint32_t* __restrict__ eblk) {
+    __shared__ uint32_t s_wave[TB / 64];
+    const size_t e = (size_t)blockIdx.x * TB + threadIdx.x;
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t wgt = e < count ? 1u + necw[args[e].cycle] : 0u;   // cycle < cycles: checked on the host
+    uint32_t v = wgt;
+#pragma unroll
+    for (unsigned off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    if (lane == 63) s_wave[wave] = v;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (unsigned w = 0; w < TB / 64; w++) {
+        if (w < wave) before += s_wave[w];
+        total += s_wave[w];
+    }
+    if (e < count) eoff[e] = before + v - wgt;
+    if (threadIdx.x == 0) eblk[blockIdx.x] = total;
+}
+
+// one lane per io row: row i < total belongs to the last ecall e with first(e) = eblk[e / TB] + eoff[e] <= i (binary
+// search; first is strictly increasing) and is its head (i = first) or its word i - first - 1, whose access is that far
+// past the first access at the ecall's cycle (binary search in the access list, which is in cycle order).  Rows from
+// total on are padding at the final position.  A word row also writes its stream tuple, Montgomery, at row POS -
+// pos_start of the matrix the digest commits to (stream: n_rows x 6, zeroed before).  The block's rows leave LDS as whole
+// lines (row_tile: stride 47, odd).  err |= 256: the side list is not the trace's ecalls -- a call number that is none of
+// the three, a result, a count of stored words or a position that is not the call's, a word that is not where READ stores
+__global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, const uint32_t* __restrict__ ecalls,
+                               const uint32_t* __restrict__ necw, const uint32_t* __restrict__ eoff, const uint32_t* __restrict__ eblk,
+                               const MemAccess* __restrict__ acc, size_t mem_count, uint32_t n_input, uint32_t pos_start,
+                               uint32_t total, size_t n_rows, uint32_t* __restrict__ out, uint32_t* __restrict__ stream,
+                               uint32_t* __restrict__ hist, uint32_t* __restrict__ err) {
+    extern __shared__ uint32_t s_rows[];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    row_tile<IO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+        const bool on = i < total;
+        bool head = false, read = false, word = false;
+        const bool halted = count && args[count - 1].t0 == 0;
+        if (on) {
+            size_t lo = 0, hi = count;   // the last e with first(e) <= i
+            while (hi - lo > 1) {
+                const size_t mid = (lo + hi) / 2;
+                if (eblk[mid / TB] + eoff[mid] <= i) lo = mid;
+                else hi = mid;
+            }
+            const EcallArg e = args[lo];
+            const uint32_t first = eblk[lo / TB] + eoff[lo], got = necw[e.cycle], k = (uint32_t)i - first;
+            bool ok;
+            if (k == 0) {
+                head = true;
+                read = e.t0 == 1;
+                ok = ecalls[2 * lo] == e.cycle && io_head_row(row, e, ecalls[2 * lo + 1], got, n_input, lo > 0, lo ? 3 * args[lo - 1].cycle + 1 : 0u);
+                // the positions chain: this call starts where the one before stopped
+                ok = ok && e.pos == (lo ? args[lo - 1].pos + necw[args[lo - 1].cycle] : pos_start);
+                io_row_tail(row, e.pos, true, halted && lo + 1 == count);
+            } else {
+                word = true;
+                size_t a = 0, b = mem_count;   // the first access at the ecall's cycle
+                while (a < b) {
+                    const size_t mid = (a + b) / 2;
+                    if (acc[mid].cycle < e.cycle) a = mid + 1;
+                    else b = mid;
+                }
+                const size_t at = a + (k - 1);
+                ok = at < mem_count && k - 1 < got && e.t0 == 1;
+                const uint32_t pos = e.pos + (k - 1);
+                if (ok) ok = io_word_row(row, e, got, k - 1, acc[at]);
+                io_row_tail(row, pos, true, 0u);
+                if (ok && pos - pos_start < n_rows) {
+                    const uint32_t t[RK_RV32LINK_TUPLE] = {row[Q_PL], row[Q_PH], row[Q_V_LO], row[Q_V_HI], 0u, 0u};
+                    for (unsigned j = 0; j < RK_RV32LINK_TUPLE; j++) stream[(size_t)(pos - pos_start) * RK_RV32LINK_TUPLE + j] = enc(t[j]);
+                }
+            }
+            if (!ok) atomicOr(err, 256u);
+        } else {
+            io_row_tail(row, pos_start + (total - (uint32_t)count), false, halted);
+        }
+        for (unsigned c : IO_RANGE_ACT) hist_add(hist, row[c], on);
+        for (unsigned c : IO_RANGE_READ) hist_add(hist, row[c], read);
+        for (unsigned c : IO_RANGE_HEAD) hist_add(hist, row[c], head);
+        for (unsigned c : IO_RANGE_WORD) hist_add(hist, row[c], word);
     });
 }
 
@@ -669,6 +797,18 @@ static size_t muldiv_rows_for(size_t count) {
     return rows;
 }
 
+// the io form: the words the segment's READ ecalls stored (the access list's entries at ecall rows), the io table's rows
+static size_t io_words_of(const ExecSegmentView& v) {
+    size_t c = 0;
+    for (const auto& m : *v.mem) c += m[0] < v.trace->size() && (*v.trace)[m[0]].ins == ECALL_WORD;
+    return c;
+}
+static size_t io_rows_for(size_t count) {
+    size_t rows = 2;
+    while (rows < count) rows <<= 1;
+    return rows;
+}
+
 // rv32im-mem: the memop / memory table's rows for `count` accesses / distinct words
 static size_t mem_rows_for(size_t count) {
     size_t rows = (size_t)1 << RK_RV32MEM_MIN_LOG_ROWS;
@@ -693,6 +833,9 @@ struct ShardOut {
     size_t memop_rows = 0;
     uint32_t* memory = nullptr;
     size_t memory_rows = 0;
+    uint32_t* io = nullptr;      // the io form
+    size_t io_rows = 0;
+    uint32_t* h_publics = nullptr;
 };
 
 // the driver's scratch: one allocation, each part's offset in words from one take(), rounded to 64 words
@@ -707,8 +850,9 @@ struct Scratch {
     size_t err, hist, bmult, pmult, pins, smult, clear_end;   // [err, clear_end): zero before the first kernel
     size_t mflag, mblk, mtotal, midx;                          // rv32im
     size_t macc, mkeys, mvals, mkeys2, mvals2, mpts, necw, hblk, htotal;   // rv32im-mem
+    size_t eargs, eoff, eblk, etotal, stream, nodes;                       // the io form
     Scratch(bool cf, bool im, bool elf, bool mem, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count,
-            size_t mem_count) {
+            size_t mem_count, size_t io_rows = 0) {
         const size_t nb = n / TB, slots = std::max<uint32_t>(n_slots, 1), sw = cf ? SHIFT_USED : 1u;
         tr = take((std::max<size_t>(cycles, 1) * sizeof(TraceRow) + 3) / 4);
         ec = take(2 * std::max<size_t>(n_ecalls, 1));
@@ -742,6 +886,16 @@ struct Scratch {
             hblk = take((mc + TB - 1) / TB);
             htotal = take(1);
         }
+        eargs = eoff = eblk = etotal = stream = nodes = 0;
+        if (io_rows) {
+            const size_t ne = std::max<size_t>(n_ecalls, 1);
+            eargs = take(5 * ne);
+            eoff = take(ne);
+            eblk = take((ne + TB - 1) / TB);
+            etotal = take(1);
+            stream = take(io_rows * RK_RV32LINK_TUPLE);
+            nodes = take(2 * io_rows * 8);
+        }
     }
 };
 
@@ -764,7 +918,18 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     RK_HIP_TRY(ctx, hipMemsetAsync(err, 0, (L.clear_end - L.err) * 4, ctx->stream));
     ImageArgs<CH::elf> image;
     if constexpr (CH::elf) image = {o.img, o.image_words};
-    hipLaunchKernelGGL(prep_kernel<CH::elf>, dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
+    const size_t n_ec = CH::io ? v.ecall_args->size() : 0;
+    const EcallArg* eargs = (const EcallArg*)(w + L.eargs);
+    if constexpr (CH::io) {   // the io form of the trace: an ecall row's a / b / res are the call's a0 / a1 / t0
+        static_assert(sizeof(EcallArg) == sizeof((*v.ecall_args)[0]), "an entry is five words, as the executor records it");
+        if (n_ec) {
+            RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.eargs, v.ecall_args->data(), n_ec * sizeof(EcallArg), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(io_patch_kernel, dim3((unsigned)((n_ec + TB - 1) / TB)), dim3(TB), 0, ctx->stream, (TraceRow*)(w + L.tr),
+                               tr.size(), eargs, n_ec, err);
+            RK_TRY(rk::post_launch(ctx, "rv32 io_patch_kernel"));
+        }
+    }
+    hipLaunchKernelGGL((prep_kernel<CH::elf, CH::io>), dim3((unsigned)nb), dim3(TB), 0, ctx->stream, d_tr, tr.size(), n, w + L.ec,
                        (uint32_t)ec_flat.size() / 2, v.pc_lo, n_slots, wval, acc, pmult, pins, err, CH::im ? mflag : nullptr, image);
     RK_TRY(rk::post_launch(ctx, "rv32 prep_kernel"));
     const size_t mem_count = CH::mem ? v.mem->size() : 0;
@@ -817,8 +982,26 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     if constexpr (CH::mem) {   // one lane per memop row (before the count columns: its counts go into theirs)
         const unsigned b = (unsigned)std::min<size_t>(o.memop_rows, TB);
         hipLaunchKernelGGL(memop_kernel, dim3((unsigned)(o.memop_rows / b)), dim3(b), b * (MO_W | 1) * 4, ctx->stream, d_tr, wval, macc,
-                           w + L.mpts, mem_count, o.memop_rows, o.memop, hist, bmult, smult, err);
+                           w + L.mpts, mem_count, o.memop_rows, o.memop, hist, bmult, smult, err, CH::io ? 1u : 0u);
         RK_TRY(rk::post_launch(ctx, "rv32 memop_kernel"));
+    }
+    if constexpr (CH::io) {   // the io rows (before the count columns: its counts go into the range table's), then the digest
+        const uint32_t total = (uint32_t)(n_ec + io_words_of(v));
+        RK_HIP_TRY(ctx, hipMemsetAsync(w + L.stream, 0, o.io_rows * RK_RV32LINK_TUPLE * 4, ctx->stream));
+        if (n_ec) {
+            const unsigned eb = (unsigned)((n_ec + TB - 1) / TB);
+            hipLaunchKernelGGL(io_offsets_kernel, dim3(eb), dim3(TB), 0, ctx->stream, eargs, n_ec, w + L.necw, w + L.eoff, w + L.eblk);
+            RK_TRY(rk::post_launch(ctx, "rv32 io_offsets_kernel"));
+            hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w + L.eblk, (size_t)eb, w + L.etotal);
+            RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+        }
+        const unsigned b = (unsigned)std::min<size_t>(o.io_rows, TB);
+        hipLaunchKernelGGL(io_rows_kernel, dim3((unsigned)(o.io_rows / b)), dim3(b), b * (IO_W | 1) * 4, ctx->stream, eargs, n_ec, w + L.ec,
+                           w + L.necw, w + L.eoff, w + L.eblk, macc, mem_count, (uint32_t)v.n_input, v.in_start, total, o.io_rows, o.io,
+                           w + L.stream, hist, err);
+        RK_TRY(rk::post_launch(ctx, "rv32 io_rows_kernel"));
+        const rk_matrix m{w + L.stream, (uint32_t)o.io_rows, RK_RV32LINK_TUPLE, 1};
+        RK_TRY(rk_mmcs_commit(ctx, &m, 1, w + L.nodes, o.h_publics + 6));
     }
     if constexpr (CH::elf) {   // the tuples are in the key: each lookup table's trace is its count column
         const struct { const uint32_t* counts; size_t n_counts, n_rows; uint32_t* out; } cols[4] = {
@@ -841,7 +1024,7 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
         RK_TRY(rk::post_launch(ctx, "rv32 range_kernel"));
     }
     hipLaunchKernelGGL(register_kernel, dim3(1), dim3(32), 32 * (REG_W | 1) * 4, ctx->stream, final_ts, init, d_tr, wval,
-                       w + L.fin, o.reg);
+                       w + L.fin, o.reg, CH::io ? 1u : 0u);
     RK_TRY(rk::post_launch(ctx, "rv32 register_kernel"));
     if (CH::cf && !CH::elf) {   // after rows_kernel (and muldiv_kernel) on the stream: the counts are complete
         hipLaunchKernelGGL(shift_kernel, dim3((1u << RK_RV32CF_SHIFT_LOG_ROWS) / TB), dim3(TB), TB * (SHIFT_W | 1) * 4,
@@ -858,7 +1041,7 @@ template <int CS>
 static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const ShardOut& o) {
     using CH = Chips<CS>;
     if (!ctx || !o.cpu || !o.program || !o.reg || !o.byte || !o.range || (CH::cf && !o.shift) || (CH::im && !o.muldiv) ||
-        (CH::mem && (!o.memop || !o.memory)))
+        (CH::mem && (!o.memop || !o.memory)) || (CH::io && (!o.io || !o.h_publics)))
         return RK_ERR_INVALID;
     ExecSegmentView v;
     RK_TRY(exec_segment_view(ex, index, &v));
@@ -899,8 +1082,29 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
             return RK_ERR_INVALID;
         }
     }
+    if (CH::io) {   // a power of two >= 2 that holds every row, at most twice the cpu table; the side list the trace's ecalls
+        const size_t need = io_rows_for(v.ecall_args->size() + io_words_of(v));
+        if (o.io_rows < 2 || o.io_rows & (o.io_rows - 1) || o.io_rows > 2 * n) {
+            ctx->last_error = "rk_exec_rv32io_shard_device: the io table's rows are not a power of two from 2 up to twice the cpu table's";
+            return RK_ERR_INVALID;
+        }
+        if (o.io_rows < need) {
+            ctx->last_error = "rk_exec_rv32io_shard_device: the io table has fewer rows than the segment needs";
+            return RK_ERR_CAPACITY;
+        }
+        if (v.n_input >= ((size_t)1 << 30)) {
+            ctx->last_error = "rk_exec_rv32io_shard_device: an input of 2^30 words or more";
+            return RK_ERR_CAPACITY;
+        }
+        static_assert(sizeof(EcallArg) == sizeof((*v.ecall_args)[0]), "an entry is five words, as the executor records it");
+        if (v.ecall_args->size() != v.ecalls->size() ||
+            !io_list_ok(v.trace->data(), cycles, (const EcallArg*)v.ecall_args->data(), v.ecall_args->size())) {
+            ctx->last_error = "rk_exec_rv32io_shard_device: the ecall side list is not the trace's ecall rows in cycle order";
+            return RK_ERR_INVALID;
+        }
+    }
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const Scratch L(CH::cf, CH::im, CH::elf, CH::mem, cycles, v.ecalls->size(), n, n_slots, m_count, mem_count);
+    const Scratch L(CH::cf, CH::im, CH::elf, CH::mem, cycles, v.ecalls->size(), n, n_slots, m_count, mem_count, CH::io ? o.io_rows : 0);
     rk::DevBuf sort_tmp;   // rocPRIM's temporary storage for the sort of mem_count pairs
     size_t sort_bytes = 0;
     if (mem_count) {
@@ -929,6 +1133,18 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
     hip(hipStreamSynchronize(ctx->stream), "sync");
     rk::dev_free(ctx, base);
     if (st != RK_OK) return st;
+    if (CH::io) {
+        if (host_fin[32] & 256) {
+            ctx->last_error = "rk_exec_rv32io_shard_device: the ecall side list is not the trace's ecalls";
+            return RK_ERR_INVALID;
+        }
+        const auto& ea = *v.ecall_args;
+        const bool halted = !ea.empty() && ea.back()[1] == 0;
+        const uint32_t exit_code = halted ? ea.back()[2] : 0u;
+        const uint32_t pub[6] = {v.in_start, v.in_start + (uint32_t)io_words_of(v), (uint32_t)v.n_input, halted ? 1u : 0u,
+                                 exit_code & 0xffffu, exit_code >> 16};
+        for (unsigned j = 0; j < 6; j++) o.h_publics[j] = enc(pub[j]);
+    }
     if (CH::mem && (host_fin[32] & 32)) {
         ctx->last_error = "rk_exec_rv32mem_shard_device: an access is not the one its instruction names";
         return RK_ERR_INTERNAL;
@@ -958,7 +1174,7 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
 }
 
 // the four preprocessed matrices of an image (rk_rv32elf_prep_device): everything is checked before the first launch
-template <bool MEM>
+template <int MEM>
 static int prep_device(rk_ctx* ctx, const Image& img, const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows,
                        uint32_t* d_byte, uint32_t* d_range, uint32_t* d_shift) {
     if (!ctx || !d_program || !d_byte || !d_range || !d_shift || (n_words && !words)) return RK_ERR_INVALID;
@@ -1140,7 +1356,7 @@ int rk_rv32elf_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_
     size_t total = 0;
     RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
     if (total != n_words) return RK_ERR_INVALID;
-    return rv32::prep_device<false>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    return rv32::prep_device<0>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
     RK_GUARD_END
 }
 int rk_rv32mem_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
@@ -1151,7 +1367,7 @@ int rk_rv32mem_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_
     size_t total = 0;
     RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
     if (total != n_words) return RK_ERR_INVALID;
-    return rv32::prep_device<true>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    return rv32::prep_device<1>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
     RK_GUARD_END
 }
 int rk_exec_rv32mem_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows) {
@@ -1163,6 +1379,41 @@ int rk_exec_rv32mem_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows,
     *memop_rows = rv32::mem_rows_for(v.mem->size());
     *memory_rows = rv32::mem_rows_for(exec_mem_words(ex, index));
     return RK_OK;
+    RK_GUARD_END
+}
+int rk_rv32io_prep_device(rk_ctx* ctx, const uint32_t* seg_vaddr, const uint32_t* seg_words, uint32_t n_segs,
+                          const uint32_t* words, size_t n_words, uint32_t* d_program, size_t program_rows, uint32_t* d_byte,
+                          uint32_t* d_range, uint32_t* d_shift) {
+    RK_GUARD_BEGIN
+    rv32::Image img;
+    size_t total = 0;
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &img, &total));
+    if (total != n_words) return RK_ERR_INVALID;
+    return rv32::prep_device<2>(ctx, img, words, n_words, d_program, program_rows, d_byte, d_range, d_shift);
+    RK_GUARD_END
+}
+int rk_exec_rv32io_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows, size_t* io_rows) {
+    RK_GUARD_BEGIN
+    if (!io_rows) return RK_ERR_INVALID;
+    RK_TRY(rk_exec_rv32mem_sizes(ex, index, memop_rows, memory_rows));
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    *io_rows = rv32::io_rows_for(v.ecall_args->size() + rv32::io_words_of(v));
+    if (*io_rows > ((size_t)2 << v.seg->po2)) return RK_ERR_CAPACITY;
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32io_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows, uint32_t* d_io,
+                                size_t io_rows, uint32_t h_publics[RK_RV32IO_PUBLICS]) {
+    RK_GUARD_BEGIN
+    rv32::ShardOut o{d_cpu, d_program_mult, program_rows, d_register, d_byte_mult, d_range_mult, d_shift_mult, d_muldiv, muldiv_rows,
+                     {}, d_image_words, 0, d_memop, memop_rows, d_memory, memory_rows, d_io, io_rows, h_publics};
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
+    return rv32::shard_device<rv32::CS_IO>(ctx, ex, index, o);
     RK_GUARD_END
 }
 int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,

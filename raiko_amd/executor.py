@@ -74,6 +74,9 @@ class Execution:
     # FINAL of every touched word, ascending -- and the run's final image of the touched words {word address: word}
     journals: Optional[list] = None
     final_memory: Optional[dict] = None
+    # with record_trace: per segment (ecall rows (k, 5): cycle, t0, a0 before, a1, input position before; the input
+    # position at the segment's start) (rk_exec_ecall_args): the side data of the io form of rv32im-mem (rv32io.py)
+    ecall_args: Optional[list] = None
 
 
 class ExecutorError(RuntimeError):
@@ -152,6 +155,7 @@ def execute(elf: bytes, input_words: Sequence[int] = (), segment_limit_po2: int 
             ex.lookup_tables = [_lookup_tables(lib, handle, sg.index) for sg in segs]
             ex.rv32 = [_rv32_side(lib, handle, sg.index) for sg in segs]
             ex.mem = [mem_accesses(lib, handle, sg.index) for sg in segs]
+            ex.ecall_args = [ecall_args(lib, handle, sg.index) for sg in segs]
         if profile:
             cnt = C.c_size_t(0)
             lib.rk_exec_profile(handle, None, None, 0, C.byref(cnt))
@@ -341,6 +345,18 @@ def mem_accesses(lib, handle, index):
     out = np.zeros((max(n.value, 1), 4), dtype=np.uint32)
     _lib.check(None, lib.rk_exec_mem_accesses(handle, index, out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n)))
     return out[: n.value]
+
+
+def ecall_args(lib, handle, index):
+    """rk_exec_ecall_args -> ((k, 5) uint32: cycle, t0, a0 before, a1, input position before; the input position at the
+    segment's start)"""
+    n, pos = C.c_size_t(0), C.c_uint32(0)
+    st = lib.rk_exec_ecall_args(handle, index, None, 0, C.byref(n), C.byref(pos))
+    if st != _lib.RK_ERR_CAPACITY:
+        _lib.check(None, st)
+    out = np.zeros((max(n.value, 1), 5), dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_ecall_args(handle, index, out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n), C.byref(pos)))
+    return out[: n.value], int(pos.value)
 
 
 # the uni-stark side of the same executions.  rv32_sets and p3_exec import this module, so these lines come last: every

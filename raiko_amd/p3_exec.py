@@ -4,7 +4,7 @@ circuit (raiko_amd/p3_trace.py) or one of the rv32 chip sets (raiko_amd/rv32_set
 import ctypes as C
 from typing import Sequence
 
-from . import _lib, p3, rv32link
+from . import _lib, p3, rv32io, rv32link
 from .executor import Stepper, execute
 from .p3_trace import next_trace_shard, p3_program_air, p3_range_air, p3_shards, p3_trace_air
 from .rv32_sets import (CHIPS, KEYED_CHIPS, RV32_CHIPS, _free, _rv32_airs_of, check_rv32_chain, execute_rv32_device,
@@ -23,23 +23,27 @@ class P3Pipeline:
     proving context), proves every shard under it, checks every proof against its root, and closes it when the run ends.
     link=True (chips="rv32im-mem" only; ValueError otherwise): the shards' memories are linked (raiko_amd/rv32link.py) --
     every proof is checked with its journal as claims, the run by rv32link.check_memory_chain from the ELF's memory
-    image, and the Execution carries ex.journals and ex.final_memory."""
+    image, and the Execution carries ex.journals and ex.final_memory.  io=True (chips="rv32im-mem" only; composes with
+    link): the ecalls are bound to the run's input (raiko_amd/rv32io.py) -- every proof is checked against its slice of
+    input_words, the run by rv32io.check_io_chain, and ex.exit_code / ex.input_words_read are the verified ones."""
 
-    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace", link=False):
+    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace", link=False, io=False):
         from .hal import HipHal, make_params
         if chips not in CHIPS:
             raise ValueError("chips must be one of %s" % (CHIPS,))
         if link and chips != "rv32im-mem":
             raise ValueError("link=True needs chips=\"rv32im-mem\"")
+        if io and chips != "rv32im-mem":
+            raise ValueError("io=True needs chips=\"rv32im-mem\"")
         self.params = params if params is not None else make_params(1)
-        self.lookups, self.chips, self.link = lookups, chips, link
+        self.lookups, self.chips, self.link, self.io = lookups, chips, link, io
         ext_w = int(self.params.ext_w)
-        self.rv32_airs = _rv32_airs_of(chips, ext_w, link) if chips in RV32_CHIPS else None
+        self.rv32_airs = _rv32_airs_of(chips, ext_w, link, io) if chips in RV32_CHIPS else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
         _lib.check(self.prove_hal._ctx, self.prove_hal._lib.rk_set_params(self.prove_hal._ctx, C.byref(self.params)))
-        if link:    # the journal's digest is committed on the witness context: under the prover's parameter set
+        if link or io:    # the digests are committed on the witness context: under the prover's parameter set
             _lib.check(self.wit_hal._ctx, self.wit_hal._lib.rk_set_params(self.wit_hal._ctx, C.byref(self.params)))
         if compile_airs:
             for a in self.rv32_airs or (self.cpu_air, self.prog_air, self.range_air):
@@ -61,8 +65,8 @@ class P3Pipeline:
         todo = queue.Queue(maxsize=3)           # back-pressure: at most three shards' tables wait for the prover
         done = queue.Queue()                    # device tables the prover is through with: freed by the thread that owns their context
         proofs, checks, kept, errors, stmts, journals = [], [], [], [], [], []
-        params, rv32i, link = self.params, self.chips in RV32_CHIPS, self.link
-        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips, link=link) if self.chips in KEYED_CHIPS else None
+        params, rv32i, link, io = self.params, self.chips in RV32_CHIPS, self.link, self.io
+        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips, link=link, io=io) if self.chips in KEYED_CHIPS else None
         vk = dict(prep_root=key.root, program_log_height=key.program_log_height) if key else {}
         try:
             stepper = Stepper(elf, input_words, shard_po2)
@@ -72,7 +76,7 @@ class P3Pipeline:
             raise
         pool = ThreadPoolExecutor(max_workers=4)
         if rv32i:
-            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key, link)
+            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key, link, io)
         else:
             next_shard = lambda: next_trace_shard(stepper, self.wit_hal, (self.cpu_air, self.prog_air, self.range_air), self.lookups)
         check = verify_rv32_shard if rv32i else p3.verify
@@ -86,6 +90,8 @@ class P3Pipeline:
                         return
                     _seg, tables, bufs, init = item[:4]
                     jk = dict(journal=item[4]) if link else {}
+                    if io:
+                        jk["input_words"] = list(input_words)
                     journals.extend(item[4:])
                     pf = p3.prove(self.prove_hal, tables, init, device_traces=[None if d is None else (_ptr(d[0]), d[1]) for d in bufs],
                                   key=key.key if key else None)
@@ -137,13 +143,17 @@ class P3Pipeline:
         if link:
             ex.journals = journals
             ex.final_memory = rv32link.check_memory_chain(journals, rv32link.memory_image(elf))
+        if io and verify:
+            code, ex.input_words_read = rv32io.check_io_chain([rv32io.publics_of(t[rv32io.IO_TABLE].public_values) for t, _i in stmts],
+                                                              list(input_words))
+            ex.exit_code = ex.exit_code if code is None else code
         return ex, proofs, kept
 
 
 def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 20, params=None, device: int = 0,
-                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace", link=False):
+                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace", link=False, io=False):
     """one program through a P3Pipeline of its own"""
-    pipe = P3Pipeline(params, device, lookups, compile_airs, chips, link)
+    pipe = P3Pipeline(params, device, lookups, compile_airs, chips, link, io)
     try:
         return pipe.run(elf, input_words, shard_po2, verify, keep_tables)
     finally:
@@ -151,7 +161,7 @@ def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), 
 
 
 def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, params=None, device: int = 0, batch: int = 3,
-                         lookups=False, chips="trace", link=False):
+                         lookups=False, chips="trace", link=False, io=False):
     """ELF -> executed shards -> one uni-stark proof per shard through rk_p3_prove_shards (every proof verified inside):
     the shape of `client.prove(&pk, stdin)` on the SP1 side (provers/sp1/driver/src/lib.rs:44-57; SHARD_SIZE / SHARD_BATCH_SIZE,
     docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)
@@ -169,28 +179,39 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     shard's journal is read off its memory table on the GPU (rk_rv32mem_journal_device), its digest is the table's public
     values, the pool's verifiers check every proof with the journal as claims (rk_p3_prove_shards_claims), and the run is
     checked by verify_rv32_execution(journals=, image=) from the ELF's memory image.  The Execution then carries
-    ex.journals and ex.final_memory (the final words of everything the run touched)."""
+    ex.journals and ex.final_memory (the final words of everything the run touched).  io=True (chips="rv32im-mem" only;
+    composes with link): the ecalls are bound to input_words (raiko_amd/rv32io.py): ten traces per shard
+    (rk_exec_rv32io_shard_device) under the io key, the pool's verifiers check every proof with its slice of the input as
+    claims, and the run is checked by verify_rv32_execution(input_words=); ex.exit_code and ex.input_words_read are then
+    what that check returns."""
     from .hal import make_params
     params = params if params is not None else make_params(1)
     if chips not in CHIPS:
         raise ValueError("chips must be one of %s" % (CHIPS,))
     if link and chips != "rv32im-mem":
         raise ValueError("link=True needs chips=\"rv32im-mem\"")
+    if io and chips != "rv32im-mem":
+        raise ValueError("io=True needs chips=\"rv32im-mem\"")
     if chips in RV32_CHIPS:
         from .hal import HipHal
         hal = HipHal(device)
         key, vk = None, {}
         try:
             if chips in KEYED_CHIPS:
-                key = setup_rv32_elf(hal, elf, params, chips=chips, link=link)
+                key = setup_rv32_elf(hal, elf, params, chips=chips, link=link, io=io)
                 vk = dict(prep_root=key.root.copy(), program_log_height=key.program_log_height)
             ex, shards, dev_traces, bufs, *journals = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
-                                                                          chips=chips, key=key, link=link)
+                                                                          chips=chips, key=key, link=link, io=io)
             hal.sync()
+            claims = [rv32link.claims_of(j) for j in journals[0]] if link else [[] for _ in shards] if io else None
+            if io:    # the prover's own statement: the slice its io table's public values name
+                words = list(input_words)
+                for c, (tables, _init) in zip(claims, shards):
+                    pub = rv32io.publics_of(tables[rv32io.IO_TABLE].public_values)
+                    c += rv32io.claims_of(pub["pos_start"], words[pub["pos_start"]:pub["pos_end"]])
             try:
                 proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces,
-                                         key=key.key if key else None,
-                                         claims=[rv32link.claims_of(j) for j in journals[0]] if link else None)
+                                         key=key.key if key else None, claims=claims)
             finally:
                 for d in bufs:
                     _free(d)
@@ -201,7 +222,12 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
         if link:
             image = rv32link.memory_image(elf)
             vk.update(journals=journals[0], image=image)
-        verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None, **vk)
+        if io:
+            vk.update(input_words=list(input_words))
+        checked = verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None, **vk)
+        if io:
+            ex.exit_code, ex.input_words_read = ex.exit_code if checked[0] is None else checked[0], checked[1]
+            del vk["input_words"]
         if link:
             ex.journals, ex.final_memory = journals[0], rv32link.check_memory_chain(journals[0], image)
             del vk["journals"], vk["image"]

@@ -9,7 +9,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, p3, rv32, rv32cf, rv32elf, rv32im, rv32link, rv32mem
+from . import _lib, p3, rv32, rv32cf, rv32elf, rv32im, rv32io, rv32link, rv32mem
 from .executor import Execution, Stepper, _rv32_side
 
 
@@ -55,6 +55,12 @@ _BY_COUNT = {}
 for _cs in SETS:
     assert (_cs.keyed, _cs.n_tables) not in _BY_COUNT, "two chip sets a verifier could not tell apart"
     _BY_COUNT[_cs.keyed, _cs.n_tables] = _cs
+# the io form of rv32im-mem (raiko_amd/rv32io.py; io=True, no chip-set name of its own): a key of its own and a tenth
+# table, `io`, sized like the memory tables
+_IO = ChipSet("rv32im-mem", rv32io, "rk_exec_rv32io_shard_device", _RV32I_CF, muldiv=True, n_mem=3, mem_slack=1,
+              prep="rk_rv32io_prep_device", extra=("image", "mem", "io"))
+assert (_IO.keyed, _IO.n_tables) not in _BY_COUNT
+_BY_COUNT[_IO.keyed, _IO.n_tables] = _IO
 
 
 def _rv32_set(chips):
@@ -64,16 +70,21 @@ def _rv32_set(chips):
     return _BY_NAME[chips].module, _BY_NAME[chips]
 
 
-def _rv32_airs_of(chips, ext_w=None, link=False):
+def _rv32_airs_of(chips, ext_w=None, link=False, io=False):
     """the AIRs of one shard of chip set `chips`, in table order.  link: the rv32im-mem set with its shard memories
-    linked (raiko_amd/rv32link.py: the memory AIR sends the journal and carries its digest)"""
-    _link_ok(chips, link)
+    linked (raiko_amd/rv32link.py: the memory AIR sends the journal and carries its digest).  io: the rv32im-mem set
+    with its ecalls bound to the input (raiko_amd/rv32io.py: ten AIRs); composes with link"""
+    _link_ok(chips, link, io)
+    if io:
+        return rv32io.airs(ext_w, link)
     return (rv32link if link else _rv32_set(chips)[0]).airs(ext_w)
 
 
-def _link_ok(chips, link):
+def _link_ok(chips, link, io=False):
     if link and chips != "rv32im-mem":
         raise ValueError("link=True needs chips=\"rv32im-mem\"")
+    if io and chips != "rv32im-mem":
+        raise ValueError("io=True needs chips=\"rv32im-mem\"")
 
 
 def p3_rv32_airs(ext_w=None):
@@ -104,14 +115,18 @@ def _host_preps(cs, image, n_tables):
     return [None if m is None else p3.to_mont(m) for m in cs.module.preps_of(image)]
 
 
-def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, params=None):
+def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, params=None, io=False, input_words=None):
     """one shard of chip set `chips` per executed segment, every table built in numpy (the set's shard_tables) from
     ex.witness, ex.rv32 and what else the set takes (image: rv32elf.program_image(elf); ex.mem) -> [(tables, init
     words)], init = the state digests as in p3_shards.  A keyed set's lookup tables carry their preprocessed matrix in
     Table.prep (p3.setup commits them).  link (rv32im-mem): rv32link's AIRs, the memory table's public values the digest
-    of the shard's journal under `params` (None: the SP1 preset) -> [(tables, init words, journal)]."""
+    of the shard's journal under `params` (None: the SP1 preset) -> [(tables, init words, journal)].  io (rv32im-mem,
+    with input_words, the run's input): rv32io's ten tables from ex.ecall_args, the io table's public values the stream
+    positions, N_INPUT, the exit and the digest of the shard's slice of the input; the result's shape is link's."""
     module, cs = _rv32_set(chips)
-    _link_ok(chips, link)
+    _link_ok(chips, link, io)
+    if io:
+        return _io_shards(ex, image, ext_w, airs, link, params, input_words)
     if link:
         module = rv32link
     if ex.witness is None or ex.rv32 is None or ("mem" in cs.extra and ex.mem is None):
@@ -126,6 +141,25 @@ def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, 
         pubs = _publics(s, start, end, len(canon))
         if link:
             pubs[rv32link.MEMORY_TABLE] = digest[0]
+        tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
+        out.append((tables, s.init_words()) + ((rv32link.journal_of_table(canon[rv32link.MEMORY_TABLE]),) if link else ()))
+    return out
+
+
+def _io_shards(ex, image, ext_w, airs, link, params, input_words):
+    """`shards` in io form"""
+    if ex.witness is None or ex.rv32 is None or ex.mem is None or ex.ecall_args is None or input_words is None:
+        raise ValueError("execute(..., record_trace=True) first, and pass the run's input_words")
+    airs = airs or rv32io.airs(ext_w, link)
+    preps = _host_preps(_IO, image, len(airs))
+    out = []
+    for s, (_code, data), (start, end, ecalls), mem, (args, pos) in zip(ex.segments, ex.witness, ex.rv32, ex.mem, ex.ecall_args):
+        canon, _pc, _regs, digest, io_pubs = rv32io.shard_tables(s, data, start, end, ecalls, image, mem, args, len(input_words), pos,
+                                                                 params=params, link=link)
+        pubs = _publics(s, start, end, len(canon))
+        pubs[rv32io.IO_TABLE] = io_pubs
+        if link:
+            pubs[rv32link.MEMORY_TABLE] = digest
         tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
         out.append((tables, s.init_words()) + ((rv32link.journal_of_table(canon[rv32link.MEMORY_TABLE]),) if link else ()))
     return out
@@ -163,22 +197,27 @@ def p3_rv32mem_shards(ex: Execution, image, ext_w=None, airs=None):
     return shards("rv32im-mem", ex, image, ext_w, airs)
 
 
-def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, link=False):
+def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, link=False, io=False):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
     rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key) /
     rk_exec_rv32mem_shard_device ("rv32im-mem", key likewise): segment `index` of an open executor as the tables of a
     shard of that chip set, written on hal's GPU -> (tables without host traces, [(device buffer, log_height)] per
     table, init words).  link (rv32im-mem, airs rv32link's): after the tables are written rk_rv32mem_journal_device reads
     the memory table, its digest (under the parameter set of hal's context, which must be the prover's) becomes that
-    table's public values and the journal (k, 3) uint32 is handed back as a fourth element"""
+    table's public values and the journal (k, 3) uint32 is handed back as a fourth element.  io (rv32im-mem, airs
+    rv32io's, key from setup_rv32_elf(io=True)): rk_exec_rv32io_shard_device writes the ten tables of the io form and
+    hands back the io table's public values, the digest of the shard's slice of the input among them (committed under
+    the parameter set of hal's context, which must be the prover's)"""
     _module, cs = _rv32_set(chips)
-    _link_ok(chips, link)
+    _link_ok(chips, link, io)
+    if io:
+        cs = _IO
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
     if cs.keyed:
-        if key is None or key.chips != chips:
-            raise ValueError("chips=\"%s\" needs the Rv32Key of setup_rv32_elf(chips=\"%s\")" % (chips, chips))
+        if key is None or key.chips != chips or key.io != io:
+            raise ValueError("chips=\"%s\" needs the Rv32Key of setup_rv32_elf(chips=\"%s\"%s)" % (chips, chips, ", io=True" if io else ""))
         rows.value = 1 << key.program_log_height
     else:
         _lib.check(None, lib.rk_exec_rv32_sizes(handle, index, C.byref(rows)))
@@ -188,7 +227,7 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
     if cs.muldiv:
         _lib.check(None, lib.rk_exec_rv32im_sizes(handle, index, C.byref(sized[0])))
     if cs.n_mem:    # a segment with more accesses than twice its cycles is refused here (RK_ERR_CAPACITY)
-        _lib.check(None, lib.rk_exec_rv32mem_sizes(handle, index, *[C.byref(r) for r in sized[cs.muldiv:]]))
+        _lib.check(None, getattr(lib, "rk_exec_rv32io_sizes" if io else "rk_exec_rv32mem_sizes")(handle, index, *[C.byref(r) for r in sized[cs.muldiv:]]))
     logs += [r.value.bit_length() - 1 for r in sized]
     counts += [r.value for r in sized]
     if len(airs) != len(logs):
@@ -200,6 +239,9 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
                  C.c_void_p(key.d_words.ptr)]
     for b, n in zip(bufs, counts):
         args += [C.c_void_p(b.ptr)] + ([] if n is None else [n])
+    io_pubs = np.zeros(rv32io.N_PUBLIC_IO, dtype=np.uint32)
+    if io:
+        args.append(io_pubs.ctypes.data_as(_lib.u32p))
     try:
         _lib.check(hal._ctx, getattr(lib, cs.entry)(hal._ctx, handle, index, *args))
     except Exception:
@@ -207,6 +249,8 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
             b.free()
         raise
     pubs = _publics(seg, start, end, len(logs))
+    if io:
+        pubs[rv32io.IO_TABLE] = io_pubs
     journal = ()
     if link:
         try:
@@ -240,13 +284,13 @@ def journal_device(hal, d_memory, log_rows, keep=False):
             b.free()
 
 
-def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None, link=False):
+def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None, link=False, io=False):
     """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) or
     rv32im-mem (nine) shard written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf" /
     "rv32im-mem") -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words),
-    or None after the last.  link: as rv32_shard_device, the journal a fifth element"""
+    or None after the last.  link: as rv32_shard_device, the journal a fifth element.  io: as rv32_shard_device"""
     seg = stepper.step()
-    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key, link))
+    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key, link, io))
 
 
 def _free(bufs):
@@ -257,20 +301,20 @@ def _free(bufs):
 
 
 def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
-                        chips="rv32i", key=None, link=False):
+                        chips="rv32i", key=None, link=False, io=False):
     """ELF -> rv32i (rv32i-cf, rv32im, rv32im-elf) shards whose tables are written on hal's GPU, one segment at a time
     (the executor's trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables,
     init)], [device traces], [[(device buffer, log_height)]] to free).  key: the Rv32Key of chips="rv32im-elf" (its AIRs
     are the shards').  link (rv32im-mem; key from setup_rv32_elf(link=True)): the shards' memories linked, the journals
-    a fifth element of the result"""
+    a fifth element of the result.  io (rv32im-mem; key from setup_rv32_elf(io=True)): the io form's ten tables"""
     from .hal import _ptr
-    _link_ok(chips, link)
-    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w, link))
+    _link_ok(chips, link, io)
+    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w, link, io))
     st = Stepper(elf, input_words, shard_po2)
     out, dev, metas, journals = [], [], [], []
     try:
         while True:
-            item = next_rv32_shard(st, hal, airs, chips, key, link)
+            item = next_rv32_shard(st, hal, airs, chips, key, link, io)
             if item is None:
                 break
             seg, tables, bufs, init = item[:4]
@@ -317,7 +361,7 @@ def rv32_publics(shards):
 
 
 def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None, journals=None,
-                          image=None):
+                          image=None, input_words=None):
     """Checks a run proven with the rv32i, rv32i-cf, rv32im, rv32im-elf or rv32im-mem chip set: every shard's proof
     (verify_rv32_shard), then check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards /
     p3_rv32cf_shards / p3_rv32im_shards / execute_rv32_device give them.  prep_root, program_log_height: the verifying
@@ -326,23 +370,28 @@ def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=
     free.  journals (one per shard) with image (rv32link.memory_image(elf)): the run was proven with link=True; every
     proof is checked with its journal (verify_rv32_shard), and after check_rv32_chain the journals are replayed from the
     ELF's memory image (rv32link.check_memory_chain): INIT of every touched word is what the shards before left there.
-    Raises ValueError naming the shard; returns True."""
+    input_words (the run's input; the run was proven with io=True, raiko_amd/rv32io.py): every proof is checked against
+    its slice of the input (verify_rv32_shard), and rv32io.check_io_chain binds the shards' stream positions to each other
+    and to the input's length; the result is then (exit code -- None for a run that has not halted --, input words read)
+    in place of True.  Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
     if journals is not None and (len(journals) != len(shards) or image is None):
         raise ValueError("journals: one per shard, with the ELF's memory image")
     for k, ((tables, init, *_j), pf) in enumerate(zip(shards, proofs)):
         rc = verify_rv32_shard(tables, pf, init, params, prep_root, program_log_height,
-                               journal=None if journals is None else journals[k])
+                               journal=None if journals is None else journals[k], input_words=input_words)
         if rc != 0:
             raise ValueError("shard %d: the proof does not verify (reason %d)" % (k, rc))
     check_rv32_chain(rv32_publics(shards), entry_pc)
     if journals is not None:
         rv32link.check_memory_chain(journals, image)
+    if input_words is not None:
+        return rv32io.check_io_chain([rv32io.publics_of(sh[0][rv32io.IO_TABLE].public_values) for sh in shards], input_words)
     return True
 
 
-def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None, journal=None) -> int:
+def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None, journal=None, input_words=None) -> int:
     """rk_p3_verify of one rv32i (five tables), rv32i-cf (six) or rv32im (seven) shard with the register / byte / range
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
@@ -352,22 +401,46 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
     refused (reason 2) unless 0 < log height <= the cpu table's + 1.  journal: the shard was proven with link=True
     (rv32link's AIRs): the digest of the journal at the proof's memory-table height is recomputed and must be that
     table's public values (reason 2 otherwise, also for a journal that is malformed or taller than the table); the proof
-    is then verified with the journal's tuples as receive claims (rk_p3_verify_claims)"""
+    is then verified with the journal's tuples as receive claims (rk_p3_verify_claims).  input_words: the shard was
+    proven with io=True (rv32io's ten AIRs, under the io key): the io table's public values must fit the input (N_INPUT
+    its length, POS_START <= POS_END <= N_INPUT), the digest of input_words[POS_START:POS_END] at the proof's io-table
+    height is recomputed and must be the table's (reason 2 otherwise), and the slice's stream tuples are added as receive
+    claims on BUS_INPUT, next to the journal's when there is one"""
     vt = rv32_verifier_tables(tables, proof, prep_root, program_log_height)
     if vt is None:
         return 2
-    if journal is None:
+    claims = []
+    if input_words is not None:
+        io = vt[rv32io.IO_TABLE] if len(vt) > rv32io.IO_TABLE else None
+        if io is None or io.public_values.size != rv32io.N_PUBLIC_IO:
+            raise ValueError("input_words go with the ten tables of an rv32im-mem shard proven with io=True")
+        pub = rv32io.publics_of(io.public_values)
+        words = rv32io.slice_of(pub, input_words)
+        if words is None:
+            return 2
+        try:
+            digest = rv32io.stream_root(pub["pos_start"], words, io.log_height, params)
+        except _lib.RkError:
+            return 2
+        if not np.array_equal(digest, pub["digest"]):
+            return 2
+        claims += rv32io.claims_of(pub["pos_start"], words)
+    elif len(vt) > rv32io.IO_TABLE:
+        raise ValueError("the ten tables of an io shard are verified with input_words")
+    if journal is not None:
+        bd = vt[rv32link.MEMORY_TABLE] if len(vt) > rv32link.MEMORY_TABLE else None
+        if bd is None or bd.public_values.size != rv32link.N_DIGEST:
+            raise ValueError("a journal goes with the nine tables of a linked rv32im-mem shard")
+        try:
+            digest = rv32link.journal_root(journal, bd.log_height, params)
+        except _lib.RkError:
+            return 2
+        if not np.array_equal(digest, bd.public_values):
+            return 2
+        claims += rv32link.claims_of(journal)
+    if journal is None and input_words is None:
         return p3.verify(vt, proof, init, params, prep_root=prep_root)
-    bd = vt[rv32link.MEMORY_TABLE] if len(vt) > rv32link.MEMORY_TABLE else None
-    if bd is None or bd.public_values.size != rv32link.N_DIGEST:
-        raise ValueError("a journal goes with the nine tables of a linked rv32im-mem shard")
-    try:
-        digest = rv32link.journal_root(journal, bd.log_height, params)
-    except _lib.RkError:
-        return 2
-    if not np.array_equal(digest, bd.public_values):
-        return 2
-    return p3.verify(vt, proof, init, params, prep_root=prep_root, claims=rv32link.claims_of(journal))
+    return p3.verify(vt, proof, init, params, prep_root=prep_root, claims=claims)
 
 
 def rv32_verifier_tables(tables, proof, prep_root=None, program_log_height=None):
@@ -410,9 +483,9 @@ class Rv32Key:
     rk_exec_rv32elf_shard_device compares the executed words with), .airs the seven AIRs.  close() frees the device
     memory."""
 
-    def __init__(self, image, seg_vaddr, seg_words, key, d_words, program_log_height, airs, chips="rv32im-elf"):
+    def __init__(self, image, seg_vaddr, seg_words, key, d_words, program_log_height, airs, chips="rv32im-elf", io=False):
         self.image, self.seg_vaddr, self.seg_words, self.key, self.d_words = image, seg_vaddr, seg_words, key, d_words
-        self.root, self.program_log_height, self.airs, self.chips = key.root, program_log_height, airs, chips
+        self.root, self.program_log_height, self.airs, self.chips, self.io = key.root, program_log_height, airs, chips, io
         self._preps = None
 
     @property
@@ -422,7 +495,7 @@ class Rv32Key:
     def host_preps(self):
         """the preprocessed matrices as the chip set's prep_tables gives them (Montgomery words), in table order"""
         if self._preps is None:
-            self._preps = _host_preps(_rv32_set(self.chips)[1], self.image, len(self.airs))
+            self._preps = _host_preps(_IO if self.io else _rv32_set(self.chips)[1], self.image, len(self.airs))
         return self._preps
 
     def close(self):
@@ -432,22 +505,24 @@ class Rv32Key:
         self.key = self.d_words = None
 
 
-def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf", link=False) -> Rv32Key:
+def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf", link=False, io=False) -> Rv32Key:
     """The setup of `client.setup(ELF)` for the rv32im-elf chip set: the ELF's program image (rk_exec_program_image), the
     four preprocessed matrices written on hal's GPU (rk_rv32elf_prep_device) and committed (rk_p3_setup) -> Rv32Key.
     params: the parameter set to put hal's context under first (None: the context's current one); ext_w: the AIRs'
     extension (default params' / the context's).  chips="rv32im-mem": that chip set's key (rk_rv32mem_prep_device: the
     program matrix has 48 columns) and nine AIRs.  link (rv32im-mem): the nine AIRs are rv32link's; the key itself --
-    the preprocessed matrices, their heights, the root -- is the same either way."""
+    the preprocessed matrices, their heights, the root -- is the same either way.  io (rv32im-mem): the key of the io
+    form (rk_rv32io_prep_device: the ecall word's tuple reads a0 and a1; another root than rv32im-mem's) and rv32io's ten
+    AIRs."""
     if chips not in KEYED_CHIPS:
         raise ValueError("chips must be one of %s" % (KEYED_CHIPS,))
-    _link_ok(chips, link)
-    cs = _rv32_set(chips)[1]
+    _link_ok(chips, link, io)
+    cs = _IO if io else _rv32_set(chips)[1]
     lib = _lib.load()
     if params is not None:
         _lib.check(hal._ctx, lib.rk_set_params(hal._ctx, C.byref(params)))
     if airs is None:
-        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w, link)
+        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w, link, io)
     vaddr, count, words = program_image_c(elf)
     rows = 2
     while rows < words.size:
@@ -475,4 +550,4 @@ def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="r
         for b in bufs.values():
             b.free()
     image = [(int(v), words[at - int(c):at].astype(np.int64)) for v, c, at in zip(vaddr, count, np.cumsum(count))]
-    return Rv32Key(image, vaddr, count, key, d_words, logs[1], airs, chips)
+    return Rv32Key(image, vaddr, count, key, d_words, logs[1], airs, chips, io)

@@ -19,7 +19,8 @@ multiset of real boundary rows equal the journal's tuples (limbs of a real row a
 journal's limbs are 14 / 16-bit by construction).  check_memory_chain replays the journals from the ELF's memory image
 (rk_exec_memory_image): INIT must be the image's word, then the image's word becomes FINAL.
 
-STILL FREE: what an ecall writes and the a0 it leaves.  COST: the verifier's work is linear in the touched words
+STILL FREE: what an ecall writes and the a0 it leaves -- unless the run is also proven with io=True (rv32io.py), which
+binds both to the run's input; the journal RK_ECALL_COMMIT appends to is then what remains.  COST: the verifier's work is linear in the touched words
 (digest, claim sum, replay); a succinct link (a Merkle image, shared challenges) would bind the same table and remains a
 follow-up.  The FRI statements (fri_*) over a linked proof are out of scope: their captures replay rk_p3_verify_key and
 stop at reason 8.

@@ -47,8 +47,9 @@ WL + 2^14 WH with a 30-bit gap would not do: p < 2^31, so p - d fits a 30-bit ga
 address -- two parallel histories -- cannot be written.
 
 STILL FREE: INIT of every touched word -- the boundary to the previous shard's FINAL and to the ELF's data image is not
-proven; shard k + 1 may start a word from any value -- what an ecall writes, and the a0 it leaves.  The boundary
-table is what a cross-shard link (a digest, shared challenges or a Merkle image) would bind.
+proven; shard k + 1 may start a word from any value (rv32link.py binds it) -- what an ecall writes, and the a0 it leaves
+(rv32io.py, io=True, binds both to the run's input and exit code; what then remains free is the journal RK_ECALL_COMMIT
+appends to).  The boundary table is what a cross-shard link (a digest, shared challenges or a Merkle image) would bind.
 
 `shard_tables` builds a shard's nine traces in numpy: the yardstick for rk_exec_rv32mem_shard_device."""
 import numpy as np
@@ -119,8 +120,10 @@ def program_air(ext_w=None):
     return b.build()
 
 
-def memop_air(ext_w=None):
-    """-> the memop Air; its `constraint_names` maps the name of each constraint to its index"""
+def memop_air(ext_w=None, io=False):
+    """-> the memop Air; its `constraint_names` maps the name of each constraint to its index.  io (rv32io.py): an ECW
+    row obeys SW's constraints -- its tuple is an io word row's (16, TS, AD, 0, V, 0): AD = A + MI, N = BB = the bytes of
+    B -- and nothing about it is free"""
     from . import p3
     b = p3.AirBuilder(MEMOP_COLS, 0, p3.EXT_W if ext_w is None else ext_w)
     L = b.local
@@ -147,7 +150,7 @@ def memop_air(ext_w=None):
     for tag, c in (("k0", G_K0), ("k1", G_K1), ("o0", G_O0), ("o1", G_O1)):
         named("bool " + tag, L(c) * (L(c) - 1))
     # the address: A + MI = AD + 2^32 K1 (not on an ECW row, whose A and MI are 0 and whose address is the witness's)
-    cpu_row = mult - ecw
+    cpu_row = mult if io else mult - ecw
     named("addr lo", cpu_row * (L(G_A_LO) + L(G_MI_LO) - L(G_AD_LO) - L(G_K0) * 65536))
     named("addr hi", cpu_row * (L(G_A_HI) + L(G_MI_HI) + L(G_K0) - L(G_AD_HI) - L(G_K1) * 65536))
     o0, o1 = L(G_O0), L(G_O1)
@@ -168,8 +171,9 @@ def memop_air(ext_w=None):
     named("n lo", L(G_N_LO) - half(n, 0))
     named("n hi", L(G_N_HI) - half(n, 2))
     store, load = sb + sh + sw, lb + lh + lw + lbu + lhu
-    named("b lo", store * (L(G_B_LO) - half(bb, 0)))
-    named("b hi", store * (L(G_B_HI) - half(bb, 2)))
+    word_store = sw + ecw if io else sw
+    named("b lo", (store + ecw if io else store) * (L(G_B_LO) - half(bb, 0)))
+    named("b hi", (store + ecw if io else store) * (L(G_B_HI) - half(bb, 2)))
     # loads: the word stays, the result is the selected byte / half / word, extended
     for k in range(4):
         named("load keeps %d" % k, load * (n[k] - w[k]))
@@ -196,9 +200,9 @@ def memop_air(ext_w=None):
         pick = o1 if k >= 2 else 1 - o1
         named("sh %d" % k, sh * (n[k] - w[k] - pick * (bb[k & 1] - w[k])))
     for k in range(4):
-        named("sw %d" % k, sw * (n[k] - bb[k]))
+        named("sw %d" % k, word_store * (n[k] - bb[k]))
     # an ECW row matches the cpu row's short tuple (16, TS): the other eight cells are 0
-    for c in MEMOP_TUPLE[2:]:
+    for c in () if io else MEMOP_TUPLE[2:]:
         named("ecw zero %d" % c, ecw * L(c))
     # the access comes after the one it follows
     named("ts", mult * (L(G_TS) - L(G_PTS) - 1 - L(G_DL) - L(G_DH) * 16384))
@@ -305,11 +309,12 @@ def cpu_rows(tr, n, end_pc, init, ecalls, mem, strict=True):
     return t, final, final_ts, hist, byte_mult, shift_mult, sends
 
 
-def memop_rows(cpu, mem, n_rows=None):
+def memop_rows(cpu, mem, n_rows=None, io=False):
     """the memop table of an access list against the cpu table its rows answer -> (table (n_rows, MEMOP_COLS) int64,
     RANGE16 counts, BYTE counts, SHIFT counts it adds).  n_rows None: 2^log_rows(count).  OP, A, MI, B and R are the cpu
     row's (R the CLAIMED result: a forged one fails the op's result constraint), the word before and after are the
-    list's, every other column the witness of the op on them"""
+    list's, every other column the witness of the op on them.  io (rv32io.py): an ECW row is written as the store of the
+    word it leaves: A its address, B and BB the word"""
     mem = _mem(mem)
     m = mem.shape[0]
     n_rows = 1 << log_rows(m) if n_rows is None else n_rows
@@ -327,12 +332,14 @@ def memop_rows(cpu, mem, n_rows=None):
     mi = live * (row[:, MIMM_LO] | row[:, MIMM_HI] << 16)
     bv = live * (row[:, B_LO] | row[:, B_HI] << 16)
     r = live * (row[:, RES_LO] | row[:, RES_HI] << 16)
+    if io:
+        a, bv = np.where(ecw == 1, (waddr << 2) & M, a), np.where(ecw == 1, new, bv)
     ad = np.where(ecw == 1, (waddr << 2) & M, (a + mi) & M)
     k0 = live * (((a & 0xFFFF) + (mi & 0xFFFF)) >> 16)
     k1 = live * (((a >> 16) + (mi >> 16) + k0) >> 16)
     o0, o1, wl = ad & 1, (ad >> 1) & 1, (ad & 0xFFFF) >> 2
     byt = lambda v, k: (v >> (8 * k)) & 255
-    store = sb + sh + sw
+    store = sb + sh + sw + (_e if io else 0)
     r_ = t[:m]
     r_[:, G_SEL:G_SEL + 9] = sel
     r_[:, G_MULT], r_[:, G_OP], r_[:, G_TS] = 1, op, 3 * cyc + 1
