@@ -777,9 +777,9 @@ int rk_exec_rv32mem_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index,
  * constraint reads: the digest of input[POS_START .. POS_END) as stream tuples -- rk_rv32mem_journal_root of the journal
  * (position, word, 0) at the io table's height.  The verifier recomputes it from ITS input, adds the stream tuples as
  * receive claims (rk_p3_verify_claims: this is the caller's duty stated there) and chains POS over the shards.
- * CONSTRAINED: what READ stores and where, the a0 every call leaves, the exit code.  STILL FREE: the bytes COMMIT appends
- * to the journal are not read through the memory argument and the journal is no public output.  The rk_p3_fri_* statements
- * do not cover an io proof, as for linked proofs.
+ * CONSTRAINED: what READ stores and where, the a0 every call leaves, the exit code.  The bytes COMMIT appends to the
+ * journal are bound by the commit form (rk_exec_rv32commit_shard_device, below), not by this one.  The rk_p3_fri_*
+ * statements do not cover an io proof, as for linked proofs.
  * rk_exec_ecall_args: per ecall row of segment `index` (needs record_trace) five words -- cycle, t0, a0 before the call,
  * a1, input position before it -- in cycle order; *pos_start (may be NULL): the input position at the segment's start.
  * RK_ERR_CAPACITY with *n set when more than `capacity` entries.  TraceRow.a / .b of an ecall row stay 0.
@@ -804,6 +804,46 @@ int rk_exec_rv32io_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, 
                                 uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
                                 uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows, uint32_t* d_io,
                                 size_t io_rows, uint32_t h_publics[RK_RV32IO_PUBLICS]);
+/* THE COMMIT FORM OF THE IO FORM: the COMMIT journal bound (raiko_amd/rv32commit.py builds the same tables in numpy, names
+ * every column and writes the AIRs).  The io form's ten tables under the io form's key (rk_rv32io_prep_device); two differ:
+ *   memop   memop_rows x RK_RV32COMMIT_MEMOP_COLS: rv32im-mem's 64 columns and ECR, the selector of a tenth row kind (op
+ *           RK_RV32COMMIT_ECR_CODE) that obeys LW's constraints: one row per word a COMMIT reads, in the cycle-order merge
+ *           of the access list and the commit reads (a COMMIT cycle holds only reads); the memory table is built over the
+ *           same merged list
+ *   io      io_rows x RK_RV32COMMIT_IO_COLS: the io form's 47 columns, then CW, S, S0, S1, CNT, C0, C1, T0B, T1B, BH7, RML,
+ *           RMH, RMH7, JPOS, JL, JL4, JH.  After a COMMIT head with a1 != 0 come ((a0 & 3) + a1 + 3) >> 2 commit-word rows:
+ *           row k sends (17, TS, (a0 & ~3) + 4 k, 0, 0, V) to memop -- V is memory's word -- and (JL, JH, V_LO, V_HI, S,
+ *           CNT) on bus RK_RV32COMMIT_BUS, which no table receives: bytes S .. S + CNT - 1 of V go to the journal at byte
+ *           offset JPOS = JL + 2^14 JH.  S is a0 & 3 on a call's first row and 0 later, S + CNT = 4 on every row but the
+ *           call's last, and REM counts a1 down by CNT to 0.  JPOS runs through every row
+ * The io table's RK_RV32COMMIT_PUBLICS public values: the io form's 14, JPOS_START, JPOS_END, then 8 words no constraint
+ * reads: the digest of the shard's commit log -- rk_rv32mem_journal_root of the journal (jpos, word, S | CNT << 16) at the
+ * io table's height.  The verifier is HANDED the log (as the link's verifier is handed the memory journal), checks its
+ * shape, recomputes the digest, adds the log's tuples as receive claims (rk_p3_verify_claims) and cuts the journal's bytes
+ * out of it; it chains JPOS over the shards.  The log shows the bytes of a COMMIT's first and last word that the call
+ * does not select.  CONSTRAINED: every byte of the journal.  The rk_p3_fri_* statements do not cover a commit proof.
+ * rk_exec_commit_reads: per word an ecall COMMIT of segment `index` reads (needs record_trace) three words -- cycle, word
+ * address, word -- in cycle order and per call in ascending address order from a0 & ~3; *jpos_start (may be NULL): the
+ * journal's length at the segment's start.  RK_ERR_CAPACITY with *n set when more than `capacity` entries.
+ * rk_exec_mem_accesses holds none of these: it returns what it returned before.
+ * rk_exec_rv32commit_sizes: rk_exec_rv32io_sizes over the merged list and with the commit-word rows counted.
+ * rk_exec_rv32commit_shard_device: rk_exec_rv32io_shard_device in commit form; d_log (io_rows x 3 words) receives the
+ * commit log, canonical, *n_log its rows.  Refusals before any launch as rk_exec_rv32io_shard_device's, the rule "no more
+ * accesses than twice the cpu table's rows" over the merged list, and RK_ERR_INVALID for commit reads that are not the
+ * words of the trace's COMMITs in cycle order or a COMMIT of 2^25 bytes and more. */
+#define RK_RV32COMMIT_MEMOP_COLS 65
+#define RK_RV32COMMIT_IO_COLS 64
+#define RK_RV32COMMIT_BUS 14
+#define RK_RV32COMMIT_ECR_CODE 17
+#define RK_RV32COMMIT_PUBLICS 24
+int rk_exec_commit_reads(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n, uint32_t* jpos_start);
+int rk_exec_rv32commit_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows, size_t* io_rows);
+int rk_exec_rv32commit_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                    const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                    uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                    uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                    uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows, uint32_t* d_io,
+                                    size_t io_rows, uint32_t h_publics[RK_RV32COMMIT_PUBLICS], uint32_t* d_log, size_t* n_log);
 /* THE LINK BETWEEN SHARD MEMORIES (raiko_amd/rv32link.py; the first of the designs a boundary table admits: a digest).
  * With the link on, a real row of the memory table also SENDS (WL, WH, I_LO, I_HI, F_LO, F_HI) on bus RK_RV32LINK_BUS,
  * which no table receives, and the table carries 8 public values no constraint reads: the digest of the shard's JOURNAL,

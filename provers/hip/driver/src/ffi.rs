@@ -99,6 +99,11 @@ pub const RK_RV32IO_IO_COLS: u32 = 47;
 pub const RK_RV32IO_BUS: u32 = 12;
 pub const RK_RV32IO_INPUT_BUS: u32 = 13;
 pub const RK_RV32IO_PUBLICS: u32 = 14;
+pub const RK_RV32COMMIT_MEMOP_COLS: u32 = 65;
+pub const RK_RV32COMMIT_IO_COLS: u32 = 64;
+pub const RK_RV32COMMIT_BUS: u32 = 14;
+pub const RK_RV32COMMIT_ECR_CODE: u32 = 17;
+pub const RK_RV32COMMIT_PUBLICS: u32 = 24;
 pub const RK_RV32LINK_BUS: u32 = 11;
 pub const RK_RV32LINK_TUPLE: u32 = 6;
 
@@ -634,6 +639,9 @@ extern "C" {
     pub fn rk_rv32io_prep_device(ctx: *mut rk_ctx, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, words: *const u32, n_words: usize, d_program: *mut u32, program_rows: usize, d_byte: *mut u32, d_range: *mut u32, d_shift: *mut u32) -> c_int;
     pub fn rk_exec_rv32io_sizes(ex: *const rk_exec, index: u32, memop_rows: *mut usize, memory_rows: *mut usize, io_rows: *mut usize) -> c_int;
     pub fn rk_exec_rv32io_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize, d_memop: *mut u32, memop_rows: usize, d_memory: *mut u32, memory_rows: usize, d_io: *mut u32, io_rows: usize, h_publics: *mut u32) -> c_int;
+    pub fn rk_exec_commit_reads(ex: *const rk_exec, index: u32, out: *mut u32, capacity: usize, n: *mut usize, jpos_start: *mut u32) -> c_int;
+    pub fn rk_exec_rv32commit_sizes(ex: *const rk_exec, index: u32, memop_rows: *mut usize, memory_rows: *mut usize, io_rows: *mut usize) -> c_int;
+    pub fn rk_exec_rv32commit_shard_device(ctx: *mut rk_ctx, ex: *const rk_exec, index: u32, seg_vaddr: *const u32, seg_words: *const u32, n_segs: u32, d_image_words: *const u32, d_cpu: *mut u32, d_program_mult: *mut u32, program_rows: usize, d_register: *mut u32, d_byte_mult: *mut u32, d_range_mult: *mut u32, d_shift_mult: *mut u32, d_muldiv: *mut u32, muldiv_rows: usize, d_memop: *mut u32, memop_rows: usize, d_memory: *mut u32, memory_rows: usize, d_io: *mut u32, io_rows: usize, h_publics: *mut u32, d_log: *mut u32, n_log: *mut usize) -> c_int;
     pub fn rk_exec_memory_image(elf: *const u8, elf_bytes: usize, out_addr: *mut u32, out_words: *mut u32, capacity: usize, n: *mut usize) -> c_int;
     pub fn rk_rv32mem_journal_device(ctx: *mut rk_ctx, d_memory: *const u32, memory_rows: usize, d_journal: *mut u32, d_link: *mut u32, d_nodes: *mut u32, n_real: *mut usize, h_root: *mut u32) -> c_int;
     pub fn rk_rv32mem_journal_root(params: *const rk_params, journal: *const u32, n: usize, log_rows: u32, root: *mut u32) -> c_int;

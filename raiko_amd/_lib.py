@@ -312,6 +312,12 @@ SYMBOLS = {
     "rk_exec_rv32io_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p]),
+    "rk_exec_commit_reads": (C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "rk_exec_rv32commit_sizes": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rk_exec_rv32commit_shard_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p,
+                                                  C.c_void_p, C.POINTER(C.c_size_t)]),
     "rk_exec_memory_image": (C.c_int, [C.c_char_p, C.c_size_t, u32p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rk_rv32mem_journal_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t), u32p]),

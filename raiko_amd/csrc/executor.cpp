@@ -123,6 +123,12 @@ struct rk_exec {
     std::vector<std::vector<std::array<uint32_t, 4>>> mem;
     std::vector<std::array<uint32_t, 4>> mem_now;
     uint32_t cycle_now = 0;
+    // per segment, with record_trace: (cycle, word address, word, word) of every word an ecall COMMIT reads, in cycle
+    // order and per call in ascending address order (rk_exec_commit_reads; the commit form of the rv32im-mem chip set):
+    // a list beside `mem`, which stays what it is; `jpos_start` the journal's length at the segment's start
+    std::vector<std::vector<std::array<uint32_t, 4>>> commit_reads;
+    std::vector<std::array<uint32_t, 4>> commit_now;
+    std::vector<uint32_t> jpos_start;
     mutable std::vector<size_t> mem_words;       // per segment: exec_mem_words's answer, SIZE_MAX until asked
     // the machine between segments (rk_exec_open / rk_exec_next_segment run it one segment at a time)
     Machine m;
@@ -313,6 +319,13 @@ int step(Machine& m, rk_exec& ex, const rk_exec_opts& o, size_t& in_pos, std::st
                     uint32_t src = m.x[10], len = m.x[11];
                     if (ex.journal.size() + (size_t)len > ((size_t)1 << 24)) return trap("journal larger than 16 MiB");
                     for (uint32_t i = 0; i < len; i++) ex.journal.push_back(m.load_byte(src + i));
+                    if (row && len) {
+                        const uint32_t n_words = ((src & 3u) + len + 3u) >> 2;
+                        for (uint32_t k = 0; k < n_words; k++) {
+                            const uint32_t ad = (src & ~3u) + 4 * k, w = m.load_word(ad);
+                            ex.commit_now.push_back({ex.cycle_now, ad >> 2, w, w});
+                        }
+                    }
                     break;
                 }
                 default: return trap("unknown ecall");
@@ -375,9 +388,10 @@ int exec_next(rk_exec* ex, int* more) {
     std::copy(m.x, m.x + 32, regs.begin());
     std::vector<std::array<uint32_t, 2>> ecalls;
     std::vector<std::array<uint32_t, 5>> ecall_args;
-    const uint32_t in_start = (uint32_t)ex->in_pos;
+    const uint32_t in_start = (uint32_t)ex->in_pos, jpos_start = (uint32_t)ex->journal.size();
     uint32_t pc_lo = 0xffffffffu, pc_hi = 0;
     ex->mem_now.clear();
+    ex->commit_now.clear();
     if (o.record_trace) trace.reserve((size_t)std::min<uint64_t>(limit, (uint64_t)1 << 22));  // 28 bytes per cycle, no regrowth copies
     while (cycles < limit) {
         if (o.session_limit && ex->total >= o.session_limit) {
@@ -423,6 +437,9 @@ int exec_next(rk_exec* ex, int* more) {
             ex->pc_range.push_back({pc_lo, pc_hi});
             ex->mem.push_back(std::move(ex->mem_now));
             ex->mem_now.clear();
+            ex->commit_reads.push_back(std::move(ex->commit_now));
+            ex->commit_now.clear();
+            ex->jpos_start.push_back(jpos_start);
         }
         if (ex->segments.size() > (1u << 20)) { ex->error = "more than 2^20 segments"; ex->st = RK_ERR_CAPACITY; }
     }
@@ -461,7 +478,7 @@ int exec_segment_view(const rk_exec* ex, uint32_t index, ExecSegmentView* out) {
     if (ex->traces[index].size() != ex->segments[index].cycles) return RK_ERR_INTERNAL;
     *out = ExecSegmentView{&ex->segments[index], &ex->traces[index], ex->regs[index].data(), &ex->ecalls[index],
                            ex->pc_range[index][0], ex->pc_range[index][1], &ex->mem[index], &ex->ecall_args[index], ex->in_start[index],
-                           (size_t)ex->o.n_input_words};
+                           (size_t)ex->o.n_input_words, &ex->commit_reads[index], ex->jpos_start[index]};
     return RK_OK;
 }
 
@@ -646,6 +663,15 @@ int rk_exec_mem_accesses(const rk_exec* ex, uint32_t index, uint32_t* out, size_
     *n = mem.size();
     if (mem.size() > capacity || (!out && !mem.empty())) return RK_ERR_CAPACITY;
     for (size_t k = 0; k < mem.size(); k++) std::copy(mem[k].begin(), mem[k].end(), out + 4 * k);
+    return RK_OK;
+}
+int rk_exec_commit_reads(const rk_exec* ex, uint32_t index, uint32_t* out, size_t capacity, size_t* n, uint32_t* jpos_start) {
+    if (!ex || !n || index >= ex->commit_reads.size()) return RK_ERR_INVALID;
+    const auto& cr = ex->commit_reads[index];
+    *n = cr.size();
+    if (jpos_start) *jpos_start = ex->jpos_start[index];
+    if (cr.size() > capacity || (!out && !cr.empty())) return RK_ERR_CAPACITY;
+    for (size_t k = 0; k < cr.size(); k++) std::copy(cr[k].begin(), cr[k].begin() + 3, out + 3 * k);
     return RK_OK;
 }
 

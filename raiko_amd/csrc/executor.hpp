@@ -26,6 +26,10 @@ struct ExecSegmentView {
     const std::vector<std::array<uint32_t, 5>>* ecall_args;
     uint32_t in_start;                                    // the input position at the segment's start
     size_t n_input;                                       // the run's input words
+    // (cycle, word address, word, word) of every word an ecall COMMIT reads, in cycle order and per call in ascending
+    // address order from a0 & ~3: a list of its own -- `mem` holds none of them (the commit form merges the two)
+    const std::vector<std::array<uint32_t, 4>>* commit_reads;
+    uint32_t jpos_start;                                  // the journal's length at the segment's start
 };
 
 // RK_ERR_INVALID: no executor, or no recorded segment `index`; RK_ERR_INTERNAL: the trace is not seg->cycles rows long.

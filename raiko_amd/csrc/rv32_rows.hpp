@@ -18,17 +18,20 @@ constexpr unsigned CPU_W = RK_RV32_CPU_COLS, PROG_W = RK_RV32_PROGRAM_COLS, REG_
                    SHIFT_W = RK_RV32CF_SHIFT_COLS, SHIFT_USED = 9 * 256, IM_CPU_W = RK_RV32IM_CPU_COLS,
                    IM_PROG_W = RK_RV32IM_PROGRAM_COLS, MD_W = RK_RV32IM_MULDIV_COLS, MEM_CPU_W = RK_RV32MEM_CPU_COLS,
                    MO_W = RK_RV32MEM_MEMOP_COLS, BD_W = RK_RV32MEM_MEMORY_COLS, IO_CPU_W = RK_RV32IO_CPU_COLS,
-                   IO_W = RK_RV32IO_IO_COLS;
+                   IO_W = RK_RV32IO_IO_COLS, CM_MO_W = RK_RV32COMMIT_MEMOP_COLS, CM_IO_W = RK_RV32COMMIT_IO_COLS;
 // the chip set a kernel writes, and what its rows are made of
-enum ChipSet : int { CS_I, CS_CF, CS_IM, CS_ELF, CS_MEM, CS_IO };
+enum ChipSet : int { CS_I, CS_CF, CS_IM, CS_ELF, CS_MEM, CS_IO, CS_COMMIT };
 template <int CS>
 struct Chips {
     // elf: rv32im's cpu, register and muldiv rows; the program, byte, range and shift traces are count columns
     // mem: rv32im-elf with nine cpu columns appended and the memop and memory tables
     // io: rv32im-mem with its ecalls bound to the input (raiko_amd/rv32io.py): seven cpu columns more and the io table
-    static constexpr bool cf = CS != CS_I, im = CS >= CS_IM, elf = CS >= CS_ELF, mem = CS >= CS_MEM, io = CS == CS_IO;
+    // commit: the io form with the COMMIT journal bound (raiko_amd/rv32commit.py): a 65th memop column, 17 io columns more
+    static constexpr bool cf = CS != CS_I, im = CS >= CS_IM, elf = CS >= CS_ELF, mem = CS >= CS_MEM, io = CS >= CS_IO,
+                          commit = CS == CS_COMMIT;
     static constexpr unsigned cpu_w = io ? IO_CPU_W : mem ? MEM_CPU_W : im ? IM_CPU_W : cf ? CF_CPU_W : CPU_W,
-                              prog_w = im ? IM_PROG_W : cf ? CF_PROG_W : PROG_W;
+                              prog_w = im ? IM_PROG_W : cf ? CF_PROG_W : PROG_W, mo_w = commit ? CM_MO_W : MO_W,
+                              io_w = commit ? CM_IO_W : IO_W;
 };
 
 // ---- cpu columns
@@ -548,6 +551,9 @@ enum : unsigned {
     G_ONE, G_AND, G_PTS = G_AND + 6, G_DL, G_DH, G_W_LO, G_W_HI, G_N_LO, G_N_HI
 };
 static_assert(G_N_HI + 1 == MO_W, "rv32im-mem memop columns");
+// the commit form (rv32commit.py): a tenth row kind, ECR, whose selector is a 65th column
+constexpr unsigned G_ECR = MO_W, ECR_CODE = RK_RV32COMMIT_ECR_CODE;
+static_assert(G_ECR + 1 == CM_MO_W, "commit memop columns");
 enum : unsigned { B_WL, B_WH, B_I_LO, B_I_HI, B_F_LO, B_F_HI, B_FTS, B_REAL, B_GL, B_GH, B_WL4, B_SAME, B_FINV };
 static_assert(B_FINV + 1 == BD_W, "rv32im-mem memory columns");
 // the limbs a real memory row sends to RANGE16 (rv32mem.py MEMORY_RANGE)
@@ -610,12 +616,15 @@ RK_HD void program_prep_row_io(uint32_t* out, const uint32_t* full, const Dec& d
 // it at its word (0: none); `row` is zero on entry but for G_ONE.  -> whether the access is the one the instruction names:
 // its address, the loaded value, the stored word
 // io (rv32io.py): an ECW row is written as the store of the word it leaves -- A its address, B and BB the word
-RK_HD bool memop_row(uint32_t* row, const MemAccess& m, const TraceRow& r, const Dec& d, uint32_t res, uint32_t pts, bool io = false) {
-    const bool ecw = d.is_sys;
-    const uint32_t op = ecw ? EC_CODE : d.mem_op, f3 = op & 3u;
-    const unsigned sel = ecw ? 8u : d.is_store ? 5u + f3 : op < 4 ? op : op - 1;
-    const uint32_t a = ecw ? (io ? m.waddr << 2 : 0u) : r.a, mi = ecw ? 0u : d.mimm, b = ecw ? (io ? m.after : 0u) : r.b,
-                   rs = ecw ? 0u : res;
+// commit (rv32commit.py; the io form's trace, whose ecall rows hold t0 in res): an access at a COMMIT row is an ECR row,
+// LW's witness of the word it reads -- A its address, R the word; `row` has CM_MO_W cells then
+RK_HD bool memop_row(uint32_t* row, const MemAccess& m, const TraceRow& r, const Dec& d, uint32_t res, uint32_t pts, bool io = false,
+                     bool commit = false) {
+    const bool ecw = d.is_sys, ecr = ecw && commit && r.res == 2;
+    const uint32_t op = ecr ? ECR_CODE : ecw ? EC_CODE : d.mem_op, f3 = op & 3u;
+    const unsigned sel = ecr ? G_ECR : ecw ? 8u : d.is_store ? 5u + f3 : op < 4 ? op : op - 1;
+    const uint32_t a = ecw ? (io ? m.waddr << 2 : 0u) : r.a, mi = ecw ? 0u : d.mimm, b = ecr ? 0u : ecw ? (io ? m.after : 0u) : r.b,
+                   rs = ecr ? m.before : ecw ? 0u : res;
     const uint32_t ad = ecw ? m.waddr << 2 : a + mi;
     const uint32_t k0 = ((a & 0xffffu) + (mi & 0xffffu)) >> 16, k1 = ((a >> 16) + (mi >> 16) + k0) >> 16;
     const uint32_t o0 = ad & 1u, o1 = (ad >> 1) & 1u, wl = (ad & 0xffffu) >> 2, off = ad & 3u, ts = 3 * m.cycle + 1;
@@ -628,7 +637,7 @@ RK_HD bool memop_row(uint32_t* row, const MemAccess& m, const TraceRow& r, const
         {G_PTS, pts}, {G_DL, (ts - pts - 1) & 0x3fffu}, {G_DH, (ts - pts - 1) >> 14}};
     for (const auto& kv : vals) row[kv[0]] = kv[1];
     row[G_S + off] = 1;
-    const bool store = ecw ? io : d.is_store;
+    const bool store = ecw ? io && !ecr : d.is_store;
     for (unsigned k = 0; k < 4; k++) {
         row[G_W + k] = (m.before >> (8 * k)) & 255u;
         row[G_N + k] = (m.after >> (8 * k)) & 255u;
@@ -644,7 +653,7 @@ RK_HD bool memop_row(uint32_t* row, const MemAccess& m, const TraceRow& r, const
     row[G_SL] = (2 * top) & 255u;
     for (unsigned j = 0; j < 6; j++) row[G_AND + j] = row[G_W + 2 * j] & row[G_W + 2 * j + 1];
     // what the instruction names
-    if (ecw) return true;
+    if (ecw) return !ecr || m.before == m.after;
     const uint32_t half = h0 | h1 << 8, sh = 8 * off;
     uint32_t want_res = 0, want_after = m.before;
     switch (sel) {
@@ -798,6 +807,96 @@ inline bool io_list_ok(const TraceRow* tr, size_t cycles, const EcallArg* args, 
     for (size_t k = 0; k < count; k++)
         if (args[k].cycle >= cycles || (k && args[k].cycle <= args[k - 1].cycle) || tr[args[k].cycle].ins != ECALL_WORD) return false;
     return want == count;
+}
+
+// ---- the commit form (rv32commit.py): the io table's 17 columns more, the commit-word rows after a COMMIT head
+enum : unsigned { Q_CW = IO_W, Q_S, Q_S0, Q_S1, Q_CNT, Q_C0, Q_C1, Q_T0B, Q_T1B, Q_BH7, Q_RML, Q_RMH, Q_RMH7, Q_JPOS, Q_JL, Q_JL4, Q_JH };
+static_assert(Q_JH + 1 == CM_IO_W, "commit io columns");
+// the limbs sent to RANGE16 beside the io form's (rv32commit.py IO_RANGE): by a COMMIT head, by a commit-word row
+constexpr unsigned IO_RANGE_COMMIT[1] = {Q_BH7}, IO_RANGE_CW[6] = {Q_RML, Q_RMH, Q_RMH7, Q_JL, Q_JL4, Q_JH};
+constexpr uint32_t MAX_COMMIT = 1u << 25;
+
+// the words a COMMIT of a1 bytes from a0 reads
+RK_HD uint32_t commit_words(uint32_t a0, uint32_t a1) { return a1 ? ((a0 & 3u) + a1 + 3u) >> 2 : 0u; }
+
+// after io_head_row(..., got = 0 for a COMMIT): the byte countdown starts at a1.  n_reads: the commit reads at the call's
+// cycle.  -> whether they are as many as the call's words and a1 is below 2^25
+RK_HD bool io_commit_head(uint32_t* row, const EcallArg& e, uint32_t n_reads) {
+    if (e.t0 != 2) return true;
+    row[Q_REM] = e.a1;
+    return n_reads == commit_words(e.a0, e.a1) && e.a1 < MAX_COMMIT;
+}
+
+// commit-word row k of COMMIT e, whose first byte lands at journal offset jpos; m: the commit read it answers; `row` is
+// zero on entry.  In closed form from (a0, a1, k): row 0 starts at byte a0 & 3 of its word, every later one at byte 0, each
+// takes bytes to its word's end or as many as are left.  -> whether m is word k of the call
+RK_HD bool io_commit_row(uint32_t* row, const EcallArg& e, uint32_t k, uint32_t jpos, const MemAccess& m) {
+    const uint32_t off = e.a0 & 3u, s = k ? 0u : off, taken = k ? 4 * k - off : 0u, before_left = e.a1 - taken;
+    const uint32_t cnt = before_left < 4 - s ? before_left : 4 - s, left = before_left - cnt, t = 4 - s - cnt;
+    const uint32_t ad = (e.a0 & ~3u) + 4 * k, before = ad - 4, jp = jpos + taken;
+    row[Q_CW] = row[Q_ACT] = 1;
+    row[Q_TS] = 3 * e.cycle + 1;
+    row[Q_OP16] = ECR_CODE;
+    row[Q_AD_LO] = ad & 0xffffu;
+    row[Q_AD_HI] = ad >> 16;
+    row[Q_AQ] = (ad & 0xffffu) >> 2;
+    if (k) {
+        row[Q_K] = ((before & 0xffffu) + 4) >> 16;
+        row[Q_K1] = ((before >> 16) + row[Q_K]) >> 16;
+    }
+    row[Q_REM] = left;
+    row[Q_RML] = left & 0xffffu;
+    row[Q_RMH] = left >> 16;
+    row[Q_S] = s;
+    row[Q_S0] = s & 1u;
+    row[Q_S1] = s >> 1;
+    row[Q_CNT] = cnt;
+    row[Q_C0] = (cnt - 1) & 1u;
+    row[Q_C1] = (cnt - 1) >> 1;
+    row[Q_T0B] = t & 1u;
+    row[Q_T1B] = t >> 1;
+    row[Q_V_LO] = m.before & 0xffffu;
+    row[Q_V_HI] = m.before >> 16;
+    row[Q_JL] = jp & 0x3fffu;
+    row[Q_JH] = jp >> 14;
+    return m.cycle == e.cycle && m.waddr == ad >> 2 && m.before == m.after && taken < e.a1;
+}
+
+// the journal position of a row (a commit-word row: where its bytes land) and what every row derives from its own cells,
+// beside io_row_tail
+RK_HD void io_commit_tail(uint32_t* row, uint32_t jpos) {
+    row[Q_JPOS] = jpos;
+    row[Q_BH7] = 128 * row[Q_B_HI];
+    row[Q_RMH7] = 128 * row[Q_RMH];
+    row[Q_JL4] = 4 * row[Q_JL];
+}
+
+// ---- what the commit witness needs of the commit reads against the side list and the access list: per COMMIT of the side
+// list, in cycle order, the words (a0 & ~3) / 4 + k for k < commit_words, each read unchanged, and nothing else; no COMMIT
+// of 2^25 bytes and more; no entry of the access list at a COMMIT's cycle.  Host code (the shard driver refuses lists that
+// fail it before anything is launched)
+inline bool commit_list_ok(const EcallArg* args, size_t n_args, const MemAccess* reads, size_t n_reads, const MemAccess* acc,
+                           size_t n_acc) {
+    size_t at = 0, ma = 0;
+    for (size_t e = 0; e < n_args; e++) {
+        if (args[e].t0 != 2) continue;
+        if (args[e].a1 >= MAX_COMMIT) return false;
+        const uint32_t n = commit_words(args[e].a0, args[e].a1);
+        for (uint32_t k = 0; k < n; k++, at++) {
+            if (at >= n_reads) return false;
+            const MemAccess& m = reads[at];
+            if (m.cycle != args[e].cycle || m.waddr != ((args[e].a0 & ~3u) + 4 * k) >> 2 || m.before != m.after) return false;
+        }
+        while (ma < n_acc && acc[ma].cycle < args[e].cycle) ma++;
+        if (ma < n_acc && acc[ma].cycle == args[e].cycle) return false;
+    }
+    return at == n_reads;
+}
+
+// the access list memop and the memory table see: the cycle-order merge of the two (out: n_acc + n_reads entries)
+inline void merge_accesses(const MemAccess* acc, size_t n_acc, const MemAccess* reads, size_t n_reads, MemAccess* out) {
+    size_t i = 0, j = 0, o = 0;
+    while (i < n_acc || j < n_reads) out[o++] = j >= n_reads || (i < n_acc && acc[i].cycle <= reads[j].cycle) ? acc[i++] : reads[j++];
 }
 
 }  // namespace rv32

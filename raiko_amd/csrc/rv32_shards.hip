@@ -601,20 +601,22 @@ __global__ void __launch_bounds__(TB) mem_link_kernel(const uint32_t* __restrict
 }
 
 // one lane per memop row: row k < count is the witness of access k, rows past count padding (ONE = 1, the rest 0); the
-// RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms
+// RANGE16 / BYTE / SHIFT counts of the active rows go to the shard's histograms.  W: MO_W, or CM_MO_W in the commit form
+// (io = 2), where an access at a COMMIT row is an ECR row
+template <unsigned W>
 __global__ void memop_kernel(const TraceRow* __restrict__ tr, const uint32_t* __restrict__ wval, const MemAccess* __restrict__ acc,
                              const uint32_t* __restrict__ pts, size_t count, size_t n_rows, uint32_t* __restrict__ out,
                              uint32_t* __restrict__ hist, uint32_t* __restrict__ byte_mult, uint32_t* __restrict__ shift_mult,
                              uint32_t* __restrict__ err, uint32_t io) {
     extern __shared__ uint32_t s_rows[];
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    row_tile<MO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+    row_tile<W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
         row[G_ONE] = 1;
         const bool on = k < count;
         if (on) {
             const MemAccess m = acc[k];
             const TraceRow r = tr[m.cycle];
-            if (!memop_row(row, m, r, decode(r.ins), wval[m.cycle], pts[k], io != 0)) atomicOr(err, 32u);   // not what the instruction names
+            if (!memop_row(row, m, r, decode(r.ins), wval[m.cycle], pts[k], io != 0, W == CM_MO_W)) atomicOr(err, 32u);   // not what the instruction names
         }
         for (unsigned c : MO_RANGE) hist_add(hist, row[c], on);
         hist_add(shift_mult, 256u + row[G_TOP], on);   // (1, top byte) -> row 256 + x
@@ -626,27 +628,62 @@ __global__ void memop_kernel(const TraceRow* __restrict__ tr, const uint32_t* __
 // per block of TB ecalls: ecall e takes 1 + GOT rows (GOT: necw at its cycle, what mem_keys_kernel counted); eoff[e] = the
 // rows of the block's ecalls before it (a wave scan, the waves' totals through LDS), eblk[block] = the block's rows, which
 // mscan_kernel turns into the rows before the block
+// COMMIT (the commit form, raiko_amd/rv32commit.py): a COMMIT takes 1 + NCW rows, NCW = commit_words(a0, a1) from its
+// arguments alone; the same pass scans NCW -- coff / cblk: the dense index of the call's first commit-log row -- and the
+// bytes a1 of the COMMITs -- joff / jblk: the call's journal position past jpos_start
+struct CommitScan {
+    uint32_t *coff, *cblk, *joff, *jblk;
+};
+template <bool COMMIT>
+struct CommitScanOf {};   // the io form: no argument bytes
+template <>
+struct CommitScanOf<true> : CommitScan {};
+template <bool COMMIT>
 __global__ void __launch_bounds__(TB) io_offsets_kernel(const EcallArg* __restrict__ args, size_t count, const uint32_t* __restrict__ necw,
-                                                         uint32_t* __restrict__ eoff, uint32_t* __restrict__ eblk) {
-    __shared__ uint32_t s_wave[TB / 64];
+                                                         uint32_t* __restrict__ eoff, uint32_t* __restrict__ eblk, CommitScanOf<COMMIT> cs) {
+    constexpr unsigned NV = COMMIT ? 3 : 1;
+    __shared__ uint32_t s_wave[NV][TB / 64];
     const size_t e = (size_t)blockIdx.x * TB + threadIdx.x;
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t wgt = e < count ? 1u + necw[args[e].cycle] : 0u;   // cycle < cycles: checked on the host
-    uint32_t v = wgt;
+    uint32_t wgt[NV] = {};
+    if (e < count) {
+        const EcallArg a = args[e];
+        wgt[0] = 1u + necw[a.cycle];   // cycle < cycles: checked on the host
+        if constexpr (COMMIT) {
+            if (a.t0 == 2) {
+                wgt[1] = commit_words(a.a0, a.a1);
+                wgt[2] = a.a1;
+                wgt[0] = 1u + wgt[1];
+            }
+        }
+    }
+    uint32_t v[NV];
 #pragma unroll
-    for (unsigned off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(v, off);
-        if (lane >= off) v += t;
+    for (unsigned j = 0; j < NV; j++) {
+        v[j] = wgt[j];
+#pragma unroll
+        for (unsigned off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(v[j], off);
+            if (lane >= off) v[j] += t;
+        }
+        if (lane == 63) s_wave[j][wave] = v[j];
     }
-    if (lane == 63) s_wave[wave] = v;
     __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (unsigned w = 0; w < TB / 64; w++) {
-        if (w < wave) before += s_wave[w];
-        total += s_wave[w];
+#pragma unroll
+    for (unsigned j = 0; j < NV; j++) {
+        uint32_t before = 0, total = 0;
+        for (unsigned w = 0; w < TB / 64; w++) {
+            if (w < wave) before += s_wave[j][w];
+            total += s_wave[j][w];
+        }
+        uint32_t *off = eoff, *blk = eblk;
+        if constexpr (COMMIT) {
+            off = j == 0 ? eoff : j == 1 ? cs.coff : cs.joff;
+            blk = j == 0 ? eblk : j == 1 ? cs.cblk : cs.jblk;
+        }
+        if (e < count) off[e] = before + v[j] - wgt[j];
+        if (threadIdx.x == 0) blk[blockIdx.x] = total;
     }
-    if (e < count) eoff[e] = before + v - wgt;
-    if (threadIdx.x == 0) eblk[blockIdx.x] = total;
 }
 
 // one lane per io row: row i < total belongs to the last ecall e with first(e) = eblk[e / TB] + eoff[e] <= i (binary
@@ -656,16 +693,33 @@ __global__ void __launch_bounds__(TB) io_offsets_kernel(const EcallArg* __restri
 // pos_start of the matrix the digest commits to (stream: n_rows x 6, zeroed before).  The block's rows leave LDS as whole
 // lines (row_tile: stride 47, odd).  err |= 256: the side list is not the trace's ecalls -- a call number that is none of
 // the three, a result, a count of stored words or a position that is not the call's, a word that is not where READ stores
+// COMMIT (the commit form): rows of CM_IO_W words (stride 65, odd; 128 rows are 33 KiB of LDS).  `acc` is the merged list,
+// so necw at a COMMIT's cycle is the count of its commit reads.  Commit-word row k of COMMIT e is computed in closed form
+// from (a0, a1, k) (io_commit_row); its word is reads[dense], dense = cblk[e / TB] + coff[e] + k -- no search --, and its
+// log tuple goes to row `dense` of the matrix the commit log's digest commits to (clog: n_rows x 6, Montgomery, zeroed
+// before) and, canonical, of dlog (n_rows x 3).  err |= 512: a commit read that is not word k of its call
+struct CommitRows {
+    const MemAccess* reads;
+    uint32_t n_reads;
+    const uint32_t *coff, *cblk, *joff, *jblk;
+    uint32_t jpos_start, jpos_end, pos_end;
+    uint32_t *clog, *dlog;
+};
+template <bool COMMIT>
+struct CommitRowsOf {};   // the io form: no argument bytes
+template <>
+struct CommitRowsOf<true> : CommitRows {};
+template <bool COMMIT>
 __global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, const uint32_t* __restrict__ ecalls,
                                const uint32_t* __restrict__ necw, const uint32_t* __restrict__ eoff, const uint32_t* __restrict__ eblk,
                                const MemAccess* __restrict__ acc, size_t mem_count, uint32_t n_input, uint32_t pos_start,
                                uint32_t total, size_t n_rows, uint32_t* __restrict__ out, uint32_t* __restrict__ stream,
-                               uint32_t* __restrict__ hist, uint32_t* __restrict__ err) {
+                               uint32_t* __restrict__ hist, uint32_t* __restrict__ err, CommitRowsOf<COMMIT> cm) {
     extern __shared__ uint32_t s_rows[];
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    row_tile<IO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
+    row_tile<COMMIT ? CM_IO_W : IO_W>(s_rows, out, (size_t)blockIdx.x * blockDim.x, n_rows, [&](uint32_t* row) {
         const bool on = i < total;
-        bool head = false, read = false, word = false;
+        bool head = false, read = false, word = false, chead = false, cw = false;
         const bool halted = count && args[count - 1].t0 == 0;
         if (on) {
             size_t lo = 0, hi = count;   // the last e with first(e) <= i
@@ -675,15 +729,45 @@ __global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, 
                 else hi = mid;
             }
             const EcallArg e = args[lo];
-            const uint32_t first = eblk[lo / TB] + eoff[lo], got = necw[e.cycle], k = (uint32_t)i - first;
-            bool ok;
+            const uint32_t first = eblk[lo / TB] + eoff[lo], k = (uint32_t)i - first;
+            const bool is_commit = COMMIT && e.t0 == 2;
+            const uint32_t got = is_commit ? 0u : necw[e.cycle];
+            uint32_t jpos = 0;
+            if constexpr (COMMIT) jpos = cm.jpos_start + cm.jblk[lo / TB] + cm.joff[lo];
+            bool ok = true;
             if (k == 0) {
                 head = true;
                 read = e.t0 == 1;
+                chead = is_commit;
                 ok = ecalls[2 * lo] == e.cycle && io_head_row(row, e, ecalls[2 * lo + 1], got, n_input, lo > 0, lo ? 3 * args[lo - 1].cycle + 1 : 0u);
                 // the positions chain: this call starts where the one before stopped
-                ok = ok && e.pos == (lo ? args[lo - 1].pos + necw[args[lo - 1].cycle] : pos_start);
+                uint32_t prev_got = 0;
+                if (lo && !(COMMIT && args[lo - 1].t0 == 2)) prev_got = necw[args[lo - 1].cycle];
+                ok = ok && e.pos == (lo ? args[lo - 1].pos + prev_got : pos_start);
+                if constexpr (COMMIT) ok = ok && io_commit_head(row, e, necw[e.cycle]);
                 io_row_tail(row, e.pos, true, halted && lo + 1 == count);
+                if constexpr (COMMIT) io_commit_tail(row, jpos);
+            } else if (is_commit) {
+                if constexpr (COMMIT) {
+                    const uint32_t dense = cm.cblk[lo / TB] + cm.coff[lo] + (k - 1);
+                    ok = k - 1 < commit_words(e.a0, e.a1) && e.a1 < MAX_COMMIT && dense < cm.n_reads && dense < n_rows;
+                    if (ok) ok = io_commit_row(row, e, k - 1, jpos, cm.reads[dense]);
+                    const uint32_t jp = row[Q_JL] | row[Q_JH] << 14;
+                    ok = ok && jp < (1u << 30);
+                    cw = ok;   // the limbs of a row that is not the call's go to no histogram
+                    io_row_tail(row, e.pos, true, 0u);
+                    io_commit_tail(row, jp);
+                    if (ok) {
+                        const uint32_t t[RK_RV32LINK_TUPLE] = {row[Q_JL], row[Q_JH], row[Q_V_LO], row[Q_V_HI], row[Q_S], row[Q_CNT]};
+                        for (unsigned j = 0; j < RK_RV32LINK_TUPLE; j++) cm.clog[(size_t)dense * RK_RV32LINK_TUPLE + j] = enc(t[j]);
+                        cm.dlog[(size_t)dense * 3 + 0] = jp;
+                        cm.dlog[(size_t)dense * 3 + 1] = row[Q_V_LO] | row[Q_V_HI] << 16;
+                        cm.dlog[(size_t)dense * 3 + 2] = row[Q_S] | row[Q_CNT] << 16;
+                    } else {
+                        atomicOr(err, 512u);
+                        ok = true;
+                    }
+                }
             } else {
                 word = true;
                 size_t a = 0, b = mem_count;   // the first access at the ecall's cycle
@@ -697,6 +781,7 @@ __global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, 
                 const uint32_t pos = e.pos + (k - 1);
                 if (ok) ok = io_word_row(row, e, got, k - 1, acc[at]);
                 io_row_tail(row, pos, true, 0u);
+                if constexpr (COMMIT) io_commit_tail(row, jpos);
                 if (ok && pos - pos_start < n_rows) {
                     const uint32_t t[RK_RV32LINK_TUPLE] = {row[Q_PL], row[Q_PH], row[Q_V_LO], row[Q_V_HI], 0u, 0u};
                     for (unsigned j = 0; j < RK_RV32LINK_TUPLE; j++) stream[(size_t)(pos - pos_start) * RK_RV32LINK_TUPLE + j] = enc(t[j]);
@@ -704,12 +789,21 @@ __global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, 
             }
             if (!ok) atomicOr(err, 256u);
         } else {
-            io_row_tail(row, pos_start + (total - (uint32_t)count), false, halted);
+            if constexpr (COMMIT) {
+                io_row_tail(row, cm.pos_end, false, halted);
+                io_commit_tail(row, cm.jpos_end);
+            } else {
+                io_row_tail(row, pos_start + (total - (uint32_t)count), false, halted);
+            }
         }
         for (unsigned c : IO_RANGE_ACT) hist_add(hist, row[c], on);
         for (unsigned c : IO_RANGE_READ) hist_add(hist, row[c], read);
         for (unsigned c : IO_RANGE_HEAD) hist_add(hist, row[c], head);
         for (unsigned c : IO_RANGE_WORD) hist_add(hist, row[c], word);
+        if constexpr (COMMIT) {
+            for (unsigned c : IO_RANGE_COMMIT) hist_add(hist, row[c], chead && row[c] < (1u << 16));
+            for (unsigned c : IO_RANGE_CW) hist_add(hist, row[c], cw);
+        }
     });
 }
 
@@ -809,6 +903,22 @@ static size_t io_rows_for(size_t count) {
     return rows;
 }
 
+// the commit form: the access list memop and the memory table see (merge_accesses), and its distinct word addresses
+static std::vector<std::array<uint32_t, 4>> merged_list(const ExecSegmentView& v) {
+    static_assert(sizeof(MemAccess) == sizeof(std::array<uint32_t, 4>), "an access is four words, as the executor records it");
+    std::vector<std::array<uint32_t, 4>> out(v.mem->size() + v.commit_reads->size());
+    merge_accesses((const MemAccess*)v.mem->data(), v.mem->size(), (const MemAccess*)v.commit_reads->data(), v.commit_reads->size(),
+                   (MemAccess*)out.data());
+    return out;
+}
+static size_t distinct_words(const std::vector<std::array<uint32_t, 4>>& list) {
+    std::vector<uint32_t> a;
+    a.reserve(list.size());
+    for (const auto& m : list) a.push_back(m[1]);
+    std::sort(a.begin(), a.end());
+    return (size_t)(std::unique(a.begin(), a.end()) - a.begin());
+}
+
 // rv32im-mem: the memop / memory table's rows for `count` accesses / distinct words
 static size_t mem_rows_for(size_t count) {
     size_t rows = (size_t)1 << RK_RV32MEM_MIN_LOG_ROWS;
@@ -836,6 +946,8 @@ struct ShardOut {
     uint32_t* io = nullptr;      // the io form
     size_t io_rows = 0;
     uint32_t* h_publics = nullptr;
+    uint32_t* log = nullptr;     // the commit form: the commit log (io_rows x 3, canonical) and its rows
+    size_t* n_log = nullptr;
 };
 
 // the driver's scratch: one allocation, each part's offset in words from one take(), rounded to 64 words
@@ -851,8 +963,9 @@ struct Scratch {
     size_t mflag, mblk, mtotal, midx;                          // rv32im
     size_t macc, mkeys, mvals, mkeys2, mvals2, mpts, necw, hblk, htotal;   // rv32im-mem
     size_t eargs, eoff, eblk, etotal, stream, nodes;                       // the io form
+    size_t creads, coff, cblk, ctotal, joff, jblk, jtotal, clog, cnodes;   // the commit form
     Scratch(bool cf, bool im, bool elf, bool mem, size_t cycles, size_t n_ecalls, size_t n, uint32_t n_slots, size_t m_count,
-            size_t mem_count, size_t io_rows = 0) {
+            size_t mem_count, size_t io_rows = 0, bool commit = false, size_t n_reads = 0) {
         const size_t nb = n / TB, slots = std::max<uint32_t>(n_slots, 1), sw = cf ? SHIFT_USED : 1u;
         tr = take((std::max<size_t>(cycles, 1) * sizeof(TraceRow) + 3) / 4);
         ec = take(2 * std::max<size_t>(n_ecalls, 1));
@@ -896,6 +1009,19 @@ struct Scratch {
             stream = take(io_rows * RK_RV32LINK_TUPLE);
             nodes = take(2 * io_rows * 8);
         }
+        creads = coff = cblk = ctotal = joff = jblk = jtotal = clog = cnodes = 0;
+        if (io_rows && commit) {
+            const size_t ne = std::max<size_t>(n_ecalls, 1);
+            creads = take(4 * std::max<size_t>(n_reads, 1));
+            coff = take(ne);
+            cblk = take((ne + TB - 1) / TB);
+            ctotal = take(1);
+            joff = take(ne);
+            jblk = take((ne + TB - 1) / TB);
+            jtotal = take(1);
+            clog = take(io_rows * RK_RV32LINK_TUPLE);
+            cnodes = take(2 * io_rows * 8);
+        }
     }
 };
 
@@ -906,6 +1032,7 @@ template <int CS>
 static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& o, const Scratch& L, uint32_t* w,
                          const std::vector<uint32_t>& ec_flat, uint32_t n_slots, size_t m_count, void* sort_tmp, size_t sort_bytes) {
     using CH = Chips<CS>;
+    constexpr int RCS = CH::commit ? (int)CS_IO : CS;   // the commit form's cpu rows are the io form's: one instantiation
     const std::vector<TraceRow>& tr = *v.trace;
     const size_t n = (size_t)1 << v.seg->po2, nb = n / TB;
     const TraceRow* d_tr = (const TraceRow*)(w + L.tr);
@@ -962,8 +1089,8 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     RK_TRY(rk::post_launch(ctx, "rv32 scan_kernel"));
     const size_t lds = TB * (CH::cpu_w | 1) * 4;
     if (lds > 64 * 1024)   // rv32im's 133-word rows: past the default dynamic LDS limit (160 KiB per CU)
-        RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)rows_kernel<CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(rows_kernel<CS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), v.seg->end_pc, acc, wval,
+        RK_HIP_TRY(ctx, hipFuncSetAttribute((const void*)rows_kernel<RCS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(rows_kernel<RCS>, dim3((unsigned)nb), dim3(TB), lds, ctx->stream, d_tr, tr.size(), v.seg->end_pc, acc, wval,
                        blk, init, o.cpu, hist, bmult, smult, w + L.necw, n);
     RK_TRY(rk::post_launch(ctx, "rv32 rows_kernel"));
     if (CH::im) {   // the muldiv rows: count per block, scan, compact, then one lane per row (before the byte / range /
@@ -981,27 +1108,56 @@ static int shard_enqueue(rk_ctx* ctx, const ExecSegmentView& v, const ShardOut& 
     }
     if constexpr (CH::mem) {   // one lane per memop row (before the count columns: its counts go into theirs)
         const unsigned b = (unsigned)std::min<size_t>(o.memop_rows, TB);
-        hipLaunchKernelGGL(memop_kernel, dim3((unsigned)(o.memop_rows / b)), dim3(b), b * (MO_W | 1) * 4, ctx->stream, d_tr, wval, macc,
+        hipLaunchKernelGGL(memop_kernel<CH::mo_w>, dim3((unsigned)(o.memop_rows / b)), dim3(b), b * (CH::mo_w | 1) * 4, ctx->stream, d_tr, wval, macc,
                            w + L.mpts, mem_count, o.memop_rows, o.memop, hist, bmult, smult, err, CH::io ? 1u : 0u);
         RK_TRY(rk::post_launch(ctx, "rv32 memop_kernel"));
     }
     if constexpr (CH::io) {   // the io rows (before the count columns: its counts go into the range table's), then the digest
-        const uint32_t total = (uint32_t)(n_ec + io_words_of(v));
+        const uint32_t total = (uint32_t)(n_ec + io_words_of(v));   // the commit form: v.mem is the merged list
         RK_HIP_TRY(ctx, hipMemsetAsync(w + L.stream, 0, o.io_rows * RK_RV32LINK_TUPLE * 4, ctx->stream));
+        CommitScanOf<CH::commit> scan;
+        CommitRowsOf<CH::commit> cm;
+        if constexpr (CH::commit) {
+            static_assert(sizeof(MemAccess) == sizeof((*v.commit_reads)[0]), "a commit read is four words, as the executor records it");
+            const size_t n_reads = v.commit_reads->size();
+            uint32_t bytes = 0;
+            for (const auto& e : *v.ecall_args) bytes += e[1] == 2 ? e[3] : 0u;
+            RK_HIP_TRY(ctx, hipMemsetAsync(w + L.clog, 0, o.io_rows * RK_RV32LINK_TUPLE * 4, ctx->stream));
+            RK_HIP_TRY(ctx, hipMemsetAsync(o.log, 0, o.io_rows * 3 * 4, ctx->stream));
+            if (n_reads)
+                RK_HIP_TRY(ctx, hipMemcpyAsync(w + L.creads, v.commit_reads->data(), n_reads * sizeof(MemAccess), hipMemcpyHostToDevice, ctx->stream));
+            scan.coff = w + L.coff, scan.cblk = w + L.cblk, scan.joff = w + L.joff, scan.jblk = w + L.jblk;
+            cm.reads = (const MemAccess*)(w + L.creads), cm.n_reads = (uint32_t)n_reads;
+            cm.coff = scan.coff, cm.cblk = scan.cblk, cm.joff = scan.joff, cm.jblk = scan.jblk;
+            cm.jpos_start = v.jpos_start, cm.jpos_end = v.jpos_start + bytes;
+            cm.pos_end = v.in_start + (uint32_t)(total - n_ec - n_reads);
+            cm.clog = w + L.clog, cm.dlog = o.log;
+        }
         if (n_ec) {
             const unsigned eb = (unsigned)((n_ec + TB - 1) / TB);
-            hipLaunchKernelGGL(io_offsets_kernel, dim3(eb), dim3(TB), 0, ctx->stream, eargs, n_ec, w + L.necw, w + L.eoff, w + L.eblk);
+            hipLaunchKernelGGL(io_offsets_kernel<CH::commit>, dim3(eb), dim3(TB), 0, ctx->stream, eargs, n_ec, w + L.necw, w + L.eoff,
+                               w + L.eblk, scan);
             RK_TRY(rk::post_launch(ctx, "rv32 io_offsets_kernel"));
             hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w + L.eblk, (size_t)eb, w + L.etotal);
             RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+            if constexpr (CH::commit) {
+                hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w + L.cblk, (size_t)eb, w + L.ctotal);
+                RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+                hipLaunchKernelGGL(mscan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w + L.jblk, (size_t)eb, w + L.jtotal);
+                RK_TRY(rk::post_launch(ctx, "rv32 mscan_kernel"));
+            }
         }
         const unsigned b = (unsigned)std::min<size_t>(o.io_rows, TB);
-        hipLaunchKernelGGL(io_rows_kernel, dim3((unsigned)(o.io_rows / b)), dim3(b), b * (IO_W | 1) * 4, ctx->stream, eargs, n_ec, w + L.ec,
-                           w + L.necw, w + L.eoff, w + L.eblk, macc, mem_count, (uint32_t)v.n_input, v.in_start, total, o.io_rows, o.io,
-                           w + L.stream, hist, err);
+        hipLaunchKernelGGL(io_rows_kernel<CH::commit>, dim3((unsigned)(o.io_rows / b)), dim3(b), b * (CH::io_w | 1) * 4, ctx->stream, eargs,
+                           n_ec, w + L.ec, w + L.necw, w + L.eoff, w + L.eblk, macc, mem_count, (uint32_t)v.n_input, v.in_start, total,
+                           o.io_rows, o.io, w + L.stream, hist, err, cm);
         RK_TRY(rk::post_launch(ctx, "rv32 io_rows_kernel"));
         const rk_matrix m{w + L.stream, (uint32_t)o.io_rows, RK_RV32LINK_TUPLE, 1};
         RK_TRY(rk_mmcs_commit(ctx, &m, 1, w + L.nodes, o.h_publics + 6));
+        if constexpr (CH::commit) {
+            const rk_matrix cl{w + L.clog, (uint32_t)o.io_rows, RK_RV32LINK_TUPLE, 1};
+            RK_TRY(rk_mmcs_commit(ctx, &cl, 1, w + L.cnodes, o.h_publics + RK_RV32IO_PUBLICS + 2));
+        }
     }
     if constexpr (CH::elf) {   // the tuples are in the key: each lookup table's trace is its count column
         const struct { const uint32_t* counts; size_t n_counts, n_rows; uint32_t* out; } cols[4] = {
@@ -1041,10 +1197,16 @@ template <int CS>
 static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const ShardOut& o) {
     using CH = Chips<CS>;
     if (!ctx || !o.cpu || !o.program || !o.reg || !o.byte || !o.range || (CH::cf && !o.shift) || (CH::im && !o.muldiv) ||
-        (CH::mem && (!o.memop || !o.memory)) || (CH::io && (!o.io || !o.h_publics)))
+        (CH::mem && (!o.memop || !o.memory)) || (CH::io && (!o.io || !o.h_publics)) || (CH::commit && (!o.log || !o.n_log)))
         return RK_ERR_INVALID;
     ExecSegmentView v;
     RK_TRY(exec_segment_view(ex, index, &v));
+    const ExecSegmentView vu = v;   // as the executor recorded it; the commit form's v.mem is the merged list
+    std::vector<std::array<uint32_t, 4>> merged;
+    if (CH::commit) {
+        merged = merged_list(v);
+        v.mem = &merged;
+    }
     const size_t cycles = v.trace->size(), n = (size_t)1 << v.seg->po2;
     if (cycles > n || n % TB) return RK_ERR_INTERNAL;
     uint32_t n_slots = 0;
@@ -1067,7 +1229,8 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
         }
         if (o.muldiv_rows & (o.muldiv_rows - 1) || o.muldiv_rows > std::max<size_t>(n, muldiv_rows_for(0))) return RK_ERR_INVALID;
     }
-    const size_t mem_count = CH::mem ? v.mem->size() : 0, mem_words = CH::mem ? exec_mem_words(ex, index) : 0;
+    const size_t mem_count = CH::mem ? v.mem->size() : 0,
+                 mem_words = CH::commit ? distinct_words(merged) : CH::mem ? exec_mem_words(ex, index) : 0;
     if (CH::mem) {   // powers of two that hold every row, at most twice the cpu table; nothing is written otherwise
         const struct { size_t rows, need; const char* what; } t[2] = {{o.memop_rows, mem_rows_for(mem_count), "memop"},
                                                                       {o.memory_rows, mem_rows_for(mem_words), "memory"}};
@@ -1103,8 +1266,19 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
             return RK_ERR_INVALID;
         }
     }
+    if (CH::commit) {   // the commit reads are the words of the trace's COMMITs; the journal stays below 2^30 bytes
+        uint64_t bytes = vu.jpos_start;
+        for (const auto& e : *vu.ecall_args) bytes += e[1] == 2 ? e[3] : 0u;
+        if (bytes >= ((uint64_t)1 << 30) ||
+            !commit_list_ok((const EcallArg*)vu.ecall_args->data(), vu.ecall_args->size(), (const MemAccess*)vu.commit_reads->data(),
+                            vu.commit_reads->size(), (const MemAccess*)vu.mem->data(), vu.mem->size())) {
+            ctx->last_error = "rk_exec_rv32commit_shard_device: the commit reads are not the words of the trace's COMMITs in cycle order";
+            return RK_ERR_INVALID;
+        }
+    }
     RK_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const Scratch L(CH::cf, CH::im, CH::elf, CH::mem, cycles, v.ecalls->size(), n, n_slots, m_count, mem_count, CH::io ? o.io_rows : 0);
+    const Scratch L(CH::cf, CH::im, CH::elf, CH::mem, cycles, v.ecalls->size(), n, n_slots, m_count, mem_count, CH::io ? o.io_rows : 0,
+                    CH::commit, CH::commit ? v.commit_reads->size() : 0);
     rk::DevBuf sort_tmp;   // rocPRIM's temporary storage for the sort of mem_count pairs
     size_t sort_bytes = 0;
     if (mem_count) {
@@ -1141,9 +1315,20 @@ static int shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const Sh
         const auto& ea = *v.ecall_args;
         const bool halted = !ea.empty() && ea.back()[1] == 0;
         const uint32_t exit_code = halted ? ea.back()[2] : 0u;
-        const uint32_t pub[6] = {v.in_start, v.in_start + (uint32_t)io_words_of(v), (uint32_t)v.n_input, halted ? 1u : 0u,
+        const uint32_t pub[6] = {v.in_start, v.in_start + (uint32_t)io_words_of(vu), (uint32_t)v.n_input, halted ? 1u : 0u,
                                  exit_code & 0xffffu, exit_code >> 16};
         for (unsigned j = 0; j < 6; j++) o.h_publics[j] = enc(pub[j]);
+        if (CH::commit) {
+            if (host_fin[32] & 512) {
+                ctx->last_error = "rk_exec_rv32commit_shard_device: a commit read is not the word of its call";
+                return RK_ERR_INVALID;
+            }
+            uint32_t bytes = 0;
+            for (const auto& e : ea) bytes += e[1] == 2 ? e[3] : 0u;
+            o.h_publics[RK_RV32IO_PUBLICS] = enc(v.jpos_start);
+            o.h_publics[RK_RV32IO_PUBLICS + 1] = enc(v.jpos_start + bytes);
+            *o.n_log = v.commit_reads->size();
+        }
     }
     if (CH::mem && (host_fin[32] & 32)) {
         ctx->last_error = "rk_exec_rv32mem_shard_device: an access is not the one its instruction names";
@@ -1414,6 +1599,33 @@ int rk_exec_rv32io_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, 
                      {}, d_image_words, 0, d_memop, memop_rows, d_memory, memory_rows, d_io, io_rows, h_publics};
     RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
     return rv32::shard_device<rv32::CS_IO>(ctx, ex, index, o);
+    RK_GUARD_END
+}
+int rk_exec_rv32commit_sizes(const rk_exec* ex, uint32_t index, size_t* memop_rows, size_t* memory_rows, size_t* io_rows) {
+    RK_GUARD_BEGIN
+    if (!memop_rows || !memory_rows || !io_rows) return RK_ERR_INVALID;
+    ExecSegmentView v;
+    RK_TRY(exec_segment_view(ex, index, &v));
+    const auto merged = rv32::merged_list(v);
+    if (merged.size() > ((size_t)2 << v.seg->po2)) return RK_ERR_CAPACITY;
+    *memop_rows = rv32::mem_rows_for(merged.size());
+    *memory_rows = rv32::mem_rows_for(rv32::distinct_words(merged));
+    *io_rows = rv32::io_rows_for(v.ecall_args->size() + rv32::io_words_of(v) + v.commit_reads->size());
+    if (*io_rows > ((size_t)2 << v.seg->po2)) return RK_ERR_CAPACITY;
+    return RK_OK;
+    RK_GUARD_END
+}
+int rk_exec_rv32commit_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,
+                                    const uint32_t* seg_words, uint32_t n_segs, const uint32_t* d_image_words, uint32_t* d_cpu,
+                                    uint32_t* d_program_mult, size_t program_rows, uint32_t* d_register, uint32_t* d_byte_mult,
+                                    uint32_t* d_range_mult, uint32_t* d_shift_mult, uint32_t* d_muldiv, size_t muldiv_rows,
+                                    uint32_t* d_memop, size_t memop_rows, uint32_t* d_memory, size_t memory_rows, uint32_t* d_io,
+                                    size_t io_rows, uint32_t h_publics[RK_RV32COMMIT_PUBLICS], uint32_t* d_log, size_t* n_log) {
+    RK_GUARD_BEGIN
+    rv32::ShardOut o{d_cpu, d_program_mult, program_rows, d_register, d_byte_mult, d_range_mult, d_shift_mult, d_muldiv, muldiv_rows,
+                     {}, d_image_words, 0, d_memop, memop_rows, d_memory, memory_rows, d_io, io_rows, h_publics, d_log, n_log};
+    RK_TRY(rv32::image_of(seg_vaddr, seg_words, n_segs, &o.img, &o.n_words));
+    return rv32::shard_device<rv32::CS_COMMIT>(ctx, ex, index, o);
     RK_GUARD_END
 }
 int rk_exec_rv32elf_shard_device(rk_ctx* ctx, const rk_exec* ex, uint32_t index, const uint32_t* seg_vaddr,

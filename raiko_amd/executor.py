@@ -77,6 +77,11 @@ class Execution:
     # with record_trace: per segment (ecall rows (k, 5): cycle, t0, a0 before, a1, input position before; the input
     # position at the segment's start) (rk_exec_ecall_args): the side data of the io form of rv32im-mem (rv32io.py)
     ecall_args: Optional[list] = None
+    # with record_trace: per segment (commit reads (k, 3): cycle, word address, word of every word an ecall COMMIT reads;
+    # the journal's length at the segment's start) (rk_exec_commit_reads): the side data of the commit form (rv32commit.py)
+    commit_reads: Optional[list] = None
+    # commit=True: per shard the commit log (k, 3) uint32 -- jpos, word, S | CNT << 16 -- the verifier is handed
+    commit_logs: Optional[list] = None
 
 
 class ExecutorError(RuntimeError):
@@ -156,6 +161,7 @@ def execute(elf: bytes, input_words: Sequence[int] = (), segment_limit_po2: int 
             ex.rv32 = [_rv32_side(lib, handle, sg.index) for sg in segs]
             ex.mem = [mem_accesses(lib, handle, sg.index) for sg in segs]
             ex.ecall_args = [ecall_args(lib, handle, sg.index) for sg in segs]
+            ex.commit_reads = [commit_reads(lib, handle, sg.index) for sg in segs]
         if profile:
             cnt = C.c_size_t(0)
             lib.rk_exec_profile(handle, None, None, 0, C.byref(cnt))
@@ -356,6 +362,17 @@ def ecall_args(lib, handle, index):
         _lib.check(None, st)
     out = np.zeros((max(n.value, 1), 5), dtype=np.uint32)
     _lib.check(None, lib.rk_exec_ecall_args(handle, index, out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n), C.byref(pos)))
+    return out[: n.value], int(pos.value)
+
+
+def commit_reads(lib, handle, index):
+    """rk_exec_commit_reads -> ((k, 3) uint32: cycle, word address, word; the journal's length at the segment's start)"""
+    n, pos = C.c_size_t(0), C.c_uint32(0)
+    st = lib.rk_exec_commit_reads(handle, index, None, 0, C.byref(n), C.byref(pos))
+    if st != _lib.RK_ERR_CAPACITY:
+        _lib.check(None, st)
+    out = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
+    _lib.check(None, lib.rk_exec_commit_reads(handle, index, out.ctypes.data_as(_lib.u32p), out.shape[0], C.byref(n), C.byref(pos)))
     return out[: n.value], int(pos.value)
 
 

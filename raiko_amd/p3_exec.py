@@ -4,7 +4,7 @@ circuit (raiko_amd/p3_trace.py) or one of the rv32 chip sets (raiko_amd/rv32_set
 import ctypes as C
 from typing import Sequence
 
-from . import _lib, p3, rv32io, rv32link
+from . import _lib, p3, rv32commit, rv32io, rv32link
 from .executor import Stepper, execute
 from .p3_trace import next_trace_shard, p3_program_air, p3_range_air, p3_shards, p3_trace_air
 from .rv32_sets import (CHIPS, KEYED_CHIPS, RV32_CHIPS, _free, _rv32_airs_of, check_rv32_chain, execute_rv32_device,
@@ -25,9 +25,12 @@ class P3Pipeline:
     every proof is checked with its journal as claims, the run by rv32link.check_memory_chain from the ELF's memory
     image, and the Execution carries ex.journals and ex.final_memory.  io=True (chips="rv32im-mem" only; composes with
     link): the ecalls are bound to the run's input (raiko_amd/rv32io.py) -- every proof is checked against its slice of
-    input_words, the run by rv32io.check_io_chain, and ex.exit_code / ex.input_words_read are the verified ones."""
+    input_words, the run by rv32io.check_io_chain, and ex.exit_code / ex.input_words_read are the verified ones.
+    commit=True (with io=True only; composes with link): the COMMIT journal is bound (raiko_amd/rv32commit.py) -- every
+    proof is checked with its commit log, the run by rv32commit.check_commit_chain, ex.commit_logs holds the logs and
+    ex.journal is the PROVEN journal, cut from them; a journal that differs from the executor's is an RkError."""
 
-    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace", link=False, io=False):
+    def __init__(self, params=None, device: int = 0, lookups=True, compile_airs=True, chips="trace", link=False, io=False, commit=False):
         from .hal import HipHal, make_params
         if chips not in CHIPS:
             raise ValueError("chips must be one of %s" % (CHIPS,))
@@ -35,10 +38,12 @@ class P3Pipeline:
             raise ValueError("link=True needs chips=\"rv32im-mem\"")
         if io and chips != "rv32im-mem":
             raise ValueError("io=True needs chips=\"rv32im-mem\"")
+        if commit and not (io and chips == "rv32im-mem"):
+            raise ValueError("commit=True needs chips=\"rv32im-mem\" and io=True")
         self.params = params if params is not None else make_params(1)
-        self.lookups, self.chips, self.link, self.io = lookups, chips, link, io
+        self.lookups, self.chips, self.link, self.io, self.commit = lookups, chips, link, io, commit
         ext_w = int(self.params.ext_w)
-        self.rv32_airs = _rv32_airs_of(chips, ext_w, link, io) if chips in RV32_CHIPS else None
+        self.rv32_airs = _rv32_airs_of(chips, ext_w, link, io, commit) if chips in RV32_CHIPS else None
         self.cpu_air = p3_trace_air(lookups, ext_w)
         self.prog_air, self.range_air = (p3_program_air(ext_w), p3_range_air(ext_w)) if lookups else (None, None)
         self.wit_hal, self.prove_hal = HipHal(device), HipHal(device)
@@ -64,9 +69,10 @@ class P3Pipeline:
         from .hal import _ptr
         todo = queue.Queue(maxsize=3)           # back-pressure: at most three shards' tables wait for the prover
         done = queue.Queue()                    # device tables the prover is through with: freed by the thread that owns their context
-        proofs, checks, kept, errors, stmts, journals = [], [], [], [], [], []
-        params, rv32i, link, io = self.params, self.chips in RV32_CHIPS, self.link, self.io
-        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips, link=link, io=io) if self.chips in KEYED_CHIPS else None
+        proofs, checks, kept, errors, stmts, journals, logs = [], [], [], [], [], [], []
+        params, rv32i, link, io, commit = self.params, self.chips in RV32_CHIPS, self.link, self.io, self.commit
+        key = setup_rv32_elf(self.prove_hal, elf, airs=self.rv32_airs, chips=self.chips, link=link, io=io, commit=commit) \
+            if self.chips in KEYED_CHIPS else None
         vk = dict(prep_root=key.root, program_log_height=key.program_log_height) if key else {}
         try:
             stepper = Stepper(elf, input_words, shard_po2)
@@ -76,7 +82,7 @@ class P3Pipeline:
             raise
         pool = ThreadPoolExecutor(max_workers=4)
         if rv32i:
-            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key, link, io)
+            next_shard = lambda: next_rv32_shard(stepper, self.wit_hal, self.rv32_airs, self.chips, key, link, io, commit)
         else:
             next_shard = lambda: next_trace_shard(stepper, self.wit_hal, (self.cpu_air, self.prog_air, self.range_air), self.lookups)
         check = verify_rv32_shard if rv32i else p3.verify
@@ -92,6 +98,10 @@ class P3Pipeline:
                     jk = dict(journal=item[4]) if link else {}
                     if io:
                         jk["input_words"] = list(input_words)
+                    if commit:
+                        jk["commit_log"] = item[-1]
+                        logs.append(item[-1])
+                        item = item[:-1]
                     journals.extend(item[4:])
                     pf = p3.prove(self.prove_hal, tables, init, device_traces=[None if d is None else (_ptr(d[0]), d[1]) for d in bufs],
                                   key=key.key if key else None)
@@ -144,16 +154,26 @@ class P3Pipeline:
             ex.journals = journals
             ex.final_memory = rv32link.check_memory_chain(journals, rv32link.memory_image(elf))
         if io and verify:
-            code, ex.input_words_read = rv32io.check_io_chain([rv32io.publics_of(t[rv32io.IO_TABLE].public_values) for t, _i in stmts],
-                                                              list(input_words))
+            code, ex.input_words_read = rv32io.check_io_chain([rv32io.publics_of(t[rv32io.IO_TABLE].public_values[:rv32io.N_PUBLIC_IO])
+                                                               for t, _i in stmts], list(input_words))
             ex.exit_code = ex.exit_code if code is None else code
+        if commit and verify:
+            pubs = [rv32commit.publics_of(t[rv32io.IO_TABLE].public_values) for t, _i in stmts]
+            rv32commit.check_commit_chain(pubs)
+            proven = b"".join(rv32commit.log_bytes(pub, log) for pub, log in zip(pubs, logs))
+            if proven != ex.journal:
+                raise _lib.RkError(_lib.RK_ERR_VERIFY, "the proven journal is not the executor's")
+            ex.journal = proven
+        if commit:
+            ex.commit_logs = logs
         return ex, proofs, kept
 
 
 def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 20, params=None, device: int = 0,
-                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace", link=False, io=False):
+                                   lookups=True, compile_airs=True, verify=True, keep_tables=False, chips="trace", link=False, io=False,
+                                   commit=False):
     """one program through a P3Pipeline of its own"""
-    pipe = P3Pipeline(params, device, lookups, compile_airs, chips, link, io)
+    pipe = P3Pipeline(params, device, lookups, compile_airs, chips, link, io, commit)
     try:
         return pipe.run(elf, input_words, shard_po2, verify, keep_tables)
     finally:
@@ -161,7 +181,7 @@ def execute_and_prove_p3_pipelined(elf: bytes, input_words: Sequence[int] = (), 
 
 
 def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, params=None, device: int = 0, batch: int = 3,
-                         lookups=False, chips="trace", link=False, io=False):
+                         lookups=False, chips="trace", link=False, io=False, commit=False):
     """ELF -> executed shards -> one uni-stark proof per shard through rk_p3_prove_shards (every proof verified inside):
     the shape of `client.prove(&pk, stdin)` on the SP1 side (provers/sp1/driver/src/lib.rs:44-57; SHARD_SIZE / SHARD_BATCH_SIZE,
     docs/README_Sp1.md:19-32) with the stand-in trace AIR in place of SP1's chips.  -> (Execution, shards, proofs)
@@ -183,7 +203,10 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
     composes with link): the ecalls are bound to input_words (raiko_amd/rv32io.py): ten traces per shard
     (rk_exec_rv32io_shard_device) under the io key, the pool's verifiers check every proof with its slice of the input as
     claims, and the run is checked by verify_rv32_execution(input_words=); ex.exit_code and ex.input_words_read are then
-    what that check returns."""
+    what that check returns.  commit=True (with io=True only; composes with link): the COMMIT journal is bound
+    (raiko_amd/rv32commit.py): ten traces per shard (rk_exec_rv32commit_shard_device) under the io key, every proof is
+    checked with its commit log as claims, the run by verify_rv32_execution(commit_logs=, expected_journal=the
+    executor's); ex.journal is then the proven journal and ex.commit_logs the logs."""
     from .hal import make_params
     params = params if params is not None else make_params(1)
     if chips not in CHIPS:
@@ -192,23 +215,29 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
         raise ValueError("link=True needs chips=\"rv32im-mem\"")
     if io and chips != "rv32im-mem":
         raise ValueError("io=True needs chips=\"rv32im-mem\"")
+    if commit and not (io and chips == "rv32im-mem"):
+        raise ValueError("commit=True needs chips=\"rv32im-mem\" and io=True")
     if chips in RV32_CHIPS:
         from .hal import HipHal
         hal = HipHal(device)
         key, vk = None, {}
         try:
             if chips in KEYED_CHIPS:
-                key = setup_rv32_elf(hal, elf, params, chips=chips, link=link, io=io)
+                key = setup_rv32_elf(hal, elf, params, chips=chips, link=link, io=io, commit=commit)
                 vk = dict(prep_root=key.root.copy(), program_log_height=key.program_log_height)
             ex, shards, dev_traces, bufs, *journals = execute_rv32_device(hal, elf, input_words, shard_po2, ext_w=int(params.ext_w),
-                                                                          chips=chips, key=key, link=link, io=io)
+                                                                          chips=chips, key=key, link=link, io=io, commit=commit)
+            logs = journals.pop() if commit else None
             hal.sync()
             claims = [rv32link.claims_of(j) for j in journals[0]] if link else [[] for _ in shards] if io else None
             if io:    # the prover's own statement: the slice its io table's public values name
                 words = list(input_words)
                 for c, (tables, _init) in zip(claims, shards):
-                    pub = rv32io.publics_of(tables[rv32io.IO_TABLE].public_values)
+                    pub = rv32io.publics_of(tables[rv32io.IO_TABLE].public_values[:rv32io.N_PUBLIC_IO])
                     c += rv32io.claims_of(pub["pos_start"], words[pub["pos_start"]:pub["pos_end"]])
+            if commit:
+                for c, log in zip(claims, logs):
+                    c += rv32commit.claims_of(log)
             try:
                 proofs = p3.prove_shards(shards, params, device=device, batch=batch, verify=True, device_traces=dev_traces,
                                          key=key.key if key else None, claims=claims)
@@ -224,10 +253,15 @@ def execute_and_prove_p3(elf: bytes, input_words: Sequence[int] = (), shard_po2:
             vk.update(journals=journals[0], image=image)
         if io:
             vk.update(input_words=list(input_words))
+        if commit:
+            vk.update(commit_logs=logs, expected_journal=ex.journal)
         checked = verify_rv32_execution(shards, proofs, params, entry_pc=ex.segments[0].start_pc if ex.segments else None, **vk)
         if io:
             ex.exit_code, ex.input_words_read = ex.exit_code if checked[0] is None else checked[0], checked[1]
             del vk["input_words"]
+        if commit:
+            ex.journal, ex.commit_logs = checked[2], logs
+            del vk["commit_logs"], vk["expected_journal"]
         if link:
             ex.journals, ex.final_memory = journals[0], rv32link.check_memory_chain(journals[0], image)
             del vk["journals"], vk["image"]

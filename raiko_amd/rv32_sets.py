@@ -9,7 +9,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, p3, rv32, rv32cf, rv32elf, rv32im, rv32io, rv32link, rv32mem
+from . import _lib, p3, rv32, rv32cf, rv32commit, rv32elf, rv32im, rv32io, rv32link, rv32mem
 from .executor import Execution, Stepper, _rv32_side
 
 
@@ -61,6 +61,14 @@ _IO = ChipSet("rv32im-mem", rv32io, "rk_exec_rv32io_shard_device", _RV32I_CF, mu
               prep="rk_rv32io_prep_device", extra=("image", "mem", "io"))
 assert (_IO.keyed, _IO.n_tables) not in _BY_COUNT
 _BY_COUNT[_IO.keyed, _IO.n_tables] = _IO
+# the commit form of the io form (raiko_amd/rv32commit.py; commit=True with io=True): the io form's key and table shapes, a
+# wider memop and io table; a verifier tells it from the io form by the io table's 24 public values, not by a count
+_COMMIT = ChipSet("rv32im-mem", rv32commit, "rk_exec_rv32commit_shard_device", _RV32I_CF, muldiv=True, n_mem=3, mem_slack=1,
+                  prep="rk_rv32io_prep_device", extra=("image", "mem", "io", "commit"))
+
+
+def _io_set(commit):
+    return _COMMIT if commit else _IO
 
 
 def _rv32_set(chips):
@@ -70,21 +78,24 @@ def _rv32_set(chips):
     return _BY_NAME[chips].module, _BY_NAME[chips]
 
 
-def _rv32_airs_of(chips, ext_w=None, link=False, io=False):
+def _rv32_airs_of(chips, ext_w=None, link=False, io=False, commit=False):
     """the AIRs of one shard of chip set `chips`, in table order.  link: the rv32im-mem set with its shard memories
     linked (raiko_amd/rv32link.py: the memory AIR sends the journal and carries its digest).  io: the rv32im-mem set
-    with its ecalls bound to the input (raiko_amd/rv32io.py: ten AIRs); composes with link"""
-    _link_ok(chips, link, io)
+    with its ecalls bound to the input (raiko_amd/rv32io.py: ten AIRs); composes with link.  commit (with io): the COMMIT
+    journal bound as well (raiko_amd/rv32commit.py: the memop and io AIRs differ)"""
+    _link_ok(chips, link, io, commit)
     if io:
-        return rv32io.airs(ext_w, link)
+        return (rv32commit if commit else rv32io).airs(ext_w, link)
     return (rv32link if link else _rv32_set(chips)[0]).airs(ext_w)
 
 
-def _link_ok(chips, link, io=False):
+def _link_ok(chips, link, io=False, commit=False):
     if link and chips != "rv32im-mem":
         raise ValueError("link=True needs chips=\"rv32im-mem\"")
     if io and chips != "rv32im-mem":
         raise ValueError("io=True needs chips=\"rv32im-mem\"")
+    if commit and not (io and chips == "rv32im-mem"):
+        raise ValueError("commit=True needs chips=\"rv32im-mem\" and io=True")
 
 
 def p3_rv32_airs(ext_w=None):
@@ -115,18 +126,20 @@ def _host_preps(cs, image, n_tables):
     return [None if m is None else p3.to_mont(m) for m in cs.module.preps_of(image)]
 
 
-def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, params=None, io=False, input_words=None):
+def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, params=None, io=False, input_words=None, commit=False):
     """one shard of chip set `chips` per executed segment, every table built in numpy (the set's shard_tables) from
     ex.witness, ex.rv32 and what else the set takes (image: rv32elf.program_image(elf); ex.mem) -> [(tables, init
     words)], init = the state digests as in p3_shards.  A keyed set's lookup tables carry their preprocessed matrix in
     Table.prep (p3.setup commits them).  link (rv32im-mem): rv32link's AIRs, the memory table's public values the digest
     of the shard's journal under `params` (None: the SP1 preset) -> [(tables, init words, journal)].  io (rv32im-mem,
     with input_words, the run's input): rv32io's ten tables from ex.ecall_args, the io table's public values the stream
-    positions, N_INPUT, the exit and the digest of the shard's slice of the input; the result's shape is link's."""
+    positions, N_INPUT, the exit and the digest of the shard's slice of the input; the result's shape is link's.  commit
+    (with io): rv32commit's ten tables from ex.commit_reads as well; the shard's commit log (k, 3) uint32 is the last
+    element of every entry."""
     module, cs = _rv32_set(chips)
-    _link_ok(chips, link, io)
+    _link_ok(chips, link, io, commit)
     if io:
-        return _io_shards(ex, image, ext_w, airs, link, params, input_words)
+        return _io_shards(ex, image, ext_w, airs, link, params, input_words, commit)
     if link:
         module = rv32link
     if ex.witness is None or ex.rv32 is None or ("mem" in cs.extra and ex.mem is None):
@@ -146,22 +159,29 @@ def shards(chips, ex: Execution, image=None, ext_w=None, airs=None, link=False, 
     return out
 
 
-def _io_shards(ex, image, ext_w, airs, link, params, input_words):
-    """`shards` in io form"""
-    if ex.witness is None or ex.rv32 is None or ex.mem is None or ex.ecall_args is None or input_words is None:
+def _io_shards(ex, image, ext_w, airs, link, params, input_words, commit=False):
+    """`shards` in io form, or in commit form"""
+    if ex.witness is None or ex.rv32 is None or ex.mem is None or ex.ecall_args is None or input_words is None or \
+            (commit and ex.commit_reads is None):
         raise ValueError("execute(..., record_trace=True) first, and pass the run's input_words")
-    airs = airs or rv32io.airs(ext_w, link)
+    airs = airs or (rv32commit if commit else rv32io).airs(ext_w, link)
     preps = _host_preps(_IO, image, len(airs))
     out = []
-    for s, (_code, data), (start, end, ecalls), mem, (args, pos) in zip(ex.segments, ex.witness, ex.rv32, ex.mem, ex.ecall_args):
-        canon, _pc, _regs, digest, io_pubs = rv32io.shard_tables(s, data, start, end, ecalls, image, mem, args, len(input_words), pos,
-                                                                 params=params, link=link)
+    for k, (s, (_code, data), (start, end, ecalls), mem, (args, pos)) in enumerate(zip(ex.segments, ex.witness, ex.rv32, ex.mem, ex.ecall_args)):
+        if commit:
+            reads, jpos = ex.commit_reads[k]
+            canon, _pc, _regs, digest, io_pubs = rv32commit.shard_tables(s, data, start, end, ecalls, image, mem, args, reads,
+                                                                         len(input_words), pos, jpos, params=params, link=link)
+        else:
+            canon, _pc, _regs, digest, io_pubs = rv32io.shard_tables(s, data, start, end, ecalls, image, mem, args, len(input_words), pos,
+                                                                     params=params, link=link)
         pubs = _publics(s, start, end, len(canon))
         pubs[rv32io.IO_TABLE] = io_pubs
         if link:
             pubs[rv32link.MEMORY_TABLE] = digest
         tables = [p3.Table(a, p3.to_mont(t), pv, prep=pm) for a, t, pv, pm in zip(airs, canon, pubs, preps)]
-        out.append((tables, s.init_words()) + ((rv32link.journal_of_table(canon[rv32link.MEMORY_TABLE]),) if link else ()))
+        out.append((tables, s.init_words()) + ((rv32link.journal_of_table(canon[rv32link.MEMORY_TABLE]),) if link else ()) +
+                   ((rv32commit.log_of_table(canon[rv32io.IO_TABLE]),) if commit else ()))
     return out
 
 
@@ -197,7 +217,7 @@ def p3_rv32mem_shards(ex: Execution, image, ext_w=None, airs=None):
     return shards("rv32im-mem", ex, image, ext_w, airs)
 
 
-def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, link=False, io=False):
+def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, link=False, io=False, commit=False):
     """rk_exec_rv32_shard_device (chips="rv32i") / rk_exec_rv32cf_shard_device ("rv32i-cf") /
     rk_exec_rv32im_shard_device ("rv32im") / rk_exec_rv32elf_shard_device ("rv32im-elf", key: the program's Rv32Key) /
     rk_exec_rv32mem_shard_device ("rv32im-mem", key likewise): segment `index` of an open executor as the tables of a
@@ -207,11 +227,13 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
     table's public values and the journal (k, 3) uint32 is handed back as a fourth element.  io (rv32im-mem, airs
     rv32io's, key from setup_rv32_elf(io=True)): rk_exec_rv32io_shard_device writes the ten tables of the io form and
     hands back the io table's public values, the digest of the shard's slice of the input among them (committed under
-    the parameter set of hal's context, which must be the prover's)"""
+    the parameter set of hal's context, which must be the prover's).  commit (with io, airs rv32commit's, the io key):
+    rk_exec_rv32commit_shard_device writes the commit form's tables, the io table's public values are its 24 and the
+    shard's commit log (k, 3) uint32 is handed back as the last element"""
     _module, cs = _rv32_set(chips)
-    _link_ok(chips, link, io)
+    _link_ok(chips, link, io, commit)
     if io:
-        cs = _IO
+        cs = _io_set(commit)
     lib = _lib.load()
     start, end, _ec = _rv32_side(lib, handle, index)
     rows = C.c_size_t(0)
@@ -227,7 +249,7 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
     if cs.muldiv:
         _lib.check(None, lib.rk_exec_rv32im_sizes(handle, index, C.byref(sized[0])))
     if cs.n_mem:    # a segment with more accesses than twice its cycles is refused here (RK_ERR_CAPACITY)
-        _lib.check(None, getattr(lib, "rk_exec_rv32io_sizes" if io else "rk_exec_rv32mem_sizes")(handle, index, *[C.byref(r) for r in sized[cs.muldiv:]]))
+        _lib.check(None, getattr(lib, "rk_exec_rv32commit_sizes" if commit else "rk_exec_rv32io_sizes" if io else "rk_exec_rv32mem_sizes")(handle, index, *[C.byref(r) for r in sized[cs.muldiv:]]))
     logs += [r.value.bit_length() - 1 for r in sized]
     counts += [r.value for r in sized]
     if len(airs) != len(logs):
@@ -239,15 +261,24 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
                  C.c_void_p(key.d_words.ptr)]
     for b, n in zip(bufs, counts):
         args += [C.c_void_p(b.ptr)] + ([] if n is None else [n])
-    io_pubs = np.zeros(rv32io.N_PUBLIC_IO, dtype=np.uint32)
+    io_pubs = np.zeros(rv32commit.N_PUBLIC_IO if commit else rv32io.N_PUBLIC_IO, dtype=np.uint32)
     if io:
         args.append(io_pubs.ctypes.data_as(_lib.u32p))
+    d_log, n_log, commit_log = None, C.c_size_t(0), ()
     try:
+        if commit:
+            d_log = hal.alloc_elem(3 << logs[rv32io.IO_TABLE])
+            args += [C.c_void_p(d_log.ptr), C.byref(n_log)]
         _lib.check(hal._ctx, getattr(lib, cs.entry)(hal._ctx, handle, index, *args))
+        if commit:
+            commit_log = (d_log.to_host().reshape(-1, 3)[: n_log.value].copy(),)
     except Exception:
         for b in bufs:
             b.free()
         raise
+    finally:
+        if d_log is not None:
+            d_log.free()
     pubs = _publics(seg, start, end, len(logs))
     if io:
         pubs[rv32io.IO_TABLE] = io_pubs
@@ -261,7 +292,7 @@ def rv32_shard_device(hal, handle, index, seg, airs, chips="rv32i", key=None, li
             raise
         pubs[rv32link.MEMORY_TABLE], journal = root, (j,)
     tables = [p3.Table.pinned(a, lg, pv) for a, lg, pv in zip(airs, logs, pubs)]
-    return (tables, list(zip(bufs, logs)), seg.init_words()) + journal
+    return (tables, list(zip(bufs, logs)), seg.init_words()) + journal + commit_log
 
 
 def journal_device(hal, d_memory, log_rows, keep=False):
@@ -284,13 +315,14 @@ def journal_device(hal, d_memory, log_rows, keep=False):
             b.free()
 
 
-def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None, link=False, io=False):
+def next_rv32_shard(stepper: Stepper, hal, airs, chips="rv32i", key=None, link=False, io=False, commit=False):
     """the next executed segment as the tables of an rv32i (five), rv32i-cf (six), rv32im or rv32im-elf (seven) or
     rv32im-mem (nine) shard written on hal's GPU (rv32_shard_device; key: the Rv32Key of chips="rv32im-elf" /
     "rv32im-mem") -> (ExecSegment, tables without host traces, [(device buffer, log_height)] per table, init words),
-    or None after the last.  link: as rv32_shard_device, the journal a fifth element.  io: as rv32_shard_device"""
+    or None after the last.  link: as rv32_shard_device, the journal a fifth element.  io: as rv32_shard_device.  commit:
+    as rv32_shard_device, the commit log the last element"""
     seg = stepper.step()
-    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key, link, io))
+    return None if seg is None else (seg, *rv32_shard_device(hal, stepper._h, seg.index, seg, airs, chips, key, link, io, commit))
 
 
 def _free(bufs):
@@ -301,23 +333,28 @@ def _free(bufs):
 
 
 def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_po2: int = 16, airs=None, ext_w=None,
-                        chips="rv32i", key=None, link=False, io=False):
+                        chips="rv32i", key=None, link=False, io=False, commit=False):
     """ELF -> rv32i (rv32i-cf, rv32im, rv32im-elf) shards whose tables are written on hal's GPU, one segment at a time
     (the executor's trace of a segment is dropped with the executor; the tables stay in HBM) -> (Execution, [(tables,
     init)], [device traces], [[(device buffer, log_height)]] to free).  key: the Rv32Key of chips="rv32im-elf" (its AIRs
     are the shards').  link (rv32im-mem; key from setup_rv32_elf(link=True)): the shards' memories linked, the journals
-    a fifth element of the result.  io (rv32im-mem; key from setup_rv32_elf(io=True)): the io form's ten tables"""
+    a fifth element of the result.  io (rv32im-mem; key from setup_rv32_elf(io=True)): the io form's ten tables.  commit
+    (with io; key from setup_rv32_elf(io=True, commit=True)): the commit form's, the shards' commit logs the last element
+    of the result"""
     from .hal import _ptr
-    _link_ok(chips, link, io)
-    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w, link, io))
+    _link_ok(chips, link, io, commit)
+    airs = airs or (key.airs if key is not None else _rv32_airs_of(chips, ext_w, link, io, commit))
     st = Stepper(elf, input_words, shard_po2)
-    out, dev, metas, journals = [], [], [], []
+    out, dev, metas, journals, logs = [], [], [], [], []
     try:
         while True:
-            item = next_rv32_shard(st, hal, airs, chips, key, link, io)
+            item = next_rv32_shard(st, hal, airs, chips, key, link, io, commit)
             if item is None:
                 break
             seg, tables, bufs, init = item[:4]
+            if commit:
+                logs.append(item[-1])
+                item = item[:-1]
             journals += item[4:]
             out.append((tables, init))
             dev.append(bufs)
@@ -330,7 +367,7 @@ def execute_rv32_device(hal, elf: bytes, input_words: Sequence[int] = (), shard_
         raise
     finally:
         st.close()
-    return (ex, out, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev) + ((journals,) if link else ())
+    return (ex, out, [[(_ptr(b), lg) for b, lg in d] for d in dev], dev) + ((journals,) if link else ()) + ((logs,) if commit else ())
 
 
 def check_rv32_chain(publics, entry_pc=None):
@@ -361,7 +398,7 @@ def rv32_publics(shards):
 
 
 def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=None, program_log_height=None, journals=None,
-                          image=None, input_words=None):
+                          image=None, input_words=None, commit_logs=None, expected_journal=None):
     """Checks a run proven with the rv32i, rv32i-cf, rv32im, rv32im-elf or rv32im-mem chip set: every shard's proof
     (verify_rv32_shard), then check_rv32_chain over the public values.  shards: [(tables, init)] as p3_rv32_shards /
     p3_rv32cf_shards / p3_rv32im_shards / execute_rv32_device give them.  prep_root, program_log_height: the verifying
@@ -373,25 +410,42 @@ def verify_rv32_execution(shards, proofs, params=None, entry_pc=None, prep_root=
     input_words (the run's input; the run was proven with io=True, raiko_amd/rv32io.py): every proof is checked against
     its slice of the input (verify_rv32_shard), and rv32io.check_io_chain binds the shards' stream positions to each other
     and to the input's length; the result is then (exit code -- None for a run that has not halted --, input words read)
-    in place of True.  Raises ValueError naming the shard; returns True."""
+    in place of True.  commit_logs (one commit log per shard, with input_words; the run was proven with commit=True,
+    raiko_amd/rv32commit.py): every proof is checked with its log (verify_rv32_shard), rv32commit.check_commit_chain binds
+    the shards' journal positions to each other, and the result is (exit code, input words read, the PROVEN journal: the
+    bytes cut from the logs); expected_journal: a run whose proven journal differs from it is refused (ValueError).
+    Raises ValueError naming the shard; returns True."""
     if len(proofs) != len(shards):
         raise ValueError("%d proofs for %d shards" % (len(proofs), len(shards)))
+    if commit_logs is not None and (len(commit_logs) != len(shards) or input_words is None):
+        raise ValueError("commit_logs: one per shard, with the run's input_words")
+    if expected_journal is not None and commit_logs is None:
+        raise ValueError("expected_journal goes with commit_logs: no other form proves the journal")
     if journals is not None and (len(journals) != len(shards) or image is None):
         raise ValueError("journals: one per shard, with the ELF's memory image")
     for k, ((tables, init, *_j), pf) in enumerate(zip(shards, proofs)):
         rc = verify_rv32_shard(tables, pf, init, params, prep_root, program_log_height,
-                               journal=None if journals is None else journals[k], input_words=input_words)
+                               journal=None if journals is None else journals[k], input_words=input_words,
+                               commit_log=None if commit_logs is None else commit_logs[k])
         if rc != 0:
             raise ValueError("shard %d: the proof does not verify (reason %d)" % (k, rc))
     check_rv32_chain(rv32_publics(shards), entry_pc)
     if journals is not None:
         rv32link.check_memory_chain(journals, image)
+    if commit_logs is not None:
+        pubs = [rv32commit.publics_of(sh[0][rv32io.IO_TABLE].public_values) for sh in shards]
+        rv32commit.check_commit_chain(pubs)
+        proven = b"".join(rv32commit.log_bytes(pub, log) for pub, log in zip(pubs, commit_logs))
+        if expected_journal is not None and proven != bytes(expected_journal):
+            raise ValueError("the proven journal (%d bytes) is not the expected one (%d bytes)" % (len(proven), len(expected_journal)))
+        return rv32io.check_io_chain(pubs, input_words) + (proven,)
     if input_words is not None:
         return rv32io.check_io_chain([rv32io.publics_of(sh[0][rv32io.IO_TABLE].public_values) for sh in shards], input_words)
     return True
 
 
-def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None, journal=None, input_words=None) -> int:
+def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_log_height=None, journal=None, input_words=None,
+                      commit_log=None) -> int:
     """rk_p3_verify of one rv32i (five tables), rv32i-cf (six) or rv32im (seven) shard with the register / byte / range
     / shift tables pinned to 32 / 2^18 / 2^16 / 2^12 rows and the cpu table to the height the statement gives; the
     muldiv table's height is the proof's, refused (reason 2) unless 0 < log height <= the cpu table's -> 0 or the
@@ -405,16 +459,23 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
     proven with io=True (rv32io's ten AIRs, under the io key): the io table's public values must fit the input (N_INPUT
     its length, POS_START <= POS_END <= N_INPUT), the digest of input_words[POS_START:POS_END] at the proof's io-table
     height is recomputed and must be the table's (reason 2 otherwise), and the slice's stream tuples are added as receive
-    claims on BUS_INPUT, next to the journal's when there is one"""
+    claims on BUS_INPUT, next to the journal's when there is one.  commit_log (with input_words): the shard was proven with
+    commit=True (rv32commit's AIRs; the io table carries 24 public values): the log must be well formed against JPOS_START
+    and JPOS_END (rv32commit.log_bytes), its digest at the proof's io-table height is recomputed and must be the table's
+    (reason 2 otherwise, before the proof is read), and its tuples are added as receive claims on BUS_COMMIT"""
     vt = rv32_verifier_tables(tables, proof, prep_root, program_log_height)
     if vt is None:
         return 2
     claims = []
+    if commit_log is not None and input_words is None:
+        raise ValueError("a commit log goes with input_words: commit=True needs io=True")
     if input_words is not None:
         io = vt[rv32io.IO_TABLE] if len(vt) > rv32io.IO_TABLE else None
-        if io is None or io.public_values.size != rv32io.N_PUBLIC_IO:
-            raise ValueError("input_words go with the ten tables of an rv32im-mem shard proven with io=True")
-        pub = rv32io.publics_of(io.public_values)
+        n_pub = rv32io.N_PUBLIC_IO if commit_log is None else rv32commit.N_PUBLIC_IO
+        if io is None or io.public_values.size != n_pub:
+            raise ValueError("input_words go with the ten tables of an rv32im-mem shard proven with io=True: 14 public values "
+                             "on the io table, or 24 and a commit log for commit=True")
+        pub = rv32io.publics_of(io.public_values) if commit_log is None else rv32commit.publics_of(io.public_values)
         words = rv32io.slice_of(pub, input_words)
         if words is None:
             return 2
@@ -425,6 +486,16 @@ def verify_rv32_shard(tables, proof, init, params=None, prep_root=None, program_
         if not np.array_equal(digest, pub["digest"]):
             return 2
         claims += rv32io.claims_of(pub["pos_start"], words)
+        if commit_log is not None:
+            if rv32commit.log_bytes(pub, commit_log) is None:
+                return 2
+            try:
+                digest = rv32commit.log_root(commit_log, io.log_height, params)
+            except _lib.RkError:
+                return 2
+            if not np.array_equal(digest, pub["commit_digest"]):
+                return 2
+            claims += rv32commit.claims_of(commit_log)
     elif len(vt) > rv32io.IO_TABLE:
         raise ValueError("the ten tables of an io shard are verified with input_words")
     if journal is not None:
@@ -505,7 +576,7 @@ class Rv32Key:
         self.key = self.d_words = None
 
 
-def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf", link=False, io=False) -> Rv32Key:
+def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="rv32im-elf", link=False, io=False, commit=False) -> Rv32Key:
     """The setup of `client.setup(ELF)` for the rv32im-elf chip set: the ELF's program image (rk_exec_program_image), the
     four preprocessed matrices written on hal's GPU (rk_rv32elf_prep_device) and committed (rk_p3_setup) -> Rv32Key.
     params: the parameter set to put hal's context under first (None: the context's current one); ext_w: the AIRs'
@@ -513,16 +584,16 @@ def setup_rv32_elf(hal, elf: bytes, params=None, ext_w=None, airs=None, chips="r
     program matrix has 48 columns) and nine AIRs.  link (rv32im-mem): the nine AIRs are rv32link's; the key itself --
     the preprocessed matrices, their heights, the root -- is the same either way.  io (rv32im-mem): the key of the io
     form (rk_rv32io_prep_device: the ecall word's tuple reads a0 and a1; another root than rv32im-mem's) and rv32io's ten
-    AIRs."""
+    AIRs.  commit (with io): the io form's key -- the decode does not differ -- and rv32commit's ten AIRs."""
     if chips not in KEYED_CHIPS:
         raise ValueError("chips must be one of %s" % (KEYED_CHIPS,))
-    _link_ok(chips, link, io)
+    _link_ok(chips, link, io, commit)
     cs = _IO if io else _rv32_set(chips)[1]
     lib = _lib.load()
     if params is not None:
         _lib.check(hal._ctx, lib.rk_set_params(hal._ctx, C.byref(params)))
     if airs is None:
-        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w, link, io)
+        airs = _rv32_airs_of(chips, int(hal.get_params().ext_w) if ext_w is None else ext_w, link, io, commit)
     vaddr, count, words = program_image_c(elf)
     rows = 2
     while rows < words.size:

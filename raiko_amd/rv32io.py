@@ -26,9 +26,10 @@ The verifier (rv32_sets.verify_rv32_shard(input_words=)) slices input_words[POS_
 (reason 2 on a mismatch) and adds the receive claims on BUS_INPUT (rk_p3_verify_claims); check_io_chain binds the shards'
 positions to each other and N_INPUT to the input's length, and returns the exit code and the words read.
 
-STILL FREE: the bytes RK_ECALL_COMMIT appends to the journal are not read through the memory argument and the journal
-is no public output (a0 and a1 of the COMMIT row are bound: that is the follow-up).  The FRI statements over an io proof
-are out of scope, as for linked proofs.
+The bytes RK_ECALL_COMMIT appends to the journal are bound by the commit form of this form (rv32commit.py, commit=True):
+commit-word rows after a COMMIT head read the call's words through the memory argument and a commit log is a public
+output.  Without it the journal is no part of the statement.  The FRI statements over an io proof are out of scope, as
+for linked proofs.
 
 `shard_tables` builds an io shard's ten traces in numpy: the yardstick for rk_exec_rv32io_shard_device."""
 import numpy as np

@@ -48,8 +48,8 @@ address -- two parallel histories -- cannot be written.
 
 STILL FREE: INIT of every touched word -- the boundary to the previous shard's FINAL and to the ELF's data image is not
 proven; shard k + 1 may start a word from any value (rv32link.py binds it) -- what an ecall writes, and the a0 it leaves
-(rv32io.py, io=True, binds both to the run's input and exit code; what then remains free is the journal RK_ECALL_COMMIT
-appends to).  The boundary table is what a cross-shard link (a digest, shared challenges or a Merkle image) would bind.
+(rv32io.py, io=True, binds both to the run's input and exit code; rv32commit.py, commit=True, binds the journal
+RK_ECALL_COMMIT appends to).  The boundary table is what a cross-shard link (a digest, shared challenges or a Merkle image) would bind.
 
 `shard_tables` builds a shard's nine traces in numpy: the yardstick for rk_exec_rv32mem_shard_device."""
 import numpy as np
@@ -82,6 +82,7 @@ G_X, G_H0, G_H1, G_TOP, G_SG, G_SL, G_ONE = range(44, 51)
 G_AND = 51                                         # the AND of each byte pair (6)
 G_PTS, G_DL, G_DH, G_W_LO, G_W_HI, G_N_LO, G_N_HI = range(57, 64)
 MEMOP_COLS = 64
+G_ECR, MEMOP_COLS_COMMIT, ECR_CODE = 64, 65, 17    # the commit form (rv32commit.py): a tenth selector, ECR, op 17
 BYTE_PAIRS = [(G_W, G_W + 1), (G_W + 2, G_W + 3), (G_N, G_N + 1), (G_N + 2, G_N + 3), (G_BB, G_BB + 1), (G_BB + 2, G_BB + 3)]
 RANGE_COLS = [G_AD_LO, G_AD_HI, G_WL, G_WL4, G_DL, G_DH]
 MEMOP_TUPLE = [G_OP, G_TS, G_A_LO, G_A_HI, G_MI_LO, G_MI_HI, G_B_LO, G_B_HI, G_R_LO, G_R_HI]
@@ -120,12 +121,15 @@ def program_air(ext_w=None):
     return b.build()
 
 
-def memop_air(ext_w=None, io=False):
+def memop_air(ext_w=None, io=False, commit=False):
     """-> the memop Air; its `constraint_names` maps the name of each constraint to its index.  io (rv32io.py): an ECW
     row obeys SW's constraints -- its tuple is an io word row's (16, TS, AD, 0, V, 0): AD = A + MI, N = BB = the bytes of
-    B -- and nothing about it is free"""
+    B -- and nothing about it is free.  commit (rv32commit.py; with io): a 65th column, the selector of an ECR row (op 17),
+    which obeys LW's constraints -- its tuple is a commit-word row's (17, TS, AD, 0, 0, V): word aligned, N = W, R = W"""
     from . import p3
-    b = p3.AirBuilder(MEMOP_COLS, 0, p3.EXT_W if ext_w is None else ext_w)
+    if commit and not io:
+        raise ValueError("commit=True needs io=True")
+    b = p3.AirBuilder(MEMOP_COLS_COMMIT if commit else MEMOP_COLS, 0, p3.EXT_W if ext_w is None else ext_w)
     L = b.local
     names = {}
     named = rv32im._namer(b, names)
@@ -142,10 +146,13 @@ def memop_air(ext_w=None, io=False):
     mult = L(G_MULT)
     for j in range(9):
         named("bool sel %d" % j, sel[j] * (sel[j] - 1))
-    named("mult", mult - lin([(s, 1) for s in sel]))
+    ecr = L(G_ECR) if commit else None
+    if commit:
+        named("bool ecr", ecr * (ecr - 1))
+    named("mult", mult - lin([(s, 1) for s in sel + ([ecr] if commit else [])]))
     named("bool mult", mult * (mult - 1))
     named("padding", b.is_transition() * (1 - mult) * b.next(G_MULT))
-    named("op", L(G_OP) - lin([(s, c) for s, c in zip(sel[1:], OP_CODES[1:])]))
+    named("op", L(G_OP) - lin([(s, c) for s, c in list(zip(sel[1:], OP_CODES[1:])) + ([(ecr, ECR_CODE)] if commit else [])]))
     named("one", L(G_ONE) - 1)
     for tag, c in (("k0", G_K0), ("k1", G_K1), ("o0", G_O0), ("o1", G_O1)):
         named("bool " + tag, L(c) * (L(c) - 1))
@@ -157,8 +164,9 @@ def memop_air(ext_w=None, io=False):
     named("addr split", L(G_AD_LO) - L(G_WL) * 4 - o1 * 2 - o0)
     named("wl4", L(G_WL4) - L(G_WL) * 4)
     named("align half", (lh + lhu + sh) * o0)
-    named("align word o0", (lw + sw + ecw) * o0)
-    named("align word o1", (lw + sw + ecw) * o1)
+    word_row = lw + sw + ecw + ecr if commit else lw + sw + ecw
+    named("align word o0", word_row * o0)
+    named("align word o1", word_row * o1)
     s = [L(G_S + k) for k in range(4)]
     named("s0", s[0] - (mult - o0) * (1 - o1))
     named("s1", s[1] - o0 * (1 - o1))
@@ -170,7 +178,7 @@ def memop_air(ext_w=None, io=False):
     named("w hi", L(G_W_HI) - half(w, 2))
     named("n lo", L(G_N_LO) - half(n, 0))
     named("n hi", L(G_N_HI) - half(n, 2))
-    store, load = sb + sh + sw, lb + lh + lw + lbu + lhu
+    store, load = sb + sh + sw, lb + lh + lw + lbu + lhu + ecr if commit else lb + lh + lw + lbu + lhu
     word_store = sw + ecw if io else sw
     named("b lo", (store + ecw if io else store) * (L(G_B_LO) - half(bb, 0)))
     named("b hi", (store + ecw if io else store) * (L(G_B_HI) - half(bb, 2)))
@@ -191,8 +199,9 @@ def memop_air(ext_w=None, io=False):
     named("lh hi", lh * (r_hi - sg * 0xFFFF))
     named("lhu lo", lhu * (r_lo - h0 - h1 * 256))
     named("lhu hi", lhu * r_hi)
-    named("lw lo", lw * (r_lo - L(G_W_LO)))
-    named("lw hi", lw * (r_hi - L(G_W_HI)))
+    word_load = lw + ecr if commit else lw
+    named("lw lo", word_load * (r_lo - L(G_W_LO)))
+    named("lw hi", word_load * (r_hi - L(G_W_HI)))
     # stores: the bytes the op names change to rs2's low bytes, the others stay
     for k in range(4):
         named("sb %d" % k, sb * (n[k] - w[k] - s[k] * (bb[0] - w[k])))
