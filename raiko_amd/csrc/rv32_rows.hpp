@@ -814,7 +814,7 @@ enum : unsigned { Q_CW = IO_W, Q_S, Q_S0, Q_S1, Q_CNT, Q_C0, Q_C1, Q_T0B, Q_T1B,
 static_assert(Q_JH + 1 == CM_IO_W, "commit io columns");
 // the limbs sent to RANGE16 beside the io form's (rv32commit.py IO_RANGE): by a COMMIT head, by a commit-word row
 constexpr unsigned IO_RANGE_COMMIT[1] = {Q_BH7}, IO_RANGE_CW[6] = {Q_RML, Q_RMH, Q_RMH7, Q_JL, Q_JL4, Q_JH};
-constexpr uint32_t MAX_COMMIT = 1u << 25;
+constexpr uint32_t MAX_COMMIT = 1u << 25, MAX_JOURNAL = 1u << 30;
 
 // the words a COMMIT of a1 bytes from a0 reads
 RK_HD uint32_t commit_words(uint32_t a0, uint32_t a1) { return a1 ? ((a0 & 3u) + a1 + 3u) >> 2 : 0u; }
@@ -825,6 +825,13 @@ RK_HD bool io_commit_head(uint32_t* row, const EcallArg& e, uint32_t n_reads) {
     if (e.t0 != 2) return true;
     row[Q_REM] = e.a1;
     return n_reads == commit_words(e.a0, e.a1) && e.a1 < MAX_COMMIT;
+}
+
+// ... with jpos, the journal offset the call's first byte lands at: also whether the journal ends below 2^30 bytes after
+// the call (rv32commit.py io_rows: JH stays a 16-bit limb).  What the witness calls
+RK_HD bool io_commit_head(uint32_t* row, const EcallArg& e, uint32_t n_reads, uint32_t jpos) {
+    if (!io_commit_head(row, e, n_reads)) return false;
+    return e.t0 != 2 || (jpos < MAX_JOURNAL && e.a1 < MAX_JOURNAL - jpos);
 }
 
 // commit-word row k of COMMIT e, whose first byte lands at journal offset jpos; m: the commit read it answers; `row` is

@@ -744,7 +744,7 @@ __global__ void io_rows_kernel(const EcallArg* __restrict__ args, size_t count, 
                 uint32_t prev_got = 0;
                 if (lo && !(COMMIT && args[lo - 1].t0 == 2)) prev_got = necw[args[lo - 1].cycle];
                 ok = ok && e.pos == (lo ? args[lo - 1].pos + prev_got : pos_start);
-                if constexpr (COMMIT) ok = ok && io_commit_head(row, e, necw[e.cycle]);
+                if constexpr (COMMIT) ok = ok && io_commit_head(row, e, necw[e.cycle], jpos);
                 io_row_tail(row, e.pos, true, halted && lo + 1 == count);
                 if constexpr (COMMIT) io_commit_tail(row, jpos);
             } else if (is_commit) {

@@ -101,7 +101,7 @@ extern "C" int emul_rv32commit_shard(const uint32_t* trace, size_t cycles, const
         if (!io_head_row(h, c, ecalls[2 * e + 1], (uint32_t)here, n_input, e > 0, prev_head_ts)) return 5;
         size_t mine = 0;
         while (dense + mine < n_reads && rd[dense + mine].cycle == c.cycle) mine++;
-        if (!io_commit_head(h, c, (uint32_t)mine)) return 5;
+        if (!io_commit_head(h, c, (uint32_t)mine, jpos)) return 5;
         halted = c.t0 == 0;
         io_row_tail(h, pos, true, halted);
         io_commit_tail(h, jpos);
