@@ -973,6 +973,41 @@ int rk_p2_chip_air(const rk_params* params, uint32_t bus, rk_air** out);
  * permutation to the next.  rk_p2_chip_air is n_out = 8; rk_p2_chip_trace writes the rows of either. */
 int rk_p2_chip_air_ex(const rk_params* params, uint32_t bus, uint32_t n_out, rk_air** out);
 int rk_p2_chip_trace(rk_ctx* ctx, const uint32_t* d_inputs, const uint32_t* d_mult, size_t n, uint32_t* d_trace);
+/* The Keccak-f[1600] chip: the permutation behind Keccak-256 as a table, the first precompile-shaped chip -- the shape
+ * of p3-keccak-air (pulled by the reference's Cargo.lock, the crate outside the reference tree: RECALLED, parity unpinned;
+ * without its preimage / export columns, and the columns below are this project's).
+ * One row per round, 25 rows per permutation: rows 0..23 are the 24 rounds, row 24 is an OUTPUT ROW -- a round with round
+ * constant 0 whose results nobody reads; it exists so that the permutation's output stands in the same columns A its
+ * input stood in, which keeps the interactions within the 120 distinct columns a table's interactions may read (input
+ * plus output are 200 limbs).  Lane (x, y) has index x + 5 y; a lane is four 16-bit limbs, little endian, or 64 bits.
+ * Columns (2537): STEP[25] one-hot round flags | A[25][4] the state entering the row, limbs | C[5][64] column parities,
+ * bits | C'[5][64] = C[x] ^ C[x-1] ^ rol(C[x+1], 1), bits | A'[25][64] the state after theta, bits | A''[25][4] the state
+ * after rho, pi, chi, limbs | the 64 bits of A''[0][0] | A'''[0][0] lane (0, 0) after iota, 4 limbs | ID | M | M_IN | M_OUT.
+ * Constraints (degree <= 3, two quotient chunks): the flags are one-hot, STEP[0] on the first row, STEP[i] goes on to the
+ * next row's STEP[i + 1 mod 25]; C, A' and the bits of A''[0][0] are boolean; C' is that xor; every limb of A is
+ * recomposed from A' ^ C ^ C'; sum_y A'[y][x][z] - C'[x][z] is 0, 2 or 4; every limb of A'' is recomposed from
+ * b ^ (~b1 & b2) over the rho / pi-permuted bits of A'; A'''[0][0] = A''[0][0] ^ rc with rc_z = sum_r STEP[r] RC[r]_z
+ * (0 on row 24); unless STEP[24], the next row's A is this row's result (A'''[0][0], A'' elsewhere) and its ID and M are
+ * this row's; M_IN = M STEP[0], M_OUT = M STEP[24].
+ * Interactions: four receives.  bus, bus + 1: (ID, limbs 0..49 of A), (ID, limbs 50..99 of A) M_IN times -- the input;
+ * bus + 2, bus + 3: the same columns M_OUT times -- the output (limb index = 4 (x + 5 y) + limb; 51 values per tuple, 103
+ * distinct columns).  M is one column under all four and constant over a permutation's rows, so a permutation that
+ * answers one of a sender's four tuples must have all four of its own matched; ID ties the halves and the two ends.  A
+ * permutation cut off by the table's end must have M = 0 -- otherwise its input is received and its output never, and
+ * the cumulative sums do not cancel (the verifier's reason 8); no constraint is needed for that.
+ * rk_keccak_chip_air: the AIR (step list written by the library; params gives the extension's W, NULL = the SP1
+ * preset; the buses bus .. bus + 3 must be canonical).  rk_keccak_chip_trace: the rows on the GPU, one wavefront per
+ * permutation -- d_states n x 25 lanes (lane x + 5 y), d_ids / d_mult n Montgomery words each or NULL for 0 .. n - 1 /
+ * ones, rows a power of two >= max(2, 25 n) and <= 2^24 (permutation slots past n, the cut-off last one included, are
+ * the zero state with M = ID = 0), d_trace rows x rk_keccak_chip_width row-major Montgomery words, ready to be an
+ * on_device rk_p3_table; d_out NULL or n x 25 lanes: the permutations' outputs.  RK_ERR_INVALID before any launch for a
+ * NULL ctx / d_states / d_trace, n = 0, or rows that are no power of two, below 25 n or above 2^24.
+ * Out of scope here: the chip as an ecall of the executor through the memory argument, a sponge / absorb table for
+ * Keccak-256 of messages, and a verifier-side claim form for public (input, output) pairs. */
+uint32_t rk_keccak_chip_width(void);
+int rk_keccak_chip_air(const rk_params* params, uint32_t bus, rk_air** out);
+int rk_keccak_chip_trace(rk_ctx* ctx, const uint64_t* d_states, const uint32_t* d_ids, const uint32_t* d_mult, size_t n, size_t rows,
+                         uint32_t* d_trace, uint64_t* d_out);
 /* One table of a proof.  trace: row-major 2^log_height x width Montgomery words (Plonky3's RowMajorMatrix), in host
  * memory or -- on_device = 1 -- in the memory of the context's GPU (left untouched). */
 typedef struct {
