@@ -1002,12 +1002,52 @@ int rk_p2_chip_trace(rk_ctx* ctx, const uint32_t* d_inputs, const uint32_t* d_mu
  * the zero state with M = ID = 0), d_trace rows x rk_keccak_chip_width row-major Montgomery words, ready to be an
  * on_device rk_p3_table; d_out NULL or n x 25 lanes: the permutations' outputs.  RK_ERR_INVALID before any launch for a
  * NULL ctx / d_states / d_trace, n = 0, or rows that are no power of two, below 25 n or above 2^24.
- * Out of scope here: the chip as an ecall of the executor through the memory argument, a sponge / absorb table for
- * Keccak-256 of messages, and a verifier-side claim form for public (input, output) pairs. */
+ * Out of scope here: the chip as an ecall of the executor through the memory argument.  The sponge table over it
+ * follows. */
 uint32_t rk_keccak_chip_width(void);
 int rk_keccak_chip_air(const rk_params* params, uint32_t bus, rk_air** out);
 int rk_keccak_chip_trace(rk_ctx* ctx, const uint64_t* d_states, const uint32_t* d_ids, const uint32_t* d_mult, size_t n, size_t rows,
                          uint32_t* d_trace, uint64_t* d_out);
+/* THE KECCAK-256 SPONGE TABLE over the chip: "the Keccak-256 of these blocks is this digest".  Rate 136 bytes = 17 lanes
+ * = 68 limbs; the table absorbs WHOLE blocks: padding (0x01 .. 0x80) lies with whoever sends them -- the verifier for
+ * public messages, later an ecall table --, the AIR has no padding constraints.  Three rows per block (a group), in this
+ * order: the X row (V[0..67] = the block's limbs, V[68..99] = 0), the I row (V = the state entering the permutation =
+ * PREV xor the block) and the O row (V = the permutation's output).  Everything the table sends stands in the one block
+ * V of 100 limb columns on different rows, so its seven interactions read 108 distinct columns.  Columns
+ * (rk_keccak_sponge_width = 2458; kc::KeccakSpongeLayout, raiko_amd/csrc/keccak_sponge.hpp): V[100] | PREV[100] (the state
+ * before this block: 0 on a message's first, else the preceding O row's V; the same on a group's rows) | MB[17][64] the
+ * bits of V's rate lanes | PB[17][64] those of PREV's | XR[68] = sum_k 2^k (mb + pb - 2 mb pb) | MSG BLK NBLK PID | KX KI KO
+ * REAL | FIRST LAST | S_IN S_OUT S_MSG S_DIG.  MB, PB and XR are constrained on every row alike (an all-zero row satisfies
+ * them); the X row's XR is what the I row's rate part must equal, its capacity part is PREV's -- both linear under IS_TRANSITION KX,
+ * which keeps the degree at 3.
+ * Constraints: the kinds are boolean, REAL their sum, X -> I -> O, an X row only after an O row (REAL falls once: real
+ * groups, then padding, and a padding row is zero); the first row is an X row with FIRST and PID 0, or padding; the last
+ * row is an O row or padding (a group the table's end cuts is not real); S_MSG = REAL KX, S_IN = REAL KI, S_OUT = REAL KO,
+ * S_DIG = KO LAST (a real row cannot withhold a send); NBLK = BLK + REAL; FIRST => BLK = 0 and PREV = 0; within a group
+ * PREV, MSG, BLK, PID, FIRST, LAST go on; PID rises by 1 a group; after an O row without LAST comes an X row of the same
+ * MSG with BLK + 1, FIRST = 0 and PREV = this V, and such a row is not the table's last; after a LAST O row a real row
+ * has FIRST.
+ * Interactions, seven sends: (PID, V[0..49]) on bus and (PID, V[50..99]) on bus + 1 S_IN times, the same on bus + 2, bus + 3
+ * S_OUT times -- the chip's four receives --; (MSG, BLK, V[0..33]) on bus + 4 and (MSG, BLK, V[34..67]) on bus + 5 S_MSG
+ * times; (MSG, NBLK, V[0..15]) on bus + 6 S_DIG times: the digest and the message's block count.  No table receives
+ * the last three: the verifier does, with claims (rk_p3_verify_claims) it binds itself.
+ * rk_keccak_sponge_air: params NULL = the SP1 preset; bus .. bus + 6 must be canonical.  rk_keccak_sponge_trace: two
+ * launches on the context's stream.  keccak_sponge_chain_kernel, one wavefront per message with lane i < 25 holding lane i
+ * of the state, writes per block the permutation's input to d_states (n_blocks x 25 lanes: exactly rk_keccak_chip_trace's
+ * d_states) and its output to d_outs, and four lanes per message to d_digests (n_msgs x 4); keccak_sponge_rows_kernel,
+ * one wavefront per block, then writes d_trace (rows x rk_keccak_sponge_width Montgomery words; block slots past
+ * n_blocks, the cut-off last one included, are zero rows).  d_blocks n_blocks x 17 lanes; d_first n_msgs + 1 words: the
+ * first block of each message, then n_blocks -- it must start at 0, rise strictly and end in n_blocks: anything else is
+ * THE CALLER'S ERROR and not detected (no access leaves the buffers, the rows are then not a valid witness); d_msg_ids
+ * NULL for 0 .. n_msgs - 1, else n_msgs Montgomery words.  RK_ERR_INVALID before any launch for a NULL ctx or buffer
+ * (d_msg_ids excepted), n_msgs = 0, n_blocks = 0, n_msgs > n_blocks, or rows that are no power of two, below
+ * rk_keccak_sponge_rows_per_block x n_blocks or above 2^24.
+ * Out of scope: the executor's ecall, SHA-3 padding and other rates, a digest binding of the claims in place of init_words. */
+uint32_t rk_keccak_sponge_width(void);
+uint32_t rk_keccak_sponge_rows_per_block(void);
+int rk_keccak_sponge_air(const rk_params* params, uint32_t bus, rk_air** out);
+int rk_keccak_sponge_trace(rk_ctx* ctx, const uint64_t* d_blocks, const uint32_t* d_first, const uint32_t* d_msg_ids, size_t n_msgs,
+                           size_t n_blocks, size_t rows, uint32_t* d_trace, uint64_t* d_states, uint64_t* d_outs, uint64_t* d_digests);
 /* One table of a proof.  trace: row-major 2^log_height x width Montgomery words (Plonky3's RowMajorMatrix), in host
  * memory or -- on_device = 1 -- in the memory of the context's GPU (left untouched). */
 typedef struct {

@@ -10,8 +10,8 @@ and the two halves of the output on bus + 2, bus + 3 (limb index = 4 (x + 5 y) +
 `claims_air` / `claims_rows` are the smallest table that uses it -- what an ecall table will look like --, and
 `prove_permutations` proves [claims, chip] in one call.
 
-Out of scope here: the chip as an ecall of the executor through the memory argument, a sponge / absorb table for
-Keccak-256 of messages, a verifier-side claim form for public (input, output) pairs."""
+Out of scope here: the chip as an ecall of the executor through the memory argument.  The sponge table for Keccak-256
+of messages and the verifier-side claim form are raiko_amd/keccak_sponge.py."""
 import ctypes as C
 
 import numpy as np
