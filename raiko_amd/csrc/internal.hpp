@@ -9,6 +9,7 @@
 #include <new>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/raiko_hip.h"
@@ -116,6 +117,12 @@ int scratch(rk_ctx* ctx, size_t bytes, void** out);  // valid until the next scr
 // caller's buffer is free on return (large uploads fall back to copy + wait)
 int upload(rk_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 int post_launch(rk_ctx* ctx, const char* what);
+// a kernel launch on the ctx stream, then post_launch: `what` names the kernel in the error
+template <class... P, class... A>
+inline int launch(rk_ctx* ctx, const char* what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, std::forward<A>(args)...);
+    return post_launch(ctx, what);
+}
 // device -> host on the ctx stream, then wait for the stream: the one way transcript-sized data reaches the host
 int d2h_sync(rk_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
 

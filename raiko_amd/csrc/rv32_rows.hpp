@@ -1,5 +1,5 @@
 // The rows of the rv32 chip sets' tables (rv32i, rv32i-cf, rv32im, rv32im-elf, rv32im-mem) as lane bodies: one call fills one row with canonical
-// values, on the GPU (rv32_shards.hip: one lane per row, staged in LDS) and under plain g++ (tests/emul/emul_rv32_rows.cpp
+// values, on the GPU (rv32_kernels.hpp, rv32_kernels_mem.hpp, rv32_prep.hip: one lane per row, staged in LDS) and under plain g++ (tests/emul/emul_rv32_rows.cpp
 // walks a trace through them against numpy).  raiko_amd/rv32.py, rv32cf.py and rv32im.py are the same in numpy and name
 // every column; each chip set's rows are the previous one's with columns appended, so each row comes in pieces.  rv32im-elf
 // (raiko_amd/rv32elf.py) is rv32im with the lookup tables' tuples preprocessed: its bodies (at the end) select those
@@ -904,6 +904,50 @@ inline bool commit_list_ok(const EcallArg* args, size_t n_args, const MemAccess*
 inline void merge_accesses(const MemAccess* acc, size_t n_acc, const MemAccess* reads, size_t n_reads, MemAccess* out) {
     size_t i = 0, j = 0, o = 0;
     while (i < n_acc || j < n_reads) out[o++] = j >= n_reads || (i < n_acc && acc[i].cycle <= reads[j].cycle) ? acc[i++] : reads[j++];
+}
+
+// ---- the shard driver's error word: what a kernel finds wrong it ORs into one device word, read back after the run
+enum ShardErr : uint32_t {
+    ERR_WORD = 1,            // prep: one pc with two instruction words (rv32im-elf: a word that is not the image's)
+    ERR_SIDE_LIST = 2,       // prep: an ecall row that is not in the side list
+    ERR_PC = 4,              // prep: a pc outside the program's slots (rv32im-elf: outside the image)
+    ERR_M_RESULT = 8,        // muldiv: the executor's result is not the op's
+    ERR_M_COUNT = 16,        // muldiv: the device's count of M rows is not the host's
+    ERR_ACCESS = 32,         // memop: an access is not what its instruction names
+    ERR_HEADS = 64,          // mem_link: the device's count of distinct words is not the host's
+    ERR_JOURNAL = 128,       // mem_journal_kernel's own flag word: the memory table is not one a journal can be read off
+    ERR_IO_LIST = 256,       // io_patch / io_rows: the ecall side list is not the trace's ecalls
+    ERR_COMMIT_READ = 512,   // io_rows: a commit read is not word k of its call
+};
+
+// What the driver returns for an error word, the muldiv rows (m_total) and the distinct words (heads) counted on the
+// device against the host's m_count and mem_words: the first check that fails, in this order.  RK_OK: the driver goes on
+// to compare the final registers.
+struct ShardVerdict {
+    int status;
+    const char* message;
+};
+template <int CS>
+inline ShardVerdict shard_verdict(uint32_t bits, uint32_t m_total, size_t m_count, uint32_t heads, size_t mem_words) {
+    using CH = Chips<CS>;
+    if (CH::io && (bits & ERR_IO_LIST))
+        return {RK_ERR_INVALID, "rk_exec_rv32io_shard_device: the ecall side list is not the trace's ecalls"};
+    if (CH::commit && (bits & ERR_COMMIT_READ))
+        return {RK_ERR_INVALID, "rk_exec_rv32commit_shard_device: a commit read is not the word of its call"};
+    if (CH::mem && (bits & ERR_ACCESS))
+        return {RK_ERR_INTERNAL, "rk_exec_rv32mem_shard_device: an access is not the one its instruction names"};
+    if (CH::mem && ((bits & ERR_HEADS) || heads != mem_words))
+        return {RK_ERR_INTERNAL, "rk_exec_rv32mem_shard_device: the distinct words on the device are not the host's"};
+    if (bits & (ERR_WORD | ERR_SIDE_LIST | ERR_PC)) {
+        if (CH::elf && (bits & (ERR_WORD | ERR_PC)))
+            return {RK_ERR_INVALID, bits & ERR_WORD ? "rk_exec_rv32elf_shard_device: an executed word is not the program image's word at its pc"
+                                                    : "rk_exec_rv32elf_shard_device: a pc executed outside the program image"};
+        return {RK_ERR_INVALID, bits & ERR_WORD ? "rk_exec_rv32_shard_device: a pc executed with two instruction words in one shard"
+                                                : "rk_exec_rv32_shard_device: trace and side list disagree"};
+    }
+    if (CH::im && (bits || m_total != m_count))
+        return {RK_ERR_INTERNAL, "rk_exec_rv32im_shard_device: an M result or the muldiv row count is not the executor's"};
+    return {RK_OK, nullptr};
 }
 
 }  // namespace rv32
