@@ -1048,6 +1048,51 @@ uint32_t rk_keccak_sponge_rows_per_block(void);
 int rk_keccak_sponge_air(const rk_params* params, uint32_t bus, rk_air** out);
 int rk_keccak_sponge_trace(rk_ctx* ctx, const uint64_t* d_blocks, const uint32_t* d_first, const uint32_t* d_msg_ids, size_t n_msgs,
                            size_t n_blocks, size_t rows, uint32_t* d_trace, uint64_t* d_states, uint64_t* d_outs, uint64_t* d_digests);
+/* THE KECCAK-256 PADDING TABLE under the sponge: "these 32-bit words, cut at this byte length and padded, are those
+ * blocks".  It RECEIVES the sponge's three sends on bus + 4 .. bus + 6 and sends what a memory-argument table can answer:
+ * one tuple a word and one a message.  The statement of [pad, sponge, chip]: for every message the sender supplies its
+ * little-endian words w_0 .. w_(NW-1), NW = ceil(len / 4) (the bytes of the last word past len are arbitrary and do not
+ * matter), len and a digest; the proof is accepted exactly when digest = Keccak-256(the first len bytes of the words).
+ * One row per word slot, 34 rows a block (rk_keccak_pad_rows_per_block).  Columns (rk_keccak_pad_width = 167;
+ * kc::KeccakPadLayout, raiko_amd/csrc/keccak_pad.hpp): B[68], a shift register of limbs -- B[66], B[67] the word PLACED on
+ * this row, next.B[j] = B[j + 2] within a block, so the block's 34th row holds the whole block -- | STEP[34] one-hot word
+ * position | W_LO W_HI the sender's word | WB[32] its bits | E[4] one-hot of len mod 4 on the END row | D[16] the digest's
+ * limbs on a message's last row | MSG BLK NBLK IDX LEN | DATA END AFTER REAL | R S_END.  A row is DATA (a word before the
+ * one that holds byte position len), END (that word) or AFTER; a padding row is zero.
+ * Constraints: the phases are boolean, REAL their sum and boolean, REAL falls once; STEP is one-hot on real rows, STEP[0]
+ * on the first row, cyclic; S_END = STEP[33] (END + AFTER) marks a message's last row, R = DATA + END - E[0] the rows that
+ * carry a word, NBLK = BLK + REAL (a real row cannot withhold a tuple); sum E = END and END (LEN - 4 IDX) = E[1] + 2 E[2] +
+ * 3 E[3]; WB boolean and recomposing W on every row, W = 0 where R = 0; the placed word B[66], B[67] = W on DATA, W's bytes
+ * below e and 0x01 above them on END, 0 on AFTER, + 0x8000 in the high limb on a message's last row (0x01 + 0x80 = 0x81:
+ * nothing carries); B[0..65] = 0 on STEP[0] and on padding rows and shifts after a real row without STEP[33]; D = 0 off a
+ * message's last row; IDX = BLK = AFTER = 0 on the first row and after a message's last; a real row that is not its
+ * message's last is followed by a real row with MSG and LEN unchanged, IDX + 1, BLK + STEP[33] and AFTER = END + AFTER (so
+ * DATA* END AFTER*: one END a message, and LEN = 4 IDX + e places it), and is not the table's last row.  Degree 3.
+ * Interactions (94 distinct columns): receives (MSG, BLK, B[0..33]) on bus + 4 and (MSG, BLK, B[34..67]) on bus + 5
+ * STEP[33] times, (MSG, NBLK, D) on bus + 6 S_END times; sends (MSG, IDX, W_LO, W_HI) on bus + 7 R times and (MSG, LEN, D)
+ * on bus + 8 S_END times.  No table receives the two sends: the verifier does, with claims (rk_p3_verify_claims).
+ * rk_keccak_pad_air: params NULL = the SP1 preset; bus .. bus + 8 must be canonical.  rk_keccak_pad_trace: two launches on
+ * the context's stream.  keccak_pad_blocks_kernel, one thread per word slot, writes d_blocks (n_blocks x 17 lanes: exactly
+ * rk_keccak_sponge_trace's d_blocks -- the padded message is never formed on the host); keccak_pad_rows_kernel, one
+ * wavefront per block slot of 34 rows, then writes d_trace (rows x rk_keccak_pad_width Montgomery words, D = 0; rows past 34 n_blocks are
+ * zero).  d_words n_words words: the messages' words back to back, each message from a word boundary; d_word_first
+ * n_msgs + 1: the first word of each message, then n_words; d_lens n_msgs byte lengths; d_first n_msgs + 1: the first block
+ * of each message, then n_blocks, where message m has len / 136 + 1 blocks.  Tables that do not agree with each other are
+ * THE CALLER'S ERROR and not detected: no access leaves the buffers (a word index is held below n_words, a block index
+ * below n_blocks), the rows are then not a valid witness.  d_msg_ids NULL for 0 .. n_msgs - 1, else n_msgs Montgomery words.
+ * rk_keccak_pad_digests: one launch that writes D from rk_keccak_sponge_trace's d_digests (n_msgs x 4 lanes), which exist
+ * only after the sponge has run over d_blocks.  Both return RK_ERR_INVALID before any launch for a NULL ctx or buffer
+ * (d_msg_ids excepted), n_msgs = 0, n_msgs > n_blocks, or rows that are no power of two, below 34 n_blocks or above 2^24.
+ * Out of scope: RK_ECALL_KECCAK itself (the executor's ecall, io-table rows that send the words, the digest's write-back,
+ * key and shard pool), sources that are not word-aligned, SHA-3's 0x06. */
+uint32_t rk_keccak_pad_width(void);
+uint32_t rk_keccak_pad_rows_per_block(void);
+int rk_keccak_pad_air(const rk_params* params, uint32_t bus, rk_air** out);
+int rk_keccak_pad_trace(rk_ctx* ctx, const uint32_t* d_words, size_t n_words, const uint32_t* d_word_first, const uint32_t* d_lens,
+                        const uint32_t* d_first, const uint32_t* d_msg_ids, size_t n_msgs, size_t n_blocks, size_t rows, uint32_t* d_trace,
+                        uint64_t* d_blocks);
+int rk_keccak_pad_digests(rk_ctx* ctx, const uint64_t* d_digests, const uint32_t* d_first, size_t n_msgs, size_t n_blocks, size_t rows,
+                          uint32_t* d_trace);
 /* One table of a proof.  trace: row-major 2^log_height x width Montgomery words (Plonky3's RowMajorMatrix), in host
  * memory or -- on_device = 1 -- in the memory of the context's GPU (left untouched). */
 typedef struct {

@@ -666,6 +666,11 @@ extern "C" {
     pub fn rk_keccak_sponge_rows_per_block() -> u32;
     pub fn rk_keccak_sponge_air(params: *const rk_params, bus: u32, out: *mut *mut rk_air) -> c_int;
     pub fn rk_keccak_sponge_trace(ctx: *mut rk_ctx, d_blocks: *const u64, d_first: *const u32, d_msg_ids: *const u32, n_msgs: usize, n_blocks: usize, rows: usize, d_trace: *mut u32, d_states: *mut u64, d_outs: *mut u64, d_digests: *mut u64) -> c_int;
+    pub fn rk_keccak_pad_width() -> u32;
+    pub fn rk_keccak_pad_rows_per_block() -> u32;
+    pub fn rk_keccak_pad_air(params: *const rk_params, bus: u32, out: *mut *mut rk_air) -> c_int;
+    pub fn rk_keccak_pad_trace(ctx: *mut rk_ctx, d_words: *const u32, n_words: usize, d_word_first: *const u32, d_lens: *const u32, d_first: *const u32, d_msg_ids: *const u32, n_msgs: usize, n_blocks: usize, rows: usize, d_trace: *mut u32, d_blocks: *mut u64) -> c_int;
+    pub fn rk_keccak_pad_digests(ctx: *mut rk_ctx, d_digests: *const u64, d_first: *const u32, n_msgs: usize, n_blocks: usize, rows: usize, d_trace: *mut u32) -> c_int;
     pub fn rk_p3_prove(ctx: *mut rk_ctx, tables: *const rk_p3_table, n_tables: u32, init_words: *const u32, n_init: usize, h_proof: *mut u32, capacity_words: usize, proof_words: *mut usize) -> c_int;
     pub fn rk_p3_setup(ctx: *mut rk_ctx, tables: *const rk_p3_table, n_tables: u32, prep_traces: *const *const u32, key: *mut *mut rk_p3_key) -> c_int;
     pub fn rk_p3_key_root(key: *const rk_p3_key, out: *mut u32) -> c_int;

@@ -354,6 +354,11 @@ SYMBOLS = {
     "rk_keccak_sponge_rows_per_block": (_u32, []),
     "rk_keccak_sponge_air": (C.c_int, [C.POINTER(RkParams), _u32, C.POINTER(_vp)]),
     "rk_keccak_sponge_trace": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "rk_keccak_pad_width": (_u32, []),
+    "rk_keccak_pad_rows_per_block": (_u32, []),
+    "rk_keccak_pad_air": (C.c_int, [C.POINTER(RkParams), _u32, C.POINTER(_vp)]),
+    "rk_keccak_pad_trace": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "rk_keccak_pad_digests": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _vp]),
     "rk_air_get_steps": (C.c_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "rk_air_destroy": (C.c_int, [_vp]),
     "rk_air_get_info": (C.c_int, [_vp, C.POINTER(RkAirInfo)]),

@@ -15,8 +15,11 @@ is LINEAR in the messages (it pads them, observes 72 words a block and inverts o
 form does not spare the verifier the bytes.  It is the harness that makes the table testable end to end with public
 messages, and its sends are the interface an ecall table will receive.
 
-Out of scope: the executor's ecall (RK_ECALL_KECCAK) and its memory-argument table, SHA-3 padding and other rates, a
-Poseidon2-digest binding of the claims in place of init."""
+The padding in circuit, for a sender that knows words and a byte length only, is the table under this one:
+raiko_amd/keccak_pad.py.
+
+Out of scope: the executor's ecall (RK_ECALL_KECCAK), SHA-3 padding and other rates, a Poseidon2-digest binding of the
+claims in place of init."""
 import ctypes as C
 
 import numpy as np
@@ -87,34 +90,40 @@ def keccak_sponge_air(params=None, bus=keccak_chip.BUS_KECCAK):
 
 class SpongeTrace:
     """what rk_keccak_sponge_trace left: .d_rows (device, rows x width Montgomery words), .rows, .d_states (device,
-    n_blocks x 25 lanes: what rk_keccak_chip_trace reads), .n_blocks, and on the host .states / .outs (n_blocks, 25)
+    n_blocks x 25 lanes: what rk_keccak_chip_trace reads), .d_digests (device, k x 4 lanes), .n_blocks, and on the host .states / .outs (n_blocks, 25)
     uint64, .digests (k, 4) uint64"""
 
 
 def keccak_sponge_trace(hal, messages, msg_ids=None, rows=None):
     """rk_keccak_sponge_trace for byte strings `messages` (padded here) -> SpongeTrace.  msg_ids: one Montgomery word
     a message (None: 0 .. k - 1); rows: a power of two >= max(2, 3 n_blocks) (None: the smallest)"""
-    from .hal import _ptr
-    lib = _lib.load()
     blocks, first = pad_blocks(messages)
     k, nb = len(first) - 1, blocks.shape[0]
     rows = min_rows(nb) if rows is None else int(rows)
     if k == 0 or rows < 2 or rows & (rows - 1) or rows < ROWS_PER_BLOCK * nb or rows > 1 << 24:
         raise _lib.RkError(_lib.RK_ERR_INVALID, "keccak_sponge_trace: %d messages, %d blocks do not fit rows = %d" % (k, nb, rows))
-    width = int(lib.rk_keccak_sponge_width())
     d_blocks = hal.copy_from_elem(blocks.view(np.uint32).reshape(-1))
     d_first = hal.copy_from_elem(first)
     d_ids = hal.copy_from_elem(np.ascontiguousarray(msg_ids, dtype=np.uint32)) if msg_ids is not None else None
     assert d_ids is None or d_ids.size() == k
+    return keccak_sponge_trace_device(hal, d_blocks, d_first, d_ids, k, nb, rows)
+
+
+def keccak_sponge_trace_device(hal, d_blocks, d_first, d_ids, k, nb, rows):
+    """rk_keccak_sponge_trace over blocks that are in HBM already -> SpongeTrace (with .d_digests, the k x 4 lanes on the
+    device).  d_blocks nb x 17 lanes, d_first k + 1 words, d_ids k Montgomery words or None: DeviceBuffers"""
+    from .hal import _ptr
+    lib = _lib.load()
+    width = int(lib.rk_keccak_sponge_width())
     t = SpongeTrace()
     t.rows, t.n_blocks = rows, nb
     t.d_rows, t.d_states = hal.alloc_elem(rows * width), hal.alloc_elem(nb * 50)
-    d_outs, d_dig = hal.alloc_elem(nb * 50), hal.alloc_elem(k * 8)
+    d_outs, t.d_digests = hal.alloc_elem(nb * 50), hal.alloc_elem(k * 8)
     _lib.check(hal._ctx, lib.rk_keccak_sponge_trace(hal._ctx, _ptr(d_blocks), _ptr(d_first), _ptr(d_ids) if d_ids is not None else None, k, nb,
-                                                    rows, _ptr(t.d_rows), _ptr(t.d_states), _ptr(d_outs), _ptr(d_dig)))
+                                                    rows, _ptr(t.d_rows), _ptr(t.d_states), _ptr(d_outs), _ptr(t.d_digests)))
     t.states = t.d_states.to_host().view(np.uint64).reshape(nb, 25)
     t.outs = d_outs.to_host().view(np.uint64).reshape(nb, 25)
-    t.digests = d_dig.to_host().view(np.uint64).reshape(k, 4)
+    t.digests = t.d_digests.to_host().view(np.uint64).reshape(k, 4)
     return t
 
 
@@ -122,9 +131,13 @@ def keccak_sponge_tables(hal, messages, params=None):
     """[sponge table, chip table] with their rows in HBM (Tables without a host trace, heights pinned, .device =
     (DeviceBuffer, log_height)): the sponge's by rk_keccak_sponge_trace, the chip's by rk_keccak_chip_trace straight
     from the d_states buffer the chain kernel left on the device.  The sponge table carries .trace_info (SpongeTrace)"""
+    return tables_of_trace(hal, keccak_sponge_trace(hal, messages), params)
+
+
+def tables_of_trace(hal, t, params=None):
+    """[sponge table, chip table] of a SpongeTrace, as keccak_sponge_tables describes them"""
     from .hal import _ptr
     lib = _lib.load()
-    t = keccak_sponge_trace(hal, messages)
     sponge = p3.Table.pinned(keccak_sponge_air(params), t.rows.bit_length() - 1)
     sponge.device, sponge.trace_info = (t.d_rows, t.rows.bit_length() - 1), t
     chip_rows = keccak_chip.min_rows(t.n_blocks)
